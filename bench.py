@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — the GPS L1 C/A IQ buffer-fill path on MI355X, BASELINE.json's metric.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 Workload (config.workload = "synth16-S as one stream", BASELINE configs[2] in the shape of configs[4]): ONE
@@ -27,9 +27,12 @@ blocks of the shard (oracle chained from the shard's seed) and one block of its 
 the stream itself reports there).  A mismatch on any rank makes the run exit non-zero.
 
 Prints ONE JSON line on rank 0.  `value` = IQ samples/s over all GPUs, from the MEDIAN of --repeats timed regions
-of K steps each, every region bracketed by barrier + synchronize on both sides with the ring drained (min / max
-beside it).  `roofline` = algorithmic HBM bytes (4 B per IQ sample) of the synthesis kernel / its HIP-event
-duration against the 8 TB/s HBM peak.  Beside it, measured in the same invocation:
+of K steps each (a plain run: ONE region, K timed steps; --full: 5), every region bracketed by barrier + synchronize
+on both sides with the ring drained (min / max beside it).  `roofline` = algorithmic HBM bytes (4 B per IQ sample) of the
+synthesis kernel / its HIP-event duration against the 8 TB/s HBM peak.
+
+A plain run does only that: set-up, warm-up, the timed steps, the outputs (--dump-outputs) and the line.  With --full
+the same invocation also runs the parity check above and measures, beside the headline:
   resident      re-runs of one 400-block batch whose descriptors and plans stay in HBM (independent blocks and
                 chained): what round 1 reported as its value
   gather        the same shard through a ring with the pinned D2H gather (PCIe-inclusive; never `value`)
@@ -50,6 +53,7 @@ rank 0 for most of the command).
                 sink and interleaved slots into the ordered one, every slot digested and compared with what the ranks rendered
 """
 import argparse
+import collections
 import hashlib
 import json
 import os
@@ -222,6 +226,44 @@ def cpu_legs_main(args):
     except Exception as e:
         out["error"] = repr(e)
     print(json.dumps(out))
+
+
+DUMP_SEED = 0xD0A9           # which blocks of the last step's slots and which samples of them --dump-outputs writes
+DUMP_BLOCKS_PER_PUSH, DUMP_SAMPLES, DUMP_END_BYTES = 4, 32768, 8 << 20   # at most 8 MiB of IQ and 11.2 MiB of end states
+
+
+def dump_outputs(out_dir, synth, pops, PB, nsamp, b0):
+    """--dump-outputs: what the last timed step handed its caller on rank 0, as float32 / float64 .npy files in out_dir.
+    pops: (push number in the shard, slot pointer, end states) of every pop of that step, in order.  The end states of all
+    its blocks (end_<field>: [blocks, nch], end_block: their numbers in the stream; a seeded sample of the blocks beyond
+    DUMP_END_BYTES of states); the IQ (32 GB a step) as a fixed sample: DUMP_SAMPLES
+    consecutive samples at a seeded offset in DUMP_BLOCKS_PER_PUSH seeded blocks of every push whose slot no later push of
+    the step has reused (a ring has `depth` slots), read back from HBM once the region is over.  iq_sample [n, samples, 2]
+    (int16 values), iq_sample_block (the block's number in the stream), iq_sample_offset (its first sample)."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    ends = np.concatenate([p[2] for p in pops])
+    blocks = np.concatenate([b0 + k * PB + np.arange(PB) for k, _, _ in pops])
+    if ends.nbytes > DUMP_END_BYTES:   # larger geometries than the headline's: a seeded sample of the blocks
+        rows = np.sort(rng.choice(ends.shape[0], size=DUMP_END_BYTES // ends[0].nbytes, replace=False))
+        ends, blocks = ends[rows], blocks[rows]
+    for f in ("carr_phase", "code_phase", "iword", "ibit", "icode", "dataBit", "codeCA"):
+        np.save(os.path.join(out_dir, "end_%s.npy" % f), ends[f].astype(np.float64))
+    np.save(os.path.join(out_dir, "end_block.npy"), blocks.astype(np.float64))
+    L = min(DUMP_SAMPLES, nsamp)
+    iq, blk, off = [], [], []
+    for i, (k, dptr, _) in enumerate(pops):
+        js = np.sort(rng.choice(PB, size=min(DUMP_BLOCKS_PER_PUSH, PB), replace=False))
+        os_ = rng.integers(0, nsamp - L + 1, size=js.size)
+        if any(p[1] == dptr for p in pops[i + 1:]):
+            continue   # its slot holds a later push now (the draws above are made all the same: the sample does not move)
+        for j, o in zip(js, os_):
+            iq.append(synth.device_read(dptr + (int(j) * nsamp + int(o)) * 4, (L, 2)))
+            blk.append(b0 + k * PB + int(j))
+            off.append(int(o))
+    np.save(os.path.join(out_dir, "iq_sample.npy"), np.asarray(iq, np.float32).reshape(-1, L, 2))
+    np.save(os.path.join(out_dir, "iq_sample_block.npy"), np.asarray(blk, np.float64))
+    np.save(os.path.join(out_dir, "iq_sample_offset.npy"), np.asarray(off, np.float64))
 
 
 def block_digest(a):
@@ -449,7 +491,7 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40, help="timed steps per region; a step is 3200 blocks of the stream")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions of --steps steps; the median is reported (default: 1, with --full 5)")
     ap.add_argument("--push-blocks", type=int, default=PUSH_BLOCKS, help="0.1 s blocks per push")
     ap.add_argument("--depth", type=int, default=6, help="ring slots")
     ap.add_argument("--nch", type=int, default=16)
@@ -466,7 +508,15 @@ def main():
     ap.add_argument("--fill-calls", type=int, default=200, help="gpsbb_fill_block_ref calls timed per case of the fill_block leg")
     ap.add_argument("--no-m1-stream", action="store_true", help="skip the 2.6 MS/s stream leg (measurement aid)")
     ap.add_argument("--cpu-legs", action="store_true", help="(internal) only the CPU baselines, as a process of their own: what rank 0 starts beside its GPU legs")
+    ap.add_argument("--full", action="store_true", help="also the parity check, the other legs (gather, m1, node driver, resident, fill_block), "
+                                                         "the CPU baselines and the roofline annotations of earlier profiles; without it only the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (a fixed sample of its IQ, its end states)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if not args.full:
+        args.no_extras = True
     if args.cpu_legs:
         return cpu_legs_main(args)
 
@@ -553,15 +603,23 @@ def main():
         if use_dist:
             dist.barrier()
 
-    def run_ring(st, first, count, depth):
-        """`count` pushes starting at push number `first` of the shard (cyclically), every slot popped; the ring ends drained"""
+    def run_ring(st, first, count, depth, keep=None):
+        """`count` pushes starting at push number `first` of the shard (cyclically), every slot popped; the ring ends drained.
+        keep: a deque that receives (push number, slot pointer, end states) of every pop"""
+        popped = 0
         for j in range(count):
             if st.pending >= depth:
-                st.pop(copy=False)
+                got = st.pop(copy=False)
+                if keep is not None:
+                    keep.append(((first + popped) % npush,) + tuple(got))
+                popped += 1
             k = (first + j) % npush
             st.push(mine[k * PB:(k + 1) * PB])
         while st.pending:
-            st.pop(copy=False)
+            got = st.pop(copy=False)
+            if keep is not None:
+                keep.append(((first + popped) % npush,) + tuple(got))
+            popped += 1
 
     # ---- headline: K steps of fresh pushes, chained on the device, IQ into HBM ----
     st = synth.stream(nch, delt, nsamp, PB, depth=args.depth, flags=pkg.CHAIN_CARRIER | pkg.STREAM_DEVICE_ONLY)
@@ -570,10 +628,11 @@ def main():
     barrier()
     st.timing_stats(reset=True)
     times = []
-    for _ in range(R):
+    last_step = collections.deque(maxlen=ppr) if args.dump_outputs and rank == 0 else None   # the pops of the last timed step
+    for i in range(R):
         barrier()
         t0 = time.perf_counter()
-        run_ring(st, pos, K * ppr, args.depth)
+        run_ring(st, pos, K * ppr, args.depth, last_step if i == R - 1 else None)
         synth.sync()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
@@ -590,6 +649,8 @@ def main():
     chain_info = {"blocks_walked_sequentially": synth.info(pkg.INFO_CHAIN_FALLBACKS), "of_block_channels": pos * PB * nch,
                   "wrap_ties_recorded": synth.info(pkg.INFO_CHAIN_TIES),
                   "lane_runs_recomputed_exactly_by_k_synth_ev": synth.info(pkg.INFO_EXACT_RUNS)}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, synth, list(last_step), PB, nsamp, b0)
     st.close()
     elapsed = statistics.median(times)
     samples_per_step = STEP_PUSHES * PB * nsamp
@@ -826,7 +887,7 @@ def main():
                      "rank0_affinity": affinity},
         }
         pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")
-        if os.path.exists(pmc):
+        if args.full and os.path.exists(pmc):
             try:
                 pj = json.load(open(pmc))
                 res["roofline"]["traffic"] = pj.get("k_synth_hbm_bytes_per_launch")
@@ -838,7 +899,7 @@ def main():
         if node:
             res["node_driver"] = node
         sq = os.path.join(ROOT, "profiles", "sq_latest.json")
-        if os.path.exists(sq):
+        if args.full and os.path.exists(sq):
             try:
                 # the bound the kernel actually runs against: VALU issue.  Wave-instructions per launch from the kept SQ counter
                 # pass (SQ_INSTS_VALU, scaled to this launch's samples), cycles per wave-instruction per SIMD from the

@@ -62,7 +62,7 @@ def test_two_ranks_through_the_device_path(pkg):
     every block cross-checked and the node driver validated at either N; so are the 2.6 MS/s stream (12 ch, the reference's
     geometry: cut, seeded and cross-checked like the headline's), the CPU baselines and the drop-in call's latency; the resident
     legs at N = 1 only."""
-    args = ["--steps", "2", "--warmup", "1", "--repeats", "2", "--push-blocks", "8", "--nsamp", "200000", "--depth", "3",
+    args = ["--full", "--steps", "2", "--warmup", "1", "--repeats", "2", "--push-blocks", "8", "--nsamp", "200000", "--depth", "3",
             "--cpu-budget", "0.4", "--parity-blocks", "2", "--m1-push-blocks", "40", "--fill-calls", "12"]
     env = {"GPSBB_BENCH_BACKEND": "gloo"}
     one = _run(1, args, env)
@@ -112,10 +112,11 @@ def test_one_rank_through_the_rccl_path(pkg):
     nccl (= RCCL) backend, GPSBB_BENCH_FORCE_DIST making it take the N > 1 branches anyway — process group on the device,
     all_reduce of device tensors for the max-over-ranks times, all_gather_object of the digests, barriers — so that the
     driver's multi-GPU run is not the first execution of that code.  The line also carries the node driver's leg."""
-    env = dict(os.environ, GPSBB_BENCH_FORCE_DIST="1")
+    # the 12 hardware queues a host exports (INTEGRATION.md), whatever the calling environment holds
+    env = dict(os.environ, GPSBB_BENCH_FORCE_DIST="1", GPU_MAX_HW_QUEUES="12")
     env.pop("GPSBB_BENCH_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "2", "--warmup", "1",
            "--repeats", "2", "--push-blocks", "8", "--nsamp", "200000", "--depth", "3", "--cpu-budget", "0.3", "--parity-blocks", "2",
            "--parity-spots", "2", "--m1-push-blocks", "40", "--fill-calls", "12"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
@@ -151,7 +152,7 @@ def test_a_wrong_kernel_fails_the_bench(pkg, tmp_path):
     they pass, the cross-check does not."""
     import subprocess
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "pluto-gps-sim_amd", "csrc"), "broken", "broken2", "VARIANT_DIR=%s" % tmp_path])
-    args = ["--steps", "1", "--warmup", "1", "--repeats", "1", "--push-blocks", "8", "--nsamp", "200000", "--depth", "3",
+    args = ["--full", "--steps", "1", "--warmup", "1", "--repeats", "1", "--push-blocks", "8", "--nsamp", "200000", "--depth", "3",
             "--cpu-budget", "0.2", "--parity-blocks", "2", "--m1-push-blocks", "16", "--fill-calls", "4"]
     r = _run(1, args, {"GPSBB_PY_LIB": str(tmp_path / "libgpsbb_broken.so")}, expect_rc=3)
     assert r["parity"]["mismatching_blocks"] >= 1 and r["parity_checked_blocks"] >= 3

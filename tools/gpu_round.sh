@@ -11,7 +11,7 @@ ROOT=$PWD
 timeout 1500 python -m pytest tests -m gpu -x -q --timeout 900 > "$OUT/pytest_gpu.log" 2>&1
 echo "pytest rc=$?" >> "$OUT/pytest_gpu.log"
 tail -4 "$OUT/pytest_gpu.log"
-timeout 900 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 900 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 tail -c 2500 "$OUT/bench.json"
 # per-kernel time of the TIMED LEG ALONE (--no-extras: no parity / cross-check / node-driver legs, whose launches run beside other
 # kernels and used to be averaged in): avg(k_synth_ev) x 8 pushes <= ms_per_step of the same run must hold

@@ -8,7 +8,7 @@ k=0
 for cfg in "$@"; do
   k=$((k+1))
   envs=""; [ "$cfg" != "-" ] && envs=$(echo "$cfg" | tr ',' ' ')
-  env GPSBB_PY_LIB=exp $envs timeout 900 python bench.py --steps 20 --repeats 3 --cpu-budget 0.3 --parity-blocks 2 --parity-spots 2 > $OUT/bench_$k.json 2> $OUT/bench_$k.err
+  env GPSBB_PY_LIB=exp $envs timeout 900 python bench.py --full --steps 20 --repeats 3 --cpu-budget 0.3 --parity-blocks 2 --parity-spots 2 > $OUT/bench_$k.json 2> $OUT/bench_$k.err
   echo "== $cfg: rc $?"
   python tools/bench_brief.py $OUT/bench_$k.json 2>&1 | head -2
 done
