@@ -53,6 +53,10 @@ extern "C" {
 #define GPSBB_NODE_DIGESTS 64u      /* every push is rendered WITH the digests of its blocks (GPSBB_PUSH_DIGEST: include/gpsbb.h): a sink
                                        that wants them calls gpsbb_node_slot_digests from inside its callback instead of reading the
                                        slot back (gpsbb_slot_digest).  Costs the synthesis ~7 %, where reading back costs it a third */
+/* The output formats of include/gpsbb.h (GPSBB_OUT_SC8(shift), GPSBB_OUT_SC1: bits 8-15) are taken in the same bits of
+ * gpsbb_node_config_t.flags and passed to every producer's ring: the sink's `iq` then points at nblocks * gpsbb_out_bytes(flags,
+ * nsamp) packed bytes (the sink casts).  GPSBB_E_BADARG with GPSBB_NODE_DEVICE_ONLY, and for gpsbb_node_run_digest (its digests
+ * are of the int16 render).  Each shard's handle counts its own SC8 clips; the node does not add them up. */
 
 /*
  * The one consumer.  `iq` = nblocks consecutive blocks (nblocks * nsamp int16 I/Q pairs, interleaved), the first of them

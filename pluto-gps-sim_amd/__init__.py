@@ -90,6 +90,16 @@ NODE_INDEXED, NODE_CONCURRENT, NODE_DEVICE_ONLY, NODE_NO_AFFINITY, NODE_FIXED_CA
 PUSH_NEW_CHAIN = 1
 PUSH_DIGEST = 2
 NODE_MAX_SHARDS = 64
+INFO_SC8_CLIPPED = 11
+# output formats of the host-bound paths (include/gpsbb.h GPSBB_OUT_*): the `fmt=` of fill_block / stream / Node / device_pack
+OUT_SC16 = 0
+OUT_SC1 = 2 << 8
+OUT_FORMAT_MASK, OUT_SHIFT_MASK = 0xF00, 0xF000
+
+
+def OUT_SC8(shift):
+    """GPSBB_OUT_SC8(shift): int8 I/Q, clamp(v >> shift, -128, 127)"""
+    return (1 << 8) | (int(shift) << 12)
 
 ERRORS = {0: "GPSBB_OK", -1: "GPSBB_E_BADARG", -2: "GPSBB_E_BADCHAN", -3: "GPSBB_E_HIP", -4: "GPSBB_E_NOMEM",
           -5: "GPSBB_E_INTERNAL", -6: "GPSBB_E_NODEVICE", -7: "GPSBB_E_STATE"}
@@ -103,6 +113,7 @@ API_SYMBOLS = [
     "gpsbb_stream_destroy", "gpsbb_stream_push", "gpsbb_stream_pop", "gpsbb_stream_pending", "gpsbb_stream_timing_stats",
     "gpsbb_codegen", "gpsbb_sincos_tables", "gpsbb_chain_carrier_host", "gpsbb_chain_carrier", "gpsbb_set_option",
     "gpsbb_get_info", "gpsbb_stream_reset", "gpsbb_device_affinity", "gpsbb_stream_push_ex", "gpsbb_stream_pop_digest", "gpsbb_host_register", "gpsbb_host_unregister",
+    "gpsbb_out_bytes", "gpsbb_device_pack",
 ]
 # ... and include/gpsbb_node.h
 NODE_API_SYMBOLS = ["gpsbb_node_create", "gpsbb_node_run", "gpsbb_node_run_digest", "gpsbb_node_slot_digests", "gpsbb_node_destroy", "gpsbb_node_plan", "gpsbb_node_begin", "gpsbb_node_feed", "gpsbb_node_end"]
@@ -192,6 +203,9 @@ def lib():
         L.gpsbb_node_feed.argtypes = [vp, vp, C.c_long]
         L.gpsbb_node_end.argtypes = [vp, vp]
         L.gpsbb_node_plan.argtypes = [C.c_long, i, i, C.POINTER(C.c_long)]
+        L.gpsbb_out_bytes.argtypes = [u, C.c_long]
+        L.gpsbb_out_bytes.restype = C.c_long
+        L.gpsbb_device_pack.argtypes = [vp, vp, C.c_long, i, u, vp]
         _lib = L
     return _lib
 
@@ -287,15 +301,24 @@ class Synth:
     def __exit__(self, *a):
         self.close()
 
-    def fill_block(self, ch, delt, nsamp, flags=0, out=None):
-        """gpsbb_fill_block(_ex): ch = CHAN_DTYPE[nch] -> (int16 [nsamp,2], STATE_DTYPE[nch]); out: the caller's iq_buff"""
+    def fill_block(self, ch, delt, nsamp, flags=0, out=None, fmt=OUT_SC16):
+        """gpsbb_fill_block(_ex): ch = CHAN_DTYPE[nch] -> (int16 [nsamp,2], STATE_DTYPE[nch]); out: the caller's iq_buff.
+        fmt (OUT_SC8(shift) / OUT_SC1): the block comes back packed — int8 [nsamp, 2] / uint8 [nsamp // 4] — and `out`, if given,
+        is any C-contiguous array of at least out_bytes(fmt, nsamp) bytes (a registered iq_buff: written straight into)."""
         ch = np.ascontiguousarray(ch, dtype=CHAN_DTYPE)
-        iq = np.empty((nsamp, 2), np.int16) if out is None else out
-        assert iq.dtype == np.int16 and iq.flags.c_contiguous and iq.size >= 2 * nsamp
+        if fmt & (OUT_FORMAT_MASK | OUT_SHIFT_MASK):
+            nbytes = out_bytes(fmt, nsamp)
+            buf = np.empty(nbytes, np.uint8) if out is None else out
+            assert buf.flags.c_contiguous and buf.nbytes >= nbytes
+        else:
+            buf = np.empty((nsamp, 2), np.int16) if out is None else out
+            assert buf.dtype == np.int16 and buf.flags.c_contiguous and buf.size >= 2 * nsamp
         st = np.zeros(ch.shape[0], STATE_DTYPE)
-        _chk(lib().gpsbb_fill_block_ex(self._h, ch.ctypes.data, ch.shape[0], delt, nsamp, flags, iq.ctypes.data,
+        _chk(lib().gpsbb_fill_block_ex(self._h, ch.ctypes.data, ch.shape[0], delt, nsamp, flags | fmt, buf.ctypes.data,
                                        st.ctypes.data), "gpsbb_fill_block_ex")
-        return iq, st
+        if fmt & (OUT_FORMAT_MASK | OUT_SHIFT_MASK):
+            return _as_out(buf, 1, nsamp, fmt)[0], st
+        return buf, st
 
     def fill_block_ref(self, chan, gain, delt, nsamp, iq, layout=None):
         """gpsbb_fill_block_ref: the reference's own channel_t[] (REF_CHANNEL_DTYPE, updated in place like the loop does,
@@ -314,8 +337,17 @@ class Synth:
     def batch(self, ch, delt, nsamp, flags=0):
         return Batch(self, ch, delt, nsamp, flags)
 
-    def stream(self, nch, delt, nsamp, blocks_per_slot, depth=3, flags=0):
-        return Stream(self, nch, delt, nsamp, blocks_per_slot, depth, flags)
+    def stream(self, nch, delt, nsamp, blocks_per_slot, depth=3, flags=0, fmt=OUT_SC16):
+        return Stream(self, nch, delt, nsamp, blocks_per_slot, depth, flags, fmt)
+
+    def device_pack(self, d_ptr, nblocks, nsamp, fmt, out=None):
+        """gpsbb_device_pack: nblocks blocks of int16 IQ in device memory, packed into host memory in format fmt -> the array of
+        iq_view's shape; out: a C-contiguous host array (pageable or pinned) of at least nblocks * out_bytes(fmt, nsamp) bytes"""
+        nbytes = nblocks * out_bytes(fmt, nsamp)
+        buf = np.empty(nbytes, np.uint8) if out is None else out
+        assert buf.flags.c_contiguous and buf.nbytes >= nbytes
+        _chk(lib().gpsbb_device_pack(self._h, C.c_void_p(int(d_ptr)), nblocks, nsamp, fmt, buf.ctypes.data), "gpsbb_device_pack")
+        return _as_out(buf, nblocks, nsamp, fmt)
 
     def sync(self):
         _chk(lib().gpsbb_sync(self._h), "gpsbb_sync")
@@ -438,12 +470,13 @@ class Batch:
 class Stream:
     """Time-sharded streaming with pinned host gather (gpsbb_stream_*)."""
 
-    def __init__(self, synth, nch, delt, nsamp, blocks_per_slot, depth=3, flags=0):
+    def __init__(self, synth, nch, delt, nsamp, blocks_per_slot, depth=3, flags=0, fmt=OUT_SC16):
         self.synth = synth
         self.nch, self.nsamp, self.bps = nch, nsamp, blocks_per_slot
         self.device_only = bool(flags & STREAM_DEVICE_ONLY)
+        self.fmt = fmt  # OUT_SC8(shift) / OUT_SC1: pop() hands out the slot's packed bytes (iq_view's shape)
         self._s = C.c_void_p()
-        _chk(lib().gpsbb_stream_create(synth._h, nch, delt, nsamp, blocks_per_slot, depth, flags,
+        _chk(lib().gpsbb_stream_create(synth._h, nch, delt, nsamp, blocks_per_slot, depth, flags | fmt,
                                        C.byref(self._s)), "gpsbb_stream_create")
 
     def close(self):
@@ -476,8 +509,7 @@ class Stream:
         _chk(lib().gpsbb_stream_pop_digest(self._s, C.byref(p), st.ctypes.data, dig.ctypes.data), "gpsbb_stream_pop_digest")
         if self.device_only:
             return p.value, st, dig
-        n = self.bps * self.nsamp * 2
-        view = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int16)), (n,)).reshape(self.bps, self.nsamp, 2)
+        view = iq_view(p.value, self.bps, self.nsamp, self.fmt)
         return (view.copy() if copy else view), st, dig
 
     def pop(self, copy=True):
@@ -488,8 +520,7 @@ class Stream:
         _chk(lib().gpsbb_stream_pop(self._s, C.byref(p), st.ctypes.data), "gpsbb_stream_pop")
         if self.device_only:
             return p.value, st
-        n = self.bps * self.nsamp * 2
-        view = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int16)), (n,)).reshape(self.bps, self.nsamp, 2)
+        view = iq_view(p.value, self.bps, self.nsamp, self.fmt)
         return (view.copy() if copy else view), st
 
     @property
@@ -545,10 +576,11 @@ def device_affinity(device):
 class Node:
     """gpsbb_node_*: nshards producer threads (one handle + one ring each, bound next to their GPU), one sink."""
 
-    def __init__(self, nshards, nch, delt, nsamp, blocks_per_slot, depth=3, flags=0, devices=None):
+    def __init__(self, nshards, nch, delt, nsamp, blocks_per_slot, depth=3, flags=0, devices=None, fmt=OUT_SC16):
         self.nshards, self.nch, self.nsamp = nshards, nch, nsamp
+        self.fmt = fmt  # OUT_SC8(shift) / OUT_SC1: the sink's iq points at packed bytes (iq_view(iq, nblocks, nsamp, fmt))
         dev = (C.c_int * nshards)(*(devices if devices is not None else range(nshards)))
-        cfg = _NodeConfig(nshards, dev, nch, delt, nsamp, blocks_per_slot, depth, flags)
+        cfg = _NodeConfig(nshards, dev, nch, delt, nsamp, blocks_per_slot, depth, flags | fmt)
         self._n = C.c_void_p()
         _chk(lib().gpsbb_node_create(C.byref(self._n), C.byref(cfg)), "gpsbb_node_create")
 
@@ -646,6 +678,53 @@ class Node:
             raise GpsbbError(rc, "gpsbb_node_end")
         return {"rc": rc, "seconds": st.seconds, "blocks": st.blocks,
                 "shards": [{k: getattr(st.shard[g], k) for k, _ in _NodeShardStats._fields_} for g in range(st.nshards)]}
+
+
+def out_bytes(fmt, nsamp):
+    """gpsbb_out_bytes: bytes of one block of nsamp samples in output format fmt (GpsbbError for a format it refuses)"""
+    n = lib().gpsbb_out_bytes(fmt, nsamp)
+    _chk(n if n < 0 else 0, "gpsbb_out_bytes")
+    return n
+
+
+def _out_layout(nblocks, nsamp, fmt):
+    f = (fmt & OUT_FORMAT_MASK) >> 8
+    return {0: (np.int16, C.c_int16, (nblocks, nsamp, 2)), 1: (np.int8, C.c_int8, (nblocks, nsamp, 2)),
+            2: (np.uint8, C.c_uint8, (nblocks, nsamp // 4))}[f]
+
+
+def iq_view(ptr, nblocks, nsamp, fmt=OUT_SC16):
+    """A numpy view of nblocks blocks in output format fmt at host address ptr (a popped slot, a node sink's iq): int16
+    [nblocks, nsamp, 2] (SC16), int8 [nblocks, nsamp, 2] (SC8), uint8 [nblocks, nsamp // 4] (SC1)"""
+    _, ct, shape = _out_layout(nblocks, nsamp, fmt)
+    return np.ctypeslib.as_array(C.cast(C.c_void_p(ptr), C.POINTER(ct)), shape)
+
+
+def _as_out(buf, nblocks, nsamp, fmt):
+    """iq_view's shape over a numpy buffer (a view of it: the buffer stays alive)"""
+    dt, _, shape = _out_layout(nblocks, nsamp, fmt)
+    n = nblocks * out_bytes(fmt, nsamp)
+    return buf.reshape(-1).view(np.uint8)[:n].view(dt).reshape(shape)
+
+
+def pack_iq(iq, fmt):
+    """The output formats in numpy (the reference the GPU's packing is checked against): iq int16 [..., nsamp, 2] -> int16 as is
+    (SC16), int8 [..., nsamp, 2] (SC8: clamp(v >> shift, -128, 127), an arithmetic shift), uint8 [..., nsamp // 4] (SC1: bit k =
+    component k > 0, component 8m in bit 7 of byte m; nsamp % 4 == 0)."""
+    a = np.asarray(iq, np.int16)
+    if a.ndim < 2 or a.shape[-1] != 2:
+        raise ValueError("iq of shape (..., nsamp, 2) wanted, got %r" % (a.shape,))
+    f, shift = (fmt & OUT_FORMAT_MASK) >> 8, (fmt & OUT_SHIFT_MASK) >> 12
+    if fmt >> 16 or f > 2 or (shift and f != 1):
+        raise ValueError("unknown output format 0x%x" % fmt)
+    if f == 0:
+        return a.copy()
+    if f == 1:
+        return np.clip(a.astype(np.int32) >> shift, -128, 127).astype(np.int8)
+    if a.shape[-2] % 4:
+        raise ValueError("1-bit output needs nsamp % 4 == 0")
+    bits = (a > 0).reshape(a.shape[:-2] + (a.shape[-2] * 2,))
+    return np.packbits(bits, axis=-1, bitorder="big")
 
 
 def block_digest_host(iq):

@@ -503,6 +503,9 @@ struct gpsbb {
     uint32_t *d_ca = nullptr;
     uint32_t *d_status = nullptr;
     unsigned long long *d_hz = nullptr;
+    unsigned long long *d_clip = nullptr; /* GPSBB_INFO_SC8_CLIPPED: the packing kernels add their saturated components here */
+    unsigned char *d_pack = nullptr;      /* device scratch of a packed fill / gpsbb_device_pack, kept between calls */
+    size_t pack_cap = 0;
     int last_hip = 0;
     gpsbb_batch *scratch = nullptr;
     unsigned char *h_bounce = nullptr; /* pinned: a fill whose iq_out lies partly in a registered range is copied through here */
@@ -768,6 +771,13 @@ extern "C" int gpsbb_get_info(gpsbb_t *h, int what, uint64_t *out)
         *out = v;
         return GPSBB_OK;
     }
+    case GPSBB_INFO_SC8_CLIPPED: {
+        HIPCHK(h, hipSetDevice(h->device));
+        unsigned long long v = 0;
+        HIPCHK(h, hipMemcpy(&v, h->d_clip, 8, hipMemcpyDeviceToHost));
+        *out = v;
+        return GPSBB_OK;
+    }
     case GPSBB_INFO_CHAIN_ON_DEVICE:
         *out = (uint64_t)h->last_chain_dev;
         return GPSBB_OK;
@@ -850,6 +860,10 @@ extern "C" void gpsbb_destroy(gpsbb_t *h)
         (void)hipFree(h->d_status);
     if (h->d_hz)
         (void)hipFree(h->d_hz);
+    if (h->d_clip)
+        (void)hipFree(h->d_clip);
+    if (h->d_pack)
+        (void)hipFree(h->d_pack);
     if (h->d_digest.p)
         (void)hipFree(h->d_digest.p);
     delete h->pool;
@@ -967,12 +981,14 @@ extern "C" int gpsbb_create(gpsbb_t **out, int device)
     if ((e = hipMalloc((void **)&h->d_ca, ca.size() * 4)) != hipSuccess) return fail(e);
     if ((e = hipMalloc((void **)&h->d_status, 4)) != hipSuccess) return fail(e);
     if ((e = hipMalloc((void **)&h->d_hz, 64)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc((void **)&h->d_clip, 8)) != hipSuccess) return fail(e);
     if ((e = hipMemcpy(h->d_tabs, tabs, sizeof tabs, hipMemcpyHostToDevice)) != hipSuccess) return fail(e);
     if ((e = hipMemcpy(h->d_ca, ca.data(), ca.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail(e);
     if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return fail(e); /* (the tables are there before any non-blocking stream runs) */
     h->h_ca = ca;
     if ((e = zero_now(h, h->d_status, 4)) != hipSuccess) return fail(e);
     if ((e = zero_now(h, h->d_hz, 64)) != hipSuccess) return fail(e);
+    if ((e = zero_now(h, h->d_clip, 8)) != hipSuccess) return fail(e);
     /* k_synth carves ~76 KB of dynamic LDS per workgroup: above the 64 KB default limit */
     if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_synth), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)sizeof(SynthLds))) != hipSuccess) return fail(e);
@@ -1613,7 +1629,7 @@ extern "C" void gpsbb_batch_destroy(gpsbb_batch_t *b)
 extern "C" int gpsbb_batch_create(gpsbb_t *h, const gpsbb_chan_t *ch, int nblocks, int nch, double delt,
                                   int nsamp, unsigned flags, gpsbb_batch_t **out)
 {
-    if (!h || !out)
+    if (!h || !out || (flags & (GPSBB_OUT_FORMAT_MASK | GPSBB_OUT_SHIFT_MASK))) /* a batch's output stays in HBM, as int16 */
         return GPSBB_E_BADARG;
     *out = nullptr;
     HIPCHK(h, hipSetDevice(h->device));
@@ -2487,7 +2503,80 @@ __global__ void k_fill_tail(const gpsbb_chan_state_t *end, const uint32_t *statu
         *host_status = *status;
 }
 
-static int fill_block_finish(gpsbb_t *h, gpsbb_batch *b, int nch, int nsamp, int16_t *iq_out, gpsbb_chan_state_t *end_state)
+/* ---- output formats (GPSBB_OUT_*) ---- */
+
+/* The output format of `flags`: 0 = SC16, PACK_SC8 (with *shift), PACK_SC1; -1 for an unknown format, a shift on anything but SC8,
+ * bits above the shift, SC1 with nsamp % 4 != 0 (GPSBB_E_BADARG).  The bits below the format are the caller's business. */
+static int out_format(unsigned flags, long nsamp, int *shift)
+{
+    const unsigned f = (flags & GPSBB_OUT_FORMAT_MASK) >> 8, sh = (flags & GPSBB_OUT_SHIFT_MASK) >> 12;
+    *shift = (int)sh;
+    if ((flags >> 16) || nsamp < 1 || f > 2 || (sh && f != 1) || (f == 2 && nsamp % 4))
+        return -1;
+    return f == 1 ? PACK_SC8 : (f == 2 ? PACK_SC1 : 0);
+}
+
+static size_t out_block_bytes(int fmt, size_t nsamp) { return fmt == PACK_SC8 ? nsamp * 2 : (fmt == PACK_SC1 ? nsamp / 4 : nsamp * 4); }
+
+extern "C" long gpsbb_out_bytes(unsigned flags, long nsamp)
+{
+    int shift;
+    const int fmt = out_format(flags, nsamp, &shift);
+    return fmt < 0 ? GPSBB_E_BADARG : (long)out_block_bytes(fmt, (size_t)nsamp);
+}
+
+/* Enqueue the packing of n int16 components at src (device memory) into dst (device memory, or host memory the device can write:
+ * pinned, registered) on `stream`.  Returns at once, like the int16 gather (k_gather_to_host): the same grid. */
+static hipError_t pack_launch(gpsbb *h, int fmt, int shift, const int16_t *src, void *dst, size_t n, hipStream_t stream)
+{
+    const int gwg = (int)GPSBB_KNOB_LONG("GPSBB_GATHER_WGS", 32);
+    if (fmt == PACK_SC8)
+        hipLaunchKernelGGL(k_pack_iq<PACK_SC8>, dim3(gwg), dim3(256), 0, stream, src, (unsigned char *)dst, n, shift, h->d_clip);
+    else
+        hipLaunchKernelGGL(k_pack_iq<PACK_SC1>, dim3(gwg), dim3(256), 0, stream, src, (unsigned char *)dst, n, shift, h->d_clip);
+    return hipGetLastError();
+}
+
+static hipError_t pack_reserve(gpsbb *h, size_t bytes)
+{
+    if (bytes <= h->pack_cap)
+        return hipSuccess;
+    if (h->d_pack)
+        (void)hipFree(h->d_pack);
+    h->d_pack = nullptr;
+    h->pack_cap = 0;
+    const hipError_t e = hipMalloc((void **)&h->d_pack, bytes);
+    if (e == hipSuccess)
+        h->pack_cap = bytes;
+    return e;
+}
+
+extern "C" int gpsbb_device_pack(gpsbb_t *h, const int16_t *d_iq, long nblocks, int nsamp, unsigned flags, void *host_dst)
+{
+    int shift;
+    const int fmt = out_format(flags, nsamp, &shift);
+    if (!h || !d_iq || !host_dst || nblocks < 1 || nsamp < 1 || fmt < 0 || (flags & 0xffu))
+        return GPSBB_E_BADARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int rc = gpsbb_sync(h); /* as gpsbb_device_digest: whatever the handle was rendering into d_iq is there */
+    if (rc != GPSBB_OK)
+        return rc;
+    const size_t bytes = (size_t)nblocks * out_block_bytes(fmt, (size_t)nsamp);
+    if (fmt == 0) {
+        HIPCHK(h, hipMemcpy(host_dst, d_iq, bytes, hipMemcpyDeviceToHost));
+        return GPSBB_OK;
+    }
+    HIPCHK(h, pack_reserve(h, bytes));
+    HIPCHK(h, pack_launch(h, fmt, shift, d_iq, h->d_pack, (size_t)nblocks * (size_t)nsamp * 2, h->s_compute));
+    HIPCHK(h, hipMemcpyAsync(host_dst, h->d_pack, bytes, hipMemcpyDeviceToHost, h->s_compute));
+    HIPCHK(h, hipStreamSynchronize(h->s_compute));
+    return GPSBB_OK;
+}
+
+/* iq_out: where the fill's bytes go on the host (nullptr: the device wrote them already); src: where they are in device memory
+ * (the render, or its packed form); bytes: how many */
+static int fill_block_finish(gpsbb_t *h, gpsbb_batch *b, int nch, int nsamp, int16_t *iq_out, gpsbb_chan_state_t *end_state,
+                             const void *src, size_t bytes)
 {
     const size_t end_bytes = (size_t)GPSBB_MAX_CHAN * sizeof(gpsbb_chan_state_t);
     if (!h->h_fill)
@@ -2509,29 +2598,29 @@ static int fill_block_finish(gpsbb_t *h, gpsbb_batch *b, int nch, int nsamp, int
      * registration pinned is one the runtime's copy refuses (hipErrorInvalidValue): through a pinned buffer of the handle's then */
     bool bounce = false;
     if (iq_out) {
-        const uintptr_t page = 4096, a = (uintptr_t)iq_out, e = a + (size_t)nsamp * 4;
+        const uintptr_t page = 4096, a = (uintptr_t)iq_out, e = a + bytes;
         for (const gpsbb::HostReg &r : h->host_regs) {
             const uintptr_t ra = (uintptr_t)r.host & ~(page - 1), re = ((uintptr_t)r.host + r.bytes + page - 1) & ~(page - 1);
             bounce = bounce || (a < re && ra < e);
         }
     }
     if (bounce) {
-        if (h->bounce_cap < (size_t)nsamp * 4) {
+        if (h->bounce_cap < bytes) {
             if (h->h_bounce)
                 (void)hipHostFree(h->h_bounce);
             h->h_bounce = nullptr;
             h->bounce_cap = 0;
-            HIPCHK(h, hipHostMalloc((void **)&h->h_bounce, (size_t)nsamp * 4, hipHostMallocDefault));
-            h->bounce_cap = (size_t)nsamp * 4;
+            HIPCHK(h, hipHostMalloc((void **)&h->h_bounce, bytes, hipHostMallocDefault));
+            h->bounce_cap = bytes;
         }
-        HIPCHK(h, hipMemcpyAsync(h->h_bounce, b->last_iq, (size_t)nsamp * 4, hipMemcpyDeviceToHost, cs));
+        HIPCHK(h, hipMemcpyAsync(h->h_bounce, src, bytes, hipMemcpyDeviceToHost, cs));
     } else if (iq_out) {
-        HIPCHK(h, hipMemcpyAsync(iq_out, b->last_iq, (size_t)nsamp * 4, hipMemcpyDeviceToHost, cs));
+        HIPCHK(h, hipMemcpyAsync(iq_out, src, bytes, hipMemcpyDeviceToHost, cs));
     }
     PUSH_MARK("iq copy");
     HIPCHK(h, hipStreamSynchronize(cs));
     if (bounce)
-        memcpy(iq_out, h->h_bounce, (size_t)nsamp * 4);
+        memcpy(iq_out, h->h_bounce, bytes);
     if (end_state)
         memcpy(end_state, h->h_fill, (size_t)nch * sizeof(gpsbb_chan_state_t));
     if (*st) {
@@ -2595,8 +2684,11 @@ extern "C" int gpsbb_fill_block_ex(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, 
             return GPSBB_E_NOMEM;
     }
     gpsbb_batch *b = h->scratch;
-    if (flags & ~GPSBB_FIXED_CARRIER & ~GPSBB_CHAIN_CARRIER)
+    int shift;
+    const int fmt = out_format(flags, nsamp, &shift);
+    if ((flags & 0xffu & ~GPSBB_FIXED_CARRIER & ~GPSBB_CHAIN_CARRIER) || fmt < 0)
         return GPSBB_E_BADARG;
+    const size_t out_bytes = out_block_bytes(fmt, (size_t)nsamp);
     g_push_trace.start();
     b->one_stream = GPSBB_KNOB_LONG("GPSBB_FILL_ONE_STREAM", 1) != 0;
     int rc = batch_setup(b, ch, 1, nch, delt, nsamp, flags & GPSBB_FIXED_CARRIER, b->one_stream ? h->s_compute : h->s_seed);
@@ -2608,16 +2700,28 @@ extern "C" int gpsbb_fill_block_ex(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, 
     int16_t *direct = nullptr;
     for (const gpsbb::HostReg &r : h->host_regs) {
         const char *q = reinterpret_cast<const char *>(iq_out);
-        if (q >= r.host && (size_t)(q - r.host) <= r.bytes && (size_t)nsamp * 4 <= r.bytes - (size_t)(q - r.host)) {
+        if (q >= r.host && (size_t)(q - r.host) <= r.bytes && out_bytes <= r.bytes - (size_t)(q - r.host)) {
             direct = reinterpret_cast<int16_t *>(r.dev + (q - r.host));
             break;
         }
     }
-    rc = gpsbb_batch_run(b, direct);
+    /* a packed format: rendered into the handle's buffer, then packed on the same stream — straight into the registered buffer, or
+     * into device scratch that is copied out as the int16 block would be */
+    rc = gpsbb_batch_run(b, fmt ? nullptr : direct);
     if (rc != GPSBB_OK)
         return rc;
     PUSH_MARK("launches");
-    rc = fill_block_finish(h, b, nch, nsamp, direct ? nullptr : iq_out, end_state);
+    const void *src = b->last_iq;
+    if (fmt) {
+        void *dst = direct;
+        if (!dst) {
+            HIPCHK(h, pack_reserve(h, out_bytes));
+            dst = h->d_pack;
+            src = h->d_pack;
+        }
+        HIPCHK(h, pack_launch(h, fmt, shift, b->last_iq, dst, (size_t)nsamp * 2, b->last_cs));
+    }
+    rc = fill_block_finish(h, b, nch, nsamp, direct ? nullptr : iq_out, end_state, src, out_bytes);
     g_push_trace.end();
     return rc;
 }
@@ -2709,6 +2813,7 @@ struct gpsbb_stream {
     int nch = 0, nsamp = 0, bps = 0, depth = 0;
     double delt = 0.0;
     unsigned flags = 0;
+    int fmt = 0, shift = 0; /* output format of the host gather (GPSBB_OUT_*: 0 int16, PACK_SC8, PACK_SC1) */
     struct Slot {
         gpsbb_batch *batch = nullptr;
         int16_t *h_iq = nullptr;            /* pinned */
@@ -2768,7 +2873,11 @@ extern "C" int gpsbb_stream_create(gpsbb_t *h, int nch, double delt, int nsamp, 
                                    int depth, unsigned flags, gpsbb_stream_t **out)
 {
     if (!h || !out || nch < 1 || nch > GPSBB_MAX_CHAN || nsamp < 1 || blocks_per_slot < 1 || depth < 2 ||
-        depth > 64 || !(delt > 0.0) || (flags & ~(GPSBB_CHAIN_CARRIER | GPSBB_FIXED_CARRIER | GPSBB_STREAM_DEVICE_ONLY)))
+        depth > 64 || !(delt > 0.0) || (flags & 0xffu & ~(GPSBB_CHAIN_CARRIER | GPSBB_FIXED_CARRIER | GPSBB_STREAM_DEVICE_ONLY)))
+        return GPSBB_E_BADARG;
+    int shift;
+    const int fmt = out_format(flags, nsamp, &shift);
+    if (fmt < 0 || (fmt && (flags & GPSBB_STREAM_DEVICE_ONLY))) /* the slots in HBM stay int16 */
         return GPSBB_E_BADARG;
     *out = nullptr;
     HIPCHK(h, hipSetDevice(h->device));
@@ -2782,8 +2891,11 @@ extern "C" int gpsbb_stream_create(gpsbb_t *h, int nch, double delt, int nsamp, 
     s->depth = depth;
     s->delt = delt;
     s->flags = flags;
+    s->fmt = fmt;
+    s->shift = shift;
     s->slots.resize(depth);
     const size_t iq_bytes = (size_t)blocks_per_slot * nsamp * 4;
+    const size_t host_bytes = (size_t)blocks_per_slot * out_block_bytes(fmt, (size_t)nsamp);
     const size_t end_bytes = (size_t)blocks_per_slot * nch * sizeof(gpsbb_chan_state_t);
     for (auto &sl : s->slots) {
         sl.batch = batch_new(h);
@@ -2793,7 +2905,7 @@ extern "C" int gpsbb_stream_create(gpsbb_t *h, int nch, double delt, int nsamp, 
         if (e == hipSuccess) sl.batch->max_sets = 1; /* consecutive pushes use different slots: one table set each */
         if (e == hipSuccess) e = (hipError_t)sl.batch->d_iq.reserve(iq_bytes / 2);
         if (e == hipSuccess && !(flags & GPSBB_STREAM_DEVICE_ONLY))
-            e = hipHostMalloc((void **)&sl.h_iq, iq_bytes, hipHostMallocDefault);
+            e = hipHostMalloc((void **)&sl.h_iq, host_bytes, hipHostMallocDefault);
         if (e == hipSuccess) e = hipHostMalloc((void **)&sl.h_end, end_bytes + 32, hipHostMallocDefault); /* + the status word */
         if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.computed, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming);
@@ -3038,7 +3150,10 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
     if (sl.h_iq) {
         const bool sdma = GPSBB_KNOB_SET("GPSBB_GATHER_SDMA"); /* experiment: the runtime's copy instead */
         const int gwg = (int)GPSBB_KNOB_LONG("GPSBB_GATHER_WGS", 32);
-        if (sdma) {
+        if (s->fmt) {
+            /* packed on the way out: the same launch that returns at once, fewer bytes over the bus */
+            HIPCHK(h, pack_launch(h, s->fmt, s->shift, b->d_iq.p, sl.h_iq, (size_t)s->bps * s->nsamp * 2, cs));
+        } else if (sdma) {
             HIPCHK(h, hipMemcpyAsync(sl.h_iq, b->d_iq.p, (size_t)s->bps * s->nsamp * 4, hipMemcpyDeviceToHost, cs));
         } else {
             hipLaunchKernelGGL(k_gather_to_host, dim3(gwg), dim3(256), 0, cs, (const gather_u32x4 *)b->d_iq.p, (gather_u32x4 *)sl.h_iq,

@@ -1384,6 +1384,125 @@ __global__ __launch_bounds__(256) void k_gather_to_host(const gather_u32x4 *__re
     }
 }
 
+/* The gather of int16 I/Q into one of the smaller output formats (include/gpsbb.h GPSBB_OUT_SC8 / GPSBB_OUT_SC1), packed on the way
+ * out: the same job as k_gather_to_host — into pinned or registered host memory, a launch that returns at once — or into device
+ * memory (gpsbb_device_pack).  The slot is one flat stream of n components I0, Q0, I1, Q1 ... (blocks are contiguous and SC1 asks
+ * for nsamp % 4 == 0, so packing the slot as one stream packs every block on its own).
+ *   SC8:  byte k = clamp(v[k] >> shift, -128, 127) (arithmetic shift); the saturated components are counted into *clip.
+ *   SC1:  bit k = v[k] > 0, byte m = components 8m .. 8m+7 with 8m in bit 7.
+ * A workgroup takes PACK_CHUNK components per round: 8 loads of 16 bytes per lane, each load of the workgroup 4 KB contiguous.  SC8
+ * stores 8 bytes per lane per load (a wavefront 512 contiguous bytes); SC1 makes one byte per lane per load, which would leave a
+ * wavefront's bytes spread over 8 stores, so they are transposed through LDS and stored as 8 contiguous bytes per lane as well.
+ * A source that is not 16-byte aligned or a destination not 8-byte aligned takes a plain per-byte loop (same bytes). */
+constexpr int PACK_SC8 = 1, PACK_SC1 = 2;
+constexpr int PACK_UNITS = 2048;             /* 16-byte loads per workgroup per round */
+constexpr size_t PACK_CHUNK = PACK_UNITS * 8; /* components per workgroup per round */
+typedef unsigned int pack_u32x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ uint32_t pack_sc8(int v, int shift, uint32_t &clip)
+{
+    const int s = v >> shift;
+    const int c = min(max(s, -128), 127);
+    clip += c != s;
+    return (uint32_t)c & 0xffu;
+}
+/* 4 components (two I/Q words) -> 4 SC8 bytes, in memory order */
+__device__ __forceinline__ uint32_t pack_sc8_word(uint32_t a, uint32_t b, int shift, uint32_t &clip)
+{
+    return pack_sc8((int)(a << 16) >> 16, shift, clip) | pack_sc8((int)a >> 16, shift, clip) << 8 |
+           pack_sc8((int)(b << 16) >> 16, shift, clip) << 16 | pack_sc8((int)b >> 16, shift, clip) << 24;
+}
+/* 8 components (16 bytes) -> one SC1 byte, component 0 in bit 7 */
+__device__ __forceinline__ uint32_t pack_sc1(gather_u32x4 q)
+{
+    const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+    uint32_t r = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        r |= (uint32_t)((int)(w[k] << 16) > 0) << (7 - 2 * k) | (uint32_t)((int)w[k] > 0x0000ffff) << (6 - 2 * k);
+    return r;
+}
+
+template <int FMT>
+__global__ __launch_bounds__(256) void k_pack_iq(const int16_t *__restrict__ src, unsigned char *__restrict__ dst, size_t n, int shift,
+                                                 unsigned long long *__restrict__ clip)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char t1[FMT == PACK_SC1 ? PACK_UNITS : 16];
+    __shared__ uint32_t wsum[4];
+    const int tid = (int)threadIdx.x;
+    uint32_t cl = 0;
+    const size_t nunits = n / 8; /* whole 16-byte loads; SC1: n % 8 == 0 */
+    if ((((uintptr_t)src & 15) | ((uintptr_t)dst & 7)) == 0) {
+        const gather_u32x4 *__restrict__ sv = reinterpret_cast<const gather_u32x4 *>(src);
+        const size_t nchunk = (nunits + PACK_UNITS - 1) / PACK_UNITS;
+        for (size_t c = blockIdx.x; c < nchunk; c += gridDim.x) {
+            const size_t u0 = c * PACK_UNITS + (size_t)tid;
+            gather_u32x4 v[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++)
+                if (u0 + (size_t)u * 256 < nunits)
+                    v[u] = __builtin_nontemporal_load(sv + u0 + (size_t)u * 256);
+            if (FMT == PACK_SC8) {
+#pragma unroll
+                for (int u = 0; u < 8; u++)
+                    if (u0 + (size_t)u * 256 < nunits) {
+                        pack_u32x2 o;
+                        o.x = pack_sc8_word(v[u].x, v[u].y, shift, cl);
+                        o.y = pack_sc8_word(v[u].z, v[u].w, shift, cl);
+                        __builtin_nontemporal_store(o, reinterpret_cast<pack_u32x2 *>(dst) + u0 + (size_t)u * 256);
+                    }
+            } else {
+#pragma unroll
+                for (int u = 0; u < 8; u++)
+                    if (u0 + (size_t)u * 256 < nunits)
+                        t1[u * 256 + tid] = (unsigned char)pack_sc1(v[u]);
+                __syncthreads();
+                /* bytes [8 tid, 8 tid + 8) of the round: the ones that exist */
+                const size_t b0 = c * PACK_UNITS + 8 * (size_t)tid;
+                if (b0 + 8 <= nunits) {
+                    const pack_u32x2 o = *reinterpret_cast<const pack_u32x2 *>(t1 + 8 * tid);
+                    __builtin_nontemporal_store(o, reinterpret_cast<pack_u32x2 *>(dst + b0));
+                } else {
+                    for (size_t b = b0; b < nunits; b++)
+                        dst[b] = t1[b - c * PACK_UNITS];
+                }
+                __syncthreads();
+            }
+        }
+        /* SC8: the last n % 8 components of a ragged slot */
+        if (FMT == PACK_SC8 && blockIdx.x == 0 && (size_t)tid < n - nunits * 8) {
+            const size_t k = nunits * 8 + (size_t)tid;
+            dst[k] = (unsigned char)pack_sc8(src[k], shift, cl);
+        }
+    } else {
+        const size_t nout = FMT == PACK_SC8 ? n : nunits;
+        for (size_t k = (size_t)blockIdx.x * 256 + (size_t)tid; k < nout; k += (size_t)gridDim.x * 256) {
+            if (FMT == PACK_SC8) {
+                dst[k] = (unsigned char)pack_sc8(src[k], shift, cl);
+            } else {
+                uint32_t r = 0;
+                for (int j = 0; j < 8; j++)
+                    r |= (uint32_t)(src[8 * k + (size_t)j] > 0) << (7 - j);
+                dst[k] = (unsigned char)r;
+            }
+        }
+    }
+    if (FMT == PACK_SC8) {
+        /* the saturated components: reduced per wavefront, one atomic per workgroup */
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1)
+            cl += (uint32_t)__shfl_down((int)cl, off);
+        if ((tid & 63) == 0)
+            wsum[tid >> 6] = cl;
+        __syncthreads();
+        if (tid == 0) {
+            const unsigned long long t = (unsigned long long)wsum[0] + wsum[1] + wsum[2] + wsum[3];
+            if (t)
+                atomicAdd(clip, t);
+        }
+    }
+}
+
 /* One 64-bit digest per block of int16 I/Q pairs in device memory (gpsbb_device_digest): the sum over the block's samples j of
  * pair_j * m_j modulo 2^64, m_j = (j * DIGEST_STEP + DIGEST_ODD) mod 2^32 — an odd weight per position, so one changed sample
  * changes the sum and two samples swapped do; order-independent as a sum, so that any partition of the block over lanes gives

@@ -514,7 +514,8 @@ void shard_main(gpsbb_node *n, Shard *sp)
     int rc = gpsbb_create(&s.h, s.device);
     if (rc == GPSBB_OK) {
         const unsigned sf = GPSBB_CHAIN_CARRIER | ((c.flags & GPSBB_NODE_FIXED_CARRIER) ? GPSBB_FIXED_CARRIER : 0u) |
-                            ((c.flags & GPSBB_NODE_DEVICE_ONLY) ? GPSBB_STREAM_DEVICE_ONLY : 0u);
+                            ((c.flags & GPSBB_NODE_DEVICE_ONLY) ? GPSBB_STREAM_DEVICE_ONLY : 0u) |
+                            (c.flags & (GPSBB_OUT_FORMAT_MASK | GPSBB_OUT_SHIFT_MASK));
         rc = gpsbb_stream_create(s.h, c.nch, c.delt, c.nsamp, c.blocks_per_slot, c.depth, sf, &s.st);
     }
     s.create_rc = rc;
@@ -564,7 +565,8 @@ void shard_main(gpsbb_node *n, Shard *sp)
                     int rc2 = gpsbb_create(&s.h, s.device);
                     if (rc2 == GPSBB_OK) {
                         const unsigned sf = GPSBB_CHAIN_CARRIER | ((c.flags & GPSBB_NODE_FIXED_CARRIER) ? GPSBB_FIXED_CARRIER : 0u) |
-                                            ((c.flags & GPSBB_NODE_DEVICE_ONLY) ? GPSBB_STREAM_DEVICE_ONLY : 0u);
+                                            ((c.flags & GPSBB_NODE_DEVICE_ONLY) ? GPSBB_STREAM_DEVICE_ONLY : 0u) |
+                                            (c.flags & (GPSBB_OUT_FORMAT_MASK | GPSBB_OUT_SHIFT_MASK));
                         rc2 = gpsbb_stream_create(s.h, c.nch, c.delt, c.nsamp, c.blocks_per_slot, c.depth, sf, &s.st);
                     }
                     s.create_rc = rc2; /* (not GPSBB_OK: every later run reports it — the node is then only good for gpsbb_node_destroy) */
@@ -591,7 +593,13 @@ extern "C" int gpsbb_node_create(gpsbb_node_t **out, const gpsbb_node_config_t *
 {
     if (!out || !cfg || cfg->nshards < 1 || cfg->nshards > GPSBB_NODE_MAX_SHARDS || cfg->nch < 1 || cfg->nch > GPSBB_MAX_CHAN ||
         !(cfg->delt > 0.0) || cfg->nsamp < 1 || cfg->blocks_per_slot < 1 || cfg->depth < 2 ||
-        (cfg->flags & ~(GPSBB_NODE_INDEXED | GPSBB_NODE_CONCURRENT | GPSBB_NODE_DEVICE_ONLY | GPSBB_NODE_NO_AFFINITY | GPSBB_NODE_FIXED_CARRIER | GPSBB_NODE_INTERLEAVED | GPSBB_NODE_DIGESTS)))
+        (cfg->flags & 0xffu & ~(GPSBB_NODE_INDEXED | GPSBB_NODE_CONCURRENT | GPSBB_NODE_DEVICE_ONLY | GPSBB_NODE_NO_AFFINITY | GPSBB_NODE_FIXED_CARRIER | GPSBB_NODE_INTERLEAVED | GPSBB_NODE_DIGESTS)))
+        return GPSBB_E_BADARG;
+    /* an output format (GPSBB_OUT_*, include/gpsbb.h) packs what the host rings gather: valid for the stream, not with rings in HBM */
+    if ((cfg->flags & (GPSBB_OUT_FORMAT_MASK | GPSBB_OUT_SHIFT_MASK)) &&
+        (gpsbb_out_bytes(cfg->flags, cfg->nsamp) < 0 || (cfg->flags & GPSBB_NODE_DEVICE_ONLY)))
+        return GPSBB_E_BADARG;
+    if (cfg->flags >> 16)
         return GPSBB_E_BADARG;
     *out = nullptr;
     gpsbb_node *n = new (std::nothrow) gpsbb_node;
@@ -951,7 +959,7 @@ extern "C" int gpsbb_node_slot_digests(gpsbb_node_t *n, int shard, uint64_t *dig
 
 extern "C" int gpsbb_node_run_digest(gpsbb_node_t *n, const gpsbb_chan_t *ch, long nblocks, uint64_t *digests, gpsbb_node_stats_t *stats)
 {
-    if (!n || !digests)
+    if (!n || !digests || (n->cfg.flags & GPSBB_OUT_FORMAT_MASK)) /* the digests are of int16 blocks: a packed host ring has none */
         return GPSBB_E_BADARG;
     n->digest_out = digests;
     const int rc = gpsbb_node_run(n, ch, nblocks, digest_sink, n, stats);

@@ -3,7 +3,7 @@
  * reference's own program structure (front end -> fill -> TX hand-off) and the fill done on an MI355X.
  *
  *   gpsbb-sim -e nav.14n [-l lat,lon,h | -c x,y,z | -u motion.csv] [-t Y/M/D,h:m:s] [-T] [-i] [-3]
- *             [-s fs_hz] [-d seconds] [-n samples_per_block] [-N channels] [-g gpu] [-F] -o out.bin
+ *             [-s fs_hz] [-d seconds] [-n samples_per_block] [-N channels] [-g gpu] [-F] [-b 1|8|16] [-q shift] -o out.bin
  *
  * Options mirror the reference's (plutogpssim.c:1991-2012, 2296-2390) where they concern the signal; the
  * Pluto-specific ones (-A -B -U -N host) have no meaning here.  -n defaults to 300000, the reference's
@@ -28,6 +28,10 @@
  * kernel buffers: 4 by default; a push only blocks when all are taken).  -R: do not register iq_buff with the library
  * (gpsbb_host_register: by default the drop-in call renders straight into it; with -R it ends with a copy, as for any buffer).  -k a,b,c keeps only those blocks in the
  * output file (a soak of hours of signal need not write them all).
+ * -b 8 / -b 1 write gps-sdr-sim's smaller sample formats on every path (include/gpsbb.h GPSBB_OUT_*): 8-bit interleaved I/Q,
+ * clamp(v >> shift, -128, 127) with -q shift (default 5: no component of the reference's tables clips at 16 channels; gps-sdr-sim
+ * fixes 4 and wraps), or 1-bit packed I/Q (v > 0, MSB first; nsamp % 4 == 0).  The GPU packs them on their way to the host, so
+ * fewer bytes cross the bus.  The single-handle paths report how many 8-bit components saturated.  Default -b 16: int16 as ever.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -44,17 +48,17 @@
 struct node_out {
     FILE *f;
     int fd;         /* >= 0: pwrite at the block's offset */
-    size_t nsamp;
+    size_t bytes;   /* per block, in the output format */
 };
 
 static int node_sink(void *user, const int16_t *iq, long first_block, int nblocks, int shard)
 {
     struct node_out *o = user;
     (void)shard;
-    const size_t bytes = (size_t)nblocks * o->nsamp * 4;
+    const size_t bytes = (size_t)nblocks * o->bytes;
     if (o->fd >= 0) {
         const char *p = (const char *)iq;
-        off_t at = (off_t)first_block * (off_t)o->nsamp * 4;
+        off_t at = (off_t)first_block * (off_t)o->bytes;
         size_t left = bytes;
         while (left) {
             const ssize_t w = pwrite(o->fd, p, left, at);
@@ -72,6 +76,7 @@ static int node_sink(void *user, const int16_t *iq, long first_block, int nblock
 /* the paced consumer of the soak: what sits behind the TX surface instead of the Pluto */
 struct paced_sink {
     FILE *f;
+    size_t bytes;           /* of a block, in the output format */
     long period_ns;         /* 0: not paced */
     int queue;              /* blocks the device holds: libiio hands a pushed buffer to the kernel and blocks only when all
                                of its kernel buffers (4 by default) are queued, so the generator may run that far ahead */
@@ -119,7 +124,8 @@ static int paced_push(void *user, const int16_t *iq, size_t nsamp)
     int want = p->nkeep == 0;
     for (int i = 0; i < p->nkeep; i++)
         want = want || p->keep[i] == k;
-    if (want && fwrite(iq, 4, nsamp, p->f) != nsamp)
+    (void)nsamp;
+    if (want && fwrite(iq, 1, p->bytes, p->f) != p->bytes)
         return -1;
     return 0;
 }
@@ -130,11 +136,20 @@ static int cmp_double(const void *a, const void *b)
     return x < y ? -1 : (x > y ? 1 : 0);
 }
 
+/* -b 8: how many components the shift let saturate (gpsbb_fill_block_ex / the ring's packing kernel counted them) */
+static void report_clipped(gpsbb_t *bb, int bits)
+{
+    uint64_t clipped = 0;
+    if (bits == 8 && gpsbb_get_info(bb, GPSBB_INFO_SC8_CLIPPED, &clipped) == GPSBB_OK)
+        fprintf(stderr, "8-bit components clipped: %llu\n", (unsigned long long)clipped);
+}
+
 static void usage(void)
 {
     fprintf(stderr, "usage: gpsbb-sim -e nav [-l lat,lon,h|-c x,y,z|-u motion.csv] [-t Y/M/D,h:m:s] [-T] [-i] [-3]\n"
                     "                 [-s fs_hz] [-d seconds] [-n samples_per_block] [-N channels] [-g gpu[,gpu...]] [-F] [-G shards [-C [-I]]]\n"
-                    "                 [-P usec_per_block] [-Q device_queue_blocks] [-S stats.json] [-k keep,blocks] -o out.bin\n");
+                    "                 [-P usec_per_block] [-Q device_queue_blocks] [-S stats.json] [-k keep,blocks] [-b 1|8|16] [-q shift]\n"
+                    "                 -o out.bin\n");
 }
 
 int main(int argc, char **argv)
@@ -159,8 +174,9 @@ int main(int argc, char **argv)
     paced.queue = 4; /* libiio's default number of kernel buffers */
     const char *stats_path = NULL;
     const char *out_path = NULL;
+    int bits = 16, shift = 5;
 
-    while ((opt = getopt(argc, argv, "e:u:c:l:s:Tt:in:N:d:o:g:3FG:P:S:k:Q:ICR")) != -1) {
+    while ((opt = getopt(argc, argv, "e:u:c:l:s:Tt:in:N:d:o:g:3FG:P:S:k:Q:ICRb:q:")) != -1) {
         switch (opt) {
         case 'e': cfg.navfile = optarg; break;
         case 'u': cfg.motion_file = optarg; break;
@@ -211,15 +227,24 @@ int main(int argc, char **argv)
             break;
         case 'F': fast = 1; break;
         case 'R': no_register = 1; break; /* the drop-in call copies into iq_buff instead of rendering straight into it */
+        case 'b': bits = atoi(optarg); break;
+        case 'q': shift = atoi(optarg); break;
         default: usage(); return 1;
         }
     }
-    if (!cfg.navfile || !out_path) {
+    if (!cfg.navfile || !out_path || (bits != 1 && bits != 8 && bits != 16) || shift < 0 || shift > 15) {
         usage();
         return 1;
     }
     if (nsamp == 0)
         nsamp = fs_hz / 10;
+    /* the output format, the same bits on every path (fill, stream, node) */
+    const unsigned oflags = bits == 8 ? GPSBB_OUT_SC8(shift) : (bits == 1 ? GPSBB_OUT_SC1 : GPSBB_OUT_SC16);
+    const long obytes = gpsbb_out_bytes(oflags, nsamp);
+    if (obytes < 0) {
+        fprintf(stderr, "ERROR: -b %d needs a block of a multiple of 4 samples (-n)\n", bits);
+        return 1;
+    }
     const double delt = 1.0 / (double)fs_hz; /* c:2397 */
     const long nblocks = (long)(duration * 10.0 + 0.5);
 
@@ -251,13 +276,13 @@ int main(int argc, char **argv)
             fprintf(stderr, "ERROR: cannot allocate the descriptors / open %s\n", out_path);
             return 1;
         }
-        struct node_out o = {fo, -1, (size_t)nsamp};
+        struct node_out o = {fo, -1, (size_t)obytes};
         unsigned nflags = interleaved ? GPSBB_NODE_INTERLEAVED : 0u; /* -C -I: the slots go round the GPUs (an ordered output scales) */
-        if (fo != stdout && ftruncate(fileno(fo), (off_t)nblocks * nsamp * 4) == 0) {
+        if (fo != stdout && ftruncate(fileno(fo), (off_t)nblocks * obytes) == 0) {
             o.fd = fileno(fo); /* a regular file: blocks are placed by index as they complete, from every shard at once */
             nflags |= GPSBB_NODE_INDEXED | GPSBB_NODE_CONCURRENT;
         }
-        gpsbb_node_config_t nc = {nshards, devs, cfg.max_chan, delt, (int)nsamp, bps, 3, nflags};
+        gpsbb_node_config_t nc = {nshards, devs, cfg.max_chan, delt, (int)nsamp, bps, 3, nflags | oflags};
         gpsbb_node_t *node = NULL;
         gpsbb_node_stats_t ns;
         rc = gpsbb_node_create(&node, &nc);
@@ -308,7 +333,7 @@ int main(int argc, char **argv)
         const int bps = nblocks < 16 ? (int)(nblocks > 0 ? nblocks : 1) : 16, depth = 3;
         gpsbb_stream_t *st = NULL;
         gpsbb_chan_t *slot = malloc((size_t)bps * cfg.max_chan * sizeof *slot);
-        rc = slot ? gpsbb_stream_create(bb, cfg.max_chan, delt, (int)nsamp, bps, depth, GPSBB_CHAIN_CARRIER, &st) : GPSBB_E_NOMEM;
+        rc = slot ? gpsbb_stream_create(bb, cfg.max_chan, delt, (int)nsamp, bps, depth, GPSBB_CHAIN_CARRIER | oflags, &st) : GPSBB_E_NOMEM;
         long pushed = 0, written = 0;
         while (rc == GPSBB_OK && slot && written < nblocks) {
             while (rc == GPSBB_OK && pushed < nblocks && gpsbb_stream_pending(st) < depth) {
@@ -322,7 +347,7 @@ int main(int argc, char **argv)
                 rc = gpsbb_stream_pop(st, &iq, NULL);
             if (rc == GPSBB_OK) {
                 const long n = nblocks - written < bps ? nblocks - written : bps;
-                if (fwrite(iq, 4, (size_t)n * (size_t)nsamp, fout) != (size_t)n * (size_t)nsamp)
+                if (fwrite(iq, (size_t)obytes, (size_t)n, fout) != (size_t)n)
                     rc = GPSBB_E_STATE;
                 written += n;
             }
@@ -331,6 +356,7 @@ int main(int argc, char **argv)
             fprintf(stderr, "ERROR: streaming: %s\n", gpsbb_strerror(rc));
         if (st)
             gpsbb_stream_destroy(st);
+        report_clipped(bb, bits);
         free(slot);
         if (fout != stdout)
             fclose(fout);
@@ -342,6 +368,7 @@ int main(int argc, char **argv)
 
     gpsbb_tx_t *tx = NULL;
     paced.f = fout;
+    paced.bytes = (size_t)obytes;
     double *lat_ms = calloc((size_t)(nblocks > 0 ? nblocks : 1), sizeof *lat_ms);
     if (gpsbb_tx_create(&tx, (size_t)nsamp, paced_push, &paced) != 0 || !lat_ms) {
         fprintf(stderr, "ERROR: cannot start the TX surface\n");
@@ -379,12 +406,12 @@ int main(int argc, char **argv)
             iq_registered = iq; /* iq_buff is one allocation for the run (c:2604): rendered into directly from here on */
         struct timespec ta, tb;
         clock_gettime(CLOCK_MONOTONIC, &ta);
-        rc = gpsbb_fill_block(bb, ch, cfg.max_chan, delt, (int)nsamp, iq, st); /* replaces c:2690-2756 */
+        rc = gpsbb_fill_block_ex(bb, ch, cfg.max_chan, delt, (int)nsamp, oflags, iq, st); /* replaces c:2690-2756 */
         clock_gettime(CLOCK_MONOTONIC, &tb);
         lat_ms[blk] = ts_ms(&tb, &ta);
         if (rc != GPSBB_OK) { /* the buffer holds no valid block: it must not reach the sink */
             gpsbb_tx_cancel(tx);
-            fprintf(stderr, "ERROR: gpsbb_fill_block: %s\n", gpsbb_strerror(rc));
+            fprintf(stderr, "ERROR: gpsbb_fill_block_ex: %s\n", gpsbb_strerror(rc));
             break;
         }
         const int stopped = gpsbb_tx_end(tx);                       /* c:2757-2759 */
@@ -430,6 +457,7 @@ int main(int argc, char **argv)
     if (gpsbb_get_hazards(bb, &hz, 0) == GPSBB_OK && (hz.itable_512 || hz.dwrd_oob))
         fprintf(stderr, "note: latent out-of-bounds cases of the reference hit: table %llu, nav words %llu\n",
                 (unsigned long long)hz.itable_512, (unsigned long long)hz.dwrd_oob);
+    report_clipped(bb, bits);
     gpsbb_destroy(bb);
     gpsfe_close(fe);
     fprintf(stderr, "%ld blocks of %ld samples written\n", blk, nsamp);
