@@ -599,6 +599,7 @@ struct gpsbb_batch {
     bool one_stream = false;       /* the drop-in call's scratch batch: upload, pre-pass and synthesis on the synthesis stream (a
                                       hop from stream to stream is 16 us of nothing for a call that takes 150: gpsbb_fill_block_ex) */
     int nblocks = 0, nch = 0, nsamp = 0, ntiles = 0;
+    int st_log2 = 0, nstates = 0;  /* the state granule of the tile tables (BatchDev::st_log2, ev_state_log2) */
     double delt = 0.0;
     unsigned flags = 0;
     uint64_t total_rows = 0;
@@ -923,6 +924,9 @@ static hipError_t zero_now(gpsbb *h, void *ptr, size_t bytes)
     return e != hipSuccess ? e : hipStreamSynchronize(h->s_upload);
 }
 
+typedef void (*EvKernelFn)(BatchDev, int16_t *);
+static EvKernelFn ev_kernel(int g, bool digest);
+
 extern "C" int gpsbb_create(gpsbb_t **out, int device)
 {
     if (!out)
@@ -992,10 +996,12 @@ extern "C" int gpsbb_create(gpsbb_t **out, int device)
     /* k_synth carves ~76 KB of dynamic LDS per workgroup: above the 64 KB default limit */
     if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_synth), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)sizeof(SynthLds))) != hipSuccess) return fail(e);
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_synth_ev), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)sizeof(EvLdsLean) + EV_PICK_LDS)) != hipSuccess) return fail(e);
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_synth_ev_digest), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)sizeof(EvLdsLean) + EV_PICK_LDS)) != hipSuccess) return fail(e);
+    for (int g = 0; g <= EV_STATE_LOG2_MAX; g++) {
+        if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(ev_kernel(g, false)), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)sizeof(EvLdsLean) + EV_PICK_LDS)) != hipSuccess) return fail(e);
+        if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(ev_kernel(g, true)), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)sizeof(EvLdsLean) + EV_PICK_LDS)) != hipSuccess) return fail(e);
+    }
     if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_synth_ev_dense), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)sizeof(EvLds) + EV_PICK_LDS)) != hipSuccess) return fail(e);
     if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_synth_ev_fixed), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1021,6 +1027,47 @@ static void chain_carrier_host(const gpsbb_chan_t *ch, int nblocks, int nch, dou
                                int nthreads, ChainCarry *carry);
 
 static bool host_seeding_wanted(const gpsbb_batch *b);
+
+/* the instance of k_lap_pass2 (kind NCO_CODE / NCO_CARR) or k_lap_pass2_2 (kind -1: both) for a state granule of 2^g tiles */
+typedef void (*LapKernelFn)(BatchDev, LapDev);
+static LapKernelFn lap_pass2_kernel(int kind, bool wide, int g)
+{
+#define GPSBB_P2(W) {{k_lap_pass2<NCO_CODE, W, 0>, k_lap_pass2<NCO_CODE, W, 1>, k_lap_pass2<NCO_CODE, W, 2>}, \
+                     {k_lap_pass2<NCO_CARR, W, 0>, k_lap_pass2<NCO_CARR, W, 1>, k_lap_pass2<NCO_CARR, W, 2>}, \
+                     {k_lap_pass2_2<W, 0>, k_lap_pass2_2<W, 1>, k_lap_pass2_2<W, 2>}}
+    static const LapKernelFn k[2][3][EV_STATE_LOG2_MAX + 1] = {GPSBB_P2(false), GPSBB_P2(true)};
+#undef GPSBB_P2
+    static_assert(NCO_CODE == 0 && NCO_CARR == 1, "lap_pass2_kernel's table");
+    return k[wide ? 1 : 0][kind < 0 ? 2 : kind][g];
+}
+
+/* the instance of k_synth_ev / k_synth_ev_digest for a state granule of 2^g tiles */
+static EvKernelFn ev_kernel(int g, bool digest)
+{
+    static const EvKernelFn k[2][EV_STATE_LOG2_MAX + 1] = {{k_synth_ev<0>, k_synth_ev<1>, k_synth_ev<2>},
+                                                            {k_synth_ev_digest<0>, k_synth_ev_digest<1>, k_synth_ev_digest<2>}};
+    return k[digest ? 1 : 0][g];
+}
+
+/* The state granule of a batch's tile tables (BatchDev::st_log2): one exact state per 2^g tiles where the breakpoint kernel proper
+ * (k_synth_ev, k_synth_ev_digest) renders behind the lap-parallel pre-pass; one per tile for every other kernel and pre-pass.  The
+ * tile anchors k_synth_ev derives from a granule's state (gpsbb_events.hip.h) assume at most one code roll-over from a granule's
+ * first sample to its last: 1023 chips take at least 15 800 samples at the steps that kernel admits (sc < 1 / 15.5), against 4 096
+ * — checked here for every channel all the same. */
+static int ev_state_log2(const gpsbb_batch *b, bool fixed)
+{
+    if (!b->ev || !b->laps || b->ev_dense || fixed)
+        return 0;
+    long g = GPSBB_KNOB_LONG("GPSBB_EV_STATE_LOG2", GPSBB_EV_STATE_LOG2);
+    g = g < 0 ? 0 : (g > EV_STATE_LOG2_MAX ? EV_STATE_LOG2_MAX : g);
+    while (g > 0 && !ev_granule_fits((int)g)) /* (a variant build's smaller budget: make r3budgets) */
+        g--;
+    const size_t nbc = (size_t)b->nblocks * b->nch;
+    for (size_t k = 0; k < nbc && g > 0; k++)
+        if (!(b->h_evc[k].sc * (double)((TILE << g) + SPT) < (double)(GPSBB_CA_LEN - 1)))
+            return 0;
+    return (int)g;
+}
 
 /* upload `bytes` from pageable `src` through the batch's pinned arena (grown at the start of a set-up) */
 /* GPSBB_PUSH_TRACE=<ms>: where the host time of a stream push goes, printed for pushes that take longer than <ms> */
@@ -1146,6 +1193,8 @@ static int batch_setup(gpsbb_batch *b, const gpsbb_chan_t *ch, int nblocks, int 
      * decline, e.g. a rate only the per-sample kernel renders) */
     b->host_seed = !lap_ok && !b->d_carry && host_seeding_wanted(b);
     b->laps = lap_ok;
+    b->st_log2 = ev_state_log2(b, fixed);
+    b->nstates = (b->ntiles + (1 << b->st_log2) - 1) >> b->st_log2;
     const bool chained = !fixed && (flags & GPSBB_CHAIN_CARRIER) && (nblocks > 1 || b->d_carry);
     b->chain_dev = chained && h->opt_chain_where != 1 && !b->host_seed;
     b->chain_fix_seq = h->opt_chain_where == 2;
@@ -1256,8 +1305,8 @@ static int batch_setup(gpsbb_batch *b, const gpsbb_chan_t *ch, int nblocks, int 
     for (int set = 0; set < b->nsets; set++) {
         HIPCHK(h, (hipError_t)b->d_end[set].reserve(nbc));
         if (b->ev) {
-            HIPCHK(h, (hipError_t)b->d_tile_x[set].reserve(2 * nbc * (size_t)b->ntiles));
-            HIPCHK(h, (hipError_t)b->d_tile_nav[set].reserve(nbc * (size_t)b->ntiles));
+            HIPCHK(h, (hipError_t)b->d_tile_x[set].reserve(2 * nbc * (size_t)b->nstates));
+            HIPCHK(h, (hipError_t)b->d_tile_nav[set].reserve(nbc * (size_t)b->nstates));
             HIPCHK(h, (hipError_t)b->d_rows[set].reserve(b->total_rows + 4, b->max_sets == 1 ? (size_t)(b->total_rows / 2) : 0));
             HIPCHK(h, (hipError_t)b->d_row_cnt[set].reserve(nbc + nvbc));
         } else {
@@ -1917,6 +1966,8 @@ static BatchDev batch_dev(const gpsbb_batch *b, int set)
     p.nch = b->nch;
     p.nsamp = b->nsamp;
     p.ntiles = b->ntiles;
+    p.st_log2 = b->st_log2;
+    p.nstates = b->nstates;
     p.delt = b->delt;
     p.flags = b->flags;
     p.tabs = b->h->d_tabs;
@@ -2094,20 +2145,14 @@ static int batch_launch(gpsbb_batch *b, int16_t *d_iq)
             hipLaunchKernelGGL(k_lap_plan2, dim3(2 * b->nch), dim3(64), 0, ss, p, L);
             hipLaunchKernelGGL(k_lap_pass1_2, dim3(cc + ck), dim3(LAP_WG), 0, ss, p, L);
             hipLaunchKernelGGL(k_lap_scan2, dim3(2 * b->nch), dim3(64), 0, ss, p, L);
-            if (wide)
-                hipLaunchKernelGGL(k_lap_pass2_2<true>, dim3(cc + ck), dim3(LAP_WG), 0, ss, p, L);
-            else
-                hipLaunchKernelGGL(k_lap_pass2_2<false>, dim3(cc + ck), dim3(LAP_WG), 0, ss, p, L);
+            hipLaunchKernelGGL(lap_pass2_kernel(-1, wide, p.st_log2), dim3(cc + ck), dim3(LAP_WG), 0, ss, p, L);
             hipLaunchKernelGGL(k_lap_repair2, dim3(2 * b->nch), dim3(64), 0, ss, p, L);
             HIPCHK(h, carry_done());
         } else {
             hipLaunchKernelGGL(k_lap_plan<NCO_CODE>, dim3(b->nch), dim3(64), 0, ss, p, L);
             hipLaunchKernelGGL(k_lap_pass1<NCO_CODE>, dim3(cc), dim3(LAP_WG), 0, ss, p, L);
             hipLaunchKernelGGL(k_lap_scan<NCO_CODE>, dim3(b->nch), dim3(64), 0, ss, p, L);
-            if (wide)
-                hipLaunchKernelGGL((k_lap_pass2<NCO_CODE, true>), dim3(cc), dim3(LAP_WG), 0, ss, p, L);
-            else
-                hipLaunchKernelGGL((k_lap_pass2<NCO_CODE, false>), dim3(cc), dim3(LAP_WG), 0, ss, p, L);
+            hipLaunchKernelGGL(lap_pass2_kernel(NCO_CODE, wide, p.st_log2), dim3(cc), dim3(LAP_WG), 0, ss, p, L);
             hipLaunchKernelGGL(k_lap_repair<NCO_CODE>, dim3(b->nch), dim3(64), 0, ss, p, L);
             if (p.kph0) {
                 /* fixed-point carrier: no chain to walk; the plan kernel leaves the end states, the tile states are a closed form */
@@ -2118,10 +2163,7 @@ static int batch_launch(gpsbb_batch *b, int16_t *d_iq)
                 hipLaunchKernelGGL(k_lap_plan<NCO_CARR>, dim3(b->nch), dim3(64), 0, ss, p, L);
                 hipLaunchKernelGGL(k_lap_pass1<NCO_CARR>, dim3(ck), dim3(LAP_WG), 0, ss, p, L);
                 hipLaunchKernelGGL(k_lap_scan<NCO_CARR>, dim3(b->nch), dim3(64), 0, ss, p, L);
-                if (wide)
-                    hipLaunchKernelGGL((k_lap_pass2<NCO_CARR, true>), dim3(ck), dim3(LAP_WG), 0, ss, p, L);
-                else
-                    hipLaunchKernelGGL((k_lap_pass2<NCO_CARR, false>), dim3(ck), dim3(LAP_WG), 0, ss, p, L);
+                hipLaunchKernelGGL(lap_pass2_kernel(NCO_CARR, wide, p.st_log2), dim3(ck), dim3(LAP_WG), 0, ss, p, L);
                 hipLaunchKernelGGL(k_lap_repair<NCO_CARR>, dim3(b->nch), dim3(64), 0, ss, p, L);
                 HIPCHK(h, carry_done());
             }
@@ -2247,10 +2289,12 @@ static int batch_launch(gpsbb_batch *b, int16_t *d_iq)
         else if (p.kph0)
             hipLaunchKernelGGL(k_synth_ev_fixed, grid, dim3(EV_WG), sizeof(EvLdsLean) + EV_PICK_LDS, sc, p, d_iq);
         else if (b->want_digest) {
-            hipLaunchKernelGGL(k_synth_ev_digest, grid, dim3(EV_WG), sizeof(EvLdsLean) + EV_PICK_LDS, sc, p, d_iq);
+            hipLaunchKernelGGL(ev_kernel(p.st_log2, true), grid, dim3(EV_WG),
+                               sizeof(EvLdsLean) + EV_PICK_LDS, sc, p, d_iq);
             digest_fused = true;
         } else
-            hipLaunchKernelGGL(k_synth_ev, grid, dim3(EV_WG), sizeof(EvLdsLean) + EV_PICK_LDS, sc, p, d_iq);
+            hipLaunchKernelGGL(ev_kernel(p.st_log2, false), grid, dim3(EV_WG),
+                               sizeof(EvLdsLean) + EV_PICK_LDS, sc, p, d_iq);
         h->last_kernel = 2;
         h->last_chain_dev = b->chain_dev && !b->chain_indep ? 1 : 0;
     } else {
@@ -3527,6 +3571,7 @@ extern "C" int gpsbb_chain_carrier(gpsbb_t *h, const gpsbb_chan_t *ch, int nbloc
             p.nch = nch;
             p.nsamp = nsamp;
             p.ntiles = (nsamp + TILE - 1) / TILE;
+            p.nstates = p.ntiles;
             p.delt = delt;
             p.flags = GPSBB_CHAIN_CARRIER;
             p.status = c->d_status;
@@ -3604,6 +3649,7 @@ extern "C" int gpsbb_chain_carrier(gpsbb_t *h, const gpsbb_chan_t *ch, int nbloc
         p.nch = nch;
         p.nsamp = nsamp;
         p.ntiles = (nsamp + TILE - 1) / TILE;
+        p.nstates = p.ntiles;
         p.delt = delt;
         p.flags = GPSBB_CHAIN_CARRIER;
         p.status = c->d_status;
@@ -3790,10 +3836,16 @@ extern "C" int gpsbb_test_model_err(gpsbb_batch_t *b, double *maxima, unsigned l
     return GPSBB_OK;
 }
 
-/* What the pre-pass of the batch's LAST run left for the model kernels — every tile state (bit patterns), every tile's data bits,
- * every end-of-block state — as three 64-bit sums of mixed words: the lap-parallel pre-pass (its reference
+/* What the pre-pass of the batch's LAST run left for the model kernels — the tile states (bit patterns) and data bits (every tile's;
+ * for the batches k_synth_ev renders, the tiles that start a granule: below), every end-of-block state — as three 64-bit sums of mixed words: the lap-parallel pre-pass (its reference
  * states on the model or pushed far off it: GPSBB_LAP_JITTER) and the row walks must leave the same bits, whatever the IQ makes of
  * them (tools/table_check.py). */
+/* the state granule the batch's tables were built with (BatchDev::st_log2), or a negative error */
+extern "C" int gpsbb_test_state_log2(gpsbb_batch_t *b)
+{
+    return b ? b->st_log2 : GPSBB_E_BADARG;
+}
+
 extern "C" int gpsbb_test_table_digest(gpsbb_batch_t *b, unsigned long long out[3])
 {
     if (!b || !out || !b->ran || !b->ev)
@@ -3804,7 +3856,14 @@ extern "C" int gpsbb_test_table_digest(gpsbb_batch_t *b, unsigned long long out[
         return rc;
     const BatchDev p = batch_dev(b, b->last_set);
     auto mix = [](unsigned long long z) { z ^= z >> 31; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 29; return z; };
-    const size_t nx = (size_t)b->nblocks * 2 * b->nch * b->ntiles, nn = (size_t)b->nblocks * b->nch * b->ntiles, ne = (size_t)b->nblocks * b->nch;
+    const size_t nst = (size_t)b->nstates;
+    const size_t nx = (size_t)b->nblocks * 2 * b->nch * nst, nn = (size_t)b->nblocks * b->nch * nst, ne = (size_t)b->nblocks * b->nch;
+    /* The states keyed by the tile t they start: every tile's, but for a batch that k_synth_ev renders — whose tables hold one state
+     * per granule behind the lap-parallel pre-pass (BatchDev::st_log2) and one per tile behind the row walks — those of the tiles that
+     * start a granule of the size the lap-parallel pre-pass would use: the two pre-passes' tables digest alike where they agree, and
+     * every other batch's are compared tile by tile */
+    const int dg = b->ev_dense || (b->flags & GPSBB_FIXED_CARRIER) ? 0 : (int)GPSBB_KNOB_LONG("GPSBB_EV_STATE_LOG2", GPSBB_EV_STATE_LOG2);
+    const int tstep = 1 << (dg > b->st_log2 ? dg : b->st_log2);
     std::vector<unsigned long long> hx(nx);
     std::vector<uint32_t> hn(nn);
     std::vector<gpsbb_chan_state_t> he(ne);
@@ -3820,13 +3879,13 @@ extern "C" int gpsbb_test_table_digest(gpsbb_batch_t *b, unsigned long long out[
             continue;
         const size_t blk = k / (size_t)b->nch, i = k % (size_t)b->nch;
         for (int kind = 0; kind < 2; kind++)
-            for (int t = 0; t < b->ntiles; t++) {
+            for (int t = 0; t < b->ntiles; t += tstep) {
                 const size_t at = (blk * 2 * b->nch + 2 * i + kind) * (size_t)b->ntiles + t;
-                out[0] += mix(hx[at] + 0x9E3779B97F4A7C15ull * (at + 1));
+                out[0] += mix(hx[(blk * 2 * b->nch + 2 * i + kind) * nst + (t >> b->st_log2)] + 0x9E3779B97F4A7C15ull * (at + 1));
             }
-        for (int t = 0; t < b->ntiles; t++) {
+        for (int t = 0; t < b->ntiles; t += tstep) {
             const size_t at = k * (size_t)b->ntiles + t;
-            out[1] += mix((unsigned long long)(hn[at] & 3u) + 0x9E3779B97F4A7C15ull * (at + 1));
+            out[1] += mix((unsigned long long)(hn[k * nst + (t >> b->st_log2)] & 3u) + 0x9E3779B97F4A7C15ull * (at + 1));
         }
         unsigned long long w[5];
         memcpy(w, &he[k], sizeof w);

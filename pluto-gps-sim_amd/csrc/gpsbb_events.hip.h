@@ -77,6 +77,7 @@ constexpr int EV_ROW_DISCARD = 15;                 /* D row of changes that fall
  * not W rounded), and the test suite asserts realised <= W / 2 for everything tested. */
 #ifndef EV_MODEL_ERR
 #define EV_MODEL_ERR 0x1p-30
+#define GPSBB_EV_MODEL_ERR_OWN 1 /* (not a variant build's budget: make r3budgets) */
 #endif
 /* The quantities a lane tests travel in GUARD FORMAT: 2^20 + value, so that one unit in the last place is 2^-32, the
  * double's low word IS the fraction (in units of 2^-32) and the low bits of its high word ARE the integer part — index,
@@ -90,6 +91,27 @@ constexpr int EV_ROW_DISCARD = 15;                 /* D row of changes that fall
 #define EV_T_EPS 0x1p-29
 #endif
 #define EV_GUARD 0x1p+20
+
+/* The STATE GRANULE (BatchDev::st_log2, ev_state_log2 in gpsbb.hip): behind the lap-parallel pre-pass k_synth_ev gets one exact
+ * state per 2^g tiles, and the chain lanes derive the anchor of tile r of a granule as fma(r * 1024, step, granule state) in guard
+ * format (then reduced by whole periods, exactly).  Against the truth, the model of a run's first sample then stands at the end of
+ * at most G*1024 + 15 rounded additions of the reference's recurrence (each within half an ulp of a number below 1024 chips:
+ * 2^-44, i.e. 2^-12 units of 2^-32; the carrier's 2^-45 index units are smaller), plus the format's roundings: the granule state
+ * put into guard format, the anchor's fma and the run's fma, half a unit each.  G = 4: 1.004 + 1.5 = 2.5 units, under
+ * EV_MODEL_ERR's 4 — W, the danger threshold and so the exact-path rate are those of G = 1.  The default is G = 2 (0.50 + 1.5 units
+ * at most).  G = 4 measures faster, but the code model's roundings add up nearly in one direction (0.25 units over a tile against
+ * 0.27 derived), and at G = 4 the realised chip-change positions reach 0.51 W (tools/model_err.py --quick): over the W / 2 the test
+ * suite holds every budget to, so G = 4 is not the default. */
+#ifndef GPSBB_EV_STATE_LOG2
+#define GPSBB_EV_STATE_LOG2 1
+#endif
+constexpr int EV_STATE_LOG2_MAX = 2;
+static_assert(GPSBB_EV_STATE_LOG2 >= 0 && GPSBB_EV_STATE_LOG2 <= EV_STATE_LOG2_MAX, "state granule: 1, 2 or 4 tiles");
+/* does a granule of 2^g tiles keep the model inside EV_MODEL_ERR (above)?  ev_state_log2 takes no larger one */
+constexpr bool ev_granule_fits(int g) { return ((double)(TILE << g) + (double)(SPT - 1)) * 0x1p-44 + 1.5 * 0x1p-32 <= EV_MODEL_ERR; }
+#ifdef GPSBB_EV_MODEL_ERR_OWN
+static_assert(ev_granule_fits(EV_STATE_LOG2_MAX), "the model of the largest state granule must stay inside the error budget");
+#endif
 
 /* A wavefront claims its next chunk of tiles with a returning atomic.  Rounds 2 and 3 issued it in inline assembly and did not
  * wait for it until the chunk's last tile — invisible to the compiler, which is free to copy or spill a register it believes
@@ -368,6 +390,48 @@ __device__ __forceinline__ EvHalf<KC> ev_first(const LDS &L, int i, const EvK &K
     return h;
 }
 
+/* what a wavefront knows about the tile it is working on */
+struct EvTile {
+    const double *ts;      /* LDS: the tile's states (mirrored where the carrier falls) */
+    const double *tile_x;  /* global, for the exact recomputation (exact, not mirrored; chain c's at [c * stride]): sg = 0 the tile's
+                              state, sg > 0 the block's first (see ev_exact_at) */
+    int ntiles;            /* tiles of the block */
+    int wt;                /* the tile */
+    int sg;                /* the state granule (BatchDev::st_log2: a compile-time constant of the kernel) */
+    uint32_t dbits, dnext; /* bit i: channel i's data bit in force at the tile's first sample / after the next roll-over is -1 (as the
+                              model sees it: past a granule's roll-over, the bit after it, and no further roll-over in the tile) */
+};
+
+/* Where the exact recomputation of a run of tile T starts: the exact state of the tile's granule (tile_x, its stride), the data
+ * bits (bit 0: in force at the granule's first sample, bit 1: after its next roll-over) and how many samples before the tile's
+ * first it lies.  Worked out in the rare branch only, from values the kernel keeps anyway: nothing of it stays live across a tile.
+ * The tile's own bits serve: where they differ from the granule's, the code anchor has been reduced, which it is only where the
+ * truth has certainly passed the roll-over (synth_ev_body): the jump from the granule's state then counts one, and bit 0 is
+ * never looked at. */
+struct EvExactAt {
+    const double *tile_x;
+    int stride;
+    uint32_t nb;
+    int n_skip;
+};
+__device__ __forceinline__ EvExactAt ev_exact_at(const EvTile &T, int i)
+{
+    EvExactAt a;
+    if (!T.sg) {
+        a.tile_x = T.tile_x;
+        a.stride = T.ntiles;
+        a.nb = ((T.dbits >> i) & 1u) | (((T.dnext >> i) & 1u) << 1);
+        a.n_skip = 0;
+    } else {
+        const int nst = (T.ntiles + (1 << T.sg) - 1) >> T.sg, g = T.wt >> T.sg;
+        a.tile_x = T.tile_x + g;
+        a.stride = nst;
+        a.nb = ((T.dbits >> i) & 1u) | (((T.dnext >> i) & 1u) << 1);
+        a.n_skip = (T.wt & ((1 << T.sg) - 1)) * TILE;
+    }
+    return a;
+}
+
 /*
  * Second half: signs, the contribution at sample 0 (into acc0) and its changes (into D).  db / db_next: the
  * data bit in force at the tile start / after the next code roll-over as masks (0 = +1, -1 = -1; wave-uniform);
@@ -375,9 +439,8 @@ __device__ __forceinline__ EvHalf<KC> ev_first(const LDS &L, int i, const EvK &K
  */
 template <int KC, bool DF, bool FIXED, class LDS>
 __device__ __forceinline__ void ev_second(LDS &L, uint32_t &drow, int wave, int lane, int i, EvHalf<KC> &h, uint32_t db, uint32_t db_next,
-                                          unsigned long long live_mask, const EvConst *kb, const double *tile_x,
-                                          int ntiles, uint32_t nb, double off, uint32_t &acc0, unsigned long long *n_exact,
-                                          const EvFixed &fx)
+                                          unsigned long long live_mask, const EvConst *kb, const EvTile &T,
+                                          double off, uint32_t &acc0, unsigned long long *n_exact, const EvFixed &fx)
 {
     const uint32_t ma = (uint32_t)(int32_t)(int8_t)(h.ch2 & 0xffu), mb = (uint32_t)(int32_t)(int8_t)(h.ch2 >> 8);
     uint32_t m0, m1;
@@ -404,11 +467,12 @@ __device__ __forceinline__ void ev_second(LDS &L, uint32_t &drow, int wave, int 
             hc = EV_SAT_HI;
             h.A[0] = 0;
             /* ... and the exact one takes its place */
+            const EvExactAt x = ev_exact_at(T, i);
             if (FIXED) /* the accumulator at the tile's first sample */
-                acc0 += ev_exact_run_fixed(L, wave, lane, i, kb + i, tile_x, ntiles, nb, (int)off,
+                acc0 += ev_exact_run_fixed(L, wave, lane, i, kb + i, x.tile_x, x.stride, x.nb, x.n_skip + (int)off,
                                            fx.ph[i] + (uint32_t)fx.n0 * (uint32_t)fx.st[i], fx.st[i]);
             else
-                acc0 += ev_exact_run(L, wave, lane, i, kb + i, tile_x, ntiles, nb, (int)off);
+                acc0 += ev_exact_run(L, wave, lane, i, kb + i, x.tile_x, x.stride, x.nb, x.n_skip + (int)off);
             atomicAdd(n_exact, 1ull);
         }
     }
@@ -431,15 +495,6 @@ __device__ __forceinline__ void ev_second(LDS &L, uint32_t &drow, int wave, int 
     /* the chip change flips the sign: -s0*A -> s1*A = 2*s1*A more */
     ev_d_add<LDS>(drow, wave, hc, signed_by(Ax << 1, m1));
 }
-
-/* what a wavefront knows about the tile it is working on */
-struct EvTile {
-    const double *ts;     /* LDS: the tile's states (mirrored where the carrier falls) */
-    const double *tile_x; /* global: the same, exact and not mirrored (for the exact recomputation): chain c's is
-                             tile_x[c * ntiles] */
-    int ntiles;
-    uint32_t dbits, dnext; /* bit i: channel i's data bit in force / after the next roll-over is -1 */
-};
 
 /*
  * A channel whose run holds more index or chip changes than the breakpoint path takes (low sample rates: at 2.6 MS/s
@@ -478,8 +533,8 @@ __device__ __forceinline__ void ev_dense(LDS &L, int wave, int lane, int i, cons
 #pragma unroll
             for (int j = 0; j < SPT; j++)
                 v[j] = 0;
-            const uint32_t nb = ((T.dbits >> i) & 1u) | (((T.dnext >> i) & 1u) << 1);
-            acc0 += ev_exact_run(L, wave, lane, i, kb + i, T.tile_x, T.ntiles, nb, (int)off);
+            const EvExactAt x = ev_exact_at(T, i);
+            acc0 += ev_exact_run(L, wave, lane, i, kb + i, x.tile_x, x.stride, x.nb, x.n_skip + (int)off);
             atomicAdd(n_exact, 1ull);
         }
     }
@@ -505,10 +560,7 @@ __device__ __forceinline__ void ev_channels(LDS &L, uint32_t &drow, int wave, in
 #define GPSBB_EV_OUT(i, h)                                                                                             \
     {                                                                                                                  \
         const uint32_t db_ = 0u - ((T.dbits >> i) & 1u), dn_ = 0u - ((T.dnext >> i) & 1u);                             \
-        const uint32_t nb_ = ((T.dbits >> i) & 1u) | (((T.dnext >> i) & 1u) << 1);                                     \
-        ev_second<KC, DF, FIXED>(L, drow, wave, lane, i, h, db_, dn_, live_mask, kb, T.tile_x,                 \
-                          T.ntiles, nb_,                                                                               \
-                          off, acc0, n_exact, fx);                                                                     \
+        ev_second<KC, DF, FIXED>(L, drow, wave, lane, i, h, db_, dn_, live_mask, kb, T, off, acc0, n_exact, fx);       \
     }
     while (mask & (mask - 1)) { /* at least two channels left */
         const int i0 = __builtin_ctz(mask);
@@ -610,7 +662,7 @@ __device__ __forceinline__ int ev_pick_block(const BatchDev &p, uint32_t slot)
  * that the common one keeps its register count: at <= 104 VGPRs four of its wavefronts leave room on a SIMD for a
  * wavefront of the pre-pass of the next push; at 120 they do not, and a CU that hosts walk wavefronts cannot take a
  * synthesis workgroup at all (measured: 2.2 -> 2.8 ms per launch beside the pre-passes). */
-template <bool DENSE, bool FIXED = false, bool DIGEST = false>
+template <bool DENSE, bool FIXED = false, bool DIGEST = false, int SG = 0>
 __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__restrict__ iq)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -721,13 +773,15 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
     /* lane c < 2*nch holds chain c = (channel c >> 1, kind c & 1) of the tile being staged */
     const bool chain_lane = lane < nch2;
     const bool mirror = chain_lane && (lane & 1) && kb[lane >> 1].down != 0;
-    /* this lane's chain (tile-contiguous) in the tile arrays */
-    const double *__restrict__ txb = p.tile_x + (size_t)b * ntw * nch2;
+    /* this lane's chain (state-contiguous) in the state arrays: one exact state per GRANULE of 2^sg tiles (BatchDev::st_log2) */
+    constexpr int sg = SG; /* == p.st_log2 (the host launches the instance of its batch's granule) */
+    const int nst = SG ? p.nstates : ntw;
+    const double *__restrict__ txb = p.tile_x + (size_t)b * nst * nch2;
     /* (a scalar base and a 32-bit element offset per lane, not a 64-bit pointer per lane: the kernel is short of registers — what
      * it spills goes to HBM, DESIGN.md 3 — and a running pointer per lane is what the compiler spilled first) */
-    const uint32_t tx_off = (uint32_t)(chain_lane ? lane : 0) * (uint32_t)ntw;
-    const uint32_t *__restrict__ tnb = p.tile_nav + (size_t)b * p.nch * ntw;
-    const uint32_t tn_off = (uint32_t)(lane < p.nch ? lane : 0) * (uint32_t)ntw;
+    const uint32_t tx_off = (uint32_t)(chain_lane ? lane : 0) * (uint32_t)nst;
+    const uint32_t *__restrict__ tnb = p.tile_nav + (size_t)b * p.nch * nst;
+    const uint32_t tn_off = (uint32_t)(lane < p.nch ? lane : 0) * (uint32_t)nst;
     const double off = (double)(lane * SPT);
     /* this lane's chain in guard format, biased (the fixed-point carrier's index is exact: no bias, see ev_first) */
     const double guard_w = EV_GUARD + ((chain_lane && !(FIXED && (lane & 1))) ? kb[lane >> 1].W : 0.0);
@@ -755,24 +809,56 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
     double ts_v = 0.0;
     uint32_t nav_v = 0;
     if (base < ntw) {
-        ts_v = chain_lane ? txb[tx_off + (uint32_t)base] : 0.0;
-        nav_v = lane < p.nch ? tnb[tn_off + (uint32_t)base] : 0u;
+        ts_v = chain_lane ? txb[tx_off + (uint32_t)(base >> sg)] : 0.0;
+        nav_v = lane < p.nch ? tnb[tn_off + (uint32_t)(base >> sg)] : 0u;
     }
     while (base < ntw) {
         const int wt = base + pos;
+        const int r = wt & ((1 << sg) - 1); /* the tile's place in its granule */
         /* the tile's states -> this wavefront's LDS slot, its data bits -> scalar masks */
-        if (chain_lane)
-            L.tstate[wave][0][lane] = (mirror ? mirror_at - ts_v : ts_v) + guard_w; /* one rounding, half a unit of 2^-32 */
+        bool rolled_over = false; /* (the code lane of a channel whose anchor has passed its granule's roll-over) */
+        if (chain_lane) {
+            double v = (mirror ? mirror_at - ts_v : ts_v) + guard_w; /* one rounding, half a unit of 2^-32 */
+            if (sg) {
+                /* The anchor of tile r of the granule: the model r*1024 steps on (one more rounding, half a unit), reduced by whole
+                 * periods where it has passed one — exactly (an integer off a number in [2^20, 2^21) that stays there), so that index
+                 * and chip start where the LDS tables (EvLdsLean::AMP, CHIPS) expect a tile to.  A code anchor is reduced only from
+                 * chip 1024 on, a whole chip clear of the model's error: the truth has certainly had the granule's roll-over, the data
+                 * bit after it is in force, and (at most one roll-over per granule: ev_state_log2) none follows in this tile.  One in
+                 * [1023, 1024) stays as it is, and the tile is rendered as one in which the roll-over is due (chip index below
+                 * 1024 + 1040 * 0.0646 < EV_CHIP_LEN_SHORT). */
+                /* the chain's step (code: sc, carrier: |S|), read here: the kernel has no register to keep it in (its address made
+                 * opaque, so that the compiler does not keep that instead) */
+                uint32_t lane_now = (uint32_t)lane;
+                asm volatile("" : "+v"(lane_now));
+                const double st = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(kb) + (lane_now >> 1) * sizeof(EvConst) +
+                                                                    ((lane_now & 1u) ? offsetof(EvConst, S) : offsetof(EvConst, sc)));
+                v = __fma_rn((double)(r * TILE), st, v);
+                const uint32_t ip = (uint32_t)__double2hiint(v) - EV_GUARD_HI; /* the integer part */
+                const uint32_t red = (lane & 1) ? (ip & ~511u) : (ip >= (uint32_t)GPSBB_CA_LEN + 1u ? (uint32_t)GPSBB_CA_LEN : 0u);
+                v -= (double)red;
+                rolled_over = !(lane & 1) && red != 0u;
+            }
+            L.tstate[wave][0][lane] = v;
+        }
+        uint32_t nav_t = nav_v; /* the tile's data bits as the model sees them */
+        if (sg) {
+            const unsigned long long rolled = __ballot(rolled_over); /* bit 2 i: channel i */
+            if (lane < p.nch && ((rolled >> (2 * lane)) & 1ull))
+                nav_t = ((nav_v >> 1) & 1u) | (nav_v & 2u); /* past the granule's roll-over: the next bit, no further one in the tile */
+        }
         EvTile T;
         T.ts = L.tstate[wave][0];
-        T.tile_x = txb + wt;
+        T.tile_x = sg ? txb : txb + wt;
         T.ntiles = ntw;
-        T.dbits = (uint32_t)__ballot(nav_v & 1u);
-        T.dnext = (uint32_t)__ballot(nav_v & 2u);
+        T.wt = wt;
+        T.sg = sg;
+        T.dbits = (uint32_t)__ballot(nav_t & 1u);
+        T.dnext = (uint32_t)__ballot(nav_t & 2u);
         EvFixed fx;
         fx.ph = FIXED ? p.kph0 + (size_t)b * p.nch : nullptr;
         fx.st = FIXED ? p.kstep + (size_t)b * p.nch : nullptr;
-        fx.n0 = wt * TILE;
+        fx.n0 = (wt - r) * TILE;
         const uint32_t dflip = T.dbits ^ T.dnext;
         /* which tile comes next, and its states on their way */
         if (pos == 0 && lane == 0) {
@@ -786,9 +872,9 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
             next_pos = 0;
         }
         const int wt_next = next_base + next_pos;
-        if (wt_next < ntw) {
-            ts_v = chain_lane ? txb[tx_off + (uint32_t)wt_next] : 0.0;
-            nav_v = lane < p.nch ? tnb[tn_off + (uint32_t)wt_next] : 0u;
+        if (wt_next < ntw && (wt_next >> sg) != (wt >> sg)) { /* (a granule's tiles share its states) */
+            ts_v = chain_lane ? txb[tx_off + (uint32_t)(wt_next >> sg)] : 0.0;
+            nav_v = lane < p.nch ? tnb[tn_off + (uint32_t)(wt_next >> sg)] : 0u;
         }
 
         const int n0 = wt * TILE + lane * SPT;
@@ -917,14 +1003,17 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
 #else
 #define GPSBB_EV_BUDGET __attribute__((amdgpu_waves_per_eu(5, 5)))
 #endif
+/* SG: the batch's state granule (BatchDev::st_log2) */
+template <int SG>
 __global__ __launch_bounds__(EV_WG) GPSBB_EV_BUDGET void k_synth_ev(BatchDev p, int16_t *__restrict__ iq)
 {
-    synth_ev_body<false>(p, iq);
+    synth_ev_body<false, false, false, SG>(p, iq);
 }
 /* ... that also leaves every block's digest (BatchDev::digest, zeroed by the host before the launch) */
+template <int SG>
 __global__ __launch_bounds__(EV_WG) __attribute__((amdgpu_waves_per_eu(5, 5))) void k_synth_ev_digest(BatchDev p, int16_t *__restrict__ iq)
 {
-    synth_ev_body<false, false, true>(p, iq);
+    synth_ev_body<false, false, true, SG>(p, iq);
 }
 __global__ __launch_bounds__(EV_WG) void k_synth_ev_dense(BatchDev p, int16_t *__restrict__ iq)
 {

@@ -256,11 +256,14 @@ struct BatchDev {
      * chain at the first sample of every tile */
     int ev;                         /* 1: this batch runs on k_synth_ev                               */
     int ev_chunk;                   /* consecutive tiles a wavefront of k_synth_ev takes at a time     */
+    int st_log2;                    /* the STATE GRANULE: tile_x / tile_nav hold one entry per 2^st_log2 tiles (k_synth_ev /
+                                       k_synth_ev_digest behind the lap-parallel pre-pass; 0 everywhere else) */
+    int nstates;                    /* entries per chain: ceil(ntiles / 2^st_log2)                    */
     uint32_t pd_danger;             /* k_synth_pd: a model's low word below this sends the lane to the exact path (2 * PD_BAND) */
-    double *tile_x;                 /* [nblocks][2*nch][ntiles]: row 2*channel = code phase (chips), 2*channel+1 =
-                                       carrier phase * 512, at sample tile*TILE (tile-contiguous per chain: the
+    double *tile_x;                 /* [nblocks][2*nch][nstates]: row 2*channel = code phase (chips), 2*channel+1 =
+                                       carrier phase * 512, at sample g*(TILE << st_log2) (state-contiguous per chain: the
                                        pre-pass writes it coalesced, k_synth_ev reads it through the L2)  */
-    uint32_t *tile_nav;             /* [nblocks][nch][ntiles]: bit 0 = the data bit in force is -1, bit 1 = the data
+    uint32_t *tile_nav;             /* [nblocks][nch][nstates]: bit 0 = the data bit in force is -1, bit 1 = the data
                                        bit after the next code roll-over is -1                         */
     const EvConst *evc;             /* [nblocks*nch]                                                  */
     int chain_dev;                  /* 1: GPSBB_CHAIN_CARRIER is resolved on the device (k_chain_prefix / k_chain_fix) */

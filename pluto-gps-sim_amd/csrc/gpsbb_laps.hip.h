@@ -455,19 +455,24 @@ __device__ __forceinline__ void lap_enter_block(const BatchDev &p, const LapDev 
  * consecutive words, in 32- and 16-byte pieces — instead of one word with every tile state: stored one by one, four bytes at a
  * time, they were more than half of what the pre-pass writes to HBM (a sector of 32 bytes per word: WRITE_SIZE).  Tiles
  * [w.navt, the first tile whose first sample is n_excl or later). */
-template <int KIND>
+/* SG (here and in lap_emit_row, lap_run, lap_walk): the batch's state granule BatchDev::st_log2 as a constant (pass 2: what
+ * costs registers as a variable shift), or -1: read it from p (the repair) */
+template <int KIND, int SG = -1>
 __device__ __forceinline__ void lap_nav_out(const BatchDev &p, int i, LapLane<KIND> &w, bool on, int n_excl, uint32_t bits)
 {
+    /* samples per state (BatchDev::st_log2): 2^tsl */
+    const uint32_t tsl = (uint32_t)__builtin_ctz(TILE) + (uint32_t)(SG >= 0 ? SG : p.st_log2);
+    const int TS = 1 << tsl;
     typedef uint32_t lap_u4 __attribute__((ext_vector_type(4)));
     const int t = w.navt;
-    int t_end = (int)(((uint32_t)n_excl + (uint32_t)(TILE - 1)) / (uint32_t)TILE);
-    t_end = t_end < p.ntiles ? t_end : p.ntiles;
+    int t_end = (int)(((uint32_t)n_excl + (uint32_t)(TS - 1)) >> tsl);
+    t_end = t_end < p.nstates ? t_end : p.nstates;
     int cnt = on && t_end > t ? t_end - t : 0;
     if (cnt > 0)
         w.navt = t_end;
     if (!__ballot(cnt > 0))
         return;
-    uint32_t *pn = p.tile_nav + ((size_t)w.b * (size_t)p.nch + i) * (size_t)p.ntiles + t;
+    uint32_t *pn = p.tile_nav + ((size_t)w.b * (size_t)p.nch + i) * (size_t)p.nstates + t;
     const lap_u4 b4 = lap_u4{bits, bits, bits, bits};
     while (__ballot(cnt > 0)) {
         const bool oct = cnt >= 8 && (reinterpret_cast<uintptr_t>(pn) & 31u) == 0;
@@ -488,17 +493,20 @@ __device__ __forceinline__ void lap_nav_out(const BatchDev &p, int i, LapLane<KI
     }
 }
 
-template <int KIND, bool WIDE>
+template <int KIND, bool WIDE, int SG = -1>
 __device__ __forceinline__ void lap_emit_row(const BatchDev &p, int i, bool on, int b, int n, int k, double x, double S, uint32_t bits)
 {
-    int t = (int)(((uint32_t)n + (uint32_t)(TILE - 1)) / (uint32_t)TILE);
-    int t_end = (int)((uint32_t)(n + k) / (uint32_t)TILE) + 1; /* one past the last tile whose first sample is in the row */
-    t_end = t_end < p.ntiles ? t_end : p.ntiles;
+    /* samples per state (BatchDev::st_log2): states at n = 0, TS, 2 TS, ... */
+    const uint32_t tsl = (uint32_t)__builtin_ctz(TILE) + (uint32_t)(SG >= 0 ? SG : p.st_log2);
+    const int TS = 1 << tsl;
+    int t = (int)(((uint32_t)n + (uint32_t)(TS - 1)) >> tsl);
+    int t_end = (int)((uint32_t)(n + k) >> tsl) + 1; /* one past the last tile whose first sample is in the row */
+    t_end = t_end < p.nstates ? t_end : p.nstates;
     int cnt = on ? t_end - t : 0;
     cnt = cnt < 0 ? 0 : cnt;
     if (!__ballot(cnt > 0))
         return;
-    double *__restrict__ tx = p.tile_x + ((size_t)b * (2 * (size_t)p.nch) + 2 * i + KIND) * (size_t)p.ntiles;
+    double *__restrict__ tx = p.tile_x + ((size_t)b * (2 * (size_t)p.nch) + 2 * i + KIND) * (size_t)p.nstates;
     /* A turn of the loop below costs the wavefront the same whether one lane or all of them have a tile to write: fine where the
      * lanes' rows are alike (neighbouring laps of one chain: each has its dozen tiles).  A FEW lanes with very long rows — a slow
      * chain, hundreds of tiles in one row, beside lanes that have none — are written by the whole wavefront instead, a lane per
@@ -514,10 +522,10 @@ __device__ __forceinline__ void lap_emit_row(const BatchDev &p, int i, bool on, 
             const double xx = bits_f64(readlane_u64(f64_bits(x), src)), SS = bits_f64(readlane_u64(f64_bits(S), src));
             const uint32_t bb = (uint32_t)__builtin_amdgcn_readlane((int)bits, src);
             double *txs = (double *)readlane_u64((uint64_t)tx, src);
-            uint32_t *tns = (uint32_t *)readlane_u64((uint64_t)(p.tile_nav + ((size_t)b * (size_t)p.nch + i) * (size_t)p.ntiles), src);
+            uint32_t *tns = (uint32_t *)readlane_u64((uint64_t)(p.tile_nav + ((size_t)b * (size_t)p.nch + i) * (size_t)p.nstates), src);
             for (int q = lane; q < c; q += 64) {
                 const int tt = t0 + q;
-                const double v = __fma_rn((double)(tt * TILE - nn), SS, xx);
+                const double v = __fma_rn((double)((tt << tsl) - nn), SS, xx);
                 txs[tt] = KIND == NCO_CARR ? mul_rn(v, 512.0) : v;
                 if (!WIDE && KIND == NCO_CODE)
                     tns[tt] = bb;
@@ -527,13 +535,13 @@ __device__ __forceinline__ void lap_emit_row(const BatchDev &p, int i, bool on, 
         }
     }
     /* the state at the row's first tile start, then 1024 steps further per tile: both exact (states of the row: fma(j, S, x) is) */
-    double v = __fma_rn((double)(t * TILE - n), S, x);
-    const double dv = mul_rn(S, (double)TILE); /* exact: a power of two */
+    double v = __fma_rn((double)((t << tsl) - n), S, x);
+    const double dv = mul_rn(S, (double)TS); /* exact: a power of two */
     double *px = tx + t;
     if (!WIDE) {
         /* (geometries whose rows hold a tile at most — the reference's 2.6 MS/s: a code period is 2.5 tiles — keep the plain loop:
          * there the pieces below find nothing to join and cost pass 2 its eighth wavefront per SIMD: - 1.8 % on that leg) */
-        uint32_t *pn = p.tile_nav + ((size_t)b * (size_t)p.nch + i) * (size_t)p.ntiles + t;
+        uint32_t *pn = p.tile_nav + ((size_t)b * (size_t)p.nch + i) * (size_t)p.nstates + t;
         for (; __ballot(cnt > 0); cnt--) {
             if (cnt > 0) {
                 *px = KIND == NCO_CARR ? mul_rn(v, 512.0) : v;
@@ -594,9 +602,11 @@ __device__ __forceinline__ void lap_emit_row(const BatchDev &p, int i, bool on, 
  * (LAP_OUT_LATE), or stands at its block's last sample + 1 (outcome 0, n == nsamp: the caller's).
  */
 constexpr int LAP_BURST = 16;
-template <int KIND, bool SNEG, bool EMIT, bool TIES, bool WIDE>
+template <int KIND, bool SNEG, bool EMIT, bool TIES, bool WIDE, int SG = -1>
 __device__ __forceinline__ void lap_run(const BatchDev &p, int i, LapLane<KIND> &w, const bool was, const int L_burst)
 {
+    const uint32_t tsl = (uint32_t)__builtin_ctz(TILE) + (uint32_t)(SG >= 0 ? SG : p.st_log2);
+    const int TS = 1 << tsl;
     constexpr int TOPEX = LapK<KIND>::TOPEX;
     constexpr int TOP = KIND == NCO_CARR ? 1022 : 1023 + 9; /* the top binade: [0.5, 1) / [512, 1024) */
     const double s = w.s;
@@ -618,9 +628,9 @@ __device__ __forceinline__ void lap_run(const BatchDev &p, int i, LapLane<KIND> 
             if (__ballot(still)) {
                 const int k = still && nmax > n ? nmax - n : 0;
                 if (EMIT && p.tile_x) {
-                    const int t0 = (int)(((uint32_t)n + (uint32_t)(TILE - 1)) / (uint32_t)TILE);
-                    if (__ballot(still && t0 * TILE <= n + k && t0 < p.ntiles))
-                        lap_emit_row<KIND, WIDE>(p, i, still, w.b, n, k, x, 0.0, w.bits);
+                    const int t0 = (int)(((uint32_t)n + (uint32_t)(TS - 1)) >> tsl);
+                    if (__ballot(still && (t0 << tsl) <= n + k && t0 < p.nstates))
+                        lap_emit_row<KIND, WIDE, SG>(p, i, still, w.b, n, k, x, 0.0, w.bits);
                 }
                 if (still) {
                     n += k;
@@ -646,8 +656,8 @@ __device__ __forceinline__ void lap_run(const BatchDev &p, int i, LapLane<KIND> 
          * stragglers costs the others more than it saves them: it takes 1 / L_burst of the lanes still walking.  (A negative
          * state has its sign in ex: d is then large.) */
         if (burst_ok && __ballot(go && d < 4)) {
-            const int r = n & (TILE - 1);
-            const bool clear = n + LAP_BURST <= nmax && (!(EMIT && p.tile_x) || (r != 0 && r + LAP_BURST <= TILE));
+            const int r = n & (TS - 1);
+            const bool clear = n + LAP_BURST <= nmax && (!(EMIT && p.tile_x) || (r != 0 && r + LAP_BURST <= TS));
             bool bq = go && d < 4 && clear;
             if (SNEG)
                 bq = bq && x >= -s; /* (a state below one step wraps with the next: the turn's business) */
@@ -720,9 +730,9 @@ __device__ __forceinline__ void lap_run(const BatchDev &p, int i, LapLane<KIND> 
         const int n1 = n + k;
         if (EMIT && p.tile_x) { /* (no tile states where only the chain is wanted: gpsbb_chain_carrier) */
             /* does a tile start inside the row (samples n .. n1)? */
-            const int t0 = (int)(((uint32_t)n + (uint32_t)(TILE - 1)) / (uint32_t)TILE);
-            if (__ballot(go && t0 * TILE <= n1 && t0 < p.ntiles))
-                lap_emit_row<KIND, WIDE>(p, i, go, w.b, n, k, x, S, w.bits);
+            const int t0 = (int)(((uint32_t)n + (uint32_t)(TS - 1)) >> tsl);
+            if (__ballot(go && (t0 << tsl) <= n1 && t0 < p.nstates))
+                lap_emit_row<KIND, WIDE, SG>(p, i, go, w.b, n, k, x, S, w.bits);
         }
         const bool step = go && n1 < nmax;
         double x2 = add_rn(x1, s);
@@ -773,7 +783,7 @@ __device__ __forceinline__ void lap_run(const BatchDev &p, int i, LapLane<KIND> 
                 w.so = 0;
             }
             if (KIND == NCO_CODE && EMIT && WIDE && p.tile_x)
-                lap_nav_out<KIND>(p, i, w, wrapped, n1 + 1, w.bits); /* the period's tiles: up to the one the next period's first sample starts */
+                lap_nav_out<KIND, SG>(p, i, w, wrapped, n1 + 1, w.bits); /* the period's tiles: up to the one the next period's first sample starts */
             if (KIND == NCO_CODE && wrapped) {
                 /* a code period is over (c:2714-2733): the data bits of the next one, should the lane go on into it — and its
                  * roll-over's data-bit fetch (past dwrd[59]?  the fetch of the roll-over that ENDS the lane's walk is the next lane's
@@ -849,9 +859,11 @@ __device__ __forceinline__ void lap_block_end(const BatchDev &p, int i, LapLane<
  * Walk every active lane from (b, n, x) to the end of its lap or of its territory, whichever comes first.  The lanes of the
  * wavefront belong to one channel i.  EMIT: leave tile states, end-of-block states; count hazards either way (w.hz).
  */
-template <int KIND, bool EMIT, bool TIES, bool WIDE = false>
+template <int KIND, bool EMIT, bool TIES, bool WIDE = false, int SG = -1>
 __device__ __forceinline__ void lap_walk(const BatchDev &p, const LapDev &L, int i, LapLane<KIND> &w)
 {
+    const uint32_t tsl = (uint32_t)__builtin_ctz(TILE) + (uint32_t)(SG >= 0 ? SG : p.st_log2);
+    const int TS = 1 << tsl;
     w.outcome = 0;
     w.so = 0;
     w.acc = lap_identity();
@@ -868,7 +880,7 @@ __device__ __forceinline__ void lap_walk(const BatchDev &p, const LapDev &L, int
             /* the roll-over that started this lap fetched a data bit (c:2732) if it started a bit: past dwrd[59]? */
             if (w.fresh && w.jc > 0 && c % 20u == 0u && c / 600u >= (uint32_t)GPSBB_N_DWRD)
                 w.hz++;
-            w.navt = (int32_t)(((uint32_t)w.n + (uint32_t)(TILE - 1)) / (uint32_t)TILE);
+            w.navt = (int32_t)(((uint32_t)w.n + (uint32_t)(TS - 1)) >> tsl);
         }
         if (w.n >= w.nmax && w.b == w.bt) { /* an empty territory (the plan put two laps on one sample) */
             w.outcome = LAP_OUT_LATE;
@@ -881,9 +893,9 @@ __device__ __forceinline__ void lap_walk(const BatchDev &p, const LapDev &L, int
          * it normally runs only one of the two) */
         const bool rise = w.active && !w.neg, fall = w.active && w.neg;
         if (__ballot(rise))
-            lap_run<KIND, false, EMIT, TIES, WIDE>(p, i, w, rise, L.burst);
+            lap_run<KIND, false, EMIT, TIES, WIDE, SG>(p, i, w, rise, L.burst);
         if (KIND == NCO_CARR && __ballot(fall))
-            lap_run<KIND, true, EMIT, TIES, WIDE>(p, i, w, fall, L.burst);
+            lap_run<KIND, true, EMIT, TIES, WIDE, SG>(p, i, w, fall, L.burst);
         /* lanes at the last sample + 1 of their block: the end state; the chain's next block, or the walk ends */
         const bool at_end = w.active && w.n >= p.nsamp;
         if (__ballot(at_end)) {
@@ -924,7 +936,7 @@ __device__ __forceinline__ void lap_walk(const BatchDev &p, const LapDev &L, int
         w.active = w.active && w.outcome == 0;
     }
     if (KIND == NCO_CODE && EMIT && WIDE && p.tile_x)
-        lap_nav_out<KIND>(p, i, w, walked, w.n, w.bits); /* what is left of the lane's last period */
+        lap_nav_out<KIND, SG>(p, i, w, walked, w.n, w.bits); /* what is left of the lane's last period */
 }
 
 /* ---- k_lap_plan ---------------------------------------------------------------------------------------------- */
@@ -1433,7 +1445,7 @@ __device__ __forceinline__ void lap_scan_body(const BatchDev &p, const LapDev &L
     }
 }
 
-template <int KIND, bool WIDE = false>
+template <int KIND, bool WIDE = false, int SG = 0>
 __device__ __forceinline__ void lap_pass2_body(const BatchDev &p, const LapDev &L, const uint32_t bx)
 {
     __shared__ LapPassLds sh;
@@ -1497,7 +1509,7 @@ __device__ __forceinline__ void lap_pass2_body(const BatchDev &p, const LapDev &
     const double x0 = head ? rec.A : __fma_rn(m, lap_unit<KIND>(), rec.A);
     const double x_next = __fma_rn(m_after, lap_unit<KIND>(), lap_next(rec.A, sh.A[wave + 1], lane));
     LapLane<KIND> w = lap_lane<KIND>(mine, x0, rec.b, rec.n0, lap_jc_of<KIND>(p, L, i, r, rec.b), has_next, nb, nn0);
-    lap_walk<KIND, true, false, WIDE>(p, L, i, w);
+    lap_walk<KIND, true, false, WIDE, SG>(p, L, i, w);
     if (mine) {
         bool ok;
         if (has_next)
@@ -1763,8 +1775,9 @@ template <int KIND>
 __global__ __launch_bounds__(64) void k_lap_scan(BatchDev p, LapDev L) { lap_scan_body<KIND>(p, L, blockIdx.x); }
 /* (WIDE: the tile states go out in 32- / 16-byte pieces where a row holds them, a code period's data bits when it is over —
  * lap_emit_row, lap_nav_out: geometries with several tiles per lap, >= 8 MS/s; the tables are the same bits either way) */
-template <int KIND, bool WIDE = false>
-__global__ __launch_bounds__(LAP_WG) GPSBB_LAP_OCC void k_lap_pass2(BatchDev p, LapDev L) { lap_pass2_body<KIND, WIDE>(p, L, blockIdx.x); }
+/* SG: the batch's state granule (BatchDev::st_log2) */
+template <int KIND, bool WIDE = false, int SG = 0>
+__global__ __launch_bounds__(LAP_WG) GPSBB_LAP_OCC void k_lap_pass2(BatchDev p, LapDev L) { lap_pass2_body<KIND, WIDE, SG>(p, L, blockIdx.x); }
 template <int KIND>
 __global__ __launch_bounds__(64) void k_lap_repair(BatchDev p, LapDev L) { lap_repair_body<KIND>(p, L, blockIdx.x); }
 
@@ -1791,14 +1804,14 @@ __global__ __launch_bounds__(64) void k_lap_scan2(BatchDev p, LapDev L)
     else
         lap_scan_body<NCO_CARR>(p, L, blockIdx.x - (uint32_t)p.nch);
 }
-template <bool WIDE = false>
+template <bool WIDE = false, int SG = 0>
 __global__ __launch_bounds__(LAP_WG) GPSBB_LAP_OCC void k_lap_pass2_2(BatchDev p, LapDev L)
 {
     const uint32_t cc = L.chunk0[NCO_CODE][p.nch] - L.chunk0[NCO_CODE][0];
     if (blockIdx.x < cc)
-        lap_pass2_body<NCO_CODE, WIDE>(p, L, blockIdx.x);
+        lap_pass2_body<NCO_CODE, WIDE, SG>(p, L, blockIdx.x);
     else
-        lap_pass2_body<NCO_CARR, WIDE>(p, L, blockIdx.x - cc);
+        lap_pass2_body<NCO_CARR, WIDE, SG>(p, L, blockIdx.x - cc);
 }
 __global__ __launch_bounds__(64) void k_lap_repair2(BatchDev p, LapDev L)
 {

@@ -234,24 +234,51 @@ __global__ __launch_bounds__(256) void k_model_err_ev(BatchDev p, double *mx, un
     if (p.ch[b * p.nch + i].prn <= 0)
         return;
     const EvConst kb = p.evc[b * p.nch + i];
-    const double *txb = p.tile_x + b * (size_t)p.ntiles * 2 * p.nch;
-    const double ts_x = txb[(size_t)(2 * i) * p.ntiles + wt], ts_y = txb[(size_t)(2 * i + 1) * p.ntiles + wt];
+    /* the tile's granule (BatchDev::st_log2) and its place in it */
+    const int sg = p.st_log2, nst = p.nstates, r = wt & ((1 << sg) - 1);
+    const double *txb = p.tile_x + b * (size_t)nst * 2 * p.nch;
+    const double ts_x_g = txb[(size_t)(2 * i) * nst + (wt >> sg)], ts_y = txb[(size_t)(2 * i + 1) * nst + (wt >> sg)];
     const bool down = kb.down != 0;
     /* exactly what synth_ev_body puts into EvLds::tstate (IEEE carrier) */
     const bool fixed = p.kph0 != nullptr; /* k_synth_ev_fixed: the carrier lanes carry no bias, a falling phase is mirrored bit by bit */
     const double guard_w = EV_GUARD + kb.W;
-    const double ts_y_m = down ? (fixed ? 512.0 - 0x1p-16 : 512.0) - ts_y : ts_y;
-    const double ytg = ts_y_m + (fixed ? EV_GUARD : guard_w), xtg = ts_x + guard_w;
+    const double ts_y_g = down ? (fixed ? 512.0 - 0x1p-16 : 512.0) - ts_y : ts_y;
+    double ytg = ts_y_g + (fixed ? EV_GUARD : guard_w), xtg = ts_x_g + guard_w;
+    /* ... with the anchor of tile r of the granule: the same fma and the same reductions by whole periods */
+    int red_laps = 0, red_wraps = 0;
+    double ts_y_m = ts_y_g, ts_x = ts_x_g; /* where the plain linear model starts (ME_PURE_*): the tile's exact state */
+    if (sg) {
+        ytg = __fma_rn((double)(r * TILE), kb.S, ytg);
+        xtg = __fma_rn((double)(r * TILE), kb.sc, xtg);
+        const uint32_t iy = (uint32_t)__double2hiint(ytg) - EV_GUARD_HI, ix = (uint32_t)__double2hiint(xtg) - EV_GUARD_HI;
+        const uint32_t ry = iy & ~511u, rx = ix >= (uint32_t)GPSBB_CA_LEN + 1u ? (uint32_t)GPSBB_CA_LEN : 0u;
+        ytg -= (double)ry;
+        xtg -= (double)rx;
+        red_laps = (int)(ry >> 9);
+        red_wraps = rx ? 1 : 0;
+    }
     MeTruth T;
     T.cp = fixed ? 0.0 : ts_y * (1.0 / 512.0);
     T.s = fixed ? 0.0 : (down ? -kb.S : kb.S) * (1.0 / 512.0);
-    T.x = ts_x;
+    T.x = ts_x_g;
     T.sc = kb.sc;
     T.laps = T.wraps = 0;
     T.down = down;
     T.fixed = fixed;
     T.st = fixed ? (uint32_t)p.kstep[b * p.nch + i] : 0u;
-    T.ph = fixed ? p.kph0[b * p.nch + i] + (uint32_t)wt * (uint32_t)TILE * T.st : 0u;
+    T.ph = fixed ? p.kph0[b * p.nch + i] + (uint32_t)(wt - r) * (uint32_t)TILE * T.st : 0u;
+    /* the truth from the granule's first sample to the tile's, then counted from the anchor's period on */
+    for (int n = 0; n < r * TILE; n++)
+        T.step();
+    T.laps -= red_laps;
+    T.wraps -= red_wraps;
+    if (sg) {
+        /* ME_PURE_* stays what it measures with one state per tile: the plain model from the tile's EXACT state (the truth here, in
+         * the anchor's coordinates).  What the granule adds — the model carried over the tiles before — is in the tested quantities
+         * (ME_Y0 .. ME_TC), which start from the anchor the kernel derives. */
+        ts_y_m = T.u();
+        ts_x = T.ux();
+    }
     MeAcc A;
     for (int q = 0; q < ME_NQ; q++)
         A.mx[q] = 0.0;
