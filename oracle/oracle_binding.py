@@ -112,21 +112,37 @@ class RefLoop:
         return iq, st
 
 
-def run_ref_sim(nav, nblocks, nsamp, fs, llh=None, motion=None, max_chan=12, opt="", extra=()):
-    """Run the scenario runner built from the reference's main() slices; returns (iq, desc, state)."""
+def ref_sim_path(max_chan=12, opt=""):
+    """The scenario runner ref_sim<max_chan><opt> under oracle/_ref/: opt "" (-O0, the reference's flags), "_O2", "_fixed"
+    (without FLOAT_CARR_PHASE), "_gpsbb" / "_fixed_gpsbb" (the sample loop replaced by libgpsbb's drop-in call)."""
+    return os.path.join(REF_DIR, "ref_sim%d%s" % (max_chan, opt))
+
+
+def run_ref_sim(nav, nblocks, nsamp, fs, llh=None, motion=None, max_chan=12, opt="", extra=(), kernels=False, timeout=None):
+    """Run the scenario runner built from the reference's main() slices; returns (iq, desc, state).
+    opt: the runner variant (ref_sim_path); extra: more arguments (the _gpsbb runners take -R, -Z).  kernels=True (a _gpsbb
+    runner) adds -K and returns (iq, desc, state, kern): kern int32 [nblocks, 2], GPSBB_INFO_LAST_KERNEL and GPSBB_INFO_PREPASS
+    after each block's call.  A runner that exits non-zero raises RuntimeError with the end of its stderr."""
     import tempfile
-    exe = os.path.join(REF_DIR, "ref_sim%d%s" % (max_chan, opt))
+    exe = ref_sim_path(max_chan, opt)
     with tempfile.TemporaryDirectory() as td:
-        iqp, dp, sp = (os.path.join(td, n) for n in ("iq.bin", "desc.bin", "state.bin"))
+        iqp, dp, sp, kp = (os.path.join(td, n) for n in ("iq.bin", "desc.bin", "state.bin", "kern.bin"))
         cmd = [exe, "-e", nav, "-s", str(int(fs)), "-n", str(nsamp), "-b", str(nblocks), "-o", iqp,
                "-d", dp, "-S", sp]
         if motion:
             cmd += ["-u", motion]
         elif llh is not None:
             cmd += ["-l", "%s,%s,%s" % tuple(llh)]
+        if kernels:
+            cmd += ["-K", kp]
         cmd += list(extra)
-        subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
+        r = subprocess.run(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=timeout)
+        if r.returncode != 0:
+            raise RuntimeError("%s exited with %d: %s" % (os.path.basename(exe), r.returncode,
+                                                          r.stderr.decode(errors="replace")[-2000:]))
         iq = np.fromfile(iqp, np.int16).reshape(nblocks, nsamp, 2)
         desc = np.fromfile(dp, CHAN_DTYPE).reshape(nblocks, max_chan)
         st = np.fromfile(sp, STATE_DTYPE).reshape(nblocks, max_chan)
+        if kernels:
+            return iq, desc, st, np.fromfile(kp, np.int32).reshape(nblocks, 2)
     return iq, desc, st

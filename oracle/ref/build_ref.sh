@@ -72,4 +72,19 @@ sed '12d' "$HDR" > "$HFIX/plutogpssim.h"
 INCF="-I$TMP -I$HFIX -I$HERE/../../include"
 $CC $REFFLAGS $INCF -DREF_MAX_CHAN=16 -shared -fPIC "$HERE/ref_harness.c" -o "$OUT/libplutoref_fixed.so" -lm -lz
 $CC $REFFLAGS $INCF -DREF_MAX_CHAN=12 -DREF_BUILD_MAIN "$HERE/ref_harness.c" -o "$OUT/ref_sim12_fixed" -lm -lz
+# The same scenario runners with the sample loop replaced by libgpsbb's drop-in call (INTEGRATION.md's binding), linked as
+# INTEGRATION.md tells the reference to link: -I<repo>/include -L<repo>/pluto-gps-sim_amd -lgpsbb, and an rpath relative to
+# the binary, so the tree's own libgpsbb.so is the one that loads wherever the tree lies.
+LIBDIR="$(cd "$HERE/../../pluto-gps-sim_amd" && pwd)"
+if [ -f "$LIBDIR/libgpsbb.so" ]; then
+    GPSBB="-DREF_USE_GPSBB -L$LIBDIR -lgpsbb -Wl,-rpath,\$ORIGIN/../../pluto-gps-sim_amd"
+    for mc in 12 16; do
+        $CC $REFFLAGS $INC -DREF_MAX_CHAN=$mc -DREF_BUILD_MAIN "$HERE/ref_harness.c" -o "$OUT/ref_sim${mc}_gpsbb" $GPSBB -lm -lz
+    done
+    $CC $REFFLAGS $INCF -DREF_MAX_CHAN=12 -DREF_BUILD_MAIN "$HERE/ref_harness.c" -o "$OUT/ref_sim12_fixed_gpsbb" $GPSBB -lm -lz
+else
+    # no stale runner may stay behind to be tested against a library it was not linked with
+    rm -f "$OUT/ref_sim12_gpsbb" "$OUT/ref_sim16_gpsbb" "$OUT/ref_sim12_fixed_gpsbb"
+    echo "build_ref: $LIBDIR/libgpsbb.so not built - ref_sim12_gpsbb, ref_sim16_gpsbb, ref_sim12_fixed_gpsbb skipped" >&2
+fi
 echo "build_ref: built $(ls "$OUT" | tr '\n' ' ')"

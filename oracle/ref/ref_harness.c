@@ -21,8 +21,24 @@
  *   c:2690-2756 THE SAMPLE LOOP                     gpsbb_chan_t for the dumps
  *   c:2764-2805 30-s maintenance, time update
  *
+ * With -DREF_USE_GPSBB the scenario runner does what INTEGRATION.md tells a maintainer to do: c:2690-2756 is not
+ * included, and libgpsbb's drop-in call takes its place.  The glue for that variant (ref_sim*_gpsbb):
+ *
+ *   reference text (compiled unchanged)           glue (this file)
+ *   ------------------------------------------    -------------------------------------------------
+ *   every slice above except c:2690-2756          INTEGRATION.md's binding: the gpsbb_refchan_layout_t taken with
+ *                                                   offsetof on the real channel_t, gpsbb_create after the calloc of
+ *                                                   iq_buff, gpsbb_fill_block_ref (without FLOAT_CARR_PHASE:
+ *                                                   gpsbb_fill_block_ref_fixed with offsetof(channel_t, carr_phasestep))
+ *                                                   where the loop was, gpsbb_destroy before iq_buff is freed; the
+ *                                                   flags -R (gpsbb_host_register iq_buff), -K file (GPSBB_INFO_LAST_KERNEL
+ *                                                   and GPSBB_INFO_PREPASS of every call, two int32) and -Z (restores
+ *                                                   every carr_phase after the call: a broken caller, for tests that
+ *                                                   must see the comparison fail)
+ *
  * Not built: the libiio TX thread (c:2058-2190), FTP fetch (c:2428-2474), signal/affinity code.
  */
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -164,6 +180,26 @@ unsigned long ref_computeChecksum(unsigned long source, int nib) { return comput
 #ifdef REF_BUILD_MAIN
 /* ---- scenario runner: main()'s control flow with the device I/O removed -------------------------- */
 
+#ifdef REF_USE_GPSBB
+/* INTEGRATION.md's binding, as a maintainer would add it to plutogpssim.c */
+static gpsbb_t *gpsbb;
+static const gpsbb_refchan_layout_t chan_layout = {
+    .stride = sizeof(channel_t),
+    .off_prn = offsetof(channel_t, prn),
+    .off_f_carr = offsetof(channel_t, f_carr),
+    .off_f_code = offsetof(channel_t, f_code),
+    .off_carr_phase = offsetof(channel_t, carr_phase),
+    .off_code_phase = offsetof(channel_t, code_phase),
+    .off_dwrd = offsetof(channel_t, dwrd),
+    .sizeof_dwrd_elem = sizeof(unsigned long),
+    .off_iword = offsetof(channel_t, iword),
+    .off_ibit = offsetof(channel_t, ibit),
+    .off_icode = offsetof(channel_t, icode),
+    .off_dataBit = offsetof(channel_t, dataBit),
+    .off_codeCA = offsetof(channel_t, codeCA),
+};
+#endif
+
 static void die(const char *m)
 {
     fprintf(stderr, "ref_sim: %s\n", m);
@@ -209,6 +245,21 @@ int main(int argc, char *argv[])
     int nblocks = 1, result, blk, use_rinex3 = 0;
     const char *iq_path = NULL, *desc_path = NULL, *state_path = NULL;
     FILE *fiq = NULL, *fdesc = NULL, *fstate = NULL;
+#ifdef REF_USE_GPSBB
+    int register_iq = 0, drop_carrier = 0, rc;
+    const char *kern_path = NULL;
+    FILE *fkern = NULL;
+    uint64_t info;
+    int32_t kern_rec[2];
+#ifdef FLOAT_CARR_PHASE
+    double saved_phase[MAX_CHAN];
+#else
+    unsigned int saved_phase[MAX_CHAN];
+#endif
+#define REF_GPSBB_OPTS "RK:Z"
+#else
+#define REF_GPSBB_OPTS ""
+#endif
 
     memset(&tmin, 0, sizeof tmin);
     memset(&gmin, 0, sizeof gmin);
@@ -222,8 +273,19 @@ int main(int argc, char *argv[])
     llh[2] = 10.0;
     llh2xyz(llh, xyz[0]);
 
-    while ((result = getopt(argc, argv, "e:u:c:l:s:Tt:in:b:o:d:S:3")) != -1) {
+    while ((result = getopt(argc, argv, "e:u:c:l:s:Tt:in:b:o:d:S:3" REF_GPSBB_OPTS)) != -1) {
         switch (result) {
+#ifdef REF_USE_GPSBB
+        case 'R':
+            register_iq = 1;
+            break;
+        case 'K':
+            kern_path = optarg;
+            break;
+        case 'Z':
+            drop_carrier = 1;
+            break;
+#endif
         case 'e':
             navfile = optarg;
             break;
@@ -279,7 +341,11 @@ int main(int argc, char *argv[])
             break;
         default:
             die("usage: ref_sim -e nav [-l lat,lon,h|-c x,y,z|-u motion.csv] [-t date] [-T] [-i] "
-                "-s fs -n nsamp -b nblocks [-o iq.bin] [-d desc.bin] [-S state.bin]");
+                "-s fs -n nsamp -b nblocks [-o iq.bin] [-d desc.bin] [-S state.bin]"
+#ifdef REF_USE_GPSBB
+                " [-R] [-K kern.bin] [-Z]"
+#endif
+            );
         }
     }
     if (navfile == NULL)
@@ -311,6 +377,19 @@ int main(int argc, char *argv[])
         die("cannot open descriptor output");
     if (state_path && !(fstate = fopen(state_path, "wb")))
         die("cannot open state output");
+#ifdef REF_USE_GPSBB
+    if (kern_path && !(fkern = fopen(kern_path, "wb")))
+        die("cannot open kernel record output");
+    /* after the IQ buffer is allocated (c:2604) */
+    if ((rc = gpsbb_create(&gpsbb, 0)) != GPSBB_OK) {
+        fprintf(stderr, "gpsbb: %s\n", gpsbb_strerror(rc));
+        exit(3);
+    }
+    if (register_iq && (rc = gpsbb_host_register(gpsbb, iq_buff, (size_t)NUM_SAMPLES * 4)) != GPSBB_OK) {
+        fprintf(stderr, "gpsbb: %s\n", gpsbb_strerror(rc));
+        exit(3);
+    }
+#endif
 
 #include "slice_chaninit.inc" /* c:2620-2632 */
 
@@ -333,7 +412,36 @@ int main(int argc, char *argv[])
             }
         }
 
+#ifdef REF_USE_GPSBB
+        /* in place of c:2690-2756 */
+        if (drop_carrier)
+            for (i = 0; i < MAX_CHAN; i++)
+                saved_phase[i] = chan[i].carr_phase;
+#ifdef FLOAT_CARR_PHASE
+        rc = gpsbb_fill_block_ref(gpsbb, chan, &chan_layout, MAX_CHAN, gain, delt, NUM_SAMPLES, iq_buff);
+#else
+        rc = gpsbb_fill_block_ref_fixed(gpsbb, chan, &chan_layout, offsetof(channel_t, carr_phasestep), MAX_CHAN, gain, delt,
+                                        NUM_SAMPLES, iq_buff);
+#endif
+        if (rc != GPSBB_OK) {
+            fprintf(stderr, "gpsbb: %s (block %d)\n", gpsbb_strerror(rc), blk);
+            exit(3);
+        }
+        if (drop_carrier)
+            for (i = 0; i < MAX_CHAN; i++)
+                chan[i].carr_phase = saved_phase[i];
+        if (fkern) {
+            if (gpsbb_get_info(gpsbb, GPSBB_INFO_LAST_KERNEL, &info) != GPSBB_OK)
+                die("gpsbb_get_info");
+            kern_rec[0] = (int32_t)info;
+            if (gpsbb_get_info(gpsbb, GPSBB_INFO_PREPASS, &info) != GPSBB_OK)
+                die("gpsbb_get_info");
+            kern_rec[1] = (int32_t)info;
+            fwrite(kern_rec, sizeof kern_rec, 1, fkern);
+        }
+#else
 #include "slice_loop.inc" /* c:2690-2756 */
+#endif
 
         if (fiq)
             fwrite(iq_buff, 4, (size_t)NUM_SAMPLES, fiq);
@@ -354,6 +462,11 @@ int main(int argc, char *argv[])
         fclose(fdesc);
     if (fstate)
         fclose(fstate);
+#ifdef REF_USE_GPSBB
+    if (fkern)
+        fclose(fkern);
+    gpsbb_destroy(gpsbb); /* before iq_buff is freed (c:2815); unregisters it */
+#endif
     free(iq_buff);
     (void)ip;
     (void)qp;

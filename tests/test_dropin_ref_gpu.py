@@ -1,0 +1,176 @@
+"""The drop-in call inside the reference's own scenario loop.
+
+oracle/_ref/ref_sim*_gpsbb are the reference's main() slices (front end, per-block seeding, 30-s maintenance) with the
+sample loop replaced by INTEGRATION.md's binding: a gpsbb_refchan_layout_t taken with offsetof on the real channel_t,
+gpsbb_fill_block_ref (gpsbb_fill_block_ref_fixed without FLOAT_CARR_PHASE) once per block, and nothing else.  Every block
+after the first is seeded by the reference's front end from what the library wrote back into channel_t, so these runs check
+the whole promise at once: the IQ, the write-back, and that the reference keeps producing its own next block.
+
+The expected bytes come from the golden fixtures (recorded from the reference's own loop) and from the CPU runners
+ref_sim12 / ref_sim16 / ref_sim12_fixed, run here with the same arguments.  Every comparison is of bytes."""
+import hashlib
+import os
+
+import numpy as np
+import pytest
+
+import oracle_binding as ob
+from conftest import GOLDEN
+
+pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not ob.have_ref(), reason="oracle/_ref not built (no reference sources here)")]
+
+SITE = ("30.286502", "120.032669", "100")
+NAV = os.path.join(GOLDEN, "synth3540.14n")
+DENSE = os.path.join(GOLDEN, "dense3540.14n")
+
+# Seconds a child may take: the GPU runners spend ~1 ms of front end and call per block (plus the runtime's start-up), the CPU
+# runner at -O0 ~75 ms per 300 000-sample block of 12 channels.
+GPU_TIMEOUT = 240
+CPU_TIMEOUT = 600
+
+# The arguments tests/golden/make_golden.py gave the reference's runner for each fixture (fs and nsamp are in the fixture).
+SCENARIOS = {
+    "static_F": dict(nav=NAV, nblocks=301, llh=SITE, max_chan=12),
+    "motion_F": dict(nav=NAV, nblocks=301, motion=os.path.join(GOLDEN, "circle_motion.csv"), max_chan=12),
+    "motion_ref_F": dict(nav=NAV, nblocks=301, motion=os.path.join(GOLDEN, "circle.csv"), max_chan=12),
+    "rinex3_F": dict(nav=os.path.join(GOLDEN, "synth3540_v3.rnx"), nblocks=301, llh=SITE, max_chan=12, extra=("-3",)),
+    "toverwrite_F": dict(nav=NAV, nblocks=301, llh=SITE, max_chan=12, extra=("-t", "2014/12/21,10:00:00", "-T")),
+    "static_F_fixed": dict(nav=NAV, nblocks=301, llh=SITE, max_chan=12, fixed=True),
+    "dense_S": dict(nav=DENSE, nblocks=2, llh=SITE, max_chan=16),
+    "swap_S": dict(nav=DENSE, nblocks=1504, llh=SITE, max_chan=16, extra=("-t", "2014/12/20,01:20:00")),
+}
+
+K_SYNTH, K_MODEL = 1, 2                    # GPSBB_INFO_LAST_KERNEL: the per-sample kernel, the model kernels (ev, ev_dense, pd)
+PRE_ROWS, PRE_HOST, PRE_LAPS = 1, 2, 3     # GPSBB_INFO_PREPASS
+
+
+def sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def runner(max_chan, fixed, gpsbb):
+    """The runner's opt suffix; a _gpsbb runner missing from a built oracle/_ref is a failure, not a skip."""
+    opt = ("_fixed" if fixed else "") + ("_gpsbb" if gpsbb else "")
+    exe = ob.ref_sim_path(max_chan, opt)
+    if not os.path.exists(exe):
+        pytest.fail("%s is missing from oracle/_ref: rebuild it (make -C oracle ref after the library)" % os.path.basename(exe))
+    return opt
+
+
+def run(nav, nblocks, nsamp, fs, max_chan=12, fixed=False, gpsbb=True, flags=(), extra=(), **where):
+    opt = runner(max_chan, fixed, gpsbb)
+    return ob.run_ref_sim(nav, nblocks, nsamp, fs, max_chan=max_chan, opt=opt, extra=tuple(extra) + tuple(flags),
+                          kernels=gpsbb, timeout=GPU_TIMEOUT if gpsbb else CPU_TIMEOUT, **where)
+
+
+def assert_same_outputs(a, b, what):
+    for name, x, y in zip(("iq", "descriptors", "end states"), a[:3], b[:3]):
+        assert x.shape == y.shape and x.tobytes() == y.tobytes(), "%s: %s differ" % (what, name)
+
+
+def test_the_dropin_runners_link_the_tree_library():
+    """Each _gpsbb runner exists and resolves libgpsbb.so to this tree's copy (an $ORIGIN-relative rpath)."""
+    import subprocess
+    lib = os.path.realpath(os.path.join(ob.HERE, "..", "pluto-gps-sim_amd", "libgpsbb.so"))
+    for mc, fixed in ((12, False), (16, False), (12, True)):
+        exe = ob.ref_sim_path(mc, runner(mc, fixed, True))
+        out = subprocess.run(["ldd", exe], capture_output=True, text=True, timeout=60).stdout
+        got = [ln.split("=>")[1].split("(")[0].strip() for ln in out.splitlines() if ln.strip().startswith("libgpsbb.so")]
+        assert got and os.path.realpath(got[0]) == lib, (exe, out)
+
+
+@pytest.mark.parametrize("name", list(SCENARIOS))
+def test_golden_scenarios_with_the_reference_as_caller(name):
+    """For every block a fixture keeps: the descriptors dumped BEFORE the call are the fixture's (for blocks after the first:
+    the reference's front end, fed by the library's write-back, reproduces its own next block), the IQ is the fixture's (SHA-256
+    of the block, and its prefix), the end state after the call is the fixture's.  Once with a pageable iq_buff, once with it
+    registered (-R): the two runs write the same files."""
+    z = np.load(os.path.join(GOLDEN, name + ".npz"))
+    fs, nsamp = int(z["fs"]), int(z["nsamp"])
+    sc = dict(SCENARIOS[name])
+    nav, nblocks = sc.pop("nav"), sc.pop("nblocks")
+    a = run(nav, nblocks, nsamp, fs, **sc)
+    b = run(nav, nblocks, nsamp, fs, flags=("-R",), **sc)
+    assert_same_outputs(a, b, "pageable vs registered iq_buff")
+    assert a[3].tobytes() == b[3].tobytes()
+    iq, desc, st, kern = a
+    assert (kern == (K_MODEL, PRE_LAPS)).all(), np.unique(kern, axis=0)   # k_synth_pd / k_synth_ev behind the lap pre-pass
+    npre = z["iq_prefix"].shape[1]
+    for j, blk in enumerate(z["blocks"]):
+        blk = int(blk)
+        assert desc[blk].tobytes() == z["desc"][j].tobytes(), (name, blk, "descriptors before the call")
+        assert sha(iq[blk]) == str(z["iq_sha256"][j]), (name, blk, "IQ")
+        assert (iq[blk, :npre] == z["iq_prefix"][j]).all(), (name, blk, "IQ prefix")
+        assert st[blk].tobytes() == z["end_state"][j].tobytes(), (name, blk, "end state")
+
+
+@pytest.mark.parametrize("fixed", [False, True], ids=["float_carrier", "fixed_carrier"])
+def test_every_block_matches_the_cpu_runner(fixed):
+    """static_F's arguments, all 301 blocks (the 30-s maintenance after block 299 included): the drop-in runner's IQ,
+    descriptors and end states are byte for byte those of the reference's own loop, run now with the same arguments."""
+    z = np.load(os.path.join(GOLDEN, "static_F.npz"))
+    fs, nsamp = int(z["fs"]), int(z["nsamp"])
+    sc = dict(SCENARIOS["static_F"])
+    nav, nblocks = sc.pop("nav"), sc.pop("nblocks")
+    want = run(nav, nblocks, nsamp, fs, fixed=fixed, gpsbb=False, **sc)
+    got = run(nav, nblocks, nsamp, fs, fixed=fixed, **sc)
+    assert_same_outputs(got, want, "drop-in vs the reference's loop")
+
+
+# Rate x MAX_CHAN x carrier: block lengths that are not multiples of 1024 or 2048 (a partial last tile, a partial last state
+# granule), 302 blocks (the 30-s maintenance after block 299, and a block after the first one it seeds), and the kernel and
+# pre-pass each rate must take.  GPSBB_INFO_LAST_KERNEL tells the per-sample kernel from the model kernels only; the last
+# column names the model kernel the library's plan (batch_setup in gpsbb.hip) gives the rate: k_synth_pd where every channel
+# is evaluated per sample (2.6, 3 MS/s), k_synth_ev_dense where only some are (the mixed band at 15.5 * 1.023 MS/s),
+# k_synth_ev above it, k_synth_ev_fixed for the 32-bit carrier.  The laps do not serve the per-sample kernel (1 MS/s): one
+# block of 12-16 channels is then seeded on host threads.
+PATHS = [
+    # fs,      max_chan, nsamp, fixed, kernel,  pre-pass,  what renders
+    (1000000, 12, 1500, False, K_SYNTH, PRE_HOST, "k_synth"),
+    (1000000, 16, 1500, False, K_SYNTH, PRE_HOST, "k_synth"),
+    (2600000, 12, 2601, False, K_MODEL, PRE_LAPS, "k_synth_pd"),
+    (2600000, 16, 2601, False, K_MODEL, PRE_LAPS, "k_synth_pd"),
+    (3000000, 12, 3001, False, K_MODEL, PRE_LAPS, "k_synth_pd"),
+    (3000000, 16, 3001, False, K_MODEL, PRE_LAPS, "k_synth_pd"),
+    (15856500, 12, 4099, False, K_MODEL, PRE_LAPS, "k_synth_ev_dense"),
+    (15856500, 16, 4099, False, K_MODEL, PRE_LAPS, "k_synth_ev_dense"),
+    (16368000, 12, 5121, False, K_MODEL, PRE_LAPS, "k_synth_ev"),
+    (16368000, 16, 5121, False, K_MODEL, PRE_LAPS, "k_synth_ev"),
+    (25000000, 12, 6143, False, K_MODEL, PRE_LAPS, "k_synth_ev"),
+    (25000000, 16, 6143, False, K_MODEL, PRE_LAPS, "k_synth_ev"),
+    (25000000, 12, 3073, True, K_MODEL, PRE_LAPS, "k_synth_ev_fixed"),
+]
+
+
+@pytest.mark.parametrize("fs,max_chan,nsamp,fixed,kernel,prepass,what", PATHS,
+                         ids=["%s-%gMSps-%dch" % (p[6], p[0] / 1e6, p[1]) for p in PATHS])
+def test_every_synthesis_path_through_the_dropin(fs, max_chan, nsamp, fixed, kernel, prepass, what):
+    """The reference's geometry at other rates (-s / -n): every block of the drop-in runner, pageable and registered, is byte
+    for byte the CPU runner's, and the kernel record is the path the rate must take, in every block."""
+    nav = NAV if max_chan == 12 else DENSE
+    nblocks = 302
+    want = run(nav, nblocks, nsamp, fs, max_chan=max_chan, fixed=fixed, gpsbb=False, llh=SITE)
+    assert (want[1]["prn"] > 0).sum(axis=1).min() >= 8, "too few channels in use to mean anything"
+    for flags in ((), ("-R",)):
+        got = run(nav, nblocks, nsamp, fs, max_chan=max_chan, fixed=fixed, flags=flags, llh=SITE)
+        assert_same_outputs(got, want, "%s %s" % (what, flags))
+        kern = got[3]
+        assert (kern[:, 0] == kernel).all() and (kern[:, 1] == prepass).all(), (what, flags, np.unique(kern, axis=0))
+
+
+def test_a_lost_carrier_write_back_is_seen():
+    """-Z puts back every carr_phase the call wrote: the broken caller a missing write-back makes.  Block 0 still matches the
+    fixture (the call rendered it right); from block 1 on the descriptors (their carrier phase, and nothing else) and the IQ
+    differ from the fixture's.  The comparisons above would have caught it."""
+    z = np.load(os.path.join(GOLDEN, "static_F.npz"))
+    fs, nsamp = int(z["fs"]), int(z["nsamp"])
+    assert list(z["blocks"][:3]) == [0, 1, 2]
+    iq, desc, st, _ = run(NAV, 3, nsamp, fs, llh=SITE, flags=("-Z",))
+    assert desc[0].tobytes() == z["desc"][0].tobytes() and sha(iq[0]) == str(z["iq_sha256"][0])
+    for blk in (1, 2):
+        want = z["desc"][blk]
+        assert desc[blk].tobytes() != want.tobytes() and sha(iq[blk]) != str(z["iq_sha256"][blk]), blk
+        assert (desc[blk]["carr_phase"] != want["carr_phase"]).all(), blk
+        for f in desc.dtype.names:
+            if f != "carr_phase":
+                assert desc[blk][f].tobytes() == want[f].tobytes(), (blk, f)
