@@ -148,6 +148,12 @@ int gpsbb_node_begin(gpsbb_node_t *n, gpsbb_node_sink_fn sink, void *user);
 int gpsbb_node_feed(gpsbb_node_t *n, const gpsbb_chan_t *ch, long nblocks);
 int gpsbb_node_end(gpsbb_node_t *n, gpsbb_node_stats_t *stats);
 
+/* Receiver noise (include/gpsbb.h gpsbb_noise_t) on every later gpsbb_node_run and begin / feed / end: block b of the stream is
+ * at position nz->sample0 + b * nsamp, whichever shard renders it — contiguous, GPSBB_NODE_INTERLEAVED, GPSBB_NODE_INDEXED, any
+ * split.  nz NULL: noise off.  GPSBB_E_BADARG with GPSBB_NODE_DEVICE_ONLY and between begin and end; while noise is set,
+ * gpsbb_node_run_digest is GPSBB_E_BADARG (its host rings are digested from the bytes that arrive). */
+int gpsbb_node_set_noise(gpsbb_node_t *n, const gpsbb_noise_t *nz);
+
 void gpsbb_node_destroy(gpsbb_node_t *n);
 
 /* which shard renders block b of an nblocks-long stream, and where the shards begin: first[0 .. nshards] (first[nshards] =

@@ -13,6 +13,7 @@ The directory name contains '-' (it mirrors the reference's repo name), so impor
 (`__graft_entry__.load_package()` and tests/conftest.py do exactly that.)
 """
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -101,6 +102,25 @@ def OUT_SC8(shift):
     """GPSBB_OUT_SC8(shift): int8 I/Q, clamp(v >> shift, -128, 127)"""
     return (1 << 8) | (int(shift) << 12)
 
+
+# receiver noise on the host-bound outputs (include/gpsbb.h gpsbb_noise_t): the `noise=` of fill_block / stream / Node
+INFO_NOISE_CLIPPED = 12
+NOISE_KNOTS = 1665
+
+
+class Noise(C.Structure):
+    """gpsbb_noise_t: seed (the Philox key), sample0 (stream position of the first sample), sigma (per component, int16 LSB),
+    shift (0..7: w = sat16((v + N) >> shift))"""
+    _fields_ = [("seed", C.c_uint64), ("sample0", C.c_uint64), ("sigma", C.c_double), ("shift", C.c_int32), ("_pad", C.c_int32)]
+
+
+def _as_noise(noise):
+    """None, a Noise, or a dict with seed / sigma and optionally sample0 / shift -> a Noise (or None)"""
+    if noise is None or isinstance(noise, Noise):
+        return noise
+    d = dict(noise)
+    return Noise(int(d["seed"]) & 0xFFFFFFFFFFFFFFFF, int(d.get("sample0", 0)), float(d["sigma"]), int(d.get("shift", 0)), 0)
+
 ERRORS = {0: "GPSBB_OK", -1: "GPSBB_E_BADARG", -2: "GPSBB_E_BADCHAN", -3: "GPSBB_E_HIP", -4: "GPSBB_E_NOMEM",
           -5: "GPSBB_E_INTERNAL", -6: "GPSBB_E_NODEVICE", -7: "GPSBB_E_STATE"}
 
@@ -114,9 +134,11 @@ API_SYMBOLS = [
     "gpsbb_codegen", "gpsbb_sincos_tables", "gpsbb_chain_carrier_host", "gpsbb_chain_carrier", "gpsbb_set_option",
     "gpsbb_get_info", "gpsbb_stream_reset", "gpsbb_device_affinity", "gpsbb_stream_push_ex", "gpsbb_stream_pop_digest", "gpsbb_host_register", "gpsbb_host_unregister",
     "gpsbb_out_bytes", "gpsbb_device_pack",
+    "gpsbb_fill_block_noise", "gpsbb_stream_set_noise", "gpsbb_device_noise", "gpsbb_noise_sigma", "gpsbb_noise_table",
 ]
 # ... and include/gpsbb_node.h
-NODE_API_SYMBOLS = ["gpsbb_node_create", "gpsbb_node_run", "gpsbb_node_run_digest", "gpsbb_node_slot_digests", "gpsbb_node_destroy", "gpsbb_node_plan", "gpsbb_node_begin", "gpsbb_node_feed", "gpsbb_node_end"]
+NODE_API_SYMBOLS = ["gpsbb_node_create", "gpsbb_node_run", "gpsbb_node_run_digest", "gpsbb_node_slot_digests", "gpsbb_node_destroy", "gpsbb_node_plan", "gpsbb_node_begin", "gpsbb_node_feed", "gpsbb_node_end",
+                    "gpsbb_node_set_noise"]
 
 
 class GpsbbError(RuntimeError):
@@ -206,6 +228,14 @@ def lib():
         L.gpsbb_out_bytes.argtypes = [u, C.c_long]
         L.gpsbb_out_bytes.restype = C.c_long
         L.gpsbb_device_pack.argtypes = [vp, vp, C.c_long, i, u, vp]
+        if hasattr(L, "gpsbb_fill_block_noise"):  # the noise calls, as a group (an older build loaded for an A/B: tools/ab_lib.sh)
+            L.gpsbb_fill_block_noise.argtypes = [vp, vp, i, d, i, u, vp, vp, vp]
+            L.gpsbb_stream_set_noise.argtypes = [vp, vp]
+            L.gpsbb_device_noise.argtypes = [vp, vp, vp, C.c_long, i, vp]
+            L.gpsbb_noise_sigma.argtypes = [d, d, d]
+            L.gpsbb_noise_sigma.restype = d
+            L.gpsbb_noise_table.argtypes = [vp, i]
+            L.gpsbb_node_set_noise.argtypes = [vp, vp]
         _lib = L
     return _lib
 
@@ -301,10 +331,11 @@ class Synth:
     def __exit__(self, *a):
         self.close()
 
-    def fill_block(self, ch, delt, nsamp, flags=0, out=None, fmt=OUT_SC16):
+    def fill_block(self, ch, delt, nsamp, flags=0, out=None, fmt=OUT_SC16, noise=None):
         """gpsbb_fill_block(_ex): ch = CHAN_DTYPE[nch] -> (int16 [nsamp,2], STATE_DTYPE[nch]); out: the caller's iq_buff.
         fmt (OUT_SC8(shift) / OUT_SC1): the block comes back packed — int8 [nsamp, 2] / uint8 [nsamp // 4] — and `out`, if given,
-        is any C-contiguous array of at least out_bytes(fmt, nsamp) bytes (a registered iq_buff: written straight into)."""
+        is any C-contiguous array of at least out_bytes(fmt, nsamp) bytes (a registered iq_buff: written straight into).
+        noise (a Noise or a dict: seed, sigma, sample0, shift): gpsbb_fill_block_noise."""
         ch = np.ascontiguousarray(ch, dtype=CHAN_DTYPE)
         if fmt & (OUT_FORMAT_MASK | OUT_SHIFT_MASK):
             nbytes = out_bytes(fmt, nsamp)
@@ -314,8 +345,13 @@ class Synth:
             buf = np.empty((nsamp, 2), np.int16) if out is None else out
             assert buf.dtype == np.int16 and buf.flags.c_contiguous and buf.size >= 2 * nsamp
         st = np.zeros(ch.shape[0], STATE_DTYPE)
-        _chk(lib().gpsbb_fill_block_ex(self._h, ch.ctypes.data, ch.shape[0], delt, nsamp, flags | fmt, buf.ctypes.data,
-                                       st.ctypes.data), "gpsbb_fill_block_ex")
+        nz = _as_noise(noise)
+        if nz is not None:
+            _chk(lib().gpsbb_fill_block_noise(self._h, ch.ctypes.data, ch.shape[0], delt, nsamp, flags | fmt, C.byref(nz),
+                                              buf.ctypes.data, st.ctypes.data), "gpsbb_fill_block_noise")
+        else:
+            _chk(lib().gpsbb_fill_block_ex(self._h, ch.ctypes.data, ch.shape[0], delt, nsamp, flags | fmt, buf.ctypes.data,
+                                           st.ctypes.data), "gpsbb_fill_block_ex")
         if fmt & (OUT_FORMAT_MASK | OUT_SHIFT_MASK):
             return _as_out(buf, 1, nsamp, fmt)[0], st
         return buf, st
@@ -337,8 +373,15 @@ class Synth:
     def batch(self, ch, delt, nsamp, flags=0):
         return Batch(self, ch, delt, nsamp, flags)
 
-    def stream(self, nch, delt, nsamp, blocks_per_slot, depth=3, flags=0, fmt=OUT_SC16):
-        return Stream(self, nch, delt, nsamp, blocks_per_slot, depth, flags, fmt)
+    def stream(self, nch, delt, nsamp, blocks_per_slot, depth=3, flags=0, fmt=OUT_SC16, noise=None):
+        return Stream(self, nch, delt, nsamp, blocks_per_slot, depth, flags, fmt, noise)
+
+    def device_noise(self, d_src, nblocks, nsamp, noise, d_dst=None):
+        """gpsbb_device_noise: nblocks blocks of int16 IQ in device memory at d_src, with noise, into d_dst (default: in place)"""
+        nz = _as_noise(noise)
+        dst = d_src if d_dst is None else d_dst
+        _chk(lib().gpsbb_device_noise(self._h, C.c_void_p(int(d_src)), C.c_void_p(int(dst)), nblocks, nsamp,
+                                      None if nz is None else C.byref(nz)), "gpsbb_device_noise")
 
     def device_pack(self, d_ptr, nblocks, nsamp, fmt, out=None):
         """gpsbb_device_pack: nblocks blocks of int16 IQ in device memory, packed into host memory in format fmt -> the array of
@@ -470,7 +513,7 @@ class Batch:
 class Stream:
     """Time-sharded streaming with pinned host gather (gpsbb_stream_*)."""
 
-    def __init__(self, synth, nch, delt, nsamp, blocks_per_slot, depth=3, flags=0, fmt=OUT_SC16):
+    def __init__(self, synth, nch, delt, nsamp, blocks_per_slot, depth=3, flags=0, fmt=OUT_SC16, noise=None):
         self.synth = synth
         self.nch, self.nsamp, self.bps = nch, nsamp, blocks_per_slot
         self.device_only = bool(flags & STREAM_DEVICE_ONLY)
@@ -478,6 +521,13 @@ class Stream:
         self._s = C.c_void_p()
         _chk(lib().gpsbb_stream_create(synth._h, nch, delt, nsamp, blocks_per_slot, depth, flags | fmt,
                                        C.byref(self._s)), "gpsbb_stream_create")
+        if noise is not None:
+            self.set_noise(noise)
+
+    def set_noise(self, noise):
+        """gpsbb_stream_set_noise: noise on the host gather from the next push on (that push at noise's sample0); None: off"""
+        nz = _as_noise(noise)
+        _chk(lib().gpsbb_stream_set_noise(self._s, None if nz is None else C.byref(nz)), "gpsbb_stream_set_noise")
 
     def close(self):
         if self._s:
@@ -576,13 +626,20 @@ def device_affinity(device):
 class Node:
     """gpsbb_node_*: nshards producer threads (one handle + one ring each, bound next to their GPU), one sink."""
 
-    def __init__(self, nshards, nch, delt, nsamp, blocks_per_slot, depth=3, flags=0, devices=None, fmt=OUT_SC16):
+    def __init__(self, nshards, nch, delt, nsamp, blocks_per_slot, depth=3, flags=0, devices=None, fmt=OUT_SC16, noise=None):
         self.nshards, self.nch, self.nsamp = nshards, nch, nsamp
         self.fmt = fmt  # OUT_SC8(shift) / OUT_SC1: the sink's iq points at packed bytes (iq_view(iq, nblocks, nsamp, fmt))
         dev = (C.c_int * nshards)(*(devices if devices is not None else range(nshards)))
         cfg = _NodeConfig(nshards, dev, nch, delt, nsamp, blocks_per_slot, depth, flags | fmt)
         self._n = C.c_void_p()
         _chk(lib().gpsbb_node_create(C.byref(self._n), C.byref(cfg)), "gpsbb_node_create")
+        if noise is not None:
+            self.set_noise(noise)
+
+    def set_noise(self, noise):
+        """gpsbb_node_set_noise: block b of every later run at stream position noise's sample0 + b * nsamp; None: off"""
+        nz = _as_noise(noise)
+        _chk(lib().gpsbb_node_set_noise(self._n, None if nz is None else C.byref(nz)), "gpsbb_node_set_noise")
 
     def close(self):
         if self._n:
@@ -725,6 +782,90 @@ def pack_iq(iq, fmt):
         raise ValueError("1-bit output needs nsamp % 4 == 0")
     bits = (a > 0).reshape(a.shape[:-2] + (a.shape[-2] * 2,))
     return np.packbits(bits, axis=-1, bitorder="big")
+
+
+def noise_sigma(cn0_dbhz, gain=1.0, delt=1 / 2.6e6):
+    """gpsbb_noise_sigma: sigma per component (int16 LSB) of a channel of gain `gain` at C/N0 cn0_dbhz, sample period delt"""
+    return lib().gpsbb_noise_sigma(float(cn0_dbhz), float(gain), float(delt))
+
+
+def noise_table():
+    """gpsbb_noise_table: the knots K of the noise's normal deviate, int32 [NOISE_KNOTS] (Q16)"""
+    n = lib().gpsbb_noise_table(None, 0)
+    k = np.zeros(n, np.int32)
+    lib().gpsbb_noise_table(k.ctypes.data, n)
+    return k
+
+
+_PHILOX_M, _PHILOX_W = (0xD2511F53, 0xCD9E8D57), (0x9E3779B9, 0xBB67AE85)
+
+
+def philox4x32_10(ctr, key):
+    """Philox4x32-10 in numpy: ctr uint32-valued [..., 4], key (k0, k1) -> uint32 [..., 4]"""
+    c = np.asarray(ctr, np.uint64) & np.uint64(0xFFFFFFFF)
+    c0, c1, c2, c3 = c[..., 0], c[..., 1], c[..., 2], c[..., 3]
+    k0, k1 = np.uint64(int(key[0]) & 0xFFFFFFFF), np.uint64(int(key[1]) & 0xFFFFFFFF)
+    m32, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+    for _ in range(10):
+        p0, p1 = np.uint64(_PHILOX_M[0]) * c0, np.uint64(_PHILOX_M[1]) * c2
+        c0, c1, c2, c3 = ((p1 >> s32) ^ c1 ^ k0), p1 & m32, ((p0 >> s32) ^ c3 ^ k1), p0 & m32
+        k0, k1 = (k0 + np.uint64(_PHILOX_W[0])) & m32, (k1 + np.uint64(_PHILOX_W[1])) & m32
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def _s256(sigma):
+    """round(256 * sigma), halves away from zero (llround): 256 * sigma is exact, so is its fraction"""
+    x = 256.0 * float(sigma)
+    fl = math.floor(x)
+    return int(fl) + (1 if x - fl >= 0.5 else 0)
+
+
+def noise_z(u, table=None):
+    """step 2 of the definition: uint32 words -> the Q16 normal deviate z (int64)"""
+    K = np.asarray(noise_table() if table is None else table, np.int64)
+    u = np.asarray(u, np.uint64)
+    t = (np.int64(0x7FFFFFFF) - (u & np.uint64(0x7FFFFFFF)).astype(np.int64))
+    e = np.frexp((t | 64).astype(np.float64))[1].astype(np.int64) - 1
+    g = e - 6
+    r = t & ((np.int64(1) << g) - 1)
+    f = np.where(g <= 16, r << np.maximum(16 - g, 0), r >> np.maximum(g - 16, 0))
+    i = np.where(t < 64, t, 64 * (e - 5) + ((t >> g) & 63))
+    a = K[i] + (((K[np.minimum(i + 1, K.size - 1)] - K[i]) * f + 32768) >> 16)
+    return np.where((u >> np.uint64(31)) != 0, -a, a)
+
+
+def noise_host(seed, sample0, nsamp, sigma, table=None):
+    """The noise N of samples sample0 .. sample0 + nsamp - 1 (steps 1-3 of include/gpsbb.h), int32 [nsamp, 2] (I, Q): the
+    reference the GPU's noise is checked against"""
+    s = np.uint64(int(sample0)) + np.arange(int(nsamp), dtype=np.uint64)
+    m = s >> np.uint64(1)
+    m0 = int(m[0]) if nsamp else 0
+    mm = np.arange(m0, (int(m[-1]) + 1) if nsamp else m0, dtype=np.uint64)
+    ctr = np.zeros(mm.shape + (4,), np.uint64)
+    ctr[:, 0] = mm & np.uint64(0xFFFFFFFF)
+    ctr[:, 1] = mm >> np.uint64(32)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    x = philox4x32_10(ctr, (seed & 0xFFFFFFFF, seed >> 32))
+    row = (m - np.uint64(m0)).astype(np.int64)
+    col = 2 * (s & np.uint64(1)).astype(np.int64)
+    u = np.stack([x[row, col], x[row, col + 1]], axis=-1)
+    z = noise_z(u, table)
+    return ((np.int64(_s256(sigma)) * z + (1 << 23)) >> 24).astype(np.int32)
+
+
+def apply_noise(iq, seed, sample0, sigma, shift, table=None):
+    """Steps 1-4 in numpy: iq int16 [..., nsamp, 2] (consecutive blocks: one stream from sample0) -> (int16 of iq's shape,
+    components saturated): w = sat16((v + N) >> shift), what pack_iq then packs"""
+    a = np.asarray(iq, np.int16)
+    if a.ndim < 2 or a.shape[-1] != 2:
+        raise ValueError("iq of shape (..., nsamp, 2) wanted, got %r" % (a.shape,))
+    if not 0 <= int(shift) <= 7:
+        raise ValueError("noise shift outside 0..7")
+    flat = a.reshape(-1, 2).astype(np.int64)
+    n = noise_host(seed, sample0, flat.shape[0], sigma, table).astype(np.int64)
+    s = (flat + n) >> int(shift)
+    w = np.clip(s, -32768, 32767)
+    return w.astype(np.int16).reshape(a.shape), int(np.count_nonzero(w != s))
 
 
 def block_digest_host(iq):

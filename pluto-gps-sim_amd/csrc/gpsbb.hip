@@ -24,6 +24,7 @@
 
 #include "gpsbb.h"
 #include "gpsbb_kernels.hip.h"
+#include "gpsbb_noise.hip.h"
 #include "gpsbb_events.hip.h"
 #include "gpsbb_dense.hip.h"
 #include "gpsbb_walk.hip.h"
@@ -505,6 +506,8 @@ struct gpsbb {
     unsigned long long *d_hz = nullptr;
     unsigned long long *d_clip = nullptr; /* GPSBB_INFO_SC8_CLIPPED: the packing kernels add their saturated components here */
     unsigned char *d_pack = nullptr;      /* device scratch of a packed fill / gpsbb_device_pack, kept between calls */
+    int2 *d_noise_tab = nullptr;          /* the noise's knots (K[i], K[i + 1] - K[i]) and ... */
+    unsigned long long *d_nclip = nullptr; /* ... GPSBB_INFO_NOISE_CLIPPED: both on the first call with noise */
     size_t pack_cap = 0;
     int last_hip = 0;
     gpsbb_batch *scratch = nullptr;
@@ -779,6 +782,15 @@ extern "C" int gpsbb_get_info(gpsbb_t *h, int what, uint64_t *out)
         *out = v;
         return GPSBB_OK;
     }
+    case GPSBB_INFO_NOISE_CLIPPED: {
+        unsigned long long v = 0;
+        if (h->d_nclip) {
+            HIPCHK(h, hipSetDevice(h->device));
+            HIPCHK(h, hipMemcpy(&v, h->d_nclip, 8, hipMemcpyDeviceToHost));
+        }
+        *out = v;
+        return GPSBB_OK;
+    }
     case GPSBB_INFO_CHAIN_ON_DEVICE:
         *out = (uint64_t)h->last_chain_dev;
         return GPSBB_OK;
@@ -865,6 +877,10 @@ extern "C" void gpsbb_destroy(gpsbb_t *h)
         (void)hipFree(h->d_clip);
     if (h->d_pack)
         (void)hipFree(h->d_pack);
+    if (h->d_noise_tab)
+        (void)hipFree(h->d_noise_tab);
+    if (h->d_nclip)
+        (void)hipFree(h->d_nclip);
     if (h->d_digest.p)
         (void)hipFree(h->d_digest.p);
     delete h->pool;
@@ -2617,6 +2633,150 @@ extern "C" int gpsbb_device_pack(gpsbb_t *h, const int16_t *d_iq, long nblocks, 
     return GPSBB_OK;
 }
 
+/* ---- receiver noise (include/gpsbb.h gpsbb_noise_t; gpsbb_noise.hip.h) ---- */
+
+/* Phi^-1(1 - q) for 0 < q < 1: Acklam's rational approximation, then one Halley step on erfc (double precision throughout) */
+static double upper_quantile(double q)
+{
+    static const double a[6] = {-3.969683028665376e+01, 2.209460984245205e+02, -2.759285104469687e+02, 1.383577518672690e+02,
+                                -3.066479806614716e+01, 2.506628277459239e+00};
+    static const double b[5] = {-5.447609879822406e+01, 1.615858368580409e+02, -1.556989798598866e+02, 6.680131188771972e+01,
+                                -1.328068155288572e+01};
+    static const double c[6] = {-7.784894002430293e-03, -3.223964580411365e-01, -2.400758277161838e+00, -2.549732539343734e+00,
+                                4.374664141464968e+00, 2.938163982698783e+00};
+    static const double d[4] = {7.784695709041462e-03, 3.224671290700398e-01, 2.445134137142996e+00, 3.754408661907416e+00};
+    const double p = q; /* x = Phi^-1(p); the answer is -x */
+    double x;
+    if (p < 0.02425) {
+        const double r = std::sqrt(-2.0 * std::log(p));
+        x = (((((c[0] * r + c[1]) * r + c[2]) * r + c[3]) * r + c[4]) * r + c[5]) / ((((d[0] * r + d[1]) * r + d[2]) * r + d[3]) * r + 1.0);
+    } else if (p <= 1.0 - 0.02425) {
+        const double r0 = p - 0.5, r = r0 * r0;
+        x = (((((a[0] * r + a[1]) * r + a[2]) * r + a[3]) * r + a[4]) * r + a[5]) * r0 /
+            (((((b[0] * r + b[1]) * r + b[2]) * r + b[3]) * r + b[4]) * r + 1.0);
+    } else {
+        const double r = std::sqrt(-2.0 * std::log(1.0 - p));
+        x = -(((((c[0] * r + c[1]) * r + c[2]) * r + c[3]) * r + c[4]) * r + c[5]) / ((((d[0] * r + d[1]) * r + d[2]) * r + d[3]) * r + 1.0);
+    }
+    for (int k = 0; k < 2; k++) {
+        const double e = 0.5 * std::erfc(-x / std::sqrt(2.0)) - p;
+        const double u = e * std::sqrt(2.0 * M_PI) * std::exp(x * x / 2.0);
+        x = x - u / (1.0 + x * u / 2.0);
+    }
+    return -x;
+}
+
+/* the knots K of step 2 (include/gpsbb.h), computed once */
+static const int32_t *noise_knots()
+{
+    static int32_t k[NOISE_KNOTS];
+    static std::once_flag once;
+    std::call_once(once, [] {
+        for (int i = 0; i < NOISE_KNOTS; i++) {
+            double t;
+            if (i < 128) {
+                t = (double)i;
+            } else {
+                const int e = i / 64 + 5;
+                t = std::ldexp(1.0, e) + (double)(i % 64) * std::ldexp(1.0, e - 6);
+            }
+            k[i] = (int32_t)std::llround(65536.0 * upper_quantile((t + 0.5) / 4294967296.0));
+        }
+    });
+    return k;
+}
+
+extern "C" int gpsbb_noise_table(int32_t *knots, int cap)
+{
+    const int32_t *k = noise_knots();
+    if (knots)
+        for (int i = 0; i < cap && i < NOISE_KNOTS; i++)
+            knots[i] = k[i];
+    return NOISE_KNOTS;
+}
+
+extern "C" double gpsbb_noise_sigma(double cn0_dbhz, double gain, double delt)
+{
+    if (!std::isfinite(cn0_dbhz) || !(gain > 0.0) || !std::isfinite(gain) || !(delt > 0.0) || !std::isfinite(delt))
+        return NAN;
+    int32_t s[512], c[512];
+    if (!make_sincos(s, c))
+        return NAN;
+    double p1 = 0.0;
+    for (int i = 0; i < 512; i++)
+        p1 += (double)c[i] * c[i] + (double)s[i] * s[i];
+    p1 /= 512.0;
+    return std::sqrt(p1 * gain * gain / delt / (2.0 * std::pow(10.0, cn0_dbhz / 10.0)));
+}
+
+/* a gpsbb_noise_t the library takes, turned into the kernel's arguments; false: GPSBB_E_BADARG */
+static bool noise_args(const gpsbb_noise_t *nz, NoiseArgs *a)
+{
+    if (!(nz->sigma > 0.0) || !(nz->sigma <= 1048576.0) || nz->shift < 0 || nz->shift > 7)
+        return false;
+    a->key0 = (uint32_t)nz->seed;
+    a->key1 = (uint32_t)(nz->seed >> 32);
+    a->sample0 = nz->sample0;
+    a->s256 = (int)std::llround(256.0 * nz->sigma);
+    a->shift = nz->shift;
+    a->shift8 = 0;
+    return true;
+}
+
+/* the knot table on the device and the clip counter: made on the handle's first call with noise */
+static hipError_t noise_ready(gpsbb *h)
+{
+    if (h->d_noise_tab)
+        return hipSuccess;
+    const int32_t *k = noise_knots();
+    std::vector<int2> t(NOISE_KNOTS - 1);
+    for (int i = 0; i + 1 < NOISE_KNOTS; i++)
+        t[i] = make_int2(k[i], k[i + 1] - k[i]);
+    hipError_t e = hipMalloc((void **)&h->d_nclip, 8);
+    if (e == hipSuccess) e = zero_now(h, h->d_nclip, 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->d_noise_tab, t.size() * sizeof(int2));
+    if (e == hipSuccess) e = hipMemcpy(h->d_noise_tab, t.data(), t.size() * sizeof(int2), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr); /* (the table is there before any non-blocking stream reads it) */
+    if (e != hipSuccess) {
+        if (h->d_noise_tab)
+            (void)hipFree(h->d_noise_tab);
+        h->d_noise_tab = nullptr;
+    }
+    return e;
+}
+
+/* Enqueue k_noise_iq: n int16 components at src (device memory) with noise into dst (device memory, or host memory the device
+ * can write) in format fmt (0 = SC16, PACK_SC8 with a.shift8, PACK_SC1).  Returns at once.  The grid is wider than the gather's:
+ * the noise costs VALU work per sample that 32 workgroups cannot issue at the rate the formats leave the GPU */
+static hipError_t noise_launch(gpsbb *h, int fmt, const NoiseArgs &a, const int16_t *src, void *dst, size_t n, hipStream_t stream)
+{
+    const size_t nchunk = (n / 8 + PACK_UNITS - 1) / PACK_UNITS;
+    const long knob = GPSBB_KNOB_LONG("GPSBB_NOISE_WGS", 256);
+    const int gwg = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1L, knob), nchunk)); /* (no workgroup without work) */
+    if (fmt == PACK_SC8)
+        hipLaunchKernelGGL(k_noise_iq<PACK_SC8>, dim3(gwg), dim3(256), 0, stream, src, dst, n, a, h->d_noise_tab, h->d_nclip, h->d_clip);
+    else if (fmt == PACK_SC1)
+        hipLaunchKernelGGL(k_noise_iq<PACK_SC1>, dim3(gwg), dim3(256), 0, stream, src, dst, n, a, h->d_noise_tab, h->d_nclip, h->d_clip);
+    else
+        hipLaunchKernelGGL(k_noise_iq<NOISE_SC16>, dim3(gwg), dim3(256), 0, stream, src, dst, n, a, h->d_noise_tab, h->d_nclip, h->d_clip);
+    return hipGetLastError();
+}
+
+extern "C" int gpsbb_device_noise(gpsbb_t *h, const int16_t *d_src, int16_t *d_dst, long nblocks, int nsamp, const gpsbb_noise_t *nz)
+{
+    NoiseArgs a;
+    if (!h || !d_src || !d_dst || !nz || nblocks < 1 || nsamp < 1 || !noise_args(nz, &a) || (((uintptr_t)d_src | (uintptr_t)d_dst) & 1))
+        return GPSBB_E_BADARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int rc = gpsbb_sync(h); /* as gpsbb_device_pack: whatever the handle was rendering into d_src is there */
+    if (rc != GPSBB_OK)
+        return rc;
+    HIPCHK(h, noise_ready(h));
+    HIPCHK(h, noise_launch(h, NOISE_SC16, a, d_src, d_dst, (size_t)nblocks * (size_t)nsamp * 2, h->s_compute));
+    HIPCHK(h, hipStreamSynchronize(h->s_compute));
+    return GPSBB_OK;
+}
+
 /* iq_out: where the fill's bytes go on the host (nullptr: the device wrote them already); src: where they are in device memory
  * (the render, or its packed form); bytes: how many */
 static int fill_block_finish(gpsbb_t *h, gpsbb_batch *b, int nch, int nsamp, int16_t *iq_out, gpsbb_chan_state_t *end_state,
@@ -2716,8 +2876,9 @@ extern "C" int gpsbb_fill_block(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, dou
     return gpsbb_fill_block_ex(h, ch, nch, delt, nsamp, 0u, iq_out, end_state);
 }
 
-extern "C" int gpsbb_fill_block_ex(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, double delt, int nsamp, unsigned flags,
-                                   int16_t *iq_out, gpsbb_chan_state_t *end_state)
+/* gpsbb_fill_block_ex, and with na gpsbb_fill_block_noise */
+static int fill_block_impl(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, double delt, int nsamp, unsigned flags, const NoiseArgs *na,
+                           int16_t *iq_out, gpsbb_chan_state_t *end_state)
 {
     if (!h || !ch || !iq_out)
         return GPSBB_E_BADARG;
@@ -2733,6 +2894,8 @@ extern "C" int gpsbb_fill_block_ex(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, 
     if ((flags & 0xffu & ~GPSBB_FIXED_CARRIER & ~GPSBB_CHAIN_CARRIER) || fmt < 0)
         return GPSBB_E_BADARG;
     const size_t out_bytes = out_block_bytes(fmt, (size_t)nsamp);
+    if (na)
+        HIPCHK(h, noise_ready(h));
     g_push_trace.start();
     b->one_stream = GPSBB_KNOB_LONG("GPSBB_FILL_ONE_STREAM", 1) != 0;
     int rc = batch_setup(b, ch, 1, nch, delt, nsamp, flags & GPSBB_FIXED_CARRIER, b->one_stream ? h->s_compute : h->s_seed);
@@ -2751,23 +2914,45 @@ extern "C" int gpsbb_fill_block_ex(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, 
     }
     /* a packed format: rendered into the handle's buffer, then packed on the same stream — straight into the registered buffer, or
      * into device scratch that is copied out as the int16 block would be */
-    rc = gpsbb_batch_run(b, fmt ? nullptr : direct);
+    /* (with noise, every format goes this way: the noise kernel reads the render and writes the bytes that leave) */
+    rc = gpsbb_batch_run(b, (fmt || na) ? nullptr : direct);
     if (rc != GPSBB_OK)
         return rc;
     PUSH_MARK("launches");
     const void *src = b->last_iq;
-    if (fmt) {
+    if (fmt || na) {
         void *dst = direct;
         if (!dst) {
             HIPCHK(h, pack_reserve(h, out_bytes));
             dst = h->d_pack;
             src = h->d_pack;
         }
-        HIPCHK(h, pack_launch(h, fmt, shift, b->last_iq, dst, (size_t)nsamp * 2, b->last_cs));
+        if (na) {
+            NoiseArgs a = *na;
+            a.shift8 = shift;
+            HIPCHK(h, noise_launch(h, fmt, a, b->last_iq, dst, (size_t)nsamp * 2, b->last_cs));
+        } else {
+            HIPCHK(h, pack_launch(h, fmt, shift, b->last_iq, dst, (size_t)nsamp * 2, b->last_cs));
+        }
     }
     rc = fill_block_finish(h, b, nch, nsamp, direct ? nullptr : iq_out, end_state, src, out_bytes);
     g_push_trace.end();
     return rc;
+}
+
+extern "C" int gpsbb_fill_block_ex(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, double delt, int nsamp, unsigned flags,
+                                   int16_t *iq_out, gpsbb_chan_state_t *end_state)
+{
+    return fill_block_impl(h, ch, nch, delt, nsamp, flags, nullptr, iq_out, end_state);
+}
+
+extern "C" int gpsbb_fill_block_noise(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, double delt, int nsamp, unsigned flags,
+                                      const gpsbb_noise_t *nz, void *iq_out, gpsbb_chan_state_t *end_state)
+{
+    NoiseArgs a;
+    if (nz && !noise_args(nz, &a))
+        return GPSBB_E_BADARG;
+    return fill_block_impl(h, ch, nch, delt, nsamp, flags, nz ? &a : nullptr, static_cast<int16_t *>(iq_out), end_state);
 }
 
 /* the reference's own channel_t[] / gain[] in, rendered, updated in place as its loop leaves them; fixed: the build without
@@ -2858,6 +3043,9 @@ struct gpsbb_stream {
     double delt = 0.0;
     unsigned flags = 0;
     int fmt = 0, shift = 0; /* output format of the host gather (GPSBB_OUT_*: 0 int16, PACK_SC8, PACK_SC1) */
+    bool noise_on = false;  /* gpsbb_stream_set_noise: the gather adds noise (k_noise_iq) */
+    NoiseArgs noise{};      /* ... its arguments, sample0 = where the last set_noise put the stream */
+    unsigned long long noise_pos = 0; /* the stream position of the next push's first sample */
     struct Slot {
         gpsbb_batch *batch = nullptr;
         int16_t *h_iq = nullptr;            /* pinned */
@@ -2990,6 +3178,27 @@ extern "C" int gpsbb_stream_reset(gpsbb_stream_t *s)
         s->fx_phase[i] = 0;
     }
     s->head = s->tail = 0;
+    s->noise_pos = s->noise.sample0;
+    return GPSBB_OK;
+}
+
+extern "C" int gpsbb_stream_set_noise(gpsbb_stream_t *s, const gpsbb_noise_t *nz)
+{
+    if (!s || (s->flags & GPSBB_STREAM_DEVICE_ONLY))
+        return GPSBB_E_BADARG;
+    if (!nz) {
+        s->noise_on = false;
+        return GPSBB_OK;
+    }
+    NoiseArgs a;
+    if (!noise_args(nz, &a))
+        return GPSBB_E_BADARG;
+    HIPCHK(s->h, hipSetDevice(s->h->device));
+    HIPCHK(s->h, noise_ready(s->h));
+    a.shift8 = s->shift;
+    s->noise = a;
+    s->noise_pos = a.sample0;
+    s->noise_on = true;
     return GPSBB_OK;
 }
 
@@ -3194,7 +3403,12 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
     if (sl.h_iq) {
         const bool sdma = GPSBB_KNOB_SET("GPSBB_GATHER_SDMA"); /* experiment: the runtime's copy instead */
         const int gwg = (int)GPSBB_KNOB_LONG("GPSBB_GATHER_WGS", 32);
-        if (s->fmt) {
+        if (s->noise_on) {
+            /* noise on the way out, in any format: the noise kernel reads the render and writes the pinned slot */
+            NoiseArgs a = s->noise;
+            a.sample0 = s->noise_pos;
+            HIPCHK(h, noise_launch(h, s->fmt, a, b->d_iq.p, sl.h_iq, (size_t)s->bps * s->nsamp * 2, cs));
+        } else if (s->fmt) {
             /* packed on the way out: the same launch that returns at once, fewer bytes over the bus */
             HIPCHK(h, pack_launch(h, s->fmt, s->shift, b->d_iq.p, sl.h_iq, (size_t)s->bps * s->nsamp * 2, cs));
         } else if (sdma) {
@@ -3231,6 +3445,8 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
     memcpy(s->rough_phase, rough_next, sizeof rough_next);
     memcpy(s->fx_prn, fx_prn_next, sizeof fx_prn_next);
     memcpy(s->fx_phase, fx_phase_next, sizeof fx_phase_next);
+    if (s->noise_on)
+        s->noise_pos += (unsigned long long)s->bps * (unsigned long long)s->nsamp;
     s->head++;
     poison.armed = false;
     g_push_trace.end();

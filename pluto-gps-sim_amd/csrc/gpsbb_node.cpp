@@ -80,6 +80,7 @@ struct Shard {
         std::vector<gpsbb_chan_t> desc; /* bps * nch descriptors, the first block's carrier phases exact */
     };
     std::deque<FedSlot> fed;
+    bool noise_set = false; /* the shard's ring has noise set (gpsbb_stream_set_noise) */
 };
 
 } /* namespace */
@@ -117,6 +118,9 @@ struct gpsbb_node {
     int carry_prn[GPSBB_MAX_CHAN] = {};
     double carry_phase[GPSBB_MAX_CHAN] = {}; /* the exact phase (the accumulator, fixed-point carrier) at pend's first block */
     double feed_t0 = 0.0, feed_chain_s = 0.0;
+    /* gpsbb_node_set_noise: block b of a run is at stream position noise.sample0 + b * nsamp */
+    bool noise_on = false;
+    gpsbb_noise_t noise{};
 };
 
 extern "C" int gpsbb_node_plan(long nblocks, int nshards, int blocks_per_slot, long *first)
@@ -210,8 +214,17 @@ inline bool digest_at_render(const gpsbb_node *n)
 {
     return (n->digest_out != nullptr && (n->cfg.flags & GPSBB_NODE_DEVICE_ONLY) != 0) || (n->cfg.flags & GPSBB_NODE_DIGESTS) != 0;
 }
-inline int shard_push(gpsbb_node *n, Shard &s, const gpsbb_chan_t *desc, unsigned flags)
+/* b0: the push's first block in the stream, where its noise starts */
+inline int shard_push(gpsbb_node *n, Shard &s, const gpsbb_chan_t *desc, unsigned flags, long b0)
 {
+    if (n->noise_on || s.noise_set) {
+        gpsbb_noise_t nz = n->noise;
+        nz.sample0 += (uint64_t)b0 * (uint64_t)n->cfg.nsamp;
+        const int rc = gpsbb_stream_set_noise(s.st, n->noise_on ? &nz : nullptr);
+        if (rc != GPSBB_OK)
+            return rc;
+        s.noise_set = n->noise_on;
+    }
     if (digest_at_render(n))
         flags |= GPSBB_PUSH_DIGEST;
     return flags ? gpsbb_stream_push_ex(s.st, desc, flags) : gpsbb_stream_push(s.st, desc);
@@ -301,7 +314,7 @@ int run_shard_interleaved(gpsbb_node *n, Shard &s)
             for (int i = 0; i < nch; i++)
                 if (s.slot_desc[i].prn > 0)
                     s.slot_desc[i].carr_phase = seeds[(size_t)b0 * nch + i];
-            rc = shard_push(n, s, s.slot_desc.data(), GPSBB_PUSH_NEW_CHAIN);
+            rc = shard_push(n, s, s.slot_desc.data(), GPSBB_PUSH_NEW_CHAIN, b0);
             if (rc != GPSBB_OK)
                 return rc;
             pushed++;
@@ -364,7 +377,7 @@ int run_shard_feed(gpsbb_node *n, Shard &s)
                 n->cv.notify_all(); /* room for the feeder */
             }
             /* (one shard: consecutive slots of one stream, the ring's own chain carries the phase across them) */
-            rc = shard_push(n, s, slot.desc.data(), c.nshards == 1 ? 0u : GPSBB_PUSH_NEW_CHAIN);
+            rc = shard_push(n, s, slot.desc.data(), c.nshards == 1 ? 0u : GPSBB_PUSH_NEW_CHAIN, slot.slot * bps);
             if (rc != GPSBB_OK)
                 return rc;
             flying.emplace_back(slot.slot * bps, slot.nb);
@@ -465,7 +478,7 @@ int run_shard(gpsbb_node *n, Shard &s)
                         s.slot_desc[i].carr_phase = seed[i];
                 src = s.slot_desc.data();
             }
-            rc = shard_push(n, s, src, 0u);
+            rc = shard_push(n, s, src, 0u, b0);
             if (rc != GPSBB_OK)
                 return rc;
             pushed++;
@@ -638,6 +651,18 @@ extern "C" int gpsbb_node_create(gpsbb_node_t **out, const gpsbb_node_config_t *
         return rc;
     }
     *out = n;
+    return GPSBB_OK;
+}
+
+extern "C" int gpsbb_node_set_noise(gpsbb_node_t *n, const gpsbb_noise_t *nz)
+{
+    if (!n || (n->cfg.flags & GPSBB_NODE_DEVICE_ONLY) || n->feeding)
+        return GPSBB_E_BADARG;
+    if (nz && (!(nz->sigma > 0.0) || !(nz->sigma <= 1048576.0) || nz->shift < 0 || nz->shift > 7))
+        return GPSBB_E_BADARG;
+    n->noise_on = nz != nullptr;
+    if (nz)
+        n->noise = *nz;
     return GPSBB_OK;
 }
 
@@ -959,7 +984,8 @@ extern "C" int gpsbb_node_slot_digests(gpsbb_node_t *n, int shard, uint64_t *dig
 
 extern "C" int gpsbb_node_run_digest(gpsbb_node_t *n, const gpsbb_chan_t *ch, long nblocks, uint64_t *digests, gpsbb_node_stats_t *stats)
 {
-    if (!n || !digests || (n->cfg.flags & GPSBB_OUT_FORMAT_MASK)) /* the digests are of int16 blocks: a packed host ring has none */
+    /* the digests are of int16 blocks: a packed host ring has none, nor has one with noise */
+    if (!n || !digests || (n->cfg.flags & GPSBB_OUT_FORMAT_MASK) || n->noise_on)
         return GPSBB_E_BADARG;
     n->digest_out = digests;
     const int rc = gpsbb_node_run(n, ch, nblocks, digest_sink, n, stats);

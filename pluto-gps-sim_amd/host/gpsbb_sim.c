@@ -32,7 +32,12 @@
  * clamp(v >> shift, -128, 127) with -q shift (default 5: no component of the reference's tables clips at 16 channels; gps-sdr-sim
  * fixes 4 and wraps), or 1-bit packed I/Q (v > 0, MSB first; nsamp % 4 == 0).  The GPU packs them on their way to the host, so
  * fewer bytes cross the bus.  The single-handle paths report how many 8-bit components saturated.  Default -b 16: int16 as ever.
+ * -W cn0[,shift] adds receiver noise (include/gpsbb.h gpsbb_noise_t) at a C/N0 of cn0 dB-Hz for a gain-1.0 channel (the reference's
+ * zenith normalisation, path loss 1.0 at 20 200 km), w = sat16((v + N) >> shift) with shift 0..7 (default 0) before the sample
+ * format packs it; -w seed picks the noise (default 1).  Block b is at stream position b * nsamp on every path, so -k keeps the
+ * bytes of the full file.  The single-handle paths report how many components the noise saturated.
  */
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -136,12 +141,15 @@ static int cmp_double(const void *a, const void *b)
     return x < y ? -1 : (x > y ? 1 : 0);
 }
 
-/* -b 8: how many components the shift let saturate (gpsbb_fill_block_ex / the ring's packing kernel counted them) */
-static void report_clipped(gpsbb_t *bb, int bits)
+/* -b 8: how many components the shift let saturate (gpsbb_fill_block_ex / the ring's packing kernel counted them); -W: how many
+ * the noise did */
+static void report_clipped(gpsbb_t *bb, int bits, int noise)
 {
     uint64_t clipped = 0;
     if (bits == 8 && gpsbb_get_info(bb, GPSBB_INFO_SC8_CLIPPED, &clipped) == GPSBB_OK)
         fprintf(stderr, "8-bit components clipped: %llu\n", (unsigned long long)clipped);
+    if (noise && gpsbb_get_info(bb, GPSBB_INFO_NOISE_CLIPPED, &clipped) == GPSBB_OK)
+        fprintf(stderr, "noise components clipped: %llu\n", (unsigned long long)clipped);
 }
 
 static void usage(void)
@@ -149,6 +157,7 @@ static void usage(void)
     fprintf(stderr, "usage: gpsbb-sim -e nav [-l lat,lon,h|-c x,y,z|-u motion.csv] [-t Y/M/D,h:m:s] [-T] [-i] [-3]\n"
                     "                 [-s fs_hz] [-d seconds] [-n samples_per_block] [-N channels] [-g gpu[,gpu...]] [-F] [-G shards [-C [-I]]]\n"
                     "                 [-P usec_per_block] [-Q device_queue_blocks] [-S stats.json] [-k keep,blocks] [-b 1|8|16] [-q shift]\n"
+                    "                 [-W cn0_dbhz[,shift]] [-w seed]\n"
                     "                 -o out.bin\n");
 }
 
@@ -175,8 +184,10 @@ int main(int argc, char **argv)
     const char *stats_path = NULL;
     const char *out_path = NULL;
     int bits = 16, shift = 5;
+    const char *noise_arg = NULL;
+    unsigned long long noise_seed = 1;
 
-    while ((opt = getopt(argc, argv, "e:u:c:l:s:Tt:in:N:d:o:g:3FG:P:S:k:Q:ICRb:q:")) != -1) {
+    while ((opt = getopt(argc, argv, "e:u:c:l:s:Tt:in:N:d:o:g:3FG:P:S:k:Q:ICRb:q:W:w:")) != -1) {
         switch (opt) {
         case 'e': cfg.navfile = optarg; break;
         case 'u': cfg.motion_file = optarg; break;
@@ -229,6 +240,8 @@ int main(int argc, char **argv)
         case 'R': no_register = 1; break; /* the drop-in call copies into iq_buff instead of rendering straight into it */
         case 'b': bits = atoi(optarg); break;
         case 'q': shift = atoi(optarg); break;
+        case 'W': noise_arg = optarg; break;
+        case 'w': noise_seed = strtoull(optarg, NULL, 0); break;
         default: usage(); return 1;
         }
     }
@@ -247,6 +260,33 @@ int main(int argc, char **argv)
     }
     const double delt = 1.0 / (double)fs_hz; /* c:2397 */
     const long nblocks = (long)(duration * 10.0 + 0.5);
+    /* -W: the noise, checked before anything is opened; block b starts at stream position b * nsamp on every path */
+    gpsbb_noise_t nz;
+    memset(&nz, 0, sizeof nz);
+    const gpsbb_noise_t *noise = NULL;
+    if (noise_arg) {
+        char *end = NULL;
+        const double cn0 = strtod(noise_arg, &end);
+        int nshift = 0, ok = end != noise_arg && isfinite(cn0);
+        if (ok && *end == ',') {
+            char *e2 = NULL;
+            const long v = strtol(end + 1, &e2, 10);
+            ok = e2 != end + 1 && *e2 == 0 && v >= 0 && v <= 7;
+            nshift = (int)v;
+        } else {
+            ok = ok && *end == 0;
+        }
+        nz.sigma = ok ? gpsbb_noise_sigma(cn0, 1.0, delt) : NAN;
+        if (!ok || !(nz.sigma > 0.0) || nz.sigma > 1048576.0) {
+            fprintf(stderr, "ERROR: -W wants a finite C/N0 in dB-Hz and a shift of 0..7 (cn0[,shift]), sigma <= 2^20\n");
+            return 1;
+        }
+        nz.seed = noise_seed;
+        nz.shift = nshift;
+        noise = &nz;
+        fprintf(stderr, "noise: C/N0 %.2f dB-Hz at gain 1.0, sigma %.1f LSB per component, shift %d, seed %llu\n", cn0, nz.sigma,
+                nshift, (unsigned long long)noise_seed);
+    }
 
     gpsfe_t *fe = NULL;
     int rc = gpsfe_open(&cfg, &fe);
@@ -286,6 +326,8 @@ int main(int argc, char **argv)
         gpsbb_node_t *node = NULL;
         gpsbb_node_stats_t ns;
         rc = gpsbb_node_create(&node, &nc);
+        if (rc == GPSBB_OK && noise)
+            rc = gpsbb_node_set_noise(node, noise);
         if (rc == GPSBB_OK && contiguous) {
             gpsfe_generate(fe, (int)nblocks, all);
             rc = gpsbb_node_run(node, all, nblocks, node_sink, &o, &ns);
@@ -334,6 +376,8 @@ int main(int argc, char **argv)
         gpsbb_stream_t *st = NULL;
         gpsbb_chan_t *slot = malloc((size_t)bps * cfg.max_chan * sizeof *slot);
         rc = slot ? gpsbb_stream_create(bb, cfg.max_chan, delt, (int)nsamp, bps, depth, GPSBB_CHAIN_CARRIER | oflags, &st) : GPSBB_E_NOMEM;
+        if (rc == GPSBB_OK && noise)
+            rc = gpsbb_stream_set_noise(st, noise); /* from block 0: every push moves the position on by its blocks */
         long pushed = 0, written = 0;
         while (rc == GPSBB_OK && slot && written < nblocks) {
             while (rc == GPSBB_OK && pushed < nblocks && gpsbb_stream_pending(st) < depth) {
@@ -356,7 +400,7 @@ int main(int argc, char **argv)
             fprintf(stderr, "ERROR: streaming: %s\n", gpsbb_strerror(rc));
         if (st)
             gpsbb_stream_destroy(st);
-        report_clipped(bb, bits);
+        report_clipped(bb, bits, noise != NULL);
         free(slot);
         if (fout != stdout)
             fclose(fout);
@@ -406,7 +450,12 @@ int main(int argc, char **argv)
             iq_registered = iq; /* iq_buff is one allocation for the run (c:2604): rendered into directly from here on */
         struct timespec ta, tb;
         clock_gettime(CLOCK_MONOTONIC, &ta);
-        rc = gpsbb_fill_block_ex(bb, ch, cfg.max_chan, delt, (int)nsamp, oflags, iq, st); /* replaces c:2690-2756 */
+        if (noise) {
+            nz.sample0 = (uint64_t)blk * (uint64_t)nsamp;
+            rc = gpsbb_fill_block_noise(bb, ch, cfg.max_chan, delt, (int)nsamp, oflags, &nz, iq, st);
+        } else {
+            rc = gpsbb_fill_block_ex(bb, ch, cfg.max_chan, delt, (int)nsamp, oflags, iq, st); /* replaces c:2690-2756 */
+        }
         clock_gettime(CLOCK_MONOTONIC, &tb);
         lat_ms[blk] = ts_ms(&tb, &ta);
         if (rc != GPSBB_OK) { /* the buffer holds no valid block: it must not reach the sink */
@@ -457,7 +506,7 @@ int main(int argc, char **argv)
     if (gpsbb_get_hazards(bb, &hz, 0) == GPSBB_OK && (hz.itable_512 || hz.dwrd_oob))
         fprintf(stderr, "note: latent out-of-bounds cases of the reference hit: table %llu, nav words %llu\n",
                 (unsigned long long)hz.itable_512, (unsigned long long)hz.dwrd_oob);
-    report_clipped(bb, bits);
+    report_clipped(bb, bits, noise != NULL);
     gpsbb_destroy(bb);
     gpsfe_close(fe);
     fprintf(stderr, "%ld blocks of %ld samples written\n", blk, nsamp);
