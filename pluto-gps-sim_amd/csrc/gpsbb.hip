@@ -473,28 +473,28 @@ constexpr int CHAIN_SEG_MIN_TILES = 16; /* ... but no segment shorter than this 
 constexpr int CHAIN_SEG_MAX = 8;        /* segments per block at most */
 constexpr int CHAIN_INDEP_MIN_TILES = 1024; /* independent blocks of at least this many tiles are cut into segments as well */
 constexpr long CHAIN_MODEL_MAX_SEGS = 4096; /* segments per channel up to which pass B starts from the host's drift model */
-constexpr unsigned STREAM_SEED_STREAMS = 4; /* pre-passes of a stream's pushes in flight.  Round 6, the lap-parallel pre-pass beside a synthesis
+constexpr unsigned STREAM_SEED_STREAMS = 2; /* pre-passes of a stream's pushes in flight.  Round 6, the lap-parallel pre-pass beside a synthesis
                                                kernel that keeps every CU to the end of its launch: for ONE handle 2, 3 and 4 give the same rate
-                                               (5.43 - 5.60e11, tools/sweep_seed_streams.sh; 3.2 / 3.1 / 3.6 - 4.3 ms of pre-pass per push: what is
-                                               in flight shares the slots the synthesis leaves) — but a second handle in the process (the node
-                                               driver's shard beside the host's own handle: bench.py's node_driver.one_shard) ran at 0.73 of the
-                                               headline with 3 and at 0.86 - 0.96 with 4 (tools/node_leg_exp.sh): which streams end up sharing a
-                                               hardware queue depends on how many each handle creates */
+                                               (5.43 - 5.60e11 at 12 hardware queues, tools/sweep_seed_streams.sh: what is in flight shares the
+                                               slots the synthesis leaves).  Two it is: with the synthesis stream and the process's null stream
+                                               that makes the four hardware queues HIP maps streams onto by default, so every one of them has a
+                                               queue to itself: a pre-pass that shares a queue with the synthesis, or with a stream that holds a
+                                               wait for one, runs after it and not beside it */
 
 struct gpsbb {
     int device = 0;
-    hipStream_t s_seed = nullptr;    /* NCO seeding pre-pass (k_seed) and descriptor uploads            */
-    hipStream_t s_more[SEED_STREAMS_MAX - 1] = {}; /* ... further ones, created on first use: every other batch, batches
-                                                      that keep several pre-passes in flight, the pushes of a stream
-                                                      (see batch_launch and seed_stream_at) */
-    hipStream_t s_upload = nullptr;  /* descriptors and plans of a set-up: a stream of their own, so that they never queue
-                                        behind an older push's pre-pass */
+    /* The streams.  gpsbb_create makes the first three: with the process's null stream they are what the steady state
+     * of a chained ring or of a re-run batch keeps busy, one hardware queue each at HIP's default of four.  The others exist once
+     * something has asked for them. */
+    hipStream_t s_seed = nullptr;    /* pre-pass: the descriptor and plan uploads of a set-up, then the NCO pre-pass (k_lap_*, k_seed, ...) */
+    hipStream_t s_more[SEED_STREAMS_MAX - 1] = {}; /* ... [0] the second one: every other batch, every other push of a stream, every other
+                                                      run of a batch with three table sets (batch_prepass_stream); [1..] experiments only */
     unsigned batches_created = 0;
-    hipStream_t s_compute = nullptr; /* synthesis kernel (k_synth)                                      */
-    hipStream_t s_compute2 = nullptr; /* ... of every other launch: consecutive synthesis kernels work on different table sets and
-                                         output ranges, so the head of one may fill the CUs the tail of the other leaves idle */
+    hipStream_t s_compute = nullptr; /* synthesis kernel, and what merely follows it in order: a device-only ring's end states and digests */
+    hipStream_t s_compute2 = nullptr; /* (experiments, GPSBB_TWO_COMPUTE_STREAMS: the synthesis of every other launch; created on first use) */
     unsigned compute_turn = 0;
-    hipStream_t s_copy = nullptr;    /* device-to-host gather                                            */
+    hipStream_t s_copy = nullptr;    /* host-bound output of a ring: gather, pack and noise kernels into pinned memory; created by the first
+                                        push that has any.  A device-only ring never touches it */
     hipStream_t s_digest = nullptr;  /* gpsbb_slot_digest, created on first use: a stream nothing else waits on (the copy stream holds a
                                         wait for every push in flight: a digest queued there ran when the whole ring had drained) */
     std::vector<uint32_t> h_ca;      /* host copy of the C/A chips (seeding of small batches on the host)  */
@@ -547,6 +547,31 @@ struct gpsbb {
         }
     } d_digest;
 };
+
+/* every stream the handle has created, in no particular order */
+template <class F>
+static void for_each_stream(const gpsbb *h, F f)
+{
+    for (hipStream_t st : {h->s_seed, h->s_compute, h->s_compute2, h->s_copy, h->s_digest})
+        if (st)
+            f(st);
+    for (hipStream_t st : h->s_more)
+        if (st)
+            f(st);
+}
+
+/* Wait for everything the handle has enqueued, whichever stream holds it: before memory any of it may touch is freed,
+ * unregistered or read by the host (gpsbb_sync, the destroy calls, gpsbb_host_unregister).  An idle stream costs a call. */
+static hipError_t drain_streams(const gpsbb *h)
+{
+    hipError_t first = hipSuccess;
+    for_each_stream(h, [&](hipStream_t st) {
+        const hipError_t e = hipStreamSynchronize(st);
+        if (first == hipSuccess)
+            first = e;
+    });
+    return first;
+}
 
 template <class T>
 struct DevBuf {
@@ -680,6 +705,7 @@ struct gpsbb_batch {
     hipEvent_t last_done = nullptr;
     bool synth_pending[NSETS] = {};
     hipEvent_t upload_done = nullptr; /* descriptors and plans of the last set-up are on the device */
+    hipStream_t upload_stream = nullptr; /* ... the stream that carried them */
     int nsets = 2;                    /* table sets in use: run k works on set k % nsets */
     unsigned run_count = 0;
     int last_set = 0;
@@ -798,11 +824,8 @@ extern "C" int gpsbb_get_info(gpsbb_t *h, int what, uint64_t *out)
         *out = (uint64_t)h->last_prepass;
         return GPSBB_OK;
     case GPSBB_INFO_STREAMS: {
-        uint64_t n = 0;
-        for (hipStream_t st : {h->s_seed, h->s_upload, h->s_compute, h->s_compute2, h->s_copy, h->s_digest})
-            n += st != nullptr;
-        for (hipStream_t st : h->s_more)
-            n += st != nullptr;
+        uint64_t n = 1; /* the process's null stream: the library's blocking copies run there, and it holds a hardware queue */
+        for_each_stream(h, [&](hipStream_t) { n++; });
         *out = n;
         return GPSBB_OK;
     }
@@ -850,21 +873,7 @@ extern "C" void gpsbb_destroy(gpsbb_t *h)
         (void)hipHostUnregister(r.host);
     h->host_regs.clear();
     chain_only_free(h);
-    if (h->s_seed)
-        (void)hipStreamSynchronize(h->s_seed);
-    for (hipStream_t st : h->s_more)
-        if (st)
-            (void)hipStreamSynchronize(st);
-    if (h->s_upload)
-        (void)hipStreamSynchronize(h->s_upload);
-    if (h->s_compute)
-        (void)hipStreamSynchronize(h->s_compute);
-    if (h->s_compute2)
-        (void)hipStreamSynchronize(h->s_compute2);
-    if (h->s_copy)
-        (void)hipStreamSynchronize(h->s_copy);
-    if (h->s_digest)
-        (void)hipStreamSynchronize(h->s_digest);
+    (void)drain_streams(h);
     if (h->d_tabs)
         (void)hipFree(h->d_tabs);
     if (h->d_ca)
@@ -885,21 +894,7 @@ extern "C" void gpsbb_destroy(gpsbb_t *h)
         (void)hipFree(h->d_digest.p);
     delete h->pool;
     h->pool = nullptr;
-    if (h->s_seed)
-        (void)hipStreamDestroy(h->s_seed);
-    for (hipStream_t st : h->s_more)
-        if (st)
-            (void)hipStreamDestroy(st);
-    if (h->s_upload)
-        (void)hipStreamDestroy(h->s_upload);
-    if (h->s_compute)
-        (void)hipStreamDestroy(h->s_compute);
-    if (h->s_compute2)
-        (void)hipStreamDestroy(h->s_compute2);
-    if (h->s_copy)
-        (void)hipStreamDestroy(h->s_copy);
-    if (h->s_digest)
-        (void)hipStreamDestroy(h->s_digest);
+    for_each_stream(h, [](hipStream_t st) { (void)hipStreamDestroy(st); });
     delete h;
 }
 
@@ -936,8 +931,8 @@ static hipError_t zero_now(gpsbb *h, void *ptr, size_t bytes)
             return hipMemsetAsync(ptr, 0, bytes, nullptr);
     }
 #endif
-    const hipError_t e = hipMemsetAsync(ptr, 0, bytes, h->s_upload);
-    return e != hipSuccess ? e : hipStreamSynchronize(h->s_upload);
+    const hipError_t e = hipMemsetAsync(ptr, 0, bytes, h->s_seed);
+    return e != hipSuccess ? e : hipStreamSynchronize(h->s_seed);
 }
 
 typedef void (*EvKernelFn)(BatchDev, int16_t *);
@@ -948,10 +943,12 @@ extern "C" int gpsbb_create(gpsbb_t **out, int device)
     if (!out)
         return GPSBB_E_BADARG;
     *out = nullptr;
-    /* Up to nine streams carry work at the same time (six pre-pass streams, upload, compute, gather).  The HIP runtime
-     * maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and streams that share one run one after the
-     * other: a host that wants the stream rates of DESIGN.md exports GPU_MAX_HW_QUEUES=12 before its first HIP call
-     * (gpsbb-sim and bench.py do).  The library itself neither reads nor writes the environment. */
+    /* The HIP runtime maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), a new stream onto a queue of its own
+     * while there is one left, and streams that share a queue run one after the other.  The steady state of a chained ring in
+     * HBM keeps three streams of the handle busy — synthesis and two pre-passes, created here, first — which with the
+     * process's null stream is that default.  A ring with host-bound output adds the copy stream: a host that runs one
+     * exports GPU_MAX_HW_QUEUES=5 or more before its first HIP call.  The library itself neither reads
+     * nor writes the environment. */
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev)
         return GPSBB_E_NODEVICE;
@@ -989,14 +986,11 @@ extern "C" int gpsbb_create(gpsbb_t **out, int device)
         const long sp = GPSBB_KNOB_LONG("GPSBB_SYNTH_STREAM_PRIO", 0);
         if (sp != 0) {
             if ((e = hipStreamCreateWithPriority(&h->s_compute, hipStreamNonBlocking, (int)sp)) != hipSuccess) return fail(e);
-            if ((e = hipStreamCreateWithPriority(&h->s_compute2, hipStreamNonBlocking, (int)sp)) != hipSuccess) return fail(e);
         } else {
             if ((e = hipStreamCreateWithFlags(&h->s_compute, hipStreamNonBlocking)) != hipSuccess) return fail(e);
-            if ((e = hipStreamCreateWithFlags(&h->s_compute2, hipStreamNonBlocking)) != hipSuccess) return fail(e);
         }
     }
-    if ((e = hipStreamCreateWithFlags(&h->s_upload, hipStreamNonBlocking)) != hipSuccess) return fail(e);
-    if ((e = hipStreamCreateWithFlags(&h->s_copy, hipStreamNonBlocking)) != hipSuccess) return fail(e);
+    if ((e = create_seed_stream(&h->s_more[0])) != hipSuccess) return fail(e);
     if ((e = hipMalloc((void **)&h->d_tabs, sizeof tabs)) != hipSuccess) return fail(e);
     if ((e = hipMalloc((void **)&h->d_ca, ca.size() * 4)) != hipSuccess) return fail(e);
     if ((e = hipMalloc((void **)&h->d_status, 4)) != hipSuccess) return fail(e);
@@ -1566,6 +1560,7 @@ static int batch_setup(gpsbb_batch *b, const gpsbb_chan_t *ch, int nblocks, int 
     if (!b->upload_done)
         HIPCHK(h, hipEventCreateWithFlags(&b->upload_done, hipEventDisableTiming));
     HIPCHK(h, hipEventRecord(b->upload_done, upload_stream));
+    b->upload_stream = upload_stream;
     b->ran = false;
     return GPSBB_OK;
 }
@@ -1605,7 +1600,7 @@ static hipError_t create_seed_stream(hipStream_t *st)
     return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
 }
 
-/* seeding stream k of the handle (0 = s_seed), created on first use */
+/* pre-pass stream k of the handle (0 = s_seed, 1 = s_more[0]: both from gpsbb_create; further ones on first use) */
 static hipError_t seed_stream_at(gpsbb *h, unsigned k, hipStream_t *out)
 {
     if (k == 0 || k >= (unsigned)SEED_STREAMS_MAX) {
@@ -1628,17 +1623,37 @@ static hipError_t use_second_seed_stream(gpsbb_batch *b)
     return seed_stream_at(b->h, 1, &b->seed_stream);
 }
 
+/* The pre-pass stream of a batch's NEXT launch; the set-up of that launch uploads on the same stream, ahead of the pre-pass,
+ * so neither waits for an event of the other.  Consecutive launches that may overlap take the handle's two pre-pass streams in
+ * turn, so that two pre-passes are in flight beside the synthesis:
+ *  - a batch with three or more table sets: run by run (two streams however many sets: a third pre-pass in flight bought nothing,
+ *    tools/sweep_seed_streams.sh, and would want a fifth hardware queue);
+ *  - a stream's slot with the device-side chain (b->d_carry set by the push, one table set): push by push (a pre-pass is a chain
+ *    of latency-bound kernels, and the ring delivers one push per (that / streams));
+ *  - anything else: the stream the batch was given when it was created (every other batch, every other slot). */
+static hipError_t batch_prepass_stream(gpsbb_batch *b, bool chain_on_device, hipStream_t *out)
+{
+    gpsbb *h = b->h;
+    *out = b->one_stream ? h->s_compute : b->seed_stream;
+    if (b->one_stream)
+        return hipSuccess;
+    if (b->nsets > 2) {
+        const unsigned base = b->seed_stream == h->s_seed ? 0u : 1u;
+        return seed_stream_at(h, (base + b->run_count) % std::min((unsigned)(b->nsets - 1), STREAM_SEED_STREAMS), out);
+    }
+    if (b->d_carry && chain_on_device) {
+        const unsigned nseed = (unsigned)GPSBB_KNOB_LONG("GPSBB_STREAM_SEED_STREAMS", STREAM_SEED_STREAMS);
+        return seed_stream_at(h, b->stream_turn % (nseed >= 1 && nseed <= (unsigned)SEED_STREAMS_MAX ? nseed : STREAM_SEED_STREAMS), out);
+    }
+    return hipSuccess;
+}
+
 extern "C" void gpsbb_batch_destroy(gpsbb_batch_t *b)
 {
     if (!b)
         return;
     (void)hipSetDevice(b->h->device);
-    (void)hipStreamSynchronize(b->h->s_seed);
-    for (hipStream_t st : b->h->s_more)
-        if (st)
-            (void)hipStreamSynchronize(st);
-    (void)hipStreamSynchronize(b->h->s_compute);
-    (void)hipStreamSynchronize(b->h->s_compute2);
+    (void)drain_streams(b->h); /* its tables, its output and its events: pre-pass, synthesis and copy streams may all hold work on them */
     b->d_ch.release();
     b->d_row_off.release();
     if (b->upload_done)
@@ -1709,12 +1724,12 @@ extern "C" int gpsbb_batch_create(gpsbb_t *h, const gpsbb_chan_t *ch, int nblock
             return e2 == hipErrorOutOfMemory ? GPSBB_E_NOMEM : GPSBB_E_HIP;
         }
     }
-    int rc = batch_setup(b, ch, nblocks, nch, delt, nsamp, flags, h->s_upload);
+    int rc = batch_setup(b, ch, nblocks, nch, delt, nsamp, flags, b->seed_stream);
     if (rc != GPSBB_OK) {
         gpsbb_batch_destroy(b);
         return rc;
     }
-    HIPCHK(h, hipStreamSynchronize(h->s_upload));
+    HIPCHK(h, hipStreamSynchronize(b->seed_stream));
     *out = b;
     return GPSBB_OK;
 }
@@ -2089,19 +2104,10 @@ static int batch_launch(gpsbb_batch *b, int16_t *d_iq)
     /* The pre-pass runs on a seeding stream of its own: it may start as soon as the synthesis kernel that last
      * read this table set has finished, i.e. it overlaps the synthesis of the runs before it.  With three sets
      * consecutive runs take the handle's two seeding streams in turn, so that two pre-passes are in flight. */
-    hipStream_t ss = b->one_stream ? h->s_compute : b->seed_stream;
-    if (b->one_stream) {
-    } else if (b->nsets > 2) {
-        const unsigned base = b->seed_stream == h->s_seed ? 0u : 1u;
-        HIPCHK(h, seed_stream_at(h, (base + b->run_count) % (unsigned)(b->nsets - 1), &ss));
-    } else if (b->d_carry && b->chain_dev) {
-        /* a stream's slot (one table set): consecutive pushes take the seeding streams in turn, so that as many
-         * pre-passes are in flight (a pre-pass is a chain of latency-bound kernels: ~12 ms whatever the size of the
-         * push, and the ring delivers one push per (that / streams)) */
-        const unsigned nseed = (unsigned)GPSBB_KNOB_LONG("GPSBB_STREAM_SEED_STREAMS", STREAM_SEED_STREAMS);
-        HIPCHK(h, seed_stream_at(h, b->stream_turn % (nseed >= 1 && nseed <= (unsigned)SEED_STREAMS_MAX ? nseed : STREAM_SEED_STREAMS), &ss));
-    }
-    if (b->upload_done)
+    hipStream_t ss = nullptr;
+    HIPCHK(h, batch_prepass_stream(b, b->chain_dev, &ss));
+    /* (a push's set-up uploaded on this very stream: in order already, and no wait packet ahead of the plan kernel) */
+    if (b->upload_done && b->upload_stream != ss)
         HIPCHK(h, hipStreamWaitEvent(ss, b->upload_done, 0));
     if (b->synth_pending[set])
         HIPCHK(h, hipStreamWaitEvent(ss, b->synth_done_ref[set], 0));
@@ -2262,8 +2268,11 @@ static int batch_launch(gpsbb_batch *b, int16_t *d_iq)
     /* consecutive launches take the two synthesis streams in turn — they work on different table sets (or, slots of
      * a ring, different batches) — except re-runs of a batch that has a single table set */
     hipStream_t sc = h->s_compute;
-    if (!one_cs && !b->one_stream && (b->nsets >= 2 || b->max_sets == 1) && ((h->compute_turn++) & 1u))
+    if (!one_cs && !b->one_stream && (b->nsets >= 2 || b->max_sets == 1) && ((h->compute_turn++) & 1u)) {
+        if (!h->s_compute2)
+            HIPCHK(h, hipStreamCreateWithFlags(&h->s_compute2, hipStreamNonBlocking));
         sc = h->s_compute2;
+    }
     b->last_cs = sc;
     if (sc != ss)
         HIPCHK(h, hipStreamWaitEvent(sc, ev[1], 0));
@@ -2373,14 +2382,7 @@ extern "C" int gpsbb_sync(gpsbb_t *h)
     if (!h)
         return GPSBB_E_BADARG;
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->s_upload));
-    HIPCHK(h, hipStreamSynchronize(h->s_seed));
-    for (hipStream_t st : h->s_more)
-        if (st)
-            HIPCHK(h, hipStreamSynchronize(st));
-    HIPCHK(h, hipStreamSynchronize(h->s_compute));
-    HIPCHK(h, hipStreamSynchronize(h->s_compute2));
-    HIPCHK(h, hipStreamSynchronize(h->s_copy));
+    HIPCHK(h, drain_streams(h));
     uint32_t st = 0;
     HIPCHK(h, hipMemcpy(&st, h->d_status, 4, hipMemcpyDeviceToHost));
     if (st) {
@@ -2862,7 +2864,9 @@ extern "C" int gpsbb_host_unregister(gpsbb_t *h, void *ptr)
     HIPCHK(h, hipSetDevice(h->device));
     for (size_t k = 0; k < h->host_regs.size(); k++)
         if (h->host_regs[k].host == static_cast<char *>(ptr)) {
-            HIPCHK(h, hipStreamSynchronize(h->s_compute)); /* nothing of a fill is in flight once the call has returned; make sure */
+            /* nothing of a fill is in flight once the call has returned, but a ring's gather or a batch given a pointer into the
+             * range may be, on any stream: drain them all before the mapping goes */
+            HIPCHK(h, drain_streams(h));
             HIPCHK(h, hipHostUnregister(ptr));
             h->host_regs.erase(h->host_regs.begin() + (long)k);
             return GPSBB_OK;
@@ -3076,13 +3080,7 @@ extern "C" void gpsbb_stream_destroy(gpsbb_stream_t *s)
     if (!s)
         return;
     (void)hipSetDevice(s->h->device);
-    (void)hipStreamSynchronize(s->h->s_seed);
-    for (hipStream_t st : s->h->s_more)
-        if (st)
-            (void)hipStreamSynchronize(st);
-    (void)hipStreamSynchronize(s->h->s_compute);
-    (void)hipStreamSynchronize(s->h->s_compute2);
-    (void)hipStreamSynchronize(s->h->s_copy);
+    (void)drain_streams(s->h); /* the carry, the pinned slots and the events: pre-pass, synthesis and copy streams hold work on them */
     delete s->carry;
     if (s->d_carry)
         (void)hipFree(s->d_carry);
@@ -3359,7 +3357,11 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
     b->fixed_prev_prn = fx_chain ? s->fx_prn : nullptr;
     b->fixed_prev_phase = fx_chain ? s->fx_phase : nullptr;
     PUSH_MARK("plan");
-    int rc = batch_setup(b, ch, s->bps, s->nch, s->delt, s->nsamp, run_flags, h->s_upload);
+    /* descriptors and plans go up on the stream that will run this push's pre-pass (a push promised the device-side chain gets it,
+     * or fails below) */
+    hipStream_t us = nullptr;
+    HIPCHK(h, batch_prepass_stream(b, b->d_carry != nullptr, &us));
+    int rc = batch_setup(b, ch, s->bps, s->nch, s->delt, s->nsamp, run_flags, us);
     PUSH_MARK("setup");
     b->fixed_prev_prn = nullptr;
     b->fixed_prev_phase = nullptr;
@@ -3396,9 +3398,17 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
     if (rc != GPSBB_OK)
         return rc;
     PUSH_MARK("rec");
-    /* gather on the side stream: pinned, asynchronous, overlaps the next push's kernels */
-    hipStream_t cs = h->s_copy;
-    HIPCHK(h, hipStreamWaitEvent(cs, b->last_done, 0));
+    /* Host-bound output: gather on the copy stream — pinned, asynchronous, overlaps the next push's kernels.  A device-only
+     * ring has none: its end states (and digests) merely follow the synthesis, so they ride behind it on its stream, with no
+     * event wait and no stream that holds one (a hardware queue whose head is a wait for a 1.5 ms kernel runs nothing that
+     * shares it until then). */
+    hipStream_t cs = b->last_cs;
+    if (sl.h_iq) {
+        if (!h->s_copy)
+            HIPCHK(h, hipStreamCreateWithFlags(&h->s_copy, hipStreamNonBlocking));
+        cs = h->s_copy;
+        HIPCHK(h, hipStreamWaitEvent(cs, b->last_done, 0));
+    }
     PUSH_MARK("wait");
     if (sl.h_iq) {
         const bool sdma = GPSBB_KNOB_SET("GPSBB_GATHER_SDMA"); /* experiment: the runtime's copy instead */

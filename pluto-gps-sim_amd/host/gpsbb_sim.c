@@ -163,8 +163,9 @@ static void usage(void)
 
 int main(int argc, char **argv)
 {
-    /* libgpsbb keeps up to nine HIP streams busy; the runtime's default of four hardware queues would make unrelated
-     * streams share one.  This is the host's call (before its first HIP call); the library does not touch the environment. */
+    /* This program runs host-bound rings, one handle per shard: more streams than the runtime's default of four hardware
+     * queues (three per handle, a copy stream each, the null stream), and streams that share a queue run one
+     * after the other.  This is the host's call (before its first HIP call); the library does not touch the environment. */
     setenv("GPU_MAX_HW_QUEUES", "12", 0);
     gpsfe_config_t cfg;
     memset(&cfg, 0, sizeof cfg);
