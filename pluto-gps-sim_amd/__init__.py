@@ -92,6 +92,8 @@ PUSH_NEW_CHAIN = 1
 PUSH_DIGEST = 2
 NODE_MAX_SHARDS = 64
 INFO_SC8_CLIPPED = 11
+INFO_LAST_VARIANT = 13  # GPSBB_VARIANT_*: which synthesis kernel exactly
+VARIANT_SYNTH, VARIANT_EV, VARIANT_EV_DENSE, VARIANT_PD_WIDE, VARIANT_PD_NARROW, VARIANT_EV_FIXED = 1, 2, 3, 4, 5, 6
 # output formats of the host-bound paths (include/gpsbb.h GPSBB_OUT_*): the `fmt=` of fill_block / stream / Node / device_pack
 OUT_SC16 = 0
 OUT_SC1 = 2 << 8
@@ -960,7 +962,20 @@ def synth_descriptors(nblocks, nch=16, seed=0x5EED, max_doppler=5000.0, first=0,
     return ch
 
 
-def grazing_descriptors(nblocks, nch, fs, nsamp, offsets, seed=1, max_doppler=5000.0, fixed=False, samples=None, tol=0.25):
+def code_rate_for(sc, fs):
+    """An f_code whose individually rounded product with delt = 1 / fs (c:2709) is exactly `sc` chips per sample: searched
+    among the doubles next to sc * fs.  None if there is none (not every product is reachable at every rate)."""
+    delt = 1.0 / fs
+    f = sc * fs
+    for _ in range(200):
+        p = f * delt
+        if p == sc:
+            return f
+        f = math.nextafter(f, math.inf if p < sc else -math.inf)
+    return None
+
+
+def grazing_descriptors(nblocks, nch, fs, nsamp, offsets, seed=1, max_doppler=5000.0, fixed=False, samples=None, tol=0.25, f_code=None):
     """Adversarial descriptors for the model kernels (k_synth_ev / k_synth_pd): every (block, channel) is aimed so that
     ONE of its NCOs lands within `k` units of 2^-32 of an integer AT a chosen sample n — the reference's own state there,
     not the linear model's: the phase is refined with the exact jump-ahead (gpsbb_nco.h through the experiments build's
@@ -968,11 +983,14 @@ def grazing_descriptors(nblocks, nch, fs, nsamp, offsets, seed=1, max_doppler=50
     where floor() of an in-tile model (c:2697 table index, c:2737 chip) can disagree with the reference and where an index
     or chip change falls (almost) exactly on a sample; k runs over `offsets` (both signs: either side of the integer, inside
     and outside the kernels' danger band).  Channel i of block b aims its carrier when (b + i) is even, its code NCO
-    otherwise; with `fixed` (the 32-bit accumulator is exact) always the code.  Returns (descriptors, targets)."""
+    otherwise; with `fixed` (the 32-bit accumulator is exact) always the code.  f_code: a code rate (Hz; one, or one per
+    channel) in place of 1.023e6 + f_carr / 1540, applied before aiming.  Returns (descriptors, targets)."""
     from fractions import Fraction
     L = exp_lib()
     rng = np.random.default_rng(seed)
     ch = synth_descriptors(nblocks, nch=nch, seed=seed, max_doppler=max_doppler)
+    if f_code is not None:
+        ch["f_code"] = np.broadcast_to(np.asarray(f_code, np.float64), (nch,))[None, :]
     delt = 1.0 / fs
     unit = Fraction(1, 1 << 32)
     targets = []

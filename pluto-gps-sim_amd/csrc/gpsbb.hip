@@ -527,6 +527,7 @@ struct gpsbb {
     int opt_chain_where = 0;  /* GPSBB_CHAIN_CARRIER: 0 automatic (on the device wherever the pre-pass runs there), 1 host threads,
                                  2 as 0 with the fix-up walking the blocks in order (k_chain_fix instead of k_chain_fix_par) */
     int last_kernel = 0;      /* synthesis kernel of the last launch: 1 per-sample, 2 breakpoint */
+    int last_variant = 0;     /* ... and which one exactly: GPSBB_VARIANT_* */
     int last_chain_dev = 0;   /* the last launch resolved GPSBB_CHAIN_CARRIER on the device */
     int last_prepass = 0;     /* pre-pass of the last launch: 1 row walks on the device, 2 host threads, 3 lap-parallel on the device */
     struct DigestBuf { /* gpsbb_device_digest's scratch, kept between calls */
@@ -788,6 +789,9 @@ extern "C" int gpsbb_get_info(gpsbb_t *h, int what, uint64_t *out)
     switch (what) {
     case GPSBB_INFO_LAST_KERNEL:
         *out = (uint64_t)h->last_kernel;
+        return GPSBB_OK;
+    case GPSBB_INFO_LAST_VARIANT:
+        *out = (uint64_t)h->last_variant;
         return GPSBB_OK;
     case GPSBB_INFO_EXACT_RUNS:
     case GPSBB_INFO_CHAIN_FALLBACKS:
@@ -2321,9 +2325,13 @@ static int batch_launch(gpsbb_batch *b, int16_t *d_iq)
             hipLaunchKernelGGL(ev_kernel(p.st_log2, false), grid, dim3(EV_WG),
                                sizeof(EvLdsLean) + EV_PICK_LDS, sc, p, d_iq);
         h->last_kernel = 2;
+        /* (the same order as the launches above; a digest-fused instantiation is the same variant) */
+        h->last_variant = b->ev_all_dense ? (b->nch <= PD_WIDE_CHAN ? GPSBB_VARIANT_PD_WIDE : GPSBB_VARIANT_PD_NARROW)
+                          : (b->ev_dense ? GPSBB_VARIANT_EV_DENSE : (p.kph0 ? GPSBB_VARIANT_EV_FIXED : GPSBB_VARIANT_EV));
         h->last_chain_dev = b->chain_dev && !b->chain_indep ? 1 : 0;
     } else {
         h->last_kernel = 1;
+        h->last_variant = GPSBB_VARIANT_SYNTH;
         h->last_chain_dev = b->chain_dev && !b->chain_indep ? 1 : 0;
         /* Workgroups per block: enough of them to oversubscribe the chip ~3x (tiles are handed out
          * dynamically in chunks, so the tail is short), never more than there are chunks; the per-block

@@ -44,7 +44,8 @@ typedef float v2f __attribute__((ext_vector_type(2)));
  * 8 * 2^-33.9 * 2^32 = 2.2, code 2 * 0.27; the tile state's and the first sample's fma half a unit each, the 15 additions
  * after it 7.5 (NOT random: the fraction of dy / dx the format drops is the same at every addition, so the half units pile
  * up): 11.24.  MEASURED over every tile of the corner workloads (tools/model_err.py): 8.55.  Round 3 had 12 here — 7 % above
- * the sum; the band is now more than twice what is realised. */
+ * the sum; the band is now more than twice what is realised.  The same along the code-rate axis (f_code*delt just above
+ * 1/15.5, 0.5 and 543/1040 - 2^-45, the chip table's reach, at 25 and 2.6 MS/s): carrier 8.52, code 6.1 (0.305 of the band). */
 #ifndef GPSBB_PD_BAND
 #define GPSBB_PD_BAND 20
 #endif

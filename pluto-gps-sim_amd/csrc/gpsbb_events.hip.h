@@ -54,7 +54,8 @@ constexpr int EV_KC_MAX = 4;                       /* carrier breakpoints a run 
 constexpr int EV_AMP_PAD = EV_KC_MAX;              /* table entries repeated after [511] */
 constexpr int EV_AMP_STRIDE = 512 + EV_AMP_PAD + 4;
 constexpr int EV_CHIP_LEN = 1024 + 544;            /* chips 0 .. 1567: a tile's model phase never passes 1023 + 1040*sc; the host admits
-                                                      sc up to (EV_CHIP_LEN - 1026) / 1040 = 0.52 chips per sample (1.96 MS/s) */
+                                                      1023 + 1040*sc + 2 <= EV_CHIP_LEN (ev_plan), i.e. sc up to (EV_CHIP_LEN - 1025) /
+                                                      1040 = 543/1040 = 0.522 chips per sample (1.96 MS/s) */
 constexpr int EV_KC_DENSE = EV_KC_MAX + 1;         /* EvConst::kc of a channel that is evaluated sample by sample (ev_dense) */
 #ifndef GPSBB_EV_CHUNK
 #define GPSBB_EV_CHUNK 4

@@ -22,7 +22,12 @@ are committed and are what the tests use on the GPU box, where /root/reference d
                  30 s maintenance gives channel 10 from PRN 11 (set) straight to PRN 18 (risen): allocateChannel's
                  fresh carrier phase must not be replaced by the departed satellite's
 
-Each file holds, per kept block: the descriptors the reference's front end produced, the first 4096 IQ
+  contract_corners.npz  the verbatim sample loop on the corner table of tests/contract_corners.py (code rates at every planner
+                 threshold, gains at the admission limit, peaks of +-32766, IEEE and fixed-point carrier): per case the
+                 descriptors, fs, nsamp, the SHA-256 of the loop's IQ and its end states.  `make_golden.py --contract-corners`
+                 writes this file alone
+
+Each other file holds, per kept block: the descriptors the reference's front end produced, the first 4096 IQ
 samples, the SHA-256 of the whole block's IQ bytes, and the channel state after the block.
 """
 import hashlib
@@ -51,8 +56,24 @@ def keep(iq, desc, st, blocks):
                 iq_prefix=iq[blocks, :PREFIX].copy(), iq_sha256=np.array([sha(iq[b]) for b in blocks]))
 
 
+def contract_corners():
+    import contract_corners as cc
+    cases = cc.table(load_package())
+    refs = {False: ob.RefLoop(""), True: ob.RefLoop("_fixed")}
+    shas, sts = [], []
+    for c in cases:
+        iq, st = refs[c["fixed"]].fill(c["ch"], 1.0 / c["fs"], c["nsamp"])
+        shas.append(sha(iq))
+        sts.append(st)
+    np.savez_compressed(os.path.join(HERE, "contract_corners.npz"), **cc.fixture_arrays(cases, shas, sts))
+    print("contract_corners: %d cases" % len(cases))
+
+
 def main():
     assert ob.have_ref(), "build oracle/_ref first (make -C oracle ref)"
+    contract_corners()
+    if "--contract-corners" in sys.argv:
+        return
     nav = os.path.join(HERE, "synth3540.14n")
     dense = os.path.join(HERE, "dense3540.14n")
     motion = os.path.join(HERE, "circle_motion.csv")

@@ -1052,6 +1052,17 @@ def test_stream_soak_small(pkg):
     fuzz_parity.stream_soak(types.SimpleNamespace(cases=30, seed=3, nsamp_max=200000, budget=3e7, ties=False, also_batch=True))
 
 
+def test_code_rate_soak_small(pkg):
+    """A slice of tools/fuzz_parity.py --code-rates: random batches whose channels each have a code rate drawn log-uniformly
+    from the whole contract (f_code*delt in [2^-20, 1.5]) and gains whose sum reaches the model kernels' admission limit
+    (either sign, some blocks just over it), IEEE and fixed-point carrier, chained or not, every pre-pass and either kernel
+    choice: bit-exact against the oracle, the first block also through the drop-in call."""
+    import types
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import fuzz_parity
+    fuzz_parity.batch_soak(types.SimpleNamespace(cases=40, seed=5, shapes=False, ev=False, only=-1, code_rates=True))
+
+
 def test_low_rate_soak_with_the_exact_path_forced_often(pkg, request):
     """k_synth_pd's rare path made common: the experiments build with the danger threshold of its models raised from 24 to
     2^22 units of 2^-32 (one test in a thousand instead of one in 10^8 sends a lane to pd_fix_sample: most wavefronts
@@ -1102,9 +1113,13 @@ def test_states_that_graze_an_integer_at_a_sample(pkg, synth, oracle, fs, nch, n
     or code phase (c:2737) is within 0, +-1, +-2 ... +-48 units of 2^-32 of an integer exactly at a sample — either side
     of it, inside the kernels' danger band (exact path) and just outside it (the model is trusted) — at run starts, run
     ends, tile edges and the block's last sample.  Everything bit-exact against the oracle, in every mode."""
+    graze(pkg, synth, oracle, fs, nch, nsamp, dopp, fixed, samples)
+
+
+def graze(pkg, synth, oracle, fs, nch, nsamp, dopp, fixed, samples, f_code=None):
     nb = 5
     ch, targets = pkg.grazing_descriptors(nb, nch, fs, nsamp, GRAZE_OFFSETS, seed=int(fs) % 1000 + nch, max_doppler=dopp,
-                                          fixed=fixed, samples=samples)
+                                          fixed=fixed, samples=samples, f_code=f_code)
     assert all(abs(t[5] - t[4]) <= 0.3 for t in targets), "the generator missed a target"
     flags = pkg.FIXED_CARRIER if fixed else 0
     want_iq, want_st, _ = oracle.fill_blocks(ch, 1.0 / fs, nsamp, fixed=fixed)
@@ -1116,6 +1131,35 @@ def test_states_that_graze_an_integer_at_a_sample(pkg, synth, oracle, fs, nch, n
     assert (iq == want_iq).all()
     for k in range(nb):
         assert_state_equal(st[k], want_st[k], ch["prn"][k] > 0)
+
+
+# the products f_code*delt ev_plan decides on (tests/contract_corners.py): the floor of the model kernels, a slow code, either
+# side of one chip change per run, and the last product the chip table reaches
+GRAZE_SC = {"2^-20": 2.0 ** -20, "1e-4": 1e-4, "1/15.5-": float(np.nextafter(1 / 15.5, 0.0)),
+            "1/15.5+": float(np.nextafter(np.nextafter(1 / 15.5, 1.0), 1.0)), "0.5": 0.5, "543/1040-": 543.0 / 1040.0 - 2.0 ** -45}
+
+
+@pytest.mark.parametrize("fs,nch,nsamp,dopp,fixed,samples,sc", [
+    (25e6, 16, 70001, 5000.0, False, None, "2^-20"),                              # k_synth_ev, rsc = 2^20
+    (25e6, 16, 70001, 5000.0, False, [16, 15, 1008, 1023, 1024, 1025, 2047, 70000, 69985, 5000, 777], "1e-4"),
+    (25e6, 16, 70001, 5000.0, False, None, "1/15.5-"),                            # ... its last product
+    (25e6, 16, 70001, 5000.0, True, None, "1/15.5-"),                             # k_synth_ev_fixed there
+    (25e6, 12, 70001, 5000.0, False, None, "1/15.5+"),                            # k_synth_pd at 25 MS/s: its first product
+    (25e6, 16, 70001, 5000.0, False, None, "0.5"),
+    (25e6, 12, 70001, 5000.0, False, [64, 63, 960, 1023, 1024, 1087, 70000, 69937, 4097], "543/1040-"),   # the chip table's reach
+    (25e6, 16, 70001, 5000.0, True, None, "543/1040-"),
+    (2.6e6, 12, 70001, 20000.0, False, None, "1/15.5+"),
+    (2.6e6, 16, 70001, 20000.0, False, None, "0.5"),
+    (2.6e6, 12, 70001, 20000.0, False, [64, 63, 960, 1023, 1024, 1087, 70000, 69937, 4097], "543/1040-"),
+    (2.6e6, 16, 70001, 5000.0, True, None, "543/1040-"),
+    (1e6, 16, 70001, 5000.0, False, None, "2^-20"),                               # k_synth_ev_dense: slow code, fast carriers
+])
+def test_code_rates_that_graze_an_integer_at_a_sample(pkg, synth, oracle, fs, nch, nsamp, dopp, fixed, samples, sc):
+    """test_states_that_graze_an_integer_at_a_sample along the code-rate axis: every channel at one of the products
+    f_code*delt the planner decides on, reached exactly, with the code NCO (and the carrier, as there) aimed at integers."""
+    f_code = pkg.code_rate_for(GRAZE_SC[sc], fs)
+    assert f_code is not None and f_code * (1.0 / fs) == GRAZE_SC[sc]
+    graze(pkg, synth, oracle, fs, nch, nsamp, dopp, fixed, samples, f_code=f_code)
 
 
 def test_the_failure_the_round_3_budgets_allowed(pkg, synth, oracle, request):
@@ -1157,7 +1201,7 @@ def test_the_failure_the_round_3_budgets_allowed(pkg, synth, oracle, request):
 def test_model_error_budgets_are_measured_not_summed(pkg, request):
     """The bit-exactness of k_synth_ev / k_synth_pd rests on |in-tile model - reference recurrence| <= W (EvConst::W,
     PD_BAND).  tools/model_err.py replays, on the experiments build of the same sources, the fast paths' own arithmetic
-    next to the reference's recurrence stepped sample by sample for every tile of 19 workloads at the corners of what
+    next to the reference's recurrence stepped sample by sample for every tile of 31 workloads at the corners of what
     the kernels take (gpsbb_modelerr.hip.h).  Asserted: no unflagged decision differs from the truth; the replay flags
     exactly the lane-runs the kernel itself sent to the exact path; the realised error of everything tested is at most HALF
     its budget; the plain linear model stays within the derived 2^-33.9 (0.27 units; EV_MODEL_ERR allows 1)."""

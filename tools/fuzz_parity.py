@@ -172,10 +172,19 @@ def main():
     ap.add_argument("--also-batch", action="store_true", help="--stream: every case also as one chained batch and as a batch of independent blocks")
     ap.add_argument("--nsamp-max", type=int, default=200000, help="--stream: longest block")
     ap.add_argument("--budget", type=float, default=3e7, help="--stream: channel-samples per case (what the CPU oracle has to walk)")
+    ap.add_argument("--code-rates", action="store_true",
+                    help="batches: every channel's code rate drawn log-uniformly over the contract (f_code*delt in [2^-20, 1.5]) "
+                         "instead of 1.023e6 + f_carr/1540, and gains whose sum(512*|gain| + 1) goes up to the model kernels' "
+                         "admission limit of 32768 (one block in five just over it), either sign")
     ap.add_argument("--only", type=int, default=-1, help="render this case only (the others' random numbers are drawn all the same)")
     a = ap.parse_args()
     if a.stream:
         return stream_soak(a)
+    return batch_soak(a)
+
+
+def batch_soak(a):
+    os.environ.setdefault("GPU_MAX_HW_QUEUES", "12")
     import torch  # noqa: F401  (first: the HIP runtime)
     from __graft_entry__ import load_package
     import oracle_binding as ob
@@ -188,6 +197,7 @@ def main():
     shapes = [(25e6, 1 << 24, 2, 1), (2.6e6, 777, 12, 3000), (10e6, 1, 16, 5000), (25e6, 1024 * 300 + 1, 16, 3),
               (25e6, 2500000, 16, 6), (1e6, 5000000, 3, 2)]
     used = {}
+    variants = {}
     prepass = {}
     REG_SAMPLES = 400000
     reg_buf = np.zeros((REG_SAMPLES, 2), np.int16)
@@ -206,6 +216,8 @@ def main():
             if a.shapes:
                 fs, nsamp, nch, nblocks = shapes[case // 2]
                 fixed, mode = False, (1, 3)[case % 2]
+            if getattr(a, "code_rates", False):
+                nsamp = max(nsamp, 3000)
             if a.ev:
                 fs = float(rng.choice([16e6, 16.368e6, 20e6, 25e6, 30e6, 2.0 ** 25, 50e6, 61.44e6]))
                 nsamp = int(rng.choice([rng.integers(1, 3000), rng.integers(3000, 300000), 1024 * int(rng.integers(1, 200))]))
@@ -220,6 +232,30 @@ def main():
                 if nch > 1:
                     ch["f_carr"][:, 1] = 1e-9 * fs
             ch["f_code"] = 1.023e6 + ch["f_carr"] / 1540.0
+            if getattr(a, "code_rates", False):
+                # the code-rate and gain axes of the contract: sc = f_code*delt log-uniform in [2^-20, 1.5] per channel (per
+                # block-channel in one case out of three), now and then every channel on one side of a planner threshold
+                sc = 2.0 ** rng.uniform(-20.0, np.log2(1.5), size=(nblocks if rng.random() < 0.33 else 1, nch))
+                pick = rng.random()
+                if pick < 0.15:
+                    sc = np.minimum(sc, 1 / 15.6)                      # k_synth_ev / k_synth_ev_fixed country
+                elif pick < 0.45:
+                    sc = np.clip(sc, 1 / 15.4, 543.0 / 1040.0 - 1e-9)  # k_synth_pd country
+                elif pick < 0.6:
+                    sc = np.minimum(sc, 543.0 / 1040.0 - 1e-9)         # mixed: k_synth_ev_dense
+                f = np.broadcast_to(sc * fs, (nblocks, nch)).copy()
+                delt_ = 1.0 / fs
+                while (f * delt_ > 1.5).any() or (f * delt_ < 2.0 ** -20).any():
+                    f = np.where(f * delt_ > 1.5, np.nextafter(f, 0.0), np.where(f * delt_ < 2.0 ** -20, np.nextafter(f, np.inf), f))
+                ch["f_code"] = f
+                # gains: sum(512*|g| + 1) of a block at a drawn fraction of 32768, the shares drawn too, either sign
+                act = np.maximum(1, nch)
+                share = rng.dirichlet(np.ones(nch), size=nblocks)
+                total = np.where(rng.random(nblocks) < 0.2, rng.uniform(1.0, 1.3, nblocks), rng.uniform(0.05, 1.0, nblocks) ** 0.5)
+                if rng.random() < 0.3:
+                    total = np.where(total < 1.0, 1.0 - 2.0 ** -rng.integers(20, 45, nblocks), total)   # grazing the limit from below
+                g = share * ((32768.0 * total - act)[:, None]) / 512.0
+                ch["gain"] = np.where(rng.random((nblocks, nch)) < 0.5, -1.0, 1.0) * np.maximum(g, 0.0)
             if rng.random() < 0.2:
                 ch["code_phase"] = np.floor(ch["code_phase"])        # starts on chip boundaries
             if rng.random() < 0.2:
@@ -246,6 +282,7 @@ def main():
             iq, st = b.read()
             b.close()
             used[synth.info(pkg.INFO_LAST_KERNEL)] = used.get(synth.info(pkg.INFO_LAST_KERNEL), 0) + 1
+            variants[synth.info(pkg.INFO_LAST_VARIANT)] = variants.get(synth.info(pkg.INFO_LAST_VARIANT), 0) + 1
             prepass[synth.info(pkg.INFO_PREPASS)] = prepass.get(synth.info(pkg.INFO_PREPASS), 0) + 1
             what = dict(case=case, fs=fs, nsamp=nsamp, nch=nch, nblocks=nblocks, fixed=fixed, chain=chain, mode=mode, kern=kern)
             if not (iq == want_iq).all():
@@ -283,8 +320,10 @@ def main():
         synth.host_unregister(reg_buf)
     print("fuzz_parity: %d cases bit-exact (seed %d), %d of them also as the drop-in call (copied / into a registered buffer); synthesis kernel used {1: per-sample, 2: breakpoint}: %r; "
           "lane-runs recomputed exactly by the breakpoint kernel: %d; pre-pass {1: row walks, 2: host threads, 3: lap-parallel}: %r; "
-          "links that did not hold: %d, laps / blocks walked again: %d" %
-          (len(shapes) * 2 if a.shapes else a.cases, a.seed, dropin, used, exact_runs, prepass, repairs, rewalked))
+          "links that did not hold: %d, laps / blocks walked again: %d; variant {1: k_synth, 2: ev, 3: ev_dense, 4: pd wide, 5: pd narrow, "
+          "6: ev_fixed}: %r" %
+          (len(shapes) * 2 if a.shapes else a.cases, a.seed, dropin, used, exact_runs, prepass, repairs, rewalked, variants))
+    return variants
 
 
 if __name__ == "__main__":

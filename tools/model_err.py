@@ -3,7 +3,8 @@
 
 Run with the experiments build (GPSBB_PY_LIB=exp).  For a set of workloads at the corners of what k_synth_ev /
 k_synth_ev_dense / k_synth_ev_fixed / k_synth_pd take — Dopplers at the edge of every breakpoint class, both signs,
-near-zero steps, |f_carr*delt| up to the contract's 0.125, code rates up to the chip table's reach, chained batches cut
+near-zero steps, |f_carr*delt| up to the contract's 0.125, code rates up to the chip table's reach, the products f_code*delt
+on either side of every threshold of ev_plan() (2^-20, 1/15.5, 543/1040), gains at the admission limit, chained batches cut
 into segments, blocks whose last tile is partial, and the grazing descriptors of grazing_descriptors() — every batch is
 rendered (checked against the CPU oracle where asked) and then every tile of it is replayed next to the reference's own
 recurrence.  Prints one JSON object: per workload the realised maxima in units of 2^-32, the same as fractions of the
@@ -126,6 +127,35 @@ def workloads(pkg, quick):
     g, _ = pkg.grazing_descriptors(nb, 16, fs, 100000, OFFSETS, seed=42, max_doppler=300000.0,
                                    samples=[64, 63, 960, 1023, 1024, 1087, 99999, 99936, 4097])
     W.append(("pd_2p6MS_grazing_fast_carriers", g, fs, 100000, 0, True))
+
+    # ---- the code-rate axis: the products f_code*delt ev_plan decides on, every channel at the same one, reached exactly ----
+    def at_sc(nch, fs, sc, seed):
+        ch = pkg.synth_descriptors(nb, nch, seed=seed)
+        f = pkg.code_rate_for(sc, fs)
+        assert f is not None, (sc, fs)
+        ch["f_code"] = f
+        return ch
+
+    below, above = float(np.nextafter(1 / 15.5, 0.0)), float(np.nextafter(np.nextafter(1 / 15.5, 1.0), 1.0))
+    reach = 543.0 / 1040.0 - 2.0 ** -45                 # the last product the chip table reaches
+    W.append(("ev_25MS_sc_2^-20", at_sc(16, 25e6, 2.0 ** -20, 51), 25e6, 70001, 0, True))     # the floor: 1 / sc = 2^20
+    W.append(("ev_25MS_sc_1e-4", at_sc(16, 25e6, 1e-4, 52), 25e6, 70001, 0, True))
+    W.append(("ev_25MS_sc_below_1_over_15p5", at_sc(16, 25e6, below, 53), 25e6, 70001, 0, True))
+    W.append(("pd_25MS_sc_above_1_over_15p5", at_sc(12, 25e6, above, 54), 25e6, 70001, 0, True))
+    W.append(("pd_25MS_sc_0p5", at_sc(16, 25e6, 0.5, 55), 25e6, 70001, 0, True))
+    W.append(("pd_25MS_sc_chip_table_reach", at_sc(12, 25e6, reach, 56), 25e6, 70001, 0, True))
+    W.append(("pd_2p6MS_sc_above_1_over_15p5", at_sc(16, 2.6e6, above, 57), 2.6e6, 70001, 0, True))
+    W.append(("pd_2p6MS_sc_0p5", at_sc(12, 2.6e6, 0.5, 58), 2.6e6, 70001, 0, True))
+    W.append(("pd_2p6MS_sc_chip_table_reach", at_sc(16, 2.6e6, reach, 59), 2.6e6, 70001, 0, True))
+    W.append(("dense_1MS_sc_2^-20", at_sc(16, 1e6, 2.0 ** -20, 60), 1e6, 70001, 0, True))     # slow code, per-sample carriers
+    chm = pkg.synth_descriptors(nb, 16, seed=61)
+    mix = [2.0 ** -20, 1e-4, below, above, 0.25, 0.5, reach]
+    chm["f_code"] = np.array([pkg.code_rate_for(mix[i % len(mix)], 25e6) for i in range(16)])[None, :]
+    W.append(("dense_25MS_mixed_code_rates", chm, 25e6, 70001, 0, True))
+    # gains at the admission limit: sum(512*|gain| + 1) a factor 1 - 2^-40 under 32768, alternating signs (peaks of +-32750)
+    chg = pkg.synth_descriptors(nb, 16, seed=62)
+    chg["gain"] = (np.where(np.arange(16) % 2 == 0, 1.0, -1.0) * ((32768.0 - 16) / 512.0 / 16 * (1 - 2.0 ** -40)))[None, :]
+    W.append(("ev_25MS_gain_at_the_limit", chg, 25e6, 70001, 0, True))
     del rng
     return W
 
