@@ -137,6 +137,7 @@ API_SYMBOLS = [
     "gpsbb_get_info", "gpsbb_stream_reset", "gpsbb_device_affinity", "gpsbb_stream_push_ex", "gpsbb_stream_pop_digest", "gpsbb_host_register", "gpsbb_host_unregister",
     "gpsbb_out_bytes", "gpsbb_device_pack",
     "gpsbb_fill_block_noise", "gpsbb_stream_set_noise", "gpsbb_device_noise", "gpsbb_noise_sigma", "gpsbb_noise_table",
+    "gpsbb_despread_segments", "gpsbb_batch_despread", "gpsbb_cn0_estimate",
 ]
 # ... and include/gpsbb_node.h
 NODE_API_SYMBOLS = ["gpsbb_node_create", "gpsbb_node_run", "gpsbb_node_run_digest", "gpsbb_node_slot_digests", "gpsbb_node_destroy", "gpsbb_node_plan", "gpsbb_node_begin", "gpsbb_node_feed", "gpsbb_node_end",
@@ -238,6 +239,12 @@ def lib():
             L.gpsbb_noise_sigma.restype = d
             L.gpsbb_noise_table.argtypes = [vp, i]
             L.gpsbb_node_set_noise.argtypes = [vp, vp]
+        if hasattr(L, "gpsbb_batch_despread"):  # the despreading calls, as a group (an older build loaded for an A/B: tools/ab_lib.sh)
+            L.gpsbb_despread_segments.argtypes = [C.c_long, i]
+            L.gpsbb_despread_segments.restype = C.c_long
+            L.gpsbb_batch_despread.argtypes = [vp, vp, u, vp, i, vp]
+            L.gpsbb_cn0_estimate.argtypes = [vp, C.c_long, C.c_long, d]
+            L.gpsbb_cn0_estimate.restype = d
         _lib = L
     return _lib
 
@@ -265,6 +272,10 @@ def exp_lib():
         L.gpsbb_test_carr_predict.restype = d
         L.gpsbb_test_fixed_tile_index.argtypes = [C.c_uint32, C.c_int32, i]
         L.gpsbb_test_fixed_tile_index.restype = d
+        L.gpsbb_test_despread_exact.argtypes = [vp]
+        L.gpsbb_test_despread_exact.restype = C.c_ulonglong
+        L.gpsbb_test_despread_ms.argtypes = [vp]
+        L.gpsbb_test_despread_ms.restype = C.c_float
         _exp_lib = L
     return _exp_lib
 
@@ -510,6 +521,17 @@ class Batch:
 
     def device_iq(self):
         return lib().gpsbb_batch_device_iq(self._b)
+
+    def despread(self, view=OUT_SC16, noise=None, seg_tiles=1, d_iq=None):
+        """gpsbb_batch_despread: the prompt sums of every channel of the last run against its own replica, in the receiver's
+        view `view` (OUT_SC16 / OUT_SC8(shift) / OUT_SC1) of the rendered IQ, with `noise` (a Noise or a dict) applied first;
+        d_iq: a device pointer (int) to the blocks, None: the last run's internal buffer -> int64 [nblocks, nch, nseg, 2] (P.i, P.q)"""
+        nseg = despread_segments(self.nsamp, seg_tiles)
+        out = np.zeros((self.nblocks, self.nch, nseg, 2), np.int64)
+        nz = _as_noise(noise)
+        _chk(lib().gpsbb_batch_despread(self._b, None if d_iq is None else C.c_void_p(int(d_iq)), view,
+                                        None if nz is None else C.byref(nz), seg_tiles, out.ctypes.data), "gpsbb_batch_despread")
+        return out
 
 
 class Stream:
@@ -868,6 +890,64 @@ def apply_noise(iq, seed, sample0, sigma, shift, table=None):
     s = (flat + n) >> int(shift)
     w = np.clip(s, -32768, 32767)
     return w.astype(np.int16).reshape(a.shape), int(np.count_nonzero(w != s))
+
+
+# ---- despreading (include/gpsbb.h, gpsbb_batch_despread): the numpy restatement the GPU's sums are checked against ----
+
+def despread_segments(nsamp, seg_tiles):
+    """gpsbb_despread_segments: ceil(nsamp / (1024 * seg_tiles))"""
+    n = lib().gpsbb_despread_segments(int(nsamp), int(seg_tiles))
+    _chk(n if n < 0 else 0, "gpsbb_despread_segments")
+    return n
+
+
+def cn0_estimate(p, seg_seconds):
+    """gpsbb_cn0_estimate over the whole segments p: int64 [n, 2] (P.i, P.q) of one channel, each seg_seconds long -> dB-Hz
+    (NaN for n < 2, a zero variance of P.q or a mean of P.i that is not positive)"""
+    a = np.ascontiguousarray(p, np.int64)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError("segments of shape (n, 2) wanted, got %r" % (a.shape,))
+    return lib().gpsbb_cn0_estimate(a.ctypes.data, a.shape[0], 1, float(seg_seconds))
+
+
+def view_host(iq, fmt=OUT_SC16, noise=None):
+    """What a receiver of output format fmt sees of the int16 render iq [..., nsamp, 2] (consecutive blocks: one stream from
+    noise.sample0): apply_noise, then the format's quantiser, unpacked -> int64 of iq's shape (SC16: w; SC8: clamp(w >> shift,
+    -128, 127); SC1: +1 where w > 0, else -1; any nsamp)"""
+    a = np.asarray(iq, np.int16)
+    nz = _as_noise(noise)
+    if nz is not None:
+        a, _ = apply_noise(a, nz.seed, nz.sample0, nz.sigma, nz.shift)
+    f, shift = (fmt & OUT_FORMAT_MASK) >> 8, (fmt & OUT_SHIFT_MASK) >> 12
+    if fmt & ~(OUT_FORMAT_MASK | OUT_SHIFT_MASK) or f > 2 or (shift and f != 1):
+        raise ValueError("unknown output format 0x%x" % fmt)
+    w = a.astype(np.int64)
+    if f == 1:
+        return np.clip(w >> shift, -128, 127)
+    if f == 2:
+        return np.where(w > 0, 1, -1).astype(np.int64)
+    return w
+
+
+def despread_host(u, replicas, seg_tiles):
+    """The prompt sums in numpy: u [nblocks, nsamp, 2] (uI, uQ: view_host's), replicas [nblocks, nch, nsamp, 2] ((c, s) of every
+    channel; zeros for an idle one) -> int64 [nblocks, nch, nseg, 2]: P.i = sum(uI*c + uQ*s), P.q = sum(uQ*c - uI*s) over the
+    segments of 1024 * seg_tiles samples (the last one shorter)"""
+    u = np.asarray(u, np.int64)
+    r = np.asarray(replicas, np.int64)
+    if u.ndim != 3 or r.ndim != 4 or u.shape[-1] != 2 or r.shape[-1] != 2 or r.shape[0] != u.shape[0] or r.shape[2] != u.shape[1]:
+        raise ValueError("u [nblocks, nsamp, 2] and replicas [nblocks, nch, nsamp, 2] wanted, got %r and %r" % (u.shape, r.shape))
+    if seg_tiles < 1:
+        raise ValueError("seg_tiles < 1")
+    nsamp = u.shape[1]
+    seg = 1024 * int(seg_tiles)
+    edges = np.arange(0, nsamp, seg)
+    out = np.zeros((r.shape[0], r.shape[1], edges.size, 2), np.int64)
+    for b in range(r.shape[0]):   # (block by block: the products of a whole batch would be held twice over)
+        ui, uq = u[b, None, :, 0], u[b, None, :, 1]
+        out[b, :, :, 0] = np.add.reduceat(ui * r[b, :, :, 0] + uq * r[b, :, :, 1], edges, axis=1)
+        out[b, :, :, 1] = np.add.reduceat(uq * r[b, :, :, 0] - ui * r[b, :, :, 1], edges, axis=1)
+    return out
 
 
 def block_digest_host(iq):

@@ -27,6 +27,7 @@
 #include "gpsbb_noise.hip.h"
 #include "gpsbb_events.hip.h"
 #include "gpsbb_dense.hip.h"
+#include "gpsbb_despread.hip.h"
 #include "gpsbb_walk.hip.h"
 #include "gpsbb_laps.hip.h"
 #include "gpsbb_nco.h"
@@ -724,6 +725,12 @@ struct gpsbb_batch {
     bool ran = false;
     int16_t *last_iq = nullptr;
     int16_t *last_ext_iq = nullptr; /* the caller's device buffer of the last run, if it used one */
+    /* gpsbb_batch_despread's scratch, kept between calls: the sums (and behind them the count of samples that took the exact
+     * path), the tile counters */
+    DevBuf<unsigned long long> d_ds;
+    DevBuf<int32_t> d_ds_ctr;
+    unsigned long long ds_last_exact = 0;
+    hipEvent_t ds_ev[2] = {}; /* (experiments build: around the last k_despread, gpsbb_test_despread_ms) */
 };
 
 #define HIPCHK(h, call)                                                                            \
@@ -1703,6 +1710,11 @@ extern "C" void gpsbb_batch_destroy(gpsbb_batch_t *b)
         (void)hipHostFree(b->hs_tile_nav);
     b->d_iq.release();
     b->d_dig.release();
+    b->d_ds.release();
+    b->d_ds_ctr.release();
+    for (auto &e : b->ds_ev)
+        if (e)
+            (void)hipEventDestroy(e);
     for (auto &t : b->evs)
         for (auto &e : t.e)
             if (e)
@@ -2785,6 +2797,125 @@ extern "C" int gpsbb_device_noise(gpsbb_t *h, const int16_t *d_src, int16_t *d_d
     HIPCHK(h, noise_launch(h, NOISE_SC16, a, d_src, d_dst, (size_t)nblocks * (size_t)nsamp * 2, h->s_compute));
     HIPCHK(h, hipStreamSynchronize(h->s_compute));
     return GPSBB_OK;
+}
+
+/* ---- despreading: the render read back the way its consumer reads it (include/gpsbb.h, gpsbb_despread.hip.h) ---- */
+
+extern "C" long gpsbb_despread_segments(long nsamp, int seg_tiles)
+{
+    if (nsamp < 1 || seg_tiles < 1)
+        return GPSBB_E_BADARG;
+    const long len = (long)TILE * seg_tiles;
+    return (nsamp + len - 1) / len;
+}
+
+typedef void (*DsKernelFn)(BatchDev, DsArgs);
+static DsKernelFn ds_kernel(int view, bool noise, int g)
+{
+#define GPSBB_DS_ROW(V, N) {k_despread<V, N, 0>, k_despread<V, N, 1>, k_despread<V, N, 2>}
+    static const DsKernelFn k[3][2][EV_STATE_LOG2_MAX + 1] = {{GPSBB_DS_ROW(DS_SC16, false), GPSBB_DS_ROW(DS_SC16, true)},
+                                                               {GPSBB_DS_ROW(PACK_SC8, false), GPSBB_DS_ROW(PACK_SC8, true)},
+                                                               {GPSBB_DS_ROW(PACK_SC1, false), GPSBB_DS_ROW(PACK_SC1, true)}};
+#undef GPSBB_DS_ROW
+    return k[view][noise ? 1 : 0][g];
+}
+
+extern "C" int gpsbb_batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, const gpsbb_noise_t *nz, int seg_tiles,
+                                    gpsbb_corr_t *out)
+{
+    if (!b)
+        return GPSBB_E_BADARG;
+    gpsbb *h = b->h;
+    int shift8 = 0;
+    NoiseArgs na;
+    memset(&na, 0, sizeof na);
+    /* (nothing is packed here, so SC1 takes any nsamp: the format is looked up for a length it accepts) */
+    const int fmt = (view & ~(GPSBB_OUT_FORMAT_MASK | GPSBB_OUT_SHIFT_MASK)) ? -1 : out_format(view, 4, &shift8);
+    if (!out || seg_tiles < 1 || fmt < 0 || (nz && !noise_args(nz, &na)) || ((uintptr_t)d_iq & 3))
+        return GPSBB_E_BADARG;
+    if (!b->ran)
+        return GPSBB_E_STATE;
+    /* the two limits of this call: the accumulator's batches, and runs of the per-sample kernel, which leave rows and no
+     * tile states */
+    if ((b->flags & GPSBB_FIXED_CARRIER) || !b->ev)
+        return GPSBB_E_BADARG;
+    const int16_t *src = d_iq ? d_iq : b->last_iq;
+    if (!src)
+        return GPSBB_E_STATE; /* the last run rendered into the caller's buffer: it has to be named */
+    HIPCHK(h, hipSetDevice(h->device));
+    const int rc = gpsbb_sync(h);
+    if (rc != GPSBB_OK)
+        return rc;
+    if (nz)
+        HIPCHK(h, noise_ready(h));
+    const long nseg = gpsbb_despread_segments(b->nsamp, seg_tiles);
+    const size_t nsum = (size_t)b->nblocks * b->nch * (size_t)nseg * 2;
+    HIPCHK(h, (hipError_t)b->d_ds.reserve(nsum + 1));
+    HIPCHK(h, (hipError_t)b->d_ds_ctr.reserve((size_t)b->nblocks));
+    hipStream_t cs = h->s_compute;
+    HIPCHK(h, hipMemsetAsync(b->d_ds.p, 0, (nsum + 1) * sizeof(unsigned long long), cs));
+    HIPCHK(h, hipMemsetAsync(b->d_ds_ctr.p, 0, (size_t)b->nblocks * sizeof(int32_t), cs));
+    const BatchDev p = batch_dev(b, b->last_set);
+    DsArgs a;
+    memset(&a, 0, sizeof a);
+    a.iq = reinterpret_cast<const uint32_t *>(src);
+    a.out = b->d_ds.p;
+    a.n_exact = b->d_ds.p + nsum;
+    a.ctr = b->d_ds_ctr.p;
+    a.seg_tiles = seg_tiles;
+    a.nseg = (int)nseg;
+    /* a chunk never spans more segments than it must, and small batches hand their tiles out one at a time */
+    const long cus = h->sm_count > 0 ? h->sm_count : 256;
+    int chunk = seg_tiles < DS_CHUNK ? seg_tiles : DS_CHUNK;
+    while (chunk > 1 && (long)b->nblocks * (((long)b->ntiles + chunk - 1) / chunk) < cus * 8 * DS_WAVES)
+        chunk--;
+    a.chunk = chunk;
+    const long chunks = ((long)b->ntiles + chunk - 1) / chunk;
+    const long max_useful = (chunks + DS_WAVES - 1) / DS_WAVES;
+    long want = (cus * 16 + b->nblocks - 1) / b->nblocks;
+    want = want < 1 ? 1 : (want > max_useful ? max_useful : want);
+    a.wgs_per_block = (int)want;
+    a.shift8 = shift8;
+    a.danger = (uint32_t)GPSBB_KNOB_LONG("GPSBB_DS_DANGER", 2u * PD_BAND); /* (larger: more samples take the exact path; a test aid) */
+    a.nz = na;
+    a.ntab = h->d_noise_tab;
+#ifdef GPSBB_EXPERIMENTS
+    for (auto &e : b->ds_ev)
+        if (!e)
+            HIPCHK(h, hipEventCreate(&e));
+    HIPCHK(h, hipEventRecord(b->ds_ev[0], cs));
+#endif
+    hipLaunchKernelGGL(ds_kernel(fmt, nz != nullptr, p.st_log2), dim3((unsigned)(want * b->nblocks)), dim3(DS_WG), 0, cs, p, a);
+    HIPCHK(h, hipGetLastError());
+#ifdef GPSBB_EXPERIMENTS
+    HIPCHK(h, hipEventRecord(b->ds_ev[1], cs));
+#endif
+    HIPCHK(h, hipMemcpyAsync(out, b->d_ds.p, nsum * sizeof(unsigned long long), hipMemcpyDeviceToHost, cs));
+    HIPCHK(h, hipMemcpyAsync(&b->ds_last_exact, b->d_ds.p + nsum, sizeof(unsigned long long), hipMemcpyDeviceToHost, cs));
+    HIPCHK(h, hipStreamSynchronize(cs));
+    return GPSBB_OK;
+}
+
+extern "C" double gpsbb_cn0_estimate(const gpsbb_corr_t *p, long n, long stride, double seg_seconds)
+{
+    if (!p || n < 2 || stride < 1 || !(seg_seconds > 0.0) || !std::isfinite(seg_seconds))
+        return NAN;
+    double mi = 0.0, mq = 0.0;
+    for (long k = 0; k < n; k++) {
+        mi += (double)p[k * stride].i;
+        mq += (double)p[k * stride].q;
+    }
+    mi /= (double)n;
+    mq /= (double)n;
+    double vq = 0.0;
+    for (long k = 0; k < n; k++) {
+        const double d = (double)p[k * stride].q - mq;
+        vq += d * d;
+    }
+    vq /= (double)(n - 1);
+    if (!(mi > 0.0) || !(vq > 0.0))
+        return NAN;
+    return 10.0 * std::log10(mi * mi / (2.0 * seg_seconds * vq));
 }
 
 /* iq_out: where the fill's bytes go on the host (nullptr: the device wrote them already); src: where they are in device memory
@@ -4163,6 +4294,15 @@ extern "C" long long gpsbb_test_read_pattern(gpsbb_t *h, const void *d_src, size
     const hipError_t e = hipStreamSynchronize(h->s_compute);
     (void)hipFree(d_sink);
     return e == hipSuccess ? (long long)(waves * per_wave) : (long long)GPSBB_E_HIP;
+}
+
+extern "C" unsigned long long gpsbb_test_despread_exact(gpsbb_batch *b) { return b ? b->ds_last_exact : 0ull; }
+extern "C" float gpsbb_test_despread_ms(gpsbb_batch *b)
+{
+    float ms = -1.0f;
+    if (!b || !b->ds_ev[0] || !b->ds_ev[1] || hipEventElapsedTime(&ms, b->ds_ev[0], b->ds_ev[1]) != hipSuccess)
+        return -1.0f;
+    return ms;
 }
 
 #ifdef GPSBB_WG_TRACE

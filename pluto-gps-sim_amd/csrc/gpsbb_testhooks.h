@@ -39,6 +39,10 @@ double gpsbb_test_fixed_tile_index(unsigned ph0, int step, int t);
 #define GPSBB_TEST_MEC_NQ 4  /* counts per channel: wrong unflagged decisions, lanes flagged, lane-runs looked at, always-exact */
 struct gpsbb_batch;
 int gpsbb_test_model_err(struct gpsbb_batch *b, double *maxima, unsigned long long *counts, int *which);
+/* samples the batch's last gpsbb_batch_despread recomputed with the exact jump-ahead (GPSBB_DS_DANGER raises the threshold) */
+unsigned long long gpsbb_test_despread_exact(struct gpsbb_batch *b);
+/* ... and what its kernel took, by HIP events on the synthesis stream, in ms (-1: none yet) */
+float gpsbb_test_despread_ms(struct gpsbb_batch *b);
 void gpsbb_test_budgets(double out[3]); /* EV_MODEL_ERR, EV_T_EPS, PD_BAND of this build, in units of 2^-32 */
 
 #ifdef __cplusplus
