@@ -154,6 +154,12 @@ int gpsbb_node_end(gpsbb_node_t *n, gpsbb_node_stats_t *stats);
  * gpsbb_node_run_digest is GPSBB_E_BADARG (its host rings are digested from the bytes that arrive). */
 int gpsbb_node_set_noise(gpsbb_node_t *n, const gpsbb_noise_t *nz);
 
+/* Interference (include/gpsbb.h gpsbb_interf_set_t) by the same rules: block b of the stream is at position
+ * set->sample0 + b * nsamp whichever shard renders it.  set NULL: off.  While noise is set too, the later of the two calls
+ * checks that sample0 and shift are equal.  GPSBB_E_BADARG as gpsbb_node_set_noise, and for a set the interference calls
+ * refuse; while interference is set, gpsbb_node_run_digest is GPSBB_E_BADARG. */
+int gpsbb_node_set_interf(gpsbb_node_t *n, const gpsbb_interf_set_t *set);
+
 void gpsbb_node_destroy(gpsbb_node_t *n);
 
 /* which shard renders block b of an nblocks-long stream, and where the shards begin: first[0 .. nshards] (first[nshards] =

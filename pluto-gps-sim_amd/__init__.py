@@ -123,6 +123,43 @@ def _as_noise(noise):
     d = dict(noise)
     return Noise(int(d["seed"]) & 0xFFFFFFFFFFFFFFFF, int(d.get("sample0", 0)), float(d["sigma"]), int(d.get("shift", 0)), 0)
 
+
+# interference on the host-bound outputs (include/gpsbb.h gpsbb_interf_t): the `interf=` of fill_block / stream / Node / despread
+INTERF_CW, INTERF_CHIRP, INTERF_MAX = 0, 1, 4
+
+
+class Interf(C.Structure):
+    """gpsbb_interf_t: one emitter (interf_make builds it from physical units)"""
+    _fields_ = [("kind", C.c_int32), ("level_q16", C.c_uint32), ("phase0", C.c_uint64), ("step", C.c_int64), ("rate", C.c_int64),
+                ("sweep", C.c_uint32), ("pulse_period", C.c_uint32), ("pulse_on", C.c_uint32), ("pulse_offset", C.c_uint32)]
+
+
+class InterfSet(C.Structure):
+    """gpsbb_interf_set_t: n emitters, the shift of step 4, the stream position of the first sample"""
+    _fields_ = [("n", C.c_int32), ("shift", C.c_int32), ("sample0", C.c_uint64), ("e", Interf * INTERF_MAX)]
+
+    def __init__(self, emitters=(), shift=0, sample0=0):
+        super().__init__()
+        emitters = list(emitters)
+        if len(emitters) > INTERF_MAX:
+            raise ValueError("at most %d emitters" % INTERF_MAX)
+        self.n, self.shift, self.sample0 = len(emitters), int(shift), int(sample0)
+        for k, e in enumerate(emitters):
+            self.e[k] = e
+
+
+def _as_interf(interf):
+    """None, an InterfSet, or a dict with emitters and optionally shift / sample0 -> an InterfSet (or None)"""
+    if interf is None or isinstance(interf, InterfSet):
+        return interf
+    d = dict(interf)
+    return InterfSet(d.get("emitters", ()), d.get("shift", 0), d.get("sample0", 0))
+
+
+def _ref(x):
+    return None if x is None else C.byref(x)
+
+
 ERRORS = {0: "GPSBB_OK", -1: "GPSBB_E_BADARG", -2: "GPSBB_E_BADCHAN", -3: "GPSBB_E_HIP", -4: "GPSBB_E_NOMEM",
           -5: "GPSBB_E_INTERNAL", -6: "GPSBB_E_NODEVICE", -7: "GPSBB_E_STATE"}
 
@@ -138,10 +175,12 @@ API_SYMBOLS = [
     "gpsbb_out_bytes", "gpsbb_device_pack",
     "gpsbb_fill_block_noise", "gpsbb_stream_set_noise", "gpsbb_device_noise", "gpsbb_noise_sigma", "gpsbb_noise_table",
     "gpsbb_despread_segments", "gpsbb_batch_despread", "gpsbb_cn0_estimate",
+    "gpsbb_interf_make", "gpsbb_interf_eval", "gpsbb_fill_block_impair", "gpsbb_stream_set_interf", "gpsbb_device_impair",
+    "gpsbb_batch_despread_impaired",
 ]
 # ... and include/gpsbb_node.h
 NODE_API_SYMBOLS = ["gpsbb_node_create", "gpsbb_node_run", "gpsbb_node_run_digest", "gpsbb_node_slot_digests", "gpsbb_node_destroy", "gpsbb_node_plan", "gpsbb_node_begin", "gpsbb_node_feed", "gpsbb_node_end",
-                    "gpsbb_node_set_noise"]
+                    "gpsbb_node_set_noise", "gpsbb_node_set_interf"]
 
 
 class GpsbbError(RuntimeError):
@@ -245,6 +284,14 @@ def lib():
             L.gpsbb_batch_despread.argtypes = [vp, vp, u, vp, i, vp]
             L.gpsbb_cn0_estimate.argtypes = [vp, C.c_long, C.c_long, d]
             L.gpsbb_cn0_estimate.restype = d
+        if hasattr(L, "gpsbb_interf_eval"):  # the interference calls, as a group (an older build loaded for an A/B: tools/ab_lib.sh)
+            L.gpsbb_interf_make.argtypes = [vp, i, d, d, d, d, d, d, d]
+            L.gpsbb_interf_eval.argtypes = [vp, C.c_uint64, C.c_long, vp]
+            L.gpsbb_fill_block_impair.argtypes = [vp, vp, i, d, i, u, vp, vp, vp, vp]
+            L.gpsbb_stream_set_interf.argtypes = [vp, vp]
+            L.gpsbb_device_impair.argtypes = [vp, vp, vp, C.c_long, i, vp, vp]
+            L.gpsbb_batch_despread_impaired.argtypes = [vp, vp, u, vp, vp, i, vp]
+            L.gpsbb_node_set_interf.argtypes = [vp, vp]
         _lib = L
     return _lib
 
@@ -344,11 +391,12 @@ class Synth:
     def __exit__(self, *a):
         self.close()
 
-    def fill_block(self, ch, delt, nsamp, flags=0, out=None, fmt=OUT_SC16, noise=None):
+    def fill_block(self, ch, delt, nsamp, flags=0, out=None, fmt=OUT_SC16, noise=None, interf=None):
         """gpsbb_fill_block(_ex): ch = CHAN_DTYPE[nch] -> (int16 [nsamp,2], STATE_DTYPE[nch]); out: the caller's iq_buff.
         fmt (OUT_SC8(shift) / OUT_SC1): the block comes back packed — int8 [nsamp, 2] / uint8 [nsamp // 4] — and `out`, if given,
         is any C-contiguous array of at least out_bytes(fmt, nsamp) bytes (a registered iq_buff: written straight into).
-        noise (a Noise or a dict: seed, sigma, sample0, shift): gpsbb_fill_block_noise."""
+        noise (a Noise or a dict: seed, sigma, sample0, shift): gpsbb_fill_block_noise.
+        interf (an InterfSet or a dict: emitters, shift, sample0): gpsbb_fill_block_impair, with or without noise."""
         ch = np.ascontiguousarray(ch, dtype=CHAN_DTYPE)
         if fmt & (OUT_FORMAT_MASK | OUT_SHIFT_MASK):
             nbytes = out_bytes(fmt, nsamp)
@@ -359,7 +407,11 @@ class Synth:
             assert buf.dtype == np.int16 and buf.flags.c_contiguous and buf.size >= 2 * nsamp
         st = np.zeros(ch.shape[0], STATE_DTYPE)
         nz = _as_noise(noise)
-        if nz is not None:
+        js = _as_interf(interf)
+        if js is not None:
+            _chk(lib().gpsbb_fill_block_impair(self._h, ch.ctypes.data, ch.shape[0], delt, nsamp, flags | fmt, _ref(nz), C.byref(js),
+                                               buf.ctypes.data, st.ctypes.data), "gpsbb_fill_block_impair")
+        elif nz is not None:
             _chk(lib().gpsbb_fill_block_noise(self._h, ch.ctypes.data, ch.shape[0], delt, nsamp, flags | fmt, C.byref(nz),
                                               buf.ctypes.data, st.ctypes.data), "gpsbb_fill_block_noise")
         else:
@@ -386,8 +438,15 @@ class Synth:
     def batch(self, ch, delt, nsamp, flags=0):
         return Batch(self, ch, delt, nsamp, flags)
 
-    def stream(self, nch, delt, nsamp, blocks_per_slot, depth=3, flags=0, fmt=OUT_SC16, noise=None):
-        return Stream(self, nch, delt, nsamp, blocks_per_slot, depth, flags, fmt, noise)
+    def stream(self, nch, delt, nsamp, blocks_per_slot, depth=3, flags=0, fmt=OUT_SC16, noise=None, interf=None):
+        return Stream(self, nch, delt, nsamp, blocks_per_slot, depth, flags, fmt, noise, interf)
+
+    def device_impair(self, d_src, nblocks, nsamp, noise, interf, d_dst=None):
+        """gpsbb_device_impair: as device_noise, with the set's interference added; noise may be None"""
+        nz, js = _as_noise(noise), _as_interf(interf)
+        dst = d_src if d_dst is None else d_dst
+        _chk(lib().gpsbb_device_impair(self._h, C.c_void_p(int(d_src)), C.c_void_p(int(dst)), nblocks, nsamp, _ref(nz), _ref(js)),
+             "gpsbb_device_impair")
 
     def device_noise(self, d_src, nblocks, nsamp, noise, d_dst=None):
         """gpsbb_device_noise: nblocks blocks of int16 IQ in device memory at d_src, with noise, into d_dst (default: in place)"""
@@ -522,13 +581,18 @@ class Batch:
     def device_iq(self):
         return lib().gpsbb_batch_device_iq(self._b)
 
-    def despread(self, view=OUT_SC16, noise=None, seg_tiles=1, d_iq=None):
+    def despread(self, view=OUT_SC16, noise=None, seg_tiles=1, d_iq=None, interf=None):
         """gpsbb_batch_despread: the prompt sums of every channel of the last run against its own replica, in the receiver's
         view `view` (OUT_SC16 / OUT_SC8(shift) / OUT_SC1) of the rendered IQ, with `noise` (a Noise or a dict) applied first;
         d_iq: a device pointer (int) to the blocks, None: the last run's internal buffer -> int64 [nblocks, nch, nseg, 2] (P.i, P.q)"""
         nseg = despread_segments(self.nsamp, seg_tiles)
         out = np.zeros((self.nblocks, self.nch, nseg, 2), np.int64)
         nz = _as_noise(noise)
+        js = _as_interf(interf)
+        if js is not None:  # gpsbb_batch_despread_impaired: the set's J added in the view
+            _chk(lib().gpsbb_batch_despread_impaired(self._b, None if d_iq is None else C.c_void_p(int(d_iq)), view, _ref(nz),
+                                                     C.byref(js), seg_tiles, out.ctypes.data), "gpsbb_batch_despread_impaired")
+            return out
         _chk(lib().gpsbb_batch_despread(self._b, None if d_iq is None else C.c_void_p(int(d_iq)), view,
                                         None if nz is None else C.byref(nz), seg_tiles, out.ctypes.data), "gpsbb_batch_despread")
         return out
@@ -537,7 +601,7 @@ class Batch:
 class Stream:
     """Time-sharded streaming with pinned host gather (gpsbb_stream_*)."""
 
-    def __init__(self, synth, nch, delt, nsamp, blocks_per_slot, depth=3, flags=0, fmt=OUT_SC16, noise=None):
+    def __init__(self, synth, nch, delt, nsamp, blocks_per_slot, depth=3, flags=0, fmt=OUT_SC16, noise=None, interf=None):
         self.synth = synth
         self.nch, self.nsamp, self.bps = nch, nsamp, blocks_per_slot
         self.device_only = bool(flags & STREAM_DEVICE_ONLY)
@@ -547,6 +611,13 @@ class Stream:
                                        C.byref(self._s)), "gpsbb_stream_create")
         if noise is not None:
             self.set_noise(noise)
+        if interf is not None:
+            self.set_interf(interf)
+
+    def set_interf(self, interf):
+        """gpsbb_stream_set_interf: interference on the host gather from the next push on (that push at the set's sample0);
+        None: off"""
+        _chk(lib().gpsbb_stream_set_interf(self._s, _ref(_as_interf(interf))), "gpsbb_stream_set_interf")
 
     def set_noise(self, noise):
         """gpsbb_stream_set_noise: noise on the host gather from the next push on (that push at noise's sample0); None: off"""
@@ -650,7 +721,8 @@ def device_affinity(device):
 class Node:
     """gpsbb_node_*: nshards producer threads (one handle + one ring each, bound next to their GPU), one sink."""
 
-    def __init__(self, nshards, nch, delt, nsamp, blocks_per_slot, depth=3, flags=0, devices=None, fmt=OUT_SC16, noise=None):
+    def __init__(self, nshards, nch, delt, nsamp, blocks_per_slot, depth=3, flags=0, devices=None, fmt=OUT_SC16, noise=None,
+                 interf=None):
         self.nshards, self.nch, self.nsamp = nshards, nch, nsamp
         self.fmt = fmt  # OUT_SC8(shift) / OUT_SC1: the sink's iq points at packed bytes (iq_view(iq, nblocks, nsamp, fmt))
         dev = (C.c_int * nshards)(*(devices if devices is not None else range(nshards)))
@@ -659,6 +731,12 @@ class Node:
         _chk(lib().gpsbb_node_create(C.byref(self._n), C.byref(cfg)), "gpsbb_node_create")
         if noise is not None:
             self.set_noise(noise)
+        if interf is not None:
+            self.set_interf(interf)
+
+    def set_interf(self, interf):
+        """gpsbb_node_set_interf: block b of every later run at stream position the set's sample0 + b * nsamp; None: off"""
+        _chk(lib().gpsbb_node_set_interf(self._n, _ref(_as_interf(interf))), "gpsbb_node_set_interf")
 
     def set_noise(self, noise):
         """gpsbb_node_set_noise: block b of every later run at stream position noise's sample0 + b * nsamp; None: off"""
@@ -892,6 +970,81 @@ def apply_noise(iq, seed, sample0, sigma, shift, table=None):
     return w.astype(np.int16).reshape(a.shape), int(np.count_nonzero(w != s))
 
 
+# ---- interference (include/gpsbb.h, gpsbb_interf_t): the numpy restatement the GPU's bytes are checked against ----
+
+def interf_make(kind, js_db, f0_hz, f1_hz=0.0, sweep_s=0.0, pulse_period_s=0.0, duty=1.0, delt=1 / 2.6e6):
+    """gpsbb_interf_make: an emitter from physical units (J/S in dB against a gain-1.0 channel, Hz, seconds) -> an Interf"""
+    e = Interf()
+    _chk(lib().gpsbb_interf_make(C.byref(e), int(kind), float(js_db), float(f0_hz), float(f1_hz), float(sweep_s),
+                                 float(pulse_period_s), float(duty), float(delt)), "gpsbb_interf_make")
+    return e
+
+
+def interf_eval(interf, s, n):
+    """gpsbb_interf_eval: J at samples s .. s + n - 1 by the library's host code -> int32 [n, 2] (I, Q)"""
+    js = _as_interf(interf)
+    out = np.zeros((int(n), 2), np.int32)
+    _chk(lib().gpsbb_interf_eval(C.byref(js), int(s), int(n), out.ctypes.data), "gpsbb_interf_eval")
+    return out
+
+
+def interf_host(interf, s, n):
+    """J at samples s .. s + n - 1 straight from the definition, every sample on its own, in numpy uint64 (which wraps mod 2^64
+    as the definition asks) -> int32 [n, 2] (I, Q).  s comes from the argument, not from the set."""
+    js = _as_interf(interf)
+    s, n = int(s), int(n)
+    if not 0 <= js.n <= INTERF_MAX or s < 0 or n < 0 or s + n > 1 << 63:
+        raise ValueError("emitter count or position range out of bounds")
+    M = (1 << 64) - 1
+    U = np.uint64
+    sin512, cos512 = (t.astype(np.int64) for t in sincos_tables())
+    pos = U(s) + np.arange(n, dtype=np.uint64)
+    J = np.zeros((n, 2), np.int64)
+
+    def tri(x):  # T(x) = x (x - 1) / 2, the product exact below 2^64 for x < 2^32
+        return (x * (x - U(1))) >> U(1)
+
+    with np.errstate(over="ignore"):
+        for e in list(js.e)[:js.n]:
+            F, R, ph0, G = U(e.step & M), U(e.rate & M), U(e.phase0 & M), np.int64(e.level_q16)
+            if e.kind == INTERF_CHIRP:
+                P = int(e.sweep)
+                phi = U((int(F) * P + int(R) * (P * (P - 1) // 2)) & M)
+                k, m = pos // U(P), pos % U(P)
+                theta = ph0 + k * phi + F * m + R * tri(m)
+            elif e.kind == INTERF_CW:
+                theta = ph0 + F * pos
+            else:
+                raise ValueError("unknown emitter kind %d" % e.kind)
+            idx = (theta >> U(55)).astype(np.int64)
+            j = np.stack([(G * cos512[idx] + 32768) >> 16, (G * sin512[idx] + 32768) >> 16], axis=-1)
+            if e.pulse_period:
+                on = ((pos + U(e.pulse_offset)) % U(e.pulse_period)) < U(e.pulse_on)
+                j = np.where(on[:, None], j, 0)
+            J += j
+    return J.astype(np.int32)
+
+
+def apply_impair(iq, noise, interf):
+    """Steps 1-4 with interference in numpy: iq int16 [..., nsamp, 2] (consecutive blocks: one stream from the set's sample0) ->
+    (int16 of iq's shape, components saturated): w = sat16((v + N + J) >> shift), N = 0 for noise None"""
+    a = np.asarray(iq, np.int16)
+    if a.ndim < 2 or a.shape[-1] != 2:
+        raise ValueError("iq of shape (..., nsamp, 2) wanted, got %r" % (a.shape,))
+    nz, js = _as_noise(noise), _as_interf(interf)
+    if not 0 <= js.shift <= 7:
+        raise ValueError("shift outside 0..7")
+    if nz is not None and (nz.sample0 != js.sample0 or nz.shift != js.shift):
+        raise ValueError("noise and interference disagree on sample0 or shift")
+    flat = a.reshape(-1, 2).astype(np.int64)
+    t = flat + interf_host(js, js.sample0, flat.shape[0]).astype(np.int64)
+    if nz is not None:
+        t = t + noise_host(nz.seed, nz.sample0, flat.shape[0], nz.sigma).astype(np.int64)
+    sft = t >> int(js.shift)
+    w = np.clip(sft, -32768, 32767)
+    return w.astype(np.int16).reshape(a.shape), int(np.count_nonzero(w != sft))
+
+
 # ---- despreading (include/gpsbb.h, gpsbb_batch_despread): the numpy restatement the GPU's sums are checked against ----
 
 def despread_segments(nsamp, seg_tiles):
@@ -910,13 +1063,15 @@ def cn0_estimate(p, seg_seconds):
     return lib().gpsbb_cn0_estimate(a.ctypes.data, a.shape[0], 1, float(seg_seconds))
 
 
-def view_host(iq, fmt=OUT_SC16, noise=None):
+def view_host(iq, fmt=OUT_SC16, noise=None, interf=None):
     """What a receiver of output format fmt sees of the int16 render iq [..., nsamp, 2] (consecutive blocks: one stream from
     noise.sample0): apply_noise, then the format's quantiser, unpacked -> int64 of iq's shape (SC16: w; SC8: clamp(w >> shift,
-    -128, 127); SC1: +1 where w > 0, else -1; any nsamp)"""
+    -128, 127); SC1: +1 where w > 0, else -1; any nsamp).  interf: apply_impair in apply_noise's place"""
     a = np.asarray(iq, np.int16)
     nz = _as_noise(noise)
-    if nz is not None:
+    if interf is not None:
+        a, _ = apply_impair(a, nz, interf)
+    elif nz is not None:
         a, _ = apply_noise(a, nz.seed, nz.sample0, nz.sigma, nz.shift)
     f, shift = (fmt & OUT_FORMAT_MASK) >> 8, (fmt & OUT_SHIFT_MASK) >> 12
     if fmt & ~(OUT_FORMAT_MASK | OUT_SHIFT_MASK) or f > 2 or (shift and f != 1):

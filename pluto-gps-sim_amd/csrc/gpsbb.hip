@@ -25,6 +25,7 @@
 #include "gpsbb.h"
 #include "gpsbb_kernels.hip.h"
 #include "gpsbb_noise.hip.h"
+#include "gpsbb_interf.hip.h"
 #include "gpsbb_events.hip.h"
 #include "gpsbb_dense.hip.h"
 #include "gpsbb_despread.hip.h"
@@ -2799,6 +2800,224 @@ extern "C" int gpsbb_device_noise(gpsbb_t *h, const int16_t *d_src, int16_t *d_d
     return GPSBB_OK;
 }
 
+/* ---- interference (include/gpsbb.h gpsbb_interf_t; gpsbb_interf.h, gpsbb_interf.hip.h) ---- */
+
+static_assert(sizeof(gpsbb_interf_t) == 48 && sizeof(gpsbb_interf_set_t) == 208, "gpsbb_interf_t / gpsbb_interf_set_t layout");
+static_assert(INTERF_MAX == GPSBB_INTERF_MAX, "INTERF_MAX");
+
+static const uint64_t INTERF_POS_END = 1ull << 63; /* positions stay below it */
+
+/* nearbyint(ldexp(x, 64)) for |x| <= 0.5 as a word mod 2^64 (+2^63 is -2^63 there) */
+static uint64_t interf_turns(double x)
+{
+    double r = std::nearbyint(std::ldexp(x, 64));
+    if (r >= 0x1p+63)
+        r -= 0x1p+64;
+    return (uint64_t)(int64_t)r;
+}
+
+extern "C" int gpsbb_interf_make(gpsbb_interf_t *e, int kind, double js_db, double f0_hz, double f1_hz, double sweep_s,
+                                 double pulse_period_s, double duty, double delt)
+{
+    if (!e || (kind != GPSBB_INTERF_CW && kind != GPSBB_INTERF_CHIRP) || !std::isfinite(js_db) || !std::isfinite(f0_hz) ||
+        !std::isfinite(delt) || !(delt > 0.0) || !std::isfinite(pulse_period_s) || pulse_period_s < 0.0)
+        return GPSBB_E_BADARG;
+    gpsbb_interf_t o;
+    memset(&o, 0, sizeof o);
+    o.kind = kind;
+    const double g = std::floor(std::pow(10.0, js_db / 20.0) * 65536.0 + 0.5); /* (positive: half away from zero is half up) */
+    if (!(g >= 1.0) || !(g <= 134217728.0))
+        return GPSBB_E_BADARG;
+    o.level_q16 = (uint32_t)g;
+    const double x0 = f0_hz * delt;
+    if (!(x0 >= -0.5) || !(x0 < 0.5))
+        return GPSBB_E_BADARG;
+    o.step = (int64_t)interf_turns(x0);
+    if (kind == GPSBB_INTERF_CHIRP) {
+        if (!std::isfinite(f1_hz) || !std::isfinite(sweep_s))
+            return GPSBB_E_BADARG;
+        const double P = std::nearbyint(sweep_s / delt), span = (f1_hz - f0_hz) * delt;
+        if (!(P >= 2.0) || !(P <= 4294967295.0) || !(span >= -1.0) || !(span <= 1.0))
+            return GPSBB_E_BADARG;
+        o.sweep = (uint32_t)P;
+        o.rate = (int64_t)interf_turns(span / P);
+    }
+    if (pulse_period_s > 0.0) {
+        const double T = std::nearbyint(pulse_period_s / delt);
+        if (!std::isfinite(duty) || !(duty > 0.0) || !(duty <= 1.0) || !(T >= 1.0) || !(T <= 4294967295.0))
+            return GPSBB_E_BADARG;
+        o.pulse_period = (uint32_t)T;
+        const double on = std::nearbyint(duty * T);
+        o.pulse_on = on < 1.0 ? 1u : (on > T ? o.pulse_period : (uint32_t)on);
+    }
+    *e = o;
+    return GPSBB_OK;
+}
+
+/* a set the library takes, as the kernels' arguments (the launch position is interf_at's); false: GPSBB_E_BADARG */
+static bool interf_args(const gpsbb_interf_set_t *set, InterfArgs *a)
+{
+    if (!set || set->n < 0 || set->n > GPSBB_INTERF_MAX || set->shift < 0 || set->shift > 7 || set->sample0 >= INTERF_POS_END)
+        return false;
+    memset(a, 0, sizeof *a);
+    a->n = set->n;
+    a->shift = set->shift;
+    a->sample0 = set->sample0;
+    for (int i = 0; i < set->n; i++) {
+        const gpsbb_interf_t &e = set->e[i];
+        InterfEm &o = a->e[i];
+        if (e.level_q16 < 1u || e.level_q16 > (1u << 27))
+            return false;
+        if (e.kind == GPSBB_INTERF_CW) {
+            if (e.sweep != 0u || e.rate != 0)
+                return false;
+        } else if (e.kind == GPSBB_INTERF_CHIRP) {
+            if (e.sweep < 2u)
+                return false;
+        } else {
+            return false;
+        }
+        if (e.pulse_period ? (e.pulse_on < 1u || e.pulse_on > e.pulse_period || e.pulse_offset >= e.pulse_period)
+                           : (e.pulse_on != 0u || e.pulse_offset != 0u))
+            return false;
+        o.phase0 = e.phase0;
+        o.F = (uint64_t)e.step;
+        o.R = (uint64_t)e.rate;
+        o.G = e.level_q16;
+        o.P = e.sweep;
+        if (o.P) {
+            o.Phi = o.F * (uint64_t)o.P + o.R * interf_tri(o.P);
+            o.magP = (uint64_t)((((unsigned __int128)1) << 64) / o.P);
+        }
+        if (e.pulse_period && e.pulse_on < e.pulse_period) { /* (a gate that is never off: continuous) */
+            o.period = e.pulse_period;
+            o.on = e.pulse_on;
+            o.offset = e.pulse_offset;
+            o.magG = (uint64_t)((((unsigned __int128)1) << 64) / o.period);
+        }
+    }
+    return true;
+}
+
+/* the launch's first sample s0 and its length; false: the range reaches 2^63 */
+static bool interf_at(InterfArgs *a, uint64_t s0, uint64_t nsamples)
+{
+    if (s0 >= INTERF_POS_END || nsamples > INTERF_POS_END - s0)
+        return false;
+    a->sample0 = s0;
+    for (int i = 0; i < a->n; i++) {
+        InterfEm &o = a->e[i];
+        if (o.P) {
+            o.k0 = s0 / o.P;
+            o.m0 = (uint32_t)(s0 % o.P);
+        }
+        if (o.period)
+            o.g0 = (uint32_t)((s0 + o.offset) % o.period);
+    }
+    return true;
+}
+
+namespace {
+struct InterfHostTab {
+    const int32_t *cos512, *sin512;
+    void operator()(uint32_t idx, int *c, int *s) const
+    {
+        *c = cos512[idx];
+        *s = sin512[idx];
+    }
+};
+} // namespace
+
+extern "C" int gpsbb_interf_eval(const gpsbb_interf_set_t *set, uint64_t s, long n, int32_t *jiq)
+{
+    InterfArgs a;
+    if (n < 0 || (n > 0 && !jiq) || !interf_args(set, &a) || !interf_at(&a, s, (uint64_t)n))
+        return GPSBB_E_BADARG;
+    static int32_t sn[512], cs[512];
+    static std::once_flag once;
+    static bool tabs_ok = false;
+    std::call_once(once, [] { tabs_ok = make_sincos(sn, cs); });
+    if (!tabs_ok)
+        return GPSBB_E_INTERNAL;
+    const InterfHostTab tab{cs, sn};
+    for (long i = 0; i < 2 * n; i++)
+        jiq[i] = 0;
+    /* as the kernel walks a 16-byte unit: one seek, then up to four steps */
+    for (int k = 0; k < a.n; k++)
+        for (long i = 0; i < n; i += 4) {
+            InterfPos p = interf_seek(a.e[k], a.sample0, (uint64_t)i);
+            for (long j = i; j < n && j < i + 4; j++) {
+                int ji = 0, jq = 0;
+                interf_step(a.e[k], p, tab, ji, jq);
+                jiq[2 * j] += ji;
+                jiq[2 * j + 1] += jq;
+            }
+        }
+    return GPSBB_OK;
+}
+
+/* a call with a set: the noise (or none) and the set checked together, at a launch of nsamples from the set's sample0 */
+struct ImpairCall {
+    ImpairArgs a;
+    bool noise;
+};
+static bool impair_args(const gpsbb_noise_t *nz, const gpsbb_interf_set_t *set, uint64_t nsamples, ImpairCall *c)
+{
+    memset(c, 0, sizeof *c);
+    if (nz && !noise_args(nz, &c->a.nz))
+        return false;
+    if (!interf_args(set, &c->a.it))
+        return false;
+    if (nz && (nz->sample0 != set->sample0 || nz->shift != set->shift))
+        return false;
+    if (!interf_at(&c->a.it, set->sample0, nsamples))
+        return false;
+    c->a.nz.sample0 = set->sample0;
+    c->a.nz.shift = set->shift;
+    c->noise = nz != nullptr;
+    return true;
+}
+
+/* Enqueue k_impair_iq, as noise_launch enqueues k_noise_iq (the same grid).  An empty set with noise IS the noise call. */
+static hipError_t impair_launch(gpsbb *h, int fmt, const ImpairArgs &a, bool noise, const int16_t *src, void *dst, size_t n,
+                                hipStream_t stream)
+{
+    if (noise && a.it.n == 0)
+        return noise_launch(h, fmt, a.nz, src, dst, n, stream);
+    const size_t nchunk = (n / 8 + PACK_UNITS - 1) / PACK_UNITS;
+    const int gwg = (int)std::max<size_t>(1, std::min<size_t>(256, nchunk));
+#define GPSBB_IMPAIR_GO(F, N) \
+    hipLaunchKernelGGL((k_impair_iq<F, N>), dim3(gwg), dim3(256), 0, stream, src, dst, n, a, h->d_noise_tab, h->d_tabs, h->d_nclip, h->d_clip)
+    if (fmt == PACK_SC8) {
+        if (noise) GPSBB_IMPAIR_GO(PACK_SC8, true); else GPSBB_IMPAIR_GO(PACK_SC8, false);
+    } else if (fmt == PACK_SC1) {
+        if (noise) GPSBB_IMPAIR_GO(PACK_SC1, true); else GPSBB_IMPAIR_GO(PACK_SC1, false);
+    } else {
+        if (noise) GPSBB_IMPAIR_GO(NOISE_SC16, true); else GPSBB_IMPAIR_GO(NOISE_SC16, false);
+    }
+#undef GPSBB_IMPAIR_GO
+    return hipGetLastError();
+}
+
+extern "C" int gpsbb_device_impair(gpsbb_t *h, const int16_t *d_src, int16_t *d_dst, long nblocks, int nsamp, const gpsbb_noise_t *nz,
+                                   const gpsbb_interf_set_t *set)
+{
+    if (!set)
+        return gpsbb_device_noise(h, d_src, d_dst, nblocks, nsamp, nz);
+    ImpairCall c;
+    if (!h || !d_src || !d_dst || nblocks < 1 || nsamp < 1 || (((uintptr_t)d_src | (uintptr_t)d_dst) & 1) ||
+        !impair_args(nz, set, (uint64_t)nblocks * (uint64_t)nsamp, &c))
+        return GPSBB_E_BADARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int rc = gpsbb_sync(h);
+    if (rc != GPSBB_OK)
+        return rc;
+    HIPCHK(h, noise_ready(h));
+    HIPCHK(h, impair_launch(h, NOISE_SC16, c.a, c.noise, d_src, d_dst, (size_t)nblocks * (size_t)nsamp * 2, h->s_compute));
+    HIPCHK(h, hipStreamSynchronize(h->s_compute));
+    return GPSBB_OK;
+}
+
 /* ---- despreading: the render read back the way its consumer reads it (include/gpsbb.h, gpsbb_despread.hip.h) ---- */
 
 extern "C" long gpsbb_despread_segments(long nsamp, int seg_tiles)
@@ -2819,9 +3038,34 @@ static DsKernelFn ds_kernel(int view, bool noise, int g)
 #undef GPSBB_DS_ROW
     return k[view][noise ? 1 : 0][g];
 }
+/* ... with the set's J in the view (gpsbb_batch_despread_impaired) */
+static DsKernelFn ds_kernel_interf(int view, bool noise, int g)
+{
+#define GPSBB_DS_ROW(V, N) {k_despread<V, N, 0, true>, k_despread<V, N, 1, true>, k_despread<V, N, 2, true>}
+    static const DsKernelFn k[3][2][EV_STATE_LOG2_MAX + 1] = {{GPSBB_DS_ROW(DS_SC16, false), GPSBB_DS_ROW(DS_SC16, true)},
+                                                               {GPSBB_DS_ROW(PACK_SC8, false), GPSBB_DS_ROW(PACK_SC8, true)},
+                                                               {GPSBB_DS_ROW(PACK_SC1, false), GPSBB_DS_ROW(PACK_SC1, true)}};
+#undef GPSBB_DS_ROW
+    return k[view][noise ? 1 : 0][g];
+}
+
+static int batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, const gpsbb_noise_t *nz, const gpsbb_interf_set_t *set,
+                          int seg_tiles, gpsbb_corr_t *out);
 
 extern "C" int gpsbb_batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, const gpsbb_noise_t *nz, int seg_tiles,
                                     gpsbb_corr_t *out)
+{
+    return batch_despread(b, d_iq, view, nz, nullptr, seg_tiles, out);
+}
+
+extern "C" int gpsbb_batch_despread_impaired(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, const gpsbb_noise_t *nz,
+                                             const gpsbb_interf_set_t *set, int seg_tiles, gpsbb_corr_t *out)
+{
+    return batch_despread(b, d_iq, view, nz, set, seg_tiles, out);
+}
+
+static int batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, const gpsbb_noise_t *nz, const gpsbb_interf_set_t *set,
+                          int seg_tiles, gpsbb_corr_t *out)
 {
     if (!b)
         return GPSBB_E_BADARG;
@@ -2829,6 +3073,9 @@ extern "C" int gpsbb_batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsig
     int shift8 = 0;
     NoiseArgs na;
     memset(&na, 0, sizeof na);
+    ImpairCall ic;
+    if (set && !impair_args(nz, set, (uint64_t)b->nblocks * (uint64_t)b->nsamp, &ic))
+        return GPSBB_E_BADARG;
     /* (nothing is packed here, so SC1 takes any nsamp: the format is looked up for a length it accepts) */
     const int fmt = (view & ~(GPSBB_OUT_FORMAT_MASK | GPSBB_OUT_SHIFT_MASK)) ? -1 : out_format(view, 4, &shift8);
     if (!out || seg_tiles < 1 || fmt < 0 || (nz && !noise_args(nz, &na)) || ((uintptr_t)d_iq & 3))
@@ -2879,13 +3126,15 @@ extern "C" int gpsbb_batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsig
     a.danger = (uint32_t)GPSBB_KNOB_LONG("GPSBB_DS_DANGER", 2u * PD_BAND); /* (larger: more samples take the exact path; a test aid) */
     a.nz = na;
     a.ntab = h->d_noise_tab;
+    if (set)
+        a.it = ic.a.it;
 #ifdef GPSBB_EXPERIMENTS
     for (auto &e : b->ds_ev)
         if (!e)
             HIPCHK(h, hipEventCreate(&e));
     HIPCHK(h, hipEventRecord(b->ds_ev[0], cs));
 #endif
-    hipLaunchKernelGGL(ds_kernel(fmt, nz != nullptr, p.st_log2), dim3((unsigned)(want * b->nblocks)), dim3(DS_WG), 0, cs, p, a);
+    hipLaunchKernelGGL(set ? ds_kernel_interf(fmt, nz != nullptr, p.st_log2) : ds_kernel(fmt, nz != nullptr, p.st_log2), dim3((unsigned)(want * b->nblocks)), dim3(DS_WG), 0, cs, p, a);
     HIPCHK(h, hipGetLastError());
 #ifdef GPSBB_EXPERIMENTS
     HIPCHK(h, hipEventRecord(b->ds_ev[1], cs));
@@ -3021,7 +3270,7 @@ extern "C" int gpsbb_fill_block(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, dou
 
 /* gpsbb_fill_block_ex, and with na gpsbb_fill_block_noise */
 static int fill_block_impl(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, double delt, int nsamp, unsigned flags, const NoiseArgs *na,
-                           int16_t *iq_out, gpsbb_chan_state_t *end_state)
+                           int16_t *iq_out, gpsbb_chan_state_t *end_state, const ImpairCall *ic = nullptr)
 {
     if (!h || !ch || !iq_out)
         return GPSBB_E_BADARG;
@@ -3037,7 +3286,7 @@ static int fill_block_impl(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, double d
     if ((flags & 0xffu & ~GPSBB_FIXED_CARRIER & ~GPSBB_CHAIN_CARRIER) || fmt < 0)
         return GPSBB_E_BADARG;
     const size_t out_bytes = out_block_bytes(fmt, (size_t)nsamp);
-    if (na)
+    if (na || ic)
         HIPCHK(h, noise_ready(h));
     g_push_trace.start();
     b->one_stream = GPSBB_KNOB_LONG("GPSBB_FILL_ONE_STREAM", 1) != 0;
@@ -3058,19 +3307,23 @@ static int fill_block_impl(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, double d
     /* a packed format: rendered into the handle's buffer, then packed on the same stream — straight into the registered buffer, or
      * into device scratch that is copied out as the int16 block would be */
     /* (with noise, every format goes this way: the noise kernel reads the render and writes the bytes that leave) */
-    rc = gpsbb_batch_run(b, (fmt || na) ? nullptr : direct);
+    rc = gpsbb_batch_run(b, (fmt || na || ic) ? nullptr : direct);
     if (rc != GPSBB_OK)
         return rc;
     PUSH_MARK("launches");
     const void *src = b->last_iq;
-    if (fmt || na) {
+    if (fmt || na || ic) {
         void *dst = direct;
         if (!dst) {
             HIPCHK(h, pack_reserve(h, out_bytes));
             dst = h->d_pack;
             src = h->d_pack;
         }
-        if (na) {
+        if (ic) {
+            ImpairArgs a = ic->a;
+            a.nz.shift8 = shift;
+            HIPCHK(h, impair_launch(h, fmt, a, ic->noise, b->last_iq, dst, (size_t)nsamp * 2, b->last_cs));
+        } else if (na) {
             NoiseArgs a = *na;
             a.shift8 = shift;
             HIPCHK(h, noise_launch(h, fmt, a, b->last_iq, dst, (size_t)nsamp * 2, b->last_cs));
@@ -3096,6 +3349,17 @@ extern "C" int gpsbb_fill_block_noise(gpsbb_t *h, const gpsbb_chan_t *ch, int nc
     if (nz && !noise_args(nz, &a))
         return GPSBB_E_BADARG;
     return fill_block_impl(h, ch, nch, delt, nsamp, flags, nz ? &a : nullptr, static_cast<int16_t *>(iq_out), end_state);
+}
+
+extern "C" int gpsbb_fill_block_impair(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, double delt, int nsamp, unsigned flags,
+                                       const gpsbb_noise_t *nz, const gpsbb_interf_set_t *set, void *iq_out, gpsbb_chan_state_t *end_state)
+{
+    if (!set)
+        return gpsbb_fill_block_noise(h, ch, nch, delt, nsamp, flags, nz, iq_out, end_state);
+    ImpairCall c;
+    if (nsamp < 1 || !impair_args(nz, set, (uint64_t)nsamp, &c))
+        return GPSBB_E_BADARG;
+    return fill_block_impl(h, ch, nch, delt, nsamp, flags, nullptr, static_cast<int16_t *>(iq_out), end_state, &c);
 }
 
 /* the reference's own channel_t[] / gain[] in, rendered, updated in place as its loop leaves them; fixed: the build without
@@ -3189,6 +3453,8 @@ struct gpsbb_stream {
     bool noise_on = false;  /* gpsbb_stream_set_noise: the gather adds noise (k_noise_iq) */
     NoiseArgs noise{};      /* ... its arguments, sample0 = where the last set_noise put the stream */
     unsigned long long noise_pos = 0; /* the stream position of the next push's first sample */
+    bool interf_on = false; /* gpsbb_stream_set_interf: the gather adds the set's J (k_impair_iq) */
+    InterfArgs interf{};    /* ... sample0 = where the last set_interf put the stream */
     struct Slot {
         gpsbb_batch *batch = nullptr;
         int16_t *h_iq = nullptr;            /* pinned */
@@ -3315,7 +3581,7 @@ extern "C" int gpsbb_stream_reset(gpsbb_stream_t *s)
         s->fx_phase[i] = 0;
     }
     s->head = s->tail = 0;
-    s->noise_pos = s->noise.sample0;
+    s->noise_pos = s->noise_on || !s->interf_on ? s->noise.sample0 : s->interf.sample0;
     return GPSBB_OK;
 }
 
@@ -3330,12 +3596,35 @@ extern "C" int gpsbb_stream_set_noise(gpsbb_stream_t *s, const gpsbb_noise_t *nz
     NoiseArgs a;
     if (!noise_args(nz, &a))
         return GPSBB_E_BADARG;
+    if (s->interf_on && (a.sample0 != s->interf.sample0 || a.shift != s->interf.shift))
+        return GPSBB_E_BADARG; /* (the later of the two calls checks the rule) */
     HIPCHK(s->h, hipSetDevice(s->h->device));
     HIPCHK(s->h, noise_ready(s->h));
     a.shift8 = s->shift;
     s->noise = a;
     s->noise_pos = a.sample0;
     s->noise_on = true;
+    return GPSBB_OK;
+}
+
+extern "C" int gpsbb_stream_set_interf(gpsbb_stream_t *s, const gpsbb_interf_set_t *set)
+{
+    if (!s || (s->flags & GPSBB_STREAM_DEVICE_ONLY))
+        return GPSBB_E_BADARG;
+    if (!set) {
+        s->interf_on = false;
+        return GPSBB_OK;
+    }
+    InterfArgs a;
+    if (!interf_args(set, &a) || !interf_at(&a, set->sample0, (uint64_t)s->bps * (uint64_t)s->nsamp))
+        return GPSBB_E_BADARG;
+    if (s->noise_on && (s->noise.sample0 != a.sample0 || s->noise.shift != a.shift))
+        return GPSBB_E_BADARG;
+    HIPCHK(s->h, hipSetDevice(s->h->device));
+    HIPCHK(s->h, noise_ready(s->h));
+    s->interf = a;
+    s->noise_pos = a.sample0;
+    s->interf_on = true;
     return GPSBB_OK;
 }
 
@@ -3378,6 +3667,8 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
         return GPSBB_E_BADARG;
     if (s->poisoned || s->head - s->tail >= (uint64_t)s->depth)
         return GPSBB_E_STATE; /* ring full: pop first */
+    if (s->interf_on && (s->noise_pos >= INTERF_POS_END || (uint64_t)s->bps * (uint64_t)s->nsamp > INTERF_POS_END - s->noise_pos))
+        return GPSBB_E_BADARG; /* the push would reach position 2^63 */
     if (new_chain) {
         /* this push does not continue the one before: every channel of its first block starts from its descriptor's phase,
          * as if it had just been allocated (c:1956-1964) — "no satellite was here before" is all the chain has to be told */
@@ -3552,7 +3843,19 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
     if (sl.h_iq) {
         const bool sdma = GPSBB_KNOB_SET("GPSBB_GATHER_SDMA"); /* experiment: the runtime's copy instead */
         const int gwg = (int)GPSBB_KNOB_LONG("GPSBB_GATHER_WGS", 32);
-        if (s->noise_on) {
+        if (s->interf_on) {
+            /* interference (and the noise, if on) on the way out: k_impair_iq in k_noise_iq's place */
+            ImpairArgs a;
+            memset(&a, 0, sizeof a);
+            if (s->noise_on)
+                a.nz = s->noise;
+            a.nz.sample0 = s->noise_pos;
+            a.nz.shift = s->interf.shift;
+            a.nz.shift8 = s->shift;
+            a.it = s->interf;
+            (void)interf_at(&a.it, s->noise_pos, (uint64_t)s->bps * (uint64_t)s->nsamp); /* (checked where the push began) */
+            HIPCHK(h, impair_launch(h, s->fmt, a, s->noise_on, b->d_iq.p, sl.h_iq, (size_t)s->bps * s->nsamp * 2, cs));
+        } else if (s->noise_on) {
             /* noise on the way out, in any format: the noise kernel reads the render and writes the pinned slot */
             NoiseArgs a = s->noise;
             a.sample0 = s->noise_pos;
@@ -3594,7 +3897,7 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
     memcpy(s->rough_phase, rough_next, sizeof rough_next);
     memcpy(s->fx_prn, fx_prn_next, sizeof fx_prn_next);
     memcpy(s->fx_phase, fx_phase_next, sizeof fx_phase_next);
-    if (s->noise_on)
+    if (s->noise_on || s->interf_on)
         s->noise_pos += (unsigned long long)s->bps * (unsigned long long)s->nsamp;
     s->head++;
     poison.armed = false;

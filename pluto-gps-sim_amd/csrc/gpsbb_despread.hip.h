@@ -35,6 +35,7 @@
 
 #include "gpsbb_dense.hip.h"
 #include "gpsbb_noise.hip.h"
+#include "gpsbb_interf.hip.h"
 
 namespace gpsbb_impl {
 
@@ -53,6 +54,7 @@ struct DsArgs {
     uint32_t danger;             /* a model's low word below this: the sample is recomputed exactly (2 * PD_BAND) */
     NoiseArgs nz;                /* NOISE: sample0 is the position of sample 0 of block 0 */
     const int2 *ntab;
+    InterfArgs it;               /* INTERF: the emitters, sample0 and shift as nz's (gpsbb_batch_despread_impaired) */
 };
 
 typedef short ds_s16x2 __attribute__((ext_vector_type(2)));
@@ -95,12 +97,34 @@ __device__ __forceinline__ uint32_t ds_model_sample(double nn, double S, double 
     return it | (((bit ^ 1u) ^ neg) << 9);
 }
 
-/* what a receiver of the view sees of the rendered pair v at sample n of block b: noise (steps 1-4 of gpsbb_noise_t), then the
- * format's quantiser, unpacked, as an int16 pair */
-template <int VIEW, bool NOISE>
-__device__ __forceinline__ uint32_t ds_view(uint32_t v, unsigned long long pos, const DsArgs &a, const int2 *ntab)
+/* the carrier tables as the replica image holds them: rep[0][k].x = (cos, sin) of index k as an int16 pair */
+struct DsRepTab {
+    const uint2 *rep;
+    __device__ __forceinline__ void operator()(uint32_t idx, int *c, int *s) const
+    {
+        const uint32_t v = rep[idx].x;
+        *c = (int)(v << 16) >> 16;
+        *s = (int)v >> 16;
+    }
+};
+
+/* what a receiver of the view sees of the rendered pair v at sample n of block b: interference and noise (steps 1-4 of
+ * gpsbb_noise_t, with gpsbb_interf_t's J), then the format's quantiser, unpacked, as an int16 pair */
+template <int VIEW, bool NOISE, bool INTERF = false>
+__device__ __forceinline__ uint32_t ds_view(uint32_t v, unsigned long long pos, const DsArgs &a, const int2 *ntab, const uint2 *rep = nullptr)
 {
     int vi = (int)(v << 16) >> 16, vq = (int)v >> 16;
+    if (INTERF) {
+        int j[2];
+        interf_run<1>(a.it, pos, DsRepTab{rep}, j);
+        vi += j[0];
+        vq += j[1];
+        if (!NOISE) {
+            uint32_t clip = 0;
+            vi = noise_apply(vi, 0, a.it.shift, clip);
+            vq = noise_apply(vq, 0, a.it.shift, clip);
+        }
+    }
     if (NOISE) {
         const unsigned long long s = a.nz.sample0 + pos;
         uint32_t x[4];
@@ -121,7 +145,7 @@ __device__ __forceinline__ uint32_t ds_view(uint32_t v, unsigned long long pos, 
 }
 
 /* SG: the batch's state granule (BatchDev::st_log2) */
-template <int VIEW, bool NOISE, int SG>
+template <int VIEW, bool NOISE, int SG, bool INTERF = false>
 __global__ __launch_bounds__(DS_WG) void k_despread(BatchDev p, DsArgs a)
 {
     __shared__ DsLds L;
@@ -195,8 +219,8 @@ __global__ __launch_bounds__(DS_WG) void k_despread(BatchDev p, DsArgs a)
                 u[j] = j * 64 < left ? iqb[(size_t)wt * TILE + j * 64 + lane] : 0u;
 #pragma unroll
             for (int j = 0; j < SPT; j++)
-                u[j] = j * 64 < left ? ds_view<VIEW, NOISE>(u[j], (unsigned long long)b * (unsigned long long)p.nsamp +
-                                                                      (unsigned long long)(wt * TILE + j * 64 + lane), a, ntab)
+                u[j] = j * 64 < left ? ds_view<VIEW, NOISE, INTERF>(u[j], (unsigned long long)b * (unsigned long long)p.nsamp +
+                                                                              (unsigned long long)(wt * TILE + j * 64 + lane), a, ntab, L.rep[0])
                                      : 0u; /* a sample that does not exist adds nothing */
             const int g = wt >> SG;
             const double n0 = (double)((wt & ((1 << SG) - 1)) * TILE + lane); /* samples since the state's */

@@ -81,6 +81,7 @@ struct Shard {
     };
     std::deque<FedSlot> fed;
     bool noise_set = false; /* the shard's ring has noise set (gpsbb_stream_set_noise) */
+    bool interf_set = false; /* ... interference (gpsbb_stream_set_interf) */
 };
 
 } /* namespace */
@@ -121,6 +122,9 @@ struct gpsbb_node {
     /* gpsbb_node_set_noise: block b of a run is at stream position noise.sample0 + b * nsamp */
     bool noise_on = false;
     gpsbb_noise_t noise{};
+    /* gpsbb_node_set_interf: likewise */
+    bool interf_on = false;
+    gpsbb_interf_set_t interf{};
 };
 
 extern "C" int gpsbb_node_plan(long nblocks, int nshards, int blocks_per_slot, long *first)
@@ -217,6 +221,13 @@ inline bool digest_at_render(const gpsbb_node *n)
 /* b0: the push's first block in the stream, where its noise starts */
 inline int shard_push(gpsbb_node *n, Shard &s, const gpsbb_chan_t *desc, unsigned flags, long b0)
 {
+    if (s.interf_set) {
+        /* off first: noise and interference move to the push's position together, and each call checks against the other */
+        const int rc = gpsbb_stream_set_interf(s.st, nullptr);
+        if (rc != GPSBB_OK)
+            return rc;
+        s.interf_set = false;
+    }
     if (n->noise_on || s.noise_set) {
         gpsbb_noise_t nz = n->noise;
         nz.sample0 += (uint64_t)b0 * (uint64_t)n->cfg.nsamp;
@@ -224,6 +235,14 @@ inline int shard_push(gpsbb_node *n, Shard &s, const gpsbb_chan_t *desc, unsigne
         if (rc != GPSBB_OK)
             return rc;
         s.noise_set = n->noise_on;
+    }
+    if (n->interf_on) {
+        gpsbb_interf_set_t js = n->interf;
+        js.sample0 += (uint64_t)b0 * (uint64_t)n->cfg.nsamp;
+        const int rc = gpsbb_stream_set_interf(s.st, &js);
+        if (rc != GPSBB_OK)
+            return rc;
+        s.interf_set = true;
     }
     if (digest_at_render(n))
         flags |= GPSBB_PUSH_DIGEST;
@@ -660,9 +679,25 @@ extern "C" int gpsbb_node_set_noise(gpsbb_node_t *n, const gpsbb_noise_t *nz)
         return GPSBB_E_BADARG;
     if (nz && (!(nz->sigma > 0.0) || !(nz->sigma <= 1048576.0) || nz->shift < 0 || nz->shift > 7))
         return GPSBB_E_BADARG;
+    if (nz && n->interf_on && (nz->sample0 != n->interf.sample0 || nz->shift != n->interf.shift))
+        return GPSBB_E_BADARG;
     n->noise_on = nz != nullptr;
     if (nz)
         n->noise = *nz;
+    return GPSBB_OK;
+}
+
+extern "C" int gpsbb_node_set_interf(gpsbb_node_t *n, const gpsbb_interf_set_t *set)
+{
+    if (!n || (n->cfg.flags & GPSBB_NODE_DEVICE_ONLY) || n->feeding)
+        return GPSBB_E_BADARG;
+    if (set && gpsbb_interf_eval(set, set->sample0, 0, nullptr) != GPSBB_OK) /* (n == 0: the set's own check) */
+        return GPSBB_E_BADARG;
+    if (set && n->noise_on && (n->noise.sample0 != set->sample0 || n->noise.shift != set->shift))
+        return GPSBB_E_BADARG;
+    n->interf_on = set != nullptr;
+    if (set)
+        n->interf = *set;
     return GPSBB_OK;
 }
 
@@ -985,7 +1020,7 @@ extern "C" int gpsbb_node_slot_digests(gpsbb_node_t *n, int shard, uint64_t *dig
 extern "C" int gpsbb_node_run_digest(gpsbb_node_t *n, const gpsbb_chan_t *ch, long nblocks, uint64_t *digests, gpsbb_node_stats_t *stats)
 {
     /* the digests are of int16 blocks: a packed host ring has none, nor has one with noise */
-    if (!n || !digests || (n->cfg.flags & GPSBB_OUT_FORMAT_MASK) || n->noise_on)
+    if (!n || !digests || (n->cfg.flags & GPSBB_OUT_FORMAT_MASK) || n->noise_on || n->interf_on)
         return GPSBB_E_BADARG;
     n->digest_out = digests;
     const int rc = gpsbb_node_run(n, ch, nblocks, digest_sink, n, stats);

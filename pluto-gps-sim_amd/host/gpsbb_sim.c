@@ -36,6 +36,10 @@
  * zenith normalisation, path loss 1.0 at 20 200 km), w = sat16((v + N) >> shift) with shift 0..7 (default 0) before the sample
  * format packs it; -w seed picks the noise (default 1).  Block b is at stream position b * nsamp on every path, so -k keeps the
  * bytes of the full file.  The single-handle paths report how many components the noise saturated.
+ * -J cw,js_db,f_hz[,pulse_period_s,duty] and -J chirp,js_db,f0_hz,f1_hz,sweep_s[,pulse_period_s,duty], up to four times, add
+ * interference (include/gpsbb.h gpsbb_interf_t): J/S in dB against a gain-1.0 channel, a tone at f_hz or a sawtooth sweep from
+ * f0_hz to f1_hz every sweep_s seconds, optionally pulsed.  It goes in where the noise goes, w = sat16((v + N + J) >> shift); with
+ * -W the shift is -W's, without it -j shift (0..7, default 0).  The same bytes on every path, as for -W.
  */
 #include <math.h>
 #include <stdio.h>
@@ -143,6 +147,45 @@ static int cmp_double(const void *a, const void *b)
 
 /* -b 8: how many components the shift let saturate (gpsbb_fill_block_ex / the ring's packing kernel counted them); -W: how many
  * the noise did */
+/* one -J argument into *e; 0 if it is not well formed (gpsbb_interf_make checks the numbers) */
+static int parse_interf(const char *arg, double delt, gpsbb_interf_t *e)
+{
+    int kind;
+    if (!strncmp(arg, "cw,", 3)) {
+        kind = GPSBB_INTERF_CW;
+        arg += 3;
+    } else if (!strncmp(arg, "chirp,", 6)) {
+        kind = GPSBB_INTERF_CHIRP;
+        arg += 6;
+    } else {
+        return 0;
+    }
+    double v[6];
+    int n = 0;
+    for (;;) {
+        char *end = NULL;
+        if (n == 6)
+            return 0;
+        v[n] = strtod(arg, &end);
+        if (end == arg || !isfinite(v[n]))
+            return 0;
+        n++;
+        if (*end == 0)
+            break;
+        if (*end != ',')
+            return 0;
+        arg = end + 1;
+    }
+    const int base = kind == GPSBB_INTERF_CW ? 2 : 4;
+    if (n != base && n != base + 2)
+        return 0;
+    const double period = n == base ? 0.0 : v[base], duty = n == base ? 1.0 : v[base + 1];
+    if (n != base && !(period > 0.0))
+        return 0;
+    return gpsbb_interf_make(e, kind, v[0], v[1], kind == GPSBB_INTERF_CW ? 0.0 : v[2], kind == GPSBB_INTERF_CW ? 0.0 : v[3], period,
+                             duty, delt) == GPSBB_OK;
+}
+
 static void report_clipped(gpsbb_t *bb, int bits, int noise)
 {
     uint64_t clipped = 0;
@@ -158,6 +201,7 @@ static void usage(void)
                     "                 [-s fs_hz] [-d seconds] [-n samples_per_block] [-N channels] [-g gpu[,gpu...]] [-F] [-G shards [-C [-I]]]\n"
                     "                 [-P usec_per_block] [-Q device_queue_blocks] [-S stats.json] [-k keep,blocks] [-b 1|8|16] [-q shift]\n"
                     "                 [-W cn0_dbhz[,shift]] [-w seed]\n"
+                    "                 [-J cw,js_db,f_hz[,period_s,duty]] [-J chirp,js_db,f0_hz,f1_hz,sweep_s[,period_s,duty]] [-j shift]\n"
                     "                 -o out.bin\n");
 }
 
@@ -187,8 +231,11 @@ int main(int argc, char **argv)
     int bits = 16, shift = 5;
     const char *noise_arg = NULL;
     unsigned long long noise_seed = 1;
+    const char *interf_arg[GPSBB_INTERF_MAX + 1];
+    int ninterf = 0;
+    const char *interf_shift_arg = NULL;
 
-    while ((opt = getopt(argc, argv, "e:u:c:l:s:Tt:in:N:d:o:g:3FG:P:S:k:Q:ICRb:q:W:w:")) != -1) {
+    while ((opt = getopt(argc, argv, "e:u:c:l:s:Tt:in:N:d:o:g:3FG:P:S:k:Q:ICRb:q:W:w:J:j:")) != -1) {
         switch (opt) {
         case 'e': cfg.navfile = optarg; break;
         case 'u': cfg.motion_file = optarg; break;
@@ -243,6 +290,12 @@ int main(int argc, char **argv)
         case 'q': shift = atoi(optarg); break;
         case 'W': noise_arg = optarg; break;
         case 'w': noise_seed = strtoull(optarg, NULL, 0); break;
+        case 'J':
+            if (ninterf <= GPSBB_INTERF_MAX)
+                interf_arg[ninterf < GPSBB_INTERF_MAX ? ninterf : GPSBB_INTERF_MAX] = optarg;
+            ninterf++;
+            break;
+        case 'j': interf_shift_arg = optarg; break;
         default: usage(); return 1;
         }
     }
@@ -288,6 +341,31 @@ int main(int argc, char **argv)
         fprintf(stderr, "noise: C/N0 %.2f dB-Hz at gain 1.0, sigma %.1f LSB per component, shift %d, seed %llu\n", cn0, nz.sigma,
                 nshift, (unsigned long long)noise_seed);
     }
+    /* -J: the interference, checked here as well; the noise's position and shift */
+    gpsbb_interf_set_t jset;
+    memset(&jset, 0, sizeof jset);
+    const gpsbb_interf_set_t *interf = NULL;
+    if (ninterf > 0 || interf_shift_arg) {
+        int ok = ninterf >= 1 && ninterf <= GPSBB_INTERF_MAX;
+        for (int k = 0; ok && k < ninterf; k++)
+            ok = parse_interf(interf_arg[k], delt, &jset.e[k]);
+        jset.n = ninterf;
+        jset.shift = noise ? nz.shift : 0;
+        if (ok && interf_shift_arg) {
+            char *e2 = NULL;
+            const long v = strtol(interf_shift_arg, &e2, 10);
+            ok = e2 != interf_shift_arg && *e2 == 0 && v >= 0 && v <= 7 && (!noise || v == nz.shift);
+            jset.shift = (int)v;
+        }
+        if (!ok) {
+            fprintf(stderr, "ERROR: -J wants cw,js_db,f_hz or chirp,js_db,f0_hz,f1_hz,sweep_s, each with an optional ,pulse_period_s,duty, "
+                            "at most %d times: |f| at most half the sampling rate, a sweep of 2 samples or more, a duty in (0, 1]; "
+                            "-j a shift of 0..7 that goes with -J (and equals -W's)\n", GPSBB_INTERF_MAX);
+            return 1;
+        }
+        interf = &jset;
+        fprintf(stderr, "interference: %d emitter%s, shift %d\n", jset.n, jset.n == 1 ? "" : "s", jset.shift);
+    }
 
     gpsfe_t *fe = NULL;
     int rc = gpsfe_open(&cfg, &fe);
@@ -329,6 +407,8 @@ int main(int argc, char **argv)
         rc = gpsbb_node_create(&node, &nc);
         if (rc == GPSBB_OK && noise)
             rc = gpsbb_node_set_noise(node, noise);
+        if (rc == GPSBB_OK && interf)
+            rc = gpsbb_node_set_interf(node, interf);
         if (rc == GPSBB_OK && contiguous) {
             gpsfe_generate(fe, (int)nblocks, all);
             rc = gpsbb_node_run(node, all, nblocks, node_sink, &o, &ns);
@@ -379,6 +459,8 @@ int main(int argc, char **argv)
         rc = slot ? gpsbb_stream_create(bb, cfg.max_chan, delt, (int)nsamp, bps, depth, GPSBB_CHAIN_CARRIER | oflags, &st) : GPSBB_E_NOMEM;
         if (rc == GPSBB_OK && noise)
             rc = gpsbb_stream_set_noise(st, noise); /* from block 0: every push moves the position on by its blocks */
+        if (rc == GPSBB_OK && interf)
+            rc = gpsbb_stream_set_interf(st, interf);
         long pushed = 0, written = 0;
         while (rc == GPSBB_OK && slot && written < nblocks) {
             while (rc == GPSBB_OK && pushed < nblocks && gpsbb_stream_pending(st) < depth) {
@@ -401,7 +483,7 @@ int main(int argc, char **argv)
             fprintf(stderr, "ERROR: streaming: %s\n", gpsbb_strerror(rc));
         if (st)
             gpsbb_stream_destroy(st);
-        report_clipped(bb, bits, noise != NULL);
+        report_clipped(bb, bits, noise != NULL || interf != NULL);
         free(slot);
         if (fout != stdout)
             fclose(fout);
@@ -451,7 +533,10 @@ int main(int argc, char **argv)
             iq_registered = iq; /* iq_buff is one allocation for the run (c:2604): rendered into directly from here on */
         struct timespec ta, tb;
         clock_gettime(CLOCK_MONOTONIC, &ta);
-        if (noise) {
+        if (interf) {
+            nz.sample0 = jset.sample0 = (uint64_t)blk * (uint64_t)nsamp;
+            rc = gpsbb_fill_block_impair(bb, ch, cfg.max_chan, delt, (int)nsamp, oflags, noise, &jset, iq, st);
+        } else if (noise) {
             nz.sample0 = (uint64_t)blk * (uint64_t)nsamp;
             rc = gpsbb_fill_block_noise(bb, ch, cfg.max_chan, delt, (int)nsamp, oflags, &nz, iq, st);
         } else {
@@ -507,7 +592,7 @@ int main(int argc, char **argv)
     if (gpsbb_get_hazards(bb, &hz, 0) == GPSBB_OK && (hz.itable_512 || hz.dwrd_oob))
         fprintf(stderr, "note: latent out-of-bounds cases of the reference hit: table %llu, nav words %llu\n",
                 (unsigned long long)hz.itable_512, (unsigned long long)hz.dwrd_oob);
-    report_clipped(bb, bits, noise != NULL);
+    report_clipped(bb, bits, noise != NULL || interf != NULL);
     gpsbb_destroy(bb);
     gpsfe_close(fe);
     fprintf(stderr, "%ld blocks of %ld samples written\n", blk, nsamp);
