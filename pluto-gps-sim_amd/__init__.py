@@ -90,6 +90,7 @@ INFO_STREAMS, INFO_HW_QUEUES, INFO_TILES_RENDERED, INFO_PREPASS = 7, 8, 9, 10
 NODE_INDEXED, NODE_CONCURRENT, NODE_DEVICE_ONLY, NODE_NO_AFFINITY, NODE_FIXED_CARRIER, NODE_INTERLEAVED, NODE_DIGESTS = 1, 2, 4, 8, 16, 32, 64
 PUSH_NEW_CHAIN = 1
 PUSH_DIGEST = 2
+PUSH_LEVEL = 4
 NODE_MAX_SHARDS = 64
 INFO_SC8_CLIPPED = 11
 INFO_LAST_VARIANT = 13  # GPSBB_VARIANT_*: which synthesis kernel exactly
@@ -160,6 +161,19 @@ def _ref(x):
     return None if x is None else C.byref(x)
 
 
+# output level (include/gpsbb.h gpsbb_level_t): one record per block, what device_level / Stream.pop_level / level_host return
+LEVEL_CLASSES = 32
+LEVEL_DTYPE = np.dtype([("n", "<u8"), ("sumsq", "<u8", (2,)), ("hist", "<u8", (2, LEVEL_CLASSES))])
+
+
+class Level(C.Structure):
+    """gpsbb_level_t: n samples, the sum of x^2 per component, hist[c][k] = components c whose x has bit length k"""
+    _fields_ = [("n", C.c_uint64), ("sumsq", C.c_uint64 * 2), ("hist", (C.c_uint64 * LEVEL_CLASSES) * 2)]
+
+
+assert LEVEL_DTYPE.itemsize == 536 and C.sizeof(Level) == 536
+
+
 ERRORS = {0: "GPSBB_OK", -1: "GPSBB_E_BADARG", -2: "GPSBB_E_BADCHAN", -3: "GPSBB_E_HIP", -4: "GPSBB_E_NOMEM",
           -5: "GPSBB_E_INTERNAL", -6: "GPSBB_E_NODEVICE", -7: "GPSBB_E_STATE"}
 
@@ -177,6 +191,7 @@ API_SYMBOLS = [
     "gpsbb_despread_segments", "gpsbb_batch_despread", "gpsbb_cn0_estimate",
     "gpsbb_interf_make", "gpsbb_interf_eval", "gpsbb_fill_block_impair", "gpsbb_stream_set_interf", "gpsbb_device_impair",
     "gpsbb_batch_despread_impaired",
+    "gpsbb_device_level", "gpsbb_level_clips", "gpsbb_level_choose", "gpsbb_level_rms", "gpsbb_stream_pop_level",
 ]
 # ... and include/gpsbb_node.h
 NODE_API_SYMBOLS = ["gpsbb_node_create", "gpsbb_node_run", "gpsbb_node_run_digest", "gpsbb_node_slot_digests", "gpsbb_node_destroy", "gpsbb_node_plan", "gpsbb_node_begin", "gpsbb_node_feed", "gpsbb_node_end",
@@ -292,6 +307,13 @@ def lib():
             L.gpsbb_device_impair.argtypes = [vp, vp, vp, C.c_long, i, vp, vp]
             L.gpsbb_batch_despread_impaired.argtypes = [vp, vp, u, vp, vp, i, vp]
             L.gpsbb_node_set_interf.argtypes = [vp, vp]
+        if hasattr(L, "gpsbb_device_level"):  # the level calls, as a group (an older build loaded for an A/B: tools/ab_lib.sh)
+            L.gpsbb_device_level.argtypes = [vp, vp, C.c_long, i, vp, vp, vp]
+            L.gpsbb_level_clips.argtypes = [vp, C.c_long, i, u, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+            L.gpsbb_level_choose.argtypes = [vp, C.c_long, u, d, C.POINTER(i), C.POINTER(i)]
+            L.gpsbb_level_rms.argtypes = [vp, C.c_long, i]
+            L.gpsbb_level_rms.restype = d
+            L.gpsbb_stream_pop_level.argtypes = [vp, C.POINTER(vp), vp, vp]
         _lib = L
     return _lib
 
@@ -448,6 +470,15 @@ class Synth:
         _chk(lib().gpsbb_device_impair(self._h, C.c_void_p(int(d_src)), C.c_void_p(int(dst)), nblocks, nsamp, _ref(nz), _ref(js)),
              "gpsbb_device_impair")
 
+    def device_level(self, d_ptr, nblocks, nsamp, noise=None, interf=None):
+        """gpsbb_device_level: the level of x = v + N + J before the shift, of nblocks blocks of int16 IQ in device memory ->
+        LEVEL_DTYPE [nblocks] (level_host is the same in numpy); noise and interf may each be None"""
+        nz, js = _as_noise(noise), _as_interf(interf)
+        out = np.zeros(nblocks, LEVEL_DTYPE)
+        _chk(lib().gpsbb_device_level(self._h, C.c_void_p(int(d_ptr)), nblocks, nsamp, _ref(nz), _ref(js), out.ctypes.data),
+             "gpsbb_device_level")
+        return out
+
     def device_noise(self, d_src, nblocks, nsamp, noise, d_dst=None):
         """gpsbb_device_noise: nblocks blocks of int16 IQ in device memory at d_src, with noise, into d_dst (default: in place)"""
         nz = _as_noise(noise)
@@ -581,6 +612,13 @@ class Batch:
     def device_iq(self):
         return lib().gpsbb_batch_device_iq(self._b)
 
+    def level(self, noise=None, interf=None, d_iq=None):
+        """gpsbb_device_level of the batch's blocks: on device_iq() (the last run's internal buffer) unless d_iq is given"""
+        p = self.device_iq() if d_iq is None else d_iq
+        if not p:
+            raise GpsbbError(-7, "Batch.level (no internal buffer: run() first, or pass d_iq)")
+        return self.synth.device_level(p, self.nblocks, self.nsamp, noise, interf)
+
     def despread(self, view=OUT_SC16, noise=None, seg_tiles=1, d_iq=None, interf=None):
         """gpsbb_batch_despread: the prompt sums of every channel of the last run against its own replica, in the receiver's
         view `view` (OUT_SC16 / OUT_SC8(shift) / OUT_SC1) of the rendered IQ, with `noise` (a Noise or a dict) applied first;
@@ -635,12 +673,13 @@ class Stream:
         except Exception:
             pass
 
-    def push(self, ch, new_chain=False, digest=False):
-        """gpsbb_stream_push(_ex); digest: GPSBB_PUSH_DIGEST — the push is rendered with its blocks' digests (pop_digest)"""
+    def push(self, ch, new_chain=False, digest=False, level=False):
+        """gpsbb_stream_push(_ex); digest: GPSBB_PUSH_DIGEST — the push is rendered with its blocks' digests (pop_digest);
+        level: GPSBB_PUSH_LEVEL — the push's slot is measured with the stream's noise and set (pop_level)"""
         ch = _as_chan(ch)
         if ch.shape != (self.bps, self.nch):
             raise ValueError("push expects [blocks_per_slot, nch] descriptors")
-        flags = (PUSH_NEW_CHAIN if new_chain else 0) | (PUSH_DIGEST if digest else 0)
+        flags = (PUSH_NEW_CHAIN if new_chain else 0) | (PUSH_DIGEST if digest else 0) | (PUSH_LEVEL if level else 0)
         if flags:
             _chk(lib().gpsbb_stream_push_ex(self._s, ch.ctypes.data, flags), "gpsbb_stream_push_ex")
         else:
@@ -656,6 +695,15 @@ class Stream:
             return p.value, st, dig
         view = iq_view(p.value, self.bps, self.nsamp, self.fmt)
         return (view.copy() if copy else view), st, dig
+
+    def pop_level(self, copy=True):
+        """gpsbb_stream_pop_level: pop() plus the popped push's levels (LEVEL_DTYPE [blocks_per_slot])"""
+        p = C.c_void_p()
+        st = np.zeros((self.bps, self.nch), STATE_DTYPE)
+        lv = np.zeros(self.bps, LEVEL_DTYPE)
+        _chk(lib().gpsbb_stream_pop_level(self._s, C.byref(p), st.ctypes.data, lv.ctypes.data), "gpsbb_stream_pop_level")
+        view = iq_view(p.value, self.bps, self.nsamp, self.fmt)
+        return (view.copy() if copy else view), st, lv
 
     def pop(self, copy=True):
         """(IQ [blocks_per_slot, nsamp, 2] int16 in the slot's pinned host buffer, end states); a stream created with
@@ -1043,6 +1091,79 @@ def apply_impair(iq, noise, interf):
     sft = t >> int(js.shift)
     w = np.clip(sft, -32768, 32767)
     return w.astype(np.int16).reshape(a.shape), int(np.count_nonzero(w != sft))
+
+
+# ---- output level (include/gpsbb.h, gpsbb_level_t): the numpy restatement the GPU's counts are checked against ----
+
+def level_class(x):
+    """m(x): the bit length of x for x >= 0 and of ~x otherwise, for |x| < 2^52 (frexp of the integer as a double is exact)"""
+    x = np.asarray(x, np.int64)
+    y = np.where(x < 0, ~x, x)
+    return np.frexp(y.astype(np.float64))[1].astype(np.int64)
+
+
+def level_host(iq, noise=None, interf=None):
+    """The level of the render iq [nblocks, nsamp, 2] (or [nsamp, 2]: one block; int16, or wider integers with |x| < 2^52 in
+    the end, for checks of the classes alone) straight from the definition:
+    x = iq + J + N in int64 over one stream from the noise's / the set's sample0, the bit length of every x, a bincount per block
+    and component, the sum of x^2 in Python integers -> LEVEL_DTYPE [nblocks].  What the GPU's result equals, field for field."""
+    a = np.asarray(iq)
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3 or a.shape[-1] != 2 or a.dtype.kind not in "iu":
+        raise ValueError("integer iq of shape (nblocks, nsamp, 2) wanted, got %s %r" % (a.dtype, a.shape))
+    nz, js = _as_noise(noise), _as_interf(interf)
+    if nz is not None and js is not None and (nz.sample0 != js.sample0 or nz.shift != js.shift):
+        raise ValueError("noise and interference disagree on sample0 or shift")
+    nb, nsamp = a.shape[:2]
+    x = a.reshape(-1, 2).astype(np.int64)
+    if js is not None:
+        x = x + interf_host(js, js.sample0, x.shape[0]).astype(np.int64)
+    if nz is not None:
+        x = x + noise_host(nz.seed, nz.sample0, x.shape[0], nz.sigma).astype(np.int64)
+    x = x.reshape(nb, nsamp, 2)
+    m = level_class(x)
+    out = np.zeros(nb, LEVEL_DTYPE)
+    out["n"] = nsamp
+    for b in range(nb):
+        for c in range(2):
+            out["hist"][b, c] = np.bincount(m[b, :, c], minlength=LEVEL_CLASSES)[:LEVEL_CLASSES]
+            xc = x[b, :, c]
+            hi, lo = xc >> 12, xc & 0xFFF  # x^2 = hi^2 2^24 + 2 hi lo 2^12 + lo^2: every partial sum far below 2^63
+            out["sumsq"][b, c] = ((int((hi * hi).sum()) << 24) + (int((hi * lo).sum()) << 13) + int((lo * lo).sum())) & 0xFFFFFFFFFFFFFFFF
+    return out
+
+
+def _as_levels(levels):
+    lv = np.ascontiguousarray(levels, dtype=LEVEL_DTYPE).reshape(-1)
+    if lv.size < 1:
+        raise ValueError("at least one level record wanted")
+    return lv
+
+
+def level_clips(levels, shift, fmt=OUT_SC16):
+    """gpsbb_level_clips -> (components step 4 saturates at `shift`, components SC8 then clamps for fmt OUT_SC8(shift8), else 0)"""
+    lv = _as_levels(levels)
+    c16, c8 = C.c_uint64(), C.c_uint64()
+    _chk(lib().gpsbb_level_clips(lv.ctypes.data, lv.size, int(shift), fmt, C.byref(c16), C.byref(c8)), "gpsbb_level_clips")
+    return int(c16.value), int(c8.value)
+
+
+def level_choose(levels, fmt, clip_ppm=100.0):
+    """gpsbb_level_choose -> (shift, shift8, met): the smallest shifts whose predicted clips stay within clip_ppm parts per million
+    of the components; met is False when even (7, 15) does not"""
+    lv = _as_levels(levels)
+    a, q = C.c_int(), C.c_int()
+    rc = lib().gpsbb_level_choose(lv.ctypes.data, lv.size, fmt, float(clip_ppm), C.byref(a), C.byref(q))
+    if rc < 0:
+        raise GpsbbError(rc, "gpsbb_level_choose")
+    return a.value, q.value, rc == 0
+
+
+def level_rms(levels, component):
+    """gpsbb_level_rms: sqrt(sum sumsq[component] / sum n) over the blocks"""
+    lv = _as_levels(levels)
+    return lib().gpsbb_level_rms(lv.ctypes.data, lv.size, int(component))
 
 
 # ---- despreading (include/gpsbb.h, gpsbb_batch_despread): the numpy restatement the GPU's sums are checked against ----

@@ -26,6 +26,7 @@
 #include "gpsbb_kernels.hip.h"
 #include "gpsbb_noise.hip.h"
 #include "gpsbb_interf.hip.h"
+#include "gpsbb_level.hip.h"
 #include "gpsbb_events.hip.h"
 #include "gpsbb_dense.hip.h"
 #include "gpsbb_despread.hip.h"
@@ -511,6 +512,8 @@ struct gpsbb {
     int2 *d_noise_tab = nullptr;          /* the noise's knots (K[i], K[i + 1] - K[i]) and ... */
     unsigned long long *d_nclip = nullptr; /* ... GPSBB_INFO_NOISE_CLIPPED: both on the first call with noise */
     size_t pack_cap = 0;
+    LevelOut *d_level = nullptr;          /* gpsbb_device_level's result on the device, kept between calls */
+    size_t level_cap = 0;                 /* ... in blocks */
     int last_hip = 0;
     gpsbb_batch *scratch = nullptr;
     unsigned char *h_bounce = nullptr; /* pinned: a fill whose iq_out lies partly in a registered range is copied through here */
@@ -904,6 +907,8 @@ extern "C" void gpsbb_destroy(gpsbb_t *h)
         (void)hipFree(h->d_nclip);
     if (h->d_digest.p)
         (void)hipFree(h->d_digest.p);
+    if (h->d_level)
+        (void)hipFree(h->d_level);
     delete h->pool;
     h->pool = nullptr;
     for_each_stream(h, [](hipStream_t st) { (void)hipStreamDestroy(st); });
@@ -3018,6 +3023,187 @@ extern "C" int gpsbb_device_impair(gpsbb_t *h, const int16_t *d_src, int16_t *d_
     return GPSBB_OK;
 }
 
+/* ---- output level (include/gpsbb.h gpsbb_level_t; gpsbb_level.hip.h) ---- */
+
+static_assert(sizeof(gpsbb_level_t) == 536 && sizeof(LevelOut) == sizeof(gpsbb_level_t), "gpsbb_level_t layout");
+static_assert(LEVEL_CLASSES == GPSBB_LEVEL_CLASSES, "LEVEL_CLASSES");
+
+/* the header's limit: nsamp * B * B < 2^64, so that no block's sum of squares leaves 64 bits */
+static bool level_fits(const ImpairArgs &a, bool noise, int nsamp)
+{
+    unsigned __int128 B = 32768;
+    if (noise) {
+        const int32_t *k = noise_knots();
+        int32_t kmax = 0;
+        for (int i = 0; i < NOISE_KNOTS; i++)
+            kmax = std::max(kmax, k[i]);
+        B += (unsigned __int128)(((long long)a.nz.s256 * kmax + (1ll << 23)) >> 24);
+    }
+    for (int i = 0; i < a.it.n; i++)
+        B += ((unsigned long long)a.it.e[i].G * 512ull + 32768ull) >> 16;
+    if (B >> 32)
+        return false;
+    const unsigned __int128 bb = B * B; /* < 2^64 */
+    return bb * (unsigned __int128)nsamp < ((unsigned __int128)1 << 64);
+}
+
+/* the arguments of a measurement of nsamples samples: nz and set as the impair calls check them, either or both absent */
+static bool level_args(const gpsbb_noise_t *nz, const gpsbb_interf_set_t *set, uint64_t nsamples, ImpairCall *c)
+{
+    if (set)
+        return impair_args(nz, set, nsamples, c);
+    memset(c, 0, sizeof *c);
+    if (nz && !noise_args(nz, &c->a.nz))
+        return false;
+    c->a.it.sample0 = c->a.nz.sample0;
+    c->noise = nz != nullptr;
+    return true;
+}
+
+/* Enqueue k_level over nblocks blocks at src into d_out (zeroed on the stream first).  The grid: the flattened (block, chunk) list,
+ * at most one workgroup per CU, as noise_launch's. */
+static hipError_t level_launch(gpsbb *h, const ImpairArgs &a, bool noise, const int16_t *src, long nblocks, int nsamp, LevelOut *d_out,
+                               hipStream_t stream)
+{
+    const hipError_t e = hipMemsetAsync(d_out, 0, (size_t)nblocks * sizeof(LevelOut), stream);
+    if (e != hipSuccess)
+        return e;
+    const int cpb = std::max(1, (nsamp / 4 + PACK_UNITS - 1) / PACK_UNITS);
+    const long long items = (long long)nblocks * cpb;
+    const int gwg = (int)std::min<long long>(256, items);
+    const bool interf = a.it.n > 0;
+#define GPSBB_LEVEL_GO(N, I) \
+    hipLaunchKernelGGL((k_level<N, I>), dim3(gwg), dim3(256), 0, stream, src, nblocks, nsamp, cpb, a, h->d_noise_tab, h->d_tabs, d_out)
+    if (noise) {
+        if (interf) GPSBB_LEVEL_GO(true, true); else GPSBB_LEVEL_GO(true, false);
+    } else {
+        if (interf) GPSBB_LEVEL_GO(false, true); else GPSBB_LEVEL_GO(false, false);
+    }
+#undef GPSBB_LEVEL_GO
+    return hipGetLastError();
+}
+
+extern "C" int gpsbb_device_level(gpsbb_t *h, const int16_t *d_iq, long nblocks, int nsamp, const gpsbb_noise_t *nz,
+                                  const gpsbb_interf_set_t *set, gpsbb_level_t *out)
+{
+    ImpairCall c;
+    if (!h || !d_iq || !out || nblocks < 1 || nsamp < 1 || ((uintptr_t)d_iq & 3) ||
+        !level_args(nz, set, (uint64_t)nblocks * (uint64_t)nsamp, &c) || !level_fits(c.a, c.noise, nsamp))
+        return GPSBB_E_BADARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int rc = gpsbb_sync(h); /* as gpsbb_device_impair: whatever the handle was rendering into d_iq is there */
+    if (rc != GPSBB_OK)
+        return rc;
+    if (c.noise)
+        HIPCHK(h, noise_ready(h));
+    if ((size_t)nblocks > h->level_cap) {
+        if (h->d_level)
+            (void)hipFree(h->d_level);
+        h->d_level = nullptr;
+        h->level_cap = 0;
+        HIPCHK(h, hipMalloc((void **)&h->d_level, (size_t)nblocks * sizeof(LevelOut)));
+        h->level_cap = (size_t)nblocks;
+    }
+    HIPCHK(h, level_launch(h, c.a, c.noise, d_iq, nblocks, nsamp, h->d_level, h->s_compute));
+    HIPCHK(h, hipMemcpyAsync(out, h->d_level, (size_t)nblocks * sizeof(LevelOut), hipMemcpyDeviceToHost, h->s_compute));
+    HIPCHK(h, hipStreamSynchronize(h->s_compute));
+    return GPSBB_OK;
+}
+
+/* components of lv[0 .. n) with m(x) > k, per component summed */
+static uint64_t level_above(const gpsbb_level_t *lv, long n, int k)
+{
+    uint64_t t = 0;
+    for (long b = 0; b < n; b++)
+        for (int c = 0; c < 2; c++)
+            for (int m = k + 1; m < GPSBB_LEVEL_CLASSES; m++)
+                t += lv[b].hist[c][m];
+    return t;
+}
+
+/* the two identities of the header: (clip16, clip8) at (a, shift8); sc8: the format is SC8 */
+static void level_clips(const gpsbb_level_t *lv, long n, int a, bool sc8, int shift8, uint64_t *clip16, uint64_t *clip8)
+{
+    const uint64_t sat = level_above(lv, n, 15 + a);
+    *clip16 = sat;
+    *clip8 = 0;
+    if (sc8) {
+        const int top = std::min(7 + shift8 + a, 15 + a); /* classes (top, 15 + a] clamp in SC8 without having saturated */
+        *clip8 = level_above(lv, n, top) - sat + (shift8 < 8 ? sat : 0);
+    }
+}
+
+/* the format bits of fmt: 0 SC16, 1 SC8, 2 SC1; -1 unknown */
+static int level_format(unsigned fmt)
+{
+    const unsigned f = (fmt & GPSBB_OUT_FORMAT_MASK) >> 8;
+    return f > 2 ? -1 : (int)f;
+}
+
+extern "C" int gpsbb_level_clips(const gpsbb_level_t *lv, long n, int shift, unsigned fmt, uint64_t *clip16, uint64_t *clip8)
+{
+    const unsigned sh8 = (fmt & GPSBB_OUT_SHIFT_MASK) >> 12;
+    const int f = level_format(fmt);
+    if (!lv || n < 1 || shift < 0 || shift > 7 || f < 0 || (fmt >> 16) || (fmt & 0xffu) || (sh8 && f != 1))
+        return GPSBB_E_BADARG;
+    uint64_t c16, c8;
+    level_clips(lv, n, shift, f == 1, (int)sh8, &c16, &c8);
+    if (clip16) *clip16 = c16;
+    if (clip8) *clip8 = c8;
+    return GPSBB_OK;
+}
+
+extern "C" int gpsbb_level_choose(const gpsbb_level_t *lv, long n, unsigned fmt, double clip_ppm, int *shift, int *shift8)
+{
+    const int f = level_format(fmt);
+    if (!lv || n < 1 || f < 0 || !(clip_ppm >= 0.0) || !shift || !shift8)
+        return GPSBB_E_BADARG;
+    uint64_t total = 0;
+    for (long b = 0; b < n; b++)
+        total += lv[b].n;
+    const double bd = std::floor(clip_ppm * 1e-6 * (double)(2 * total));
+    const uint64_t budget = bd >= 0x1p+64 ? ~0ull : (uint64_t)bd;
+    int over = 0, a = 0, q = 0;
+    uint64_t c16 = 0, c8 = 0;
+    for (a = 0; a <= 7; a++) {
+        level_clips(lv, n, a, false, 0, &c16, &c8);
+        if (c16 <= budget)
+            break;
+    }
+    if (a > 7) {
+        a = 7;
+        over = 1;
+    }
+    if (f == 1 && over) {
+        q = 15; /* nothing scales this into int16: both largest values */
+    } else if (f == 1) {
+        for (q = 0; q <= 15; q++) {
+            level_clips(lv, n, a, true, q, &c16, &c8);
+            if (c8 <= budget)
+                break;
+        }
+        if (q > 15) {
+            q = 15;
+            over = 1;
+        }
+    }
+    *shift = a;
+    *shift8 = q;
+    return over;
+}
+
+extern "C" double gpsbb_level_rms(const gpsbb_level_t *lv, long n, int component)
+{
+    if (!lv || n < 1 || component < 0 || component > 1)
+        return NAN;
+    long double sq = 0.0L, cnt = 0.0L;
+    for (long b = 0; b < n; b++) {
+        sq += (long double)lv[b].sumsq[component];
+        cnt += (long double)lv[b].n;
+    }
+    return cnt > 0.0L ? (double)sqrtl(sq / cnt) : NAN;
+}
+
 /* ---- despreading: the render read back the way its consumer reads it (include/gpsbb.h, gpsbb_despread.hip.h) ---- */
 
 extern "C" long gpsbb_despread_segments(long nsamp, int seg_tiles)
@@ -3461,6 +3647,9 @@ struct gpsbb_stream {
         gpsbb_chan_state_t *h_end = nullptr; /* pinned */
         unsigned long long *h_dig = nullptr; /* pinned, on the first GPSBB_PUSH_DIGEST: the push's block digests */
         bool has_dig = false;
+        LevelOut *d_lvl = nullptr;           /* on the first GPSBB_PUSH_LEVEL: the push's block levels on the device ... */
+        LevelOut *h_lvl = nullptr;           /* ... and pinned, behind the gather on its stream */
+        bool has_lvl = false;
         hipEvent_t computed = nullptr, copied = nullptr;
     };
     std::vector<Slot> slots;
@@ -3497,6 +3686,8 @@ extern "C" void gpsbb_stream_destroy(gpsbb_stream_t *s)
         if (sl.batch) gpsbb_batch_destroy(sl.batch);
         if (sl.h_iq) (void)hipHostFree(sl.h_iq);
         if (sl.h_dig) (void)hipHostFree(sl.h_dig);
+        if (sl.h_lvl) (void)hipHostFree(sl.h_lvl);
+        if (sl.d_lvl) (void)hipFree(sl.d_lvl);
         if (sl.h_end) (void)hipHostFree(sl.h_end);
         if (sl.computed) (void)hipEventDestroy(sl.computed);
         if (sl.copied) (void)hipEventDestroy(sl.copied);
@@ -3650,18 +3841,20 @@ extern "C" int gpsbb_stream_timing_stats(gpsbb_stream_t *s, int *nruns, float *m
     return GPSBB_OK;
 }
 
-static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain, bool want_digest);
+static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain, bool want_digest, bool want_level);
 
-extern "C" int gpsbb_stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch) { return stream_push(s, ch, false, false); }
+extern "C" int gpsbb_stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch) { return stream_push(s, ch, false, false, false); }
 
 extern "C" int gpsbb_stream_push_ex(gpsbb_stream_t *s, const gpsbb_chan_t *ch, unsigned flags)
 {
-    if (flags & ~(GPSBB_PUSH_NEW_CHAIN | GPSBB_PUSH_DIGEST))
+    if (flags & ~(GPSBB_PUSH_NEW_CHAIN | GPSBB_PUSH_DIGEST | GPSBB_PUSH_LEVEL))
         return GPSBB_E_BADARG;
-    return stream_push(s, ch, (flags & GPSBB_PUSH_NEW_CHAIN) != 0, (flags & GPSBB_PUSH_DIGEST) != 0);
+    if ((flags & GPSBB_PUSH_LEVEL) && ((flags & GPSBB_PUSH_DIGEST) || (s && (s->flags & GPSBB_STREAM_DEVICE_ONLY))))
+        return GPSBB_E_BADARG; /* (measured on the gather's stream: a ring without one, or a push whose digests ride elsewhere) */
+    return stream_push(s, ch, (flags & GPSBB_PUSH_NEW_CHAIN) != 0, (flags & GPSBB_PUSH_DIGEST) != 0, (flags & GPSBB_PUSH_LEVEL) != 0);
 }
 
-static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain, bool want_digest)
+static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain, bool want_digest, bool want_level)
 {
     if (!s || !ch)
         return GPSBB_E_BADARG;
@@ -3669,6 +3862,26 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
         return GPSBB_E_STATE; /* ring full: pop first */
     if (s->interf_on && (s->noise_pos >= INTERF_POS_END || (uint64_t)s->bps * (uint64_t)s->nsamp > INTERF_POS_END - s->noise_pos))
         return GPSBB_E_BADARG; /* the push would reach position 2^63 */
+    /* GPSBB_PUSH_LEVEL: what k_level will be given, checked and its memory made before anything of the push exists */
+    ImpairArgs lvl_args;
+    memset(&lvl_args, 0, sizeof lvl_args);
+    if (want_level) {
+        if (s->noise_on)
+            lvl_args.nz = s->noise;
+        lvl_args.nz.sample0 = s->noise_pos;
+        if (s->interf_on) {
+            lvl_args.it = s->interf;
+            (void)interf_at(&lvl_args.it, s->noise_pos, (uint64_t)s->bps * (uint64_t)s->nsamp); /* (the range: checked above) */
+        }
+        if (!level_fits(lvl_args, s->noise_on, s->nsamp))
+            return GPSBB_E_BADARG;
+        auto &lsl = s->slots[s->head % s->depth];
+        HIPCHK(s->h, hipSetDevice(s->h->device));
+        if (!lsl.d_lvl)
+            HIPCHK(s->h, hipMalloc((void **)&lsl.d_lvl, (size_t)s->bps * sizeof(LevelOut)));
+        if (!lsl.h_lvl)
+            HIPCHK(s->h, hipHostMalloc((void **)&lsl.h_lvl, (size_t)s->bps * sizeof(LevelOut), hipHostMallocDefault));
+    }
     if (new_chain) {
         /* this push does not continue the one before: every channel of its first block starts from its descriptor's phase,
          * as if it had just been allocated (c:1956-1964) — "no satellite was here before" is all the chain has to be told */
@@ -3822,6 +4035,7 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
     if (want_digest && !sl.h_dig)
         HIPCHK(h, hipHostMalloc((void **)&sl.h_dig, (size_t)s->bps * sizeof(unsigned long long), hipHostMallocDefault));
     sl.has_dig = false;
+    sl.has_lvl = false;
     rc = batch_launch(b, b->d_iq.p);
     PUSH_MARK("launch");
     b->d_carry = nullptr;
@@ -3884,6 +4098,12 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
         HIPCHK(h, hipMemcpyAsync(sl.h_dig, b->d_dig.p, (size_t)s->bps * sizeof(unsigned long long), hipMemcpyDeviceToHost, cs));
         sl.has_dig = true;
     }
+    if (want_level) {
+        /* the slot measured where it is gathered: behind the gather, on its stream, results through pinned memory */
+        HIPCHK(h, level_launch(h, lvl_args, s->noise_on, b->d_iq.p, s->bps, s->nsamp, sl.d_lvl, cs));
+        HIPCHK(h, hipMemcpyAsync(sl.h_lvl, sl.d_lvl, (size_t)s->bps * sizeof(LevelOut), hipMemcpyDeviceToHost, cs));
+        sl.has_lvl = true;
+    }
     PUSH_MARK("endst");
     HIPCHK(h, hipEventRecord(sl.copied, cs));
     /* commit */
@@ -3910,7 +4130,19 @@ extern "C" int gpsbb_stream_pop(gpsbb_stream_t *s, const int16_t **iq, gpsbb_cha
     return gpsbb_stream_pop_digest(s, iq, end_state, nullptr);
 }
 
+static int stream_pop(gpsbb_stream_t *s, const int16_t **iq, gpsbb_chan_state_t *end_state, uint64_t *digests, gpsbb_level_t *levels);
+
 extern "C" int gpsbb_stream_pop_digest(gpsbb_stream_t *s, const int16_t **iq, gpsbb_chan_state_t *end_state, uint64_t *digests)
+{
+    return stream_pop(s, iq, end_state, digests, nullptr);
+}
+
+extern "C" int gpsbb_stream_pop_level(gpsbb_stream_t *s, const int16_t **iq, gpsbb_chan_state_t *end_state, gpsbb_level_t *levels)
+{
+    return stream_pop(s, iq, end_state, nullptr, levels);
+}
+
+static int stream_pop(gpsbb_stream_t *s, const int16_t **iq, gpsbb_chan_state_t *end_state, uint64_t *digests, gpsbb_level_t *levels)
 {
     if (!s || !iq)
         return GPSBB_E_BADARG;
@@ -3918,6 +4150,8 @@ extern "C" int gpsbb_stream_pop_digest(gpsbb_stream_t *s, const int16_t **iq, gp
         return GPSBB_E_STATE;
     if (digests && !s->slots[s->tail % s->depth].has_dig)
         return GPSBB_E_STATE; /* the slot was not pushed with GPSBB_PUSH_DIGEST */
+    if (levels && !s->slots[s->tail % s->depth].has_lvl)
+        return GPSBB_E_STATE; /* ... nor with GPSBB_PUSH_LEVEL */
     gpsbb *h = s->h;
     HIPCHK(h, hipSetDevice(h->device));
     auto &sl = s->slots[s->tail % s->depth];
@@ -3927,6 +4161,8 @@ extern "C" int gpsbb_stream_pop_digest(gpsbb_stream_t *s, const int16_t **iq, gp
         memcpy(end_state, sl.h_end, (size_t)s->bps * s->nch * sizeof(gpsbb_chan_state_t));
     if (digests)
         memcpy(digests, sl.h_dig, (size_t)s->bps * sizeof(unsigned long long));
+    if (levels)
+        memcpy(levels, sl.h_lvl, (size_t)s->bps * sizeof(gpsbb_level_t));
     s->tail++;
     uint32_t st = 0;
     memcpy(&st, (const char *)sl.h_end + (((size_t)s->bps * s->nch * sizeof(gpsbb_chan_state_t) + 15) & ~(size_t)15), 4);

@@ -75,6 +75,27 @@ __device__ __forceinline__ void impair_unit(gather_u32x4 q, unsigned long long s
     }
 }
 
+/* impair_unit stopped before the shift: the 8 values x = v + N + J of step 4 (k_level measures them, gpsbb_level.hip.h) */
+template <bool ODD, bool NOISE>
+__device__ __forceinline__ void impair_unit_x(gather_u32x4 q, unsigned long long s, const NoiseArgs &a, const int2 *tab, const int jj[8],
+                                              int xo[8])
+{
+    uint32_t x[12];
+    if (NOISE) {
+        const unsigned long long m = s >> 1;
+        noise_philox((uint32_t)m, (uint32_t)(m >> 32), a.key0, a.key1, x);
+        noise_philox((uint32_t)(m + 1), (uint32_t)((m + 1) >> 32), a.key0, a.key1, x + 4);
+        if (ODD)
+            noise_philox((uint32_t)(m + 2), (uint32_t)((m + 2) >> 32), a.key0, a.key1, x + 8);
+    }
+    const uint32_t v[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const int c = (j & 1) ? (int)v[j >> 1] >> 16 : (int)(v[j >> 1] << 16) >> 16;
+        xo[j] = c + jj[j] + (NOISE ? noise_n(x[(ODD ? 2 : 0) + j], tab, a.s256) : 0);
+    }
+}
+
 /* noise_comp with J: one component k of the source (the ragged tail and the unaligned path) */
 template <bool NOISE>
 __device__ __forceinline__ int impair_comp(int v, size_t k, const ImpairArgs &a, const int2 *tab, const uint32_t *cs, uint32_t &clip)

@@ -40,6 +40,12 @@
  * interference (include/gpsbb.h gpsbb_interf_t): J/S in dB against a gain-1.0 channel, a tone at f_hz or a sawtooth sweep from
  * f0_hz to f1_hz every sweep_s seconds, optionally pulsed.  It goes in where the noise goes, w = sat16((v + N + J) >> shift); with
  * -W the shift is -W's, without it -j shift (0..7, default 0).  The same bytes on every path, as for -W.
+ * -A clip_ppm chooses both shifts from a measurement (include/gpsbb.h gpsbb_level_t) instead of taking them from -W cn0,shift / -j
+ * and -q: before generating, the scenario's first min(blocks, 10) blocks are rendered as a resident batch, measured with the
+ * run's own -W noise and -J emitters from position 0 (gpsbb_device_level) and the smallest shifts whose predicted clips stay
+ * within clip_ppm parts per million are taken (gpsbb_level_choose; 100 is the usual budget).  The run then goes on exactly as if
+ * those shifts had been given: the bytes are those of the explicit options, on every path.  The choice is made once, from the
+ * first second: a power change later in the run shows up in the clip counters, not in the scale.
  */
 #include <math.h>
 #include <stdio.h>
@@ -195,6 +201,56 @@ static void report_clipped(gpsbb_t *bb, int bits, int noise)
         fprintf(stderr, "noise components clipped: %llu\n", (unsigned long long)clipped);
 }
 
+/* -A: the first K blocks of the scenario rendered as a resident batch on `gpu`, measured with the run's noise and emitters from
+ * position 0, and the shifts chosen for clip_ppm.  The front end is opened a second time for it: the run's own starts afresh. */
+static int agc_choose(const gpsfe_config_t *cfg, int gpu, double delt, long nsamp, long nblocks, unsigned oflags, double clip_ppm,
+                      const gpsbb_noise_t *noise, const gpsbb_interf_set_t *interf, int *a_out, int *q_out)
+{
+    const int K = nblocks < 10 ? (int)(nblocks > 0 ? nblocks : 1) : 10;
+    gpsfe_t *fe = NULL;
+    gpsbb_t *bb = NULL;
+    gpsbb_batch_t *bt = NULL;
+    gpsbb_chan_t *ch = malloc((size_t)K * cfg->max_chan * sizeof *ch);
+    gpsbb_level_t *lv = malloc((size_t)K * sizeof *lv);
+    int ok = ch && lv && gpsfe_open(cfg, &fe) == GPSFE_OK;
+    int rc = GPSBB_OK;
+    if (ok) {
+        gpsfe_generate(fe, K, ch);
+        rc = gpsbb_create(&bb, gpu);
+        if (rc == GPSBB_OK) rc = gpsbb_batch_create(bb, ch, K, cfg->max_chan, delt, (int)nsamp, GPSBB_CHAIN_CARRIER, &bt);
+        if (rc == GPSBB_OK) rc = gpsbb_batch_run(bt, NULL);
+        if (rc == GPSBB_OK) rc = gpsbb_sync(bb);
+        if (rc == GPSBB_OK) rc = gpsbb_device_level(bb, gpsbb_batch_device_iq(bt), K, (int)nsamp, noise, interf, lv);
+        if (rc == GPSBB_OK) {
+            rc = gpsbb_level_choose(lv, K, oflags, clip_ppm, a_out, q_out);
+            if (rc == 1)
+                fprintf(stderr, "agc: even the largest shifts leave more than %g ppm clipped\n", clip_ppm);
+            rc = rc < 0 ? rc : GPSBB_OK;
+        }
+        if (rc == GPSBB_OK) {
+            uint64_t c16 = 0, c8 = 0, n = 0;
+            const unsigned f = (oflags & GPSBB_OUT_FORMAT_MASK) == (GPSBB_OUT_SC8(0) & GPSBB_OUT_FORMAT_MASK) ? GPSBB_OUT_SC8(*q_out)
+                                                                                                              : (oflags & GPSBB_OUT_FORMAT_MASK);
+            (void)gpsbb_level_clips(lv, K, *a_out, f, &c16, &c8);
+            for (int b = 0; b < K; b++)
+                n += 2 * lv[b].n;
+            fprintf(stderr, "agc: shift %d, q %d, rms %.1f %.1f, predicted clips %llu %llu of %llu components (%d blocks)\n", *a_out, *q_out,
+                    gpsbb_level_rms(lv, K, 0), gpsbb_level_rms(lv, K, 1), (unsigned long long)c16, (unsigned long long)c8,
+                    (unsigned long long)n, K);
+        } else {
+            fprintf(stderr, "ERROR: -A: %s\n", gpsbb_strerror(rc));
+        }
+    } else {
+        fprintf(stderr, "ERROR: -A: cannot prepare the measurement\n");
+    }
+    if (bt) gpsbb_batch_destroy(bt);
+    if (bb) gpsbb_destroy(bb);
+    if (fe) gpsfe_close(fe);
+    free(ch);
+    free(lv);
+    return ok && rc == GPSBB_OK;
+}
+
 static void usage(void)
 {
     fprintf(stderr, "usage: gpsbb-sim -e nav [-l lat,lon,h|-c x,y,z|-u motion.csv] [-t Y/M/D,h:m:s] [-T] [-i] [-3]\n"
@@ -202,6 +258,9 @@ static void usage(void)
                     "                 [-P usec_per_block] [-Q device_queue_blocks] [-S stats.json] [-k keep,blocks] [-b 1|8|16] [-q shift]\n"
                     "                 [-W cn0_dbhz[,shift]] [-w seed]\n"
                     "                 [-J cw,js_db,f_hz[,period_s,duty]] [-J chirp,js_db,f0_hz,f1_hz,sweep_s[,period_s,duty]] [-j shift]\n"
+                    "                 [-A clip_ppm]   choose the -W/-j shift and -q from the level of the first second (up to 10 blocks),\n"
+                    "                                 once: a later power change shows in the clip counters, not in the scale;\n"
+                    "                                 not together with -q, -j or a shift inside -W cn0,shift\n"
                     "                 -o out.bin\n");
 }
 
@@ -228,14 +287,15 @@ int main(int argc, char **argv)
     paced.queue = 4; /* libiio's default number of kernel buffers */
     const char *stats_path = NULL;
     const char *out_path = NULL;
-    int bits = 16, shift = 5;
+    int bits = 16, shift = 5, shift_given = 0;
+    const char *agc_arg = NULL;
     const char *noise_arg = NULL;
     unsigned long long noise_seed = 1;
     const char *interf_arg[GPSBB_INTERF_MAX + 1];
     int ninterf = 0;
     const char *interf_shift_arg = NULL;
 
-    while ((opt = getopt(argc, argv, "e:u:c:l:s:Tt:in:N:d:o:g:3FG:P:S:k:Q:ICRb:q:W:w:J:j:")) != -1) {
+    while ((opt = getopt(argc, argv, "e:u:c:l:s:Tt:in:N:d:o:g:3FG:P:S:k:Q:ICRb:q:W:w:J:j:A:")) != -1) {
         switch (opt) {
         case 'e': cfg.navfile = optarg; break;
         case 'u': cfg.motion_file = optarg; break;
@@ -287,7 +347,8 @@ int main(int argc, char **argv)
         case 'F': fast = 1; break;
         case 'R': no_register = 1; break; /* the drop-in call copies into iq_buff instead of rendering straight into it */
         case 'b': bits = atoi(optarg); break;
-        case 'q': shift = atoi(optarg); break;
+        case 'q': shift = atoi(optarg); shift_given = 1; break;
+        case 'A': agc_arg = optarg; break;
         case 'W': noise_arg = optarg; break;
         case 'w': noise_seed = strtoull(optarg, NULL, 0); break;
         case 'J':
@@ -303,10 +364,21 @@ int main(int argc, char **argv)
         usage();
         return 1;
     }
+    double agc_ppm = 0.0;
+    if (agc_arg) {
+        char *end = NULL;
+        agc_ppm = strtod(agc_arg, &end);
+        if (end == agc_arg || *end != 0 || !(agc_ppm >= 0.0) || !isfinite(agc_ppm) || shift_given || interf_shift_arg ||
+            (noise_arg && strchr(noise_arg, ','))) {
+            fprintf(stderr, "ERROR: -A wants a clip budget in ppm (>= 0) and chooses the shifts itself: not with -q, -j or -W cn0,shift\n");
+            usage();
+            return 1;
+        }
+    }
     if (nsamp == 0)
         nsamp = fs_hz / 10;
     /* the output format, the same bits on every path (fill, stream, node) */
-    const unsigned oflags = bits == 8 ? GPSBB_OUT_SC8(shift) : (bits == 1 ? GPSBB_OUT_SC1 : GPSBB_OUT_SC16);
+    unsigned oflags = bits == 8 ? GPSBB_OUT_SC8(shift) : (bits == 1 ? GPSBB_OUT_SC1 : GPSBB_OUT_SC16);
     const long obytes = gpsbb_out_bytes(oflags, nsamp);
     if (obytes < 0) {
         fprintf(stderr, "ERROR: -b %d needs a block of a multiple of 4 samples (-n)\n", bits);
@@ -367,6 +439,18 @@ int main(int argc, char **argv)
         fprintf(stderr, "interference: %d emitter%s, shift %d\n", jset.n, jset.n == 1 ? "" : "s", jset.shift);
     }
 
+    if (agc_arg) {
+        /* -A: both shifts from the level of the first blocks; from here on the run is the one of the explicit options */
+        int a = 0, q = 0;
+        if (!agc_choose(&cfg, nshards > 0 && ndev > 0 ? devs[0] : gpu, delt, nsamp, nblocks, oflags, agc_ppm, noise, interf, &a, &q))
+            return 1;
+        nz.shift = a;
+        jset.shift = a;
+        if (bits == 8) {
+            shift = q;
+            oflags = GPSBB_OUT_SC8(shift);
+        }
+    }
     gpsfe_t *fe = NULL;
     int rc = gpsfe_open(&cfg, &fe);
     if (rc != GPSFE_OK) {
