@@ -2613,17 +2613,8 @@ extern "C" long gpsbb_out_bytes(unsigned flags, long nsamp)
     return fmt < 0 ? GPSBB_E_BADARG : (long)out_block_bytes(fmt, (size_t)nsamp);
 }
 
-/* Enqueue the packing of n int16 components at src (device memory) into dst (device memory, or host memory the device can write:
- * pinned, registered) on `stream`.  Returns at once, like the int16 gather (k_gather_to_host): the same grid. */
-static hipError_t pack_launch(gpsbb *h, int fmt, int shift, const int16_t *src, void *dst, size_t n, hipStream_t stream)
-{
-    const int gwg = (int)GPSBB_KNOB_LONG("GPSBB_GATHER_WGS", 32);
-    if (fmt == PACK_SC8)
-        hipLaunchKernelGGL(k_pack_iq<PACK_SC8>, dim3(gwg), dim3(256), 0, stream, src, (unsigned char *)dst, n, shift, h->d_clip);
-    else
-        hipLaunchKernelGGL(k_pack_iq<PACK_SC1>, dim3(gwg), dim3(256), 0, stream, src, (unsigned char *)dst, n, shift, h->d_clip);
-    return hipGetLastError();
-}
+struct ImpairCall;
+static hipError_t out_launch(gpsbb *h, int fmt, int shift8, const ImpairCall *ic, const int16_t *src, void *dst, size_t n, hipStream_t stream);
 
 static hipError_t pack_reserve(gpsbb *h, size_t bytes)
 {
@@ -2655,7 +2646,7 @@ extern "C" int gpsbb_device_pack(gpsbb_t *h, const int16_t *d_iq, long nblocks, 
         return GPSBB_OK;
     }
     HIPCHK(h, pack_reserve(h, bytes));
-    HIPCHK(h, pack_launch(h, fmt, shift, d_iq, h->d_pack, (size_t)nblocks * (size_t)nsamp * 2, h->s_compute));
+    HIPCHK(h, out_launch(h, fmt, shift, nullptr, d_iq, h->d_pack, (size_t)nblocks * (size_t)nsamp * 2, h->s_compute));
     HIPCHK(h, hipMemcpyAsync(host_dst, h->d_pack, bytes, hipMemcpyDeviceToHost, h->s_compute));
     HIPCHK(h, hipStreamSynchronize(h->s_compute));
     return GPSBB_OK;
@@ -2773,36 +2764,11 @@ static hipError_t noise_ready(gpsbb *h)
     return e;
 }
 
-/* Enqueue k_noise_iq: n int16 components at src (device memory) with noise into dst (device memory, or host memory the device
- * can write) in format fmt (0 = SC16, PACK_SC8 with a.shift8, PACK_SC1).  Returns at once.  The grid is wider than the gather's:
- * the noise costs VALU work per sample that 32 workgroups cannot issue at the rate the formats leave the GPU */
-static hipError_t noise_launch(gpsbb *h, int fmt, const NoiseArgs &a, const int16_t *src, void *dst, size_t n, hipStream_t stream)
-{
-    const size_t nchunk = (n / 8 + PACK_UNITS - 1) / PACK_UNITS;
-    const long knob = GPSBB_KNOB_LONG("GPSBB_NOISE_WGS", 256);
-    const int gwg = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1L, knob), nchunk)); /* (no workgroup without work) */
-    if (fmt == PACK_SC8)
-        hipLaunchKernelGGL(k_noise_iq<PACK_SC8>, dim3(gwg), dim3(256), 0, stream, src, dst, n, a, h->d_noise_tab, h->d_nclip, h->d_clip);
-    else if (fmt == PACK_SC1)
-        hipLaunchKernelGGL(k_noise_iq<PACK_SC1>, dim3(gwg), dim3(256), 0, stream, src, dst, n, a, h->d_noise_tab, h->d_nclip, h->d_clip);
-    else
-        hipLaunchKernelGGL(k_noise_iq<NOISE_SC16>, dim3(gwg), dim3(256), 0, stream, src, dst, n, a, h->d_noise_tab, h->d_nclip, h->d_clip);
-    return hipGetLastError();
-}
-
 extern "C" int gpsbb_device_noise(gpsbb_t *h, const int16_t *d_src, int16_t *d_dst, long nblocks, int nsamp, const gpsbb_noise_t *nz)
 {
-    NoiseArgs a;
-    if (!h || !d_src || !d_dst || !nz || nblocks < 1 || nsamp < 1 || !noise_args(nz, &a) || (((uintptr_t)d_src | (uintptr_t)d_dst) & 1))
+    if (!nz)
         return GPSBB_E_BADARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    const int rc = gpsbb_sync(h); /* as gpsbb_device_pack: whatever the handle was rendering into d_src is there */
-    if (rc != GPSBB_OK)
-        return rc;
-    HIPCHK(h, noise_ready(h));
-    HIPCHK(h, noise_launch(h, NOISE_SC16, a, d_src, d_dst, (size_t)nblocks * (size_t)nsamp * 2, h->s_compute));
-    HIPCHK(h, hipStreamSynchronize(h->s_compute));
-    return GPSBB_OK;
+    return gpsbb_device_impair(h, d_src, d_dst, nblocks, nsamp, nz, nullptr);
 }
 
 /* ---- interference (include/gpsbb.h gpsbb_interf_t; gpsbb_interf.h, gpsbb_interf.hip.h) ---- */
@@ -2961,64 +2927,87 @@ extern "C" int gpsbb_interf_eval(const gpsbb_interf_set_t *set, uint64_t s, long
     return GPSBB_OK;
 }
 
-/* a call with a set: the noise (or none) and the set checked together, at a launch of nsamples from the set's sample0 */
+/* What happens to the render on the way out: the noise (or none) and the set (or none) of one call, checked together, at a
+ * launch of nsamples from their common sample0.  Neither: the plain gather or pack. */
 struct ImpairCall {
-    ImpairArgs a;
-    bool noise;
+    ImpairArgs a; /* a.nz.sample0 == a.it.sample0 and a.nz.shift == a.it.shift: the launch's */
+    bool noise;   /* nz was given */
+    bool set;     /* a set was given (an empty one too: its shift and its range still hold) */
+    bool any() const { return noise || set; }
 };
-static bool impair_args(const gpsbb_noise_t *nz, const gpsbb_interf_set_t *set, uint64_t nsamples, ImpairCall *c)
+
+/* the launch's first sample s0 and its length; false: with a set, the range reaches 2^63 */
+static bool impair_at(ImpairCall *c, uint64_t s0, uint64_t nsamples)
 {
-    memset(c, 0, sizeof *c);
-    if (nz && !noise_args(nz, &c->a.nz))
-        return false;
-    if (!interf_args(set, &c->a.it))
-        return false;
-    if (nz && (nz->sample0 != set->sample0 || nz->shift != set->shift))
-        return false;
-    if (!interf_at(&c->a.it, set->sample0, nsamples))
-        return false;
-    c->a.nz.sample0 = set->sample0;
-    c->a.nz.shift = set->shift;
-    c->noise = nz != nullptr;
-    return true;
+    c->a.nz.sample0 = c->a.it.sample0 = s0;
+    return !c->set || interf_at(&c->a.it, s0, nsamples);
 }
 
-/* Enqueue k_impair_iq, as noise_launch enqueues k_noise_iq (the same grid).  An empty set with noise IS the noise call. */
-static hipError_t impair_launch(gpsbb *h, int fmt, const ImpairArgs &a, bool noise, const int16_t *src, void *dst, size_t n,
-                                hipStream_t stream)
+/* nz and set as every call that takes them checks them, either or both absent; false: GPSBB_E_BADARG */
+static bool impair_make(const gpsbb_noise_t *nz, const gpsbb_interf_set_t *set, uint64_t nsamples, ImpairCall *c)
 {
-    if (noise && a.it.n == 0)
-        return noise_launch(h, fmt, a.nz, src, dst, n, stream);
-    const size_t nchunk = (n / 8 + PACK_UNITS - 1) / PACK_UNITS;
-    const int gwg = (int)std::max<size_t>(1, std::min<size_t>(256, nchunk));
-#define GPSBB_IMPAIR_GO(F, N) \
-    hipLaunchKernelGGL((k_impair_iq<F, N>), dim3(gwg), dim3(256), 0, stream, src, dst, n, a, h->d_noise_tab, h->d_tabs, h->d_nclip, h->d_clip)
-    if (fmt == PACK_SC8) {
-        if (noise) GPSBB_IMPAIR_GO(PACK_SC8, true); else GPSBB_IMPAIR_GO(PACK_SC8, false);
-    } else if (fmt == PACK_SC1) {
-        if (noise) GPSBB_IMPAIR_GO(PACK_SC1, true); else GPSBB_IMPAIR_GO(PACK_SC1, false);
-    } else {
-        if (noise) GPSBB_IMPAIR_GO(NOISE_SC16, true); else GPSBB_IMPAIR_GO(NOISE_SC16, false);
+    memset(c, 0, sizeof *c);
+    c->noise = nz != nullptr;
+    c->set = set != nullptr;
+    if (nz && !noise_args(nz, &c->a.nz))
+        return false;
+    if (set) {
+        if (!interf_args(set, &c->a.it))
+            return false;
+        if (nz && (nz->sample0 != set->sample0 || nz->shift != set->shift))
+            return false;
+        c->a.nz.shift = set->shift;
     }
-#undef GPSBB_IMPAIR_GO
+    return impair_at(c, set ? set->sample0 : c->a.nz.sample0, nsamples);
+}
+
+/* Enqueue what takes n int16 components at src (device memory) to dst (device memory, or host memory the device can write: pinned,
+ * registered) in format fmt (0 = SC16, PACK_SC8 with shift8, PACK_SC1) on `stream`.  Returns at once.  Without impairments (ic
+ * null) the plain gather or pack on GPSBB_GATHER_WGS workgroups; with them k_impair_iq on a wider grid: noise and emitters cost
+ * VALU work per sample that 32 workgroups cannot issue at the rate the formats leave the GPU.  An empty set with noise
+ * IS the noise launch. */
+static hipError_t out_launch(gpsbb *h, int fmt, int shift8, const ImpairCall *ic, const int16_t *src, void *dst, size_t n, hipStream_t stream)
+{
+    if (!ic) {
+        const int gwg = (int)GPSBB_KNOB_LONG("GPSBB_GATHER_WGS", 32);
+        if (fmt == PACK_SC8)
+            hipLaunchKernelGGL(k_pack_iq<PACK_SC8>, dim3(gwg), dim3(256), 0, stream, src, (unsigned char *)dst, n, shift8, h->d_clip);
+        else if (fmt == PACK_SC1)
+            hipLaunchKernelGGL(k_pack_iq<PACK_SC1>, dim3(gwg), dim3(256), 0, stream, src, (unsigned char *)dst, n, shift8, h->d_clip);
+        else
+            hipLaunchKernelGGL(k_gather_to_host, dim3(gwg), dim3(256), 0, stream, (const gather_u32x4 *)src, (gather_u32x4 *)dst,
+                               (n * 2 + 15) / 16);
+        return hipGetLastError();
+    }
+    ImpairArgs a = ic->a;
+    a.nz.shift8 = shift8;
+    const size_t nchunk = (n / 8 + PACK_UNITS - 1) / PACK_UNITS;
+    const long knob = GPSBB_KNOB_LONG("GPSBB_NOISE_WGS", 256);
+    const int gwg = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1L, knob), nchunk)); /* (no workgroup without work) */
+    typedef void (*ImpairKernelFn)(const int16_t *, void *, size_t, ImpairArgs, const int2 *, const int32_t *, unsigned long long *,
+                                   unsigned long long *);
+#define GPSBB_IMPAIR_ROW(F) {k_impair_iq<F, true, false>, k_impair_iq<F, true, true>, k_impair_iq<F, false, true>}
+    static const ImpairKernelFn k[3][3] = {GPSBB_IMPAIR_ROW(NOISE_SC16), GPSBB_IMPAIR_ROW(PACK_SC8), GPSBB_IMPAIR_ROW(PACK_SC1)};
+#undef GPSBB_IMPAIR_ROW
+    /* (a set without noise, an empty one too, runs the emitter loop: its shift still holds) */
+    hipLaunchKernelGGL(k[fmt][!ic->noise ? 2 : (a.it.n > 0 ? 1 : 0)], dim3(gwg), dim3(256), 0, stream, src, dst, n, a, h->d_noise_tab,
+                       h->d_tabs, h->d_nclip, h->d_clip);
     return hipGetLastError();
 }
 
 extern "C" int gpsbb_device_impair(gpsbb_t *h, const int16_t *d_src, int16_t *d_dst, long nblocks, int nsamp, const gpsbb_noise_t *nz,
                                    const gpsbb_interf_set_t *set)
 {
-    if (!set)
-        return gpsbb_device_noise(h, d_src, d_dst, nblocks, nsamp, nz);
     ImpairCall c;
-    if (!h || !d_src || !d_dst || nblocks < 1 || nsamp < 1 || (((uintptr_t)d_src | (uintptr_t)d_dst) & 1) ||
-        !impair_args(nz, set, (uint64_t)nblocks * (uint64_t)nsamp, &c))
+    if (!h || !d_src || !d_dst || (!nz && !set) || nblocks < 1 || nsamp < 1 || (((uintptr_t)d_src | (uintptr_t)d_dst) & 1) ||
+        !impair_make(nz, set, (uint64_t)nblocks * (uint64_t)nsamp, &c))
         return GPSBB_E_BADARG;
     HIPCHK(h, hipSetDevice(h->device));
-    const int rc = gpsbb_sync(h);
+    const int rc = gpsbb_sync(h); /* as gpsbb_device_pack: whatever the handle was rendering into d_src is there */
     if (rc != GPSBB_OK)
         return rc;
     HIPCHK(h, noise_ready(h));
-    HIPCHK(h, impair_launch(h, NOISE_SC16, c.a, c.noise, d_src, d_dst, (size_t)nblocks * (size_t)nsamp * 2, h->s_compute));
+    HIPCHK(h, out_launch(h, NOISE_SC16, 0, &c, d_src, d_dst, (size_t)nblocks * (size_t)nsamp * 2, h->s_compute));
     HIPCHK(h, hipStreamSynchronize(h->s_compute));
     return GPSBB_OK;
 }
@@ -3047,21 +3036,8 @@ static bool level_fits(const ImpairArgs &a, bool noise, int nsamp)
     return bb * (unsigned __int128)nsamp < ((unsigned __int128)1 << 64);
 }
 
-/* the arguments of a measurement of nsamples samples: nz and set as the impair calls check them, either or both absent */
-static bool level_args(const gpsbb_noise_t *nz, const gpsbb_interf_set_t *set, uint64_t nsamples, ImpairCall *c)
-{
-    if (set)
-        return impair_args(nz, set, nsamples, c);
-    memset(c, 0, sizeof *c);
-    if (nz && !noise_args(nz, &c->a.nz))
-        return false;
-    c->a.it.sample0 = c->a.nz.sample0;
-    c->noise = nz != nullptr;
-    return true;
-}
-
 /* Enqueue k_level over nblocks blocks at src into d_out (zeroed on the stream first).  The grid: the flattened (block, chunk) list,
- * at most one workgroup per CU, as noise_launch's. */
+ * at most one workgroup per CU, as k_impair_iq's. */
 static hipError_t level_launch(gpsbb *h, const ImpairArgs &a, bool noise, const int16_t *src, long nblocks, int nsamp, LevelOut *d_out,
                                hipStream_t stream)
 {
@@ -3088,7 +3064,7 @@ extern "C" int gpsbb_device_level(gpsbb_t *h, const int16_t *d_iq, long nblocks,
 {
     ImpairCall c;
     if (!h || !d_iq || !out || nblocks < 1 || nsamp < 1 || ((uintptr_t)d_iq & 3) ||
-        !level_args(nz, set, (uint64_t)nblocks * (uint64_t)nsamp, &c) || !level_fits(c.a, c.noise, nsamp))
+        !impair_make(nz, set, (uint64_t)nblocks * (uint64_t)nsamp, &c) || !level_fits(c.a, c.noise, nsamp))
         return GPSBB_E_BADARG;
     HIPCHK(h, hipSetDevice(h->device));
     const int rc = gpsbb_sync(h); /* as gpsbb_device_impair: whatever the handle was rendering into d_iq is there */
@@ -3257,14 +3233,12 @@ static int batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, 
         return GPSBB_E_BADARG;
     gpsbb *h = b->h;
     int shift8 = 0;
-    NoiseArgs na;
-    memset(&na, 0, sizeof na);
     ImpairCall ic;
-    if (set && !impair_args(nz, set, (uint64_t)b->nblocks * (uint64_t)b->nsamp, &ic))
+    if (!impair_make(nz, set, (uint64_t)b->nblocks * (uint64_t)b->nsamp, &ic))
         return GPSBB_E_BADARG;
     /* (nothing is packed here, so SC1 takes any nsamp: the format is looked up for a length it accepts) */
     const int fmt = (view & ~(GPSBB_OUT_FORMAT_MASK | GPSBB_OUT_SHIFT_MASK)) ? -1 : out_format(view, 4, &shift8);
-    if (!out || seg_tiles < 1 || fmt < 0 || (nz && !noise_args(nz, &na)) || ((uintptr_t)d_iq & 3))
+    if (!out || seg_tiles < 1 || fmt < 0 || ((uintptr_t)d_iq & 3))
         return GPSBB_E_BADARG;
     if (!b->ran)
         return GPSBB_E_STATE;
@@ -3310,10 +3284,9 @@ static int batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, 
     a.wgs_per_block = (int)want;
     a.shift8 = shift8;
     a.danger = (uint32_t)GPSBB_KNOB_LONG("GPSBB_DS_DANGER", 2u * PD_BAND); /* (larger: more samples take the exact path; a test aid) */
-    a.nz = na;
+    a.nz = ic.a.nz;
     a.ntab = h->d_noise_tab;
-    if (set)
-        a.it = ic.a.it;
+    a.it = ic.a.it;
 #ifdef GPSBB_EXPERIMENTS
     for (auto &e : b->ds_ev)
         if (!e)
@@ -3454,9 +3427,9 @@ extern "C" int gpsbb_fill_block(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, dou
     return gpsbb_fill_block_ex(h, ch, nch, delt, nsamp, 0u, iq_out, end_state);
 }
 
-/* gpsbb_fill_block_ex, and with na gpsbb_fill_block_noise */
-static int fill_block_impl(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, double delt, int nsamp, unsigned flags, const NoiseArgs *na,
-                           int16_t *iq_out, gpsbb_chan_state_t *end_state, const ImpairCall *ic = nullptr)
+/* gpsbb_fill_block_ex, and with ic gpsbb_fill_block_noise / gpsbb_fill_block_impair */
+static int fill_block_impl(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, double delt, int nsamp, unsigned flags, const ImpairCall *ic,
+                           int16_t *iq_out, gpsbb_chan_state_t *end_state)
 {
     if (!h || !ch || !iq_out)
         return GPSBB_E_BADARG;
@@ -3472,7 +3445,7 @@ static int fill_block_impl(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, double d
     if ((flags & 0xffu & ~GPSBB_FIXED_CARRIER & ~GPSBB_CHAIN_CARRIER) || fmt < 0)
         return GPSBB_E_BADARG;
     const size_t out_bytes = out_block_bytes(fmt, (size_t)nsamp);
-    if (na || ic)
+    if (ic)
         HIPCHK(h, noise_ready(h));
     g_push_trace.start();
     b->one_stream = GPSBB_KNOB_LONG("GPSBB_FILL_ONE_STREAM", 1) != 0;
@@ -3492,30 +3465,20 @@ static int fill_block_impl(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, double d
     }
     /* a packed format: rendered into the handle's buffer, then packed on the same stream — straight into the registered buffer, or
      * into device scratch that is copied out as the int16 block would be */
-    /* (with noise, every format goes this way: the noise kernel reads the render and writes the bytes that leave) */
-    rc = gpsbb_batch_run(b, (fmt || na || ic) ? nullptr : direct);
+    /* (with impairments, every format goes this way: k_impair_iq reads the render and writes the bytes that leave) */
+    rc = gpsbb_batch_run(b, (fmt || ic) ? nullptr : direct);
     if (rc != GPSBB_OK)
         return rc;
     PUSH_MARK("launches");
     const void *src = b->last_iq;
-    if (fmt || na || ic) {
+    if (fmt || ic) {
         void *dst = direct;
         if (!dst) {
             HIPCHK(h, pack_reserve(h, out_bytes));
             dst = h->d_pack;
             src = h->d_pack;
         }
-        if (ic) {
-            ImpairArgs a = ic->a;
-            a.nz.shift8 = shift;
-            HIPCHK(h, impair_launch(h, fmt, a, ic->noise, b->last_iq, dst, (size_t)nsamp * 2, b->last_cs));
-        } else if (na) {
-            NoiseArgs a = *na;
-            a.shift8 = shift;
-            HIPCHK(h, noise_launch(h, fmt, a, b->last_iq, dst, (size_t)nsamp * 2, b->last_cs));
-        } else {
-            HIPCHK(h, pack_launch(h, fmt, shift, b->last_iq, dst, (size_t)nsamp * 2, b->last_cs));
-        }
+        HIPCHK(h, out_launch(h, fmt, shift, ic, b->last_iq, dst, (size_t)nsamp * 2, b->last_cs));
     }
     rc = fill_block_finish(h, b, nch, nsamp, direct ? nullptr : iq_out, end_state, src, out_bytes);
     g_push_trace.end();
@@ -3531,21 +3494,16 @@ extern "C" int gpsbb_fill_block_ex(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, 
 extern "C" int gpsbb_fill_block_noise(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, double delt, int nsamp, unsigned flags,
                                       const gpsbb_noise_t *nz, void *iq_out, gpsbb_chan_state_t *end_state)
 {
-    NoiseArgs a;
-    if (nz && !noise_args(nz, &a))
-        return GPSBB_E_BADARG;
-    return fill_block_impl(h, ch, nch, delt, nsamp, flags, nz ? &a : nullptr, static_cast<int16_t *>(iq_out), end_state);
+    return gpsbb_fill_block_impair(h, ch, nch, delt, nsamp, flags, nz, nullptr, iq_out, end_state);
 }
 
 extern "C" int gpsbb_fill_block_impair(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, double delt, int nsamp, unsigned flags,
                                        const gpsbb_noise_t *nz, const gpsbb_interf_set_t *set, void *iq_out, gpsbb_chan_state_t *end_state)
 {
-    if (!set)
-        return gpsbb_fill_block_noise(h, ch, nch, delt, nsamp, flags, nz, iq_out, end_state);
     ImpairCall c;
-    if (nsamp < 1 || !impair_args(nz, set, (uint64_t)nsamp, &c))
+    if (nsamp < 1 || !impair_make(nz, set, (uint64_t)nsamp, &c))
         return GPSBB_E_BADARG;
-    return fill_block_impl(h, ch, nch, delt, nsamp, flags, nullptr, static_cast<int16_t *>(iq_out), end_state, &c);
+    return fill_block_impl(h, ch, nch, delt, nsamp, flags, c.any() ? &c : nullptr, static_cast<int16_t *>(iq_out), end_state);
 }
 
 /* the reference's own channel_t[] / gain[] in, rendered, updated in place as its loop leaves them; fixed: the build without
@@ -3636,11 +3594,10 @@ struct gpsbb_stream {
     double delt = 0.0;
     unsigned flags = 0;
     int fmt = 0, shift = 0; /* output format of the host gather (GPSBB_OUT_*: 0 int16, PACK_SC8, PACK_SC1) */
-    bool noise_on = false;  /* gpsbb_stream_set_noise: the gather adds noise (k_noise_iq) */
-    NoiseArgs noise{};      /* ... its arguments, sample0 = where the last set_noise put the stream */
-    unsigned long long noise_pos = 0; /* the stream position of the next push's first sample */
-    bool interf_on = false; /* gpsbb_stream_set_interf: the gather adds the set's J (k_impair_iq) */
-    InterfArgs interf{};    /* ... sample0 = where the last set_interf put the stream */
+    bool noise_on = false;  /* gpsbb_stream_set_noise: the gather adds noise (k_impair_iq) ... */
+    bool interf_on = false; /* ... gpsbb_stream_set_interf: and the set's J */
+    ImpairArgs impair{};    /* their arguments: nz and it each as its setter left it, sample0 = where that call put the stream */
+    unsigned long long out_pos = 0; /* the stream position of the next push's first sample */
     struct Slot {
         gpsbb_batch *batch = nullptr;
         int16_t *h_iq = nullptr;            /* pinned */
@@ -3772,7 +3729,7 @@ extern "C" int gpsbb_stream_reset(gpsbb_stream_t *s)
         s->fx_phase[i] = 0;
     }
     s->head = s->tail = 0;
-    s->noise_pos = s->noise_on || !s->interf_on ? s->noise.sample0 : s->interf.sample0;
+    s->out_pos = s->noise_on || !s->interf_on ? s->impair.nz.sample0 : s->impair.it.sample0;
     return GPSBB_OK;
 }
 
@@ -3787,13 +3744,12 @@ extern "C" int gpsbb_stream_set_noise(gpsbb_stream_t *s, const gpsbb_noise_t *nz
     NoiseArgs a;
     if (!noise_args(nz, &a))
         return GPSBB_E_BADARG;
-    if (s->interf_on && (a.sample0 != s->interf.sample0 || a.shift != s->interf.shift))
+    if (s->interf_on && (a.sample0 != s->impair.it.sample0 || a.shift != s->impair.it.shift))
         return GPSBB_E_BADARG; /* (the later of the two calls checks the rule) */
     HIPCHK(s->h, hipSetDevice(s->h->device));
     HIPCHK(s->h, noise_ready(s->h));
-    a.shift8 = s->shift;
-    s->noise = a;
-    s->noise_pos = a.sample0;
+    s->impair.nz = a;
+    s->out_pos = a.sample0;
     s->noise_on = true;
     return GPSBB_OK;
 }
@@ -3809,12 +3765,12 @@ extern "C" int gpsbb_stream_set_interf(gpsbb_stream_t *s, const gpsbb_interf_set
     InterfArgs a;
     if (!interf_args(set, &a) || !interf_at(&a, set->sample0, (uint64_t)s->bps * (uint64_t)s->nsamp))
         return GPSBB_E_BADARG;
-    if (s->noise_on && (s->noise.sample0 != a.sample0 || s->noise.shift != a.shift))
+    if (s->noise_on && (s->impair.nz.sample0 != a.sample0 || s->impair.nz.shift != a.shift))
         return GPSBB_E_BADARG;
     HIPCHK(s->h, hipSetDevice(s->h->device));
     HIPCHK(s->h, noise_ready(s->h));
-    s->interf = a;
-    s->noise_pos = a.sample0;
+    s->impair.it = a;
+    s->out_pos = a.sample0;
     s->interf_on = true;
     return GPSBB_OK;
 }
@@ -3854,26 +3810,34 @@ extern "C" int gpsbb_stream_push_ex(gpsbb_stream_t *s, const gpsbb_chan_t *ch, u
     return stream_push(s, ch, (flags & GPSBB_PUSH_NEW_CHAIN) != 0, (flags & GPSBB_PUSH_DIGEST) != 0, (flags & GPSBB_PUSH_LEVEL) != 0);
 }
 
+/* what the next push's gather and measurement are given: the ring's noise and set, whichever are on, at its position; false: with a
+ * set, the push would reach position 2^63 */
+static bool stream_impair(const gpsbb_stream *s, ImpairCall *c)
+{
+    memset(c, 0, sizeof *c);
+    c->noise = s->noise_on;
+    c->set = s->interf_on;
+    if (s->noise_on)
+        c->a.nz = s->impair.nz;
+    if (s->interf_on) {
+        c->a.it = s->impair.it;
+        c->a.nz.shift = s->impair.it.shift;
+    }
+    return impair_at(c, s->out_pos, (uint64_t)s->bps * (uint64_t)s->nsamp);
+}
+
 static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain, bool want_digest, bool want_level)
 {
     if (!s || !ch)
         return GPSBB_E_BADARG;
     if (s->poisoned || s->head - s->tail >= (uint64_t)s->depth)
         return GPSBB_E_STATE; /* ring full: pop first */
-    if (s->interf_on && (s->noise_pos >= INTERF_POS_END || (uint64_t)s->bps * (uint64_t)s->nsamp > INTERF_POS_END - s->noise_pos))
+    ImpairCall ic; /* the one value the gather and k_level are both given */
+    if (!stream_impair(s, &ic))
         return GPSBB_E_BADARG; /* the push would reach position 2^63 */
-    /* GPSBB_PUSH_LEVEL: what k_level will be given, checked and its memory made before anything of the push exists */
-    ImpairArgs lvl_args;
-    memset(&lvl_args, 0, sizeof lvl_args);
     if (want_level) {
-        if (s->noise_on)
-            lvl_args.nz = s->noise;
-        lvl_args.nz.sample0 = s->noise_pos;
-        if (s->interf_on) {
-            lvl_args.it = s->interf;
-            (void)interf_at(&lvl_args.it, s->noise_pos, (uint64_t)s->bps * (uint64_t)s->nsamp); /* (the range: checked above) */
-        }
-        if (!level_fits(lvl_args, s->noise_on, s->nsamp))
+        /* GPSBB_PUSH_LEVEL: what k_level will be given is checked, and its memory made, before anything of the push exists */
+        if (!level_fits(ic.a, ic.noise, s->nsamp))
             return GPSBB_E_BADARG;
         auto &lsl = s->slots[s->head % s->depth];
         HIPCHK(s->h, hipSetDevice(s->h->device));
@@ -4056,33 +4020,11 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
     PUSH_MARK("wait");
     if (sl.h_iq) {
         const bool sdma = GPSBB_KNOB_SET("GPSBB_GATHER_SDMA"); /* experiment: the runtime's copy instead */
-        const int gwg = (int)GPSBB_KNOB_LONG("GPSBB_GATHER_WGS", 32);
-        if (s->interf_on) {
-            /* interference (and the noise, if on) on the way out: k_impair_iq in k_noise_iq's place */
-            ImpairArgs a;
-            memset(&a, 0, sizeof a);
-            if (s->noise_on)
-                a.nz = s->noise;
-            a.nz.sample0 = s->noise_pos;
-            a.nz.shift = s->interf.shift;
-            a.nz.shift8 = s->shift;
-            a.it = s->interf;
-            (void)interf_at(&a.it, s->noise_pos, (uint64_t)s->bps * (uint64_t)s->nsamp); /* (checked where the push began) */
-            HIPCHK(h, impair_launch(h, s->fmt, a, s->noise_on, b->d_iq.p, sl.h_iq, (size_t)s->bps * s->nsamp * 2, cs));
-        } else if (s->noise_on) {
-            /* noise on the way out, in any format: the noise kernel reads the render and writes the pinned slot */
-            NoiseArgs a = s->noise;
-            a.sample0 = s->noise_pos;
-            HIPCHK(h, noise_launch(h, s->fmt, a, b->d_iq.p, sl.h_iq, (size_t)s->bps * s->nsamp * 2, cs));
-        } else if (s->fmt) {
-            /* packed on the way out: the same launch that returns at once, fewer bytes over the bus */
-            HIPCHK(h, pack_launch(h, s->fmt, s->shift, b->d_iq.p, sl.h_iq, (size_t)s->bps * s->nsamp * 2, cs));
-        } else if (sdma) {
+        if (sdma && !ic.any() && !s->fmt) {
             HIPCHK(h, hipMemcpyAsync(sl.h_iq, b->d_iq.p, (size_t)s->bps * s->nsamp * 4, hipMemcpyDeviceToHost, cs));
         } else {
-            hipLaunchKernelGGL(k_gather_to_host, dim3(gwg), dim3(256), 0, cs, (const gather_u32x4 *)b->d_iq.p, (gather_u32x4 *)sl.h_iq,
-                               ((size_t)s->bps * s->nsamp * 4 + 15) / 16);
-            HIPCHK(h, hipGetLastError());
+            /* the plain gather, packed, or with noise and interference on the way out: the same launch that returns at once */
+            HIPCHK(h, out_launch(h, s->fmt, s->shift, ic.any() ? &ic : nullptr, b->d_iq.p, sl.h_iq, (size_t)s->bps * s->nsamp * 2, cs));
         }
     }
     PUSH_MARK("iq");
@@ -4100,7 +4042,7 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
     }
     if (want_level) {
         /* the slot measured where it is gathered: behind the gather, on its stream, results through pinned memory */
-        HIPCHK(h, level_launch(h, lvl_args, s->noise_on, b->d_iq.p, s->bps, s->nsamp, sl.d_lvl, cs));
+        HIPCHK(h, level_launch(h, ic.a, ic.noise, b->d_iq.p, s->bps, s->nsamp, sl.d_lvl, cs));
         HIPCHK(h, hipMemcpyAsync(sl.h_lvl, sl.d_lvl, (size_t)s->bps * sizeof(LevelOut), hipMemcpyDeviceToHost, cs));
         sl.has_lvl = true;
     }
@@ -4118,7 +4060,7 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
     memcpy(s->fx_prn, fx_prn_next, sizeof fx_prn_next);
     memcpy(s->fx_phase, fx_phase_next, sizeof fx_phase_next);
     if (s->noise_on || s->interf_on)
-        s->noise_pos += (unsigned long long)s->bps * (unsigned long long)s->nsamp;
+        s->out_pos += (unsigned long long)s->bps * (unsigned long long)s->nsamp;
     s->head++;
     poison.armed = false;
     g_push_trace.end();

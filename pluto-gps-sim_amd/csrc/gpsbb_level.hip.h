@@ -1,8 +1,9 @@
 /* The level of the host-bound output before its two shifts (include/gpsbb.h, gpsbb_level_t: the definition in full).  For every
  * block, the histogram of the bit length m(x) of x = v + N + J — step 4's value before the shift — and the exact sum of x^2, per
  * component.  The histogram decides both clip counters for every (shift, shift8) (gpsbb_level_clips), so one pass over the render
- * chooses them (gpsbb_level_choose).  k_level<NOISE, INTERF> has k_impair_iq's read side and stores no samples: noise and emitters
- * are regenerated at their absolute positions.  Hand-written HIP for gfx950. */
+ * chooses them (gpsbb_level_choose).  k_level<NOISE, INTERF> has k_impair_iq's read side — the same impair_unit_x and
+ * impair_sample_x make its x — and stores no samples: noise and emitters are regenerated at their absolute positions.
+ * Hand-written HIP for gfx950. */
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -33,26 +34,6 @@ __device__ __forceinline__ void level_add(uint32_t *hw /* [LEVEL_CLASSES][LEVEL_
 {
     atomicAdd(&hw[level_class(x) * LEVEL_COPIES + (lane & (LEVEL_COPIES - 1))], 1u);
     sq += (unsigned long long)((long long)x * (long long)x);
-}
-
-/* x of the one sample d samples after the launch's first (a block's head and tail: not on a 16-byte boundary) */
-template <bool NOISE, bool INTERF>
-__device__ __forceinline__ void level_sample(uint32_t v, unsigned long long d, const ImpairArgs &a, const int2 *tab, const uint32_t *cs,
-                                             int &xi, int &xq)
-{
-    int j[2] = {0, 0};
-    if (INTERF)
-        interf_run<1>(a.it, d, InterfLdsTab{cs}, j);
-    int ni = 0, nq = 0;
-    if (NOISE) {
-        const unsigned long long s = a.nz.sample0 + d;
-        uint32_t x[4];
-        noise_philox((uint32_t)(s >> 1), (uint32_t)(s >> 33), a.nz.key0, a.nz.key1, x);
-        ni = noise_n((s & 1) ? x[2] : x[0], tab, a.nz.s256); /* (selects: no indexed private array) */
-        nq = noise_n((s & 1) ? x[3] : x[1], tab, a.nz.s256);
-    }
-    xi = ((int)(v << 16) >> 16) + j[0] + ni;
-    xq = ((int)v >> 16) + j[1] + nq;
 }
 
 /* nblocks blocks of nsamp int16 pairs at src (4-byte aligned), block b at stream position a.nz.sample0 + b * nsamp.  The grid is a
@@ -130,8 +111,9 @@ __global__ __launch_bounds__(256) void k_level(const int16_t *src, long nblocks,
             const long long nh = gh - g0, nt = g1 - gt;
             if (tid < nh + nt) {
                 const long long g = tid < nh ? g0 + tid : gt + (tid - nh);
-                int xi, xq;
-                level_sample<NOISE, INTERF>(reinterpret_cast<const uint32_t *>(src)[g], (unsigned long long)g, a, tab, cs, xi, xq);
+                const uint32_t v = reinterpret_cast<const uint32_t *>(src)[g];
+                int xi = (int)(v << 16) >> 16, xq = (int)v >> 16;
+                impair_sample_x<NOISE, INTERF>(xi, xq, (unsigned long long)g, a, tab, InterfLdsTab{cs});
                 level_add(hi, xi, lane, sqi);
                 level_add(hq, xq, lane, sqq);
             }

@@ -104,6 +104,49 @@ def test_fill_with_interference_every_format(pkg, synth, oracle, fs, nsamp, nch,
         assert L.gpsbb_host_unregister(synth._h, reg.ctypes.data) == 0
 
 
+@pytest.mark.parametrize("nsamp", [4, 5, 8196, 8197])
+def test_fill_with_impairments_small_shapes(pkg, synth, nsamp):
+    """the shapes the blocks above never have.  4 samples: one 16-byte unit and no tail; 5: a ragged tail of two components for SC16
+    and SC8; 8196: 2049 units, so the second chunk of 2048 holds a single one (the chunk loop, the guard per load, SC1's partial
+    store); 8197: that and the tail.  Each at an odd and an even position — an SC1 block above always starts on an odd one, so
+    its units never took the two-pair path — with the full set and noise, the set alone, an empty set with noise and the noise
+    alone through the NULL-set call, in every format nsamp allows, pageable and 8 bytes into a registered buffer whose start is
+    64-byte aligned: SC16's destination is then off its 16 bytes and takes the per-component path."""
+    L = pkg.lib()
+    fs, nch = 2.6e6, 12
+    delt = 1.0 / fs
+    ch = pkg.synth_descriptors(1, nch=nch, seed=106)[0]
+    iq16, _ = synth.fill_block(ch, delt, nsamp)
+    raw = np.zeros(nsamp * 4 + 4096 + 64, np.uint8)
+    reg = raw[(-raw.ctypes.data) % 64:][:nsamp * 4 + 4096]
+    assert reg.ctypes.data % 64 == 0
+    assert L.gpsbb_host_register(synth._h, reg.ctypes.data, reg.nbytes) == 0
+    try:
+        for s0 in (12345, 12346):
+            nz = pkg.Noise(7, s0, pkg.noise_sigma(45.0, 1.0, delt), 1, 0)
+            full, empty = pkg.InterfSet(emitters(pkg, delt), 1, s0), pkg.InterfSet([], 1, s0)
+            for fmt in FORMATS(pkg):
+                if fmt == pkg.OUT_SC1 and nsamp % 4:
+                    continue
+                nb = pkg.out_bytes(fmt, nsamp)
+                for noise, st in ((nz, full), (None, full), (nz, empty), (nz, None)):
+                    exp, n = impaired(pkg, iq16, noise, empty if st is None else st, fmt)
+                    exp = np.ascontiguousarray(exp).view(np.uint8).ravel()
+                    assert exp.size == nb
+                    for where in ("pageable", "registered+8"):
+                        reg[:] = 0x5A
+                        out = np.full(nb, 0x5A, np.uint8) if where == "pageable" else reg[8:8 + nb]
+                        c0 = nclipped(pkg, synth)
+                        assert L.gpsbb_fill_block_impair(synth._h, ch.ctypes.data, nch, delt, nsamp, fmt, C.byref(noise) if noise else None,
+                                                         C.byref(st) if st is not None else None, out.ctypes.data, None) == 0
+                        assert (out == exp).all(), (s0, hex(fmt), where, noise is not None, None if st is None else st.n)
+                        assert nclipped(pkg, synth) - c0 == n
+                        if where != "pageable":
+                            assert (reg[:8] == 0x5A).all() and (reg[8 + nb:] == 0x5A).all()
+    finally:
+        assert L.gpsbb_host_unregister(synth._h, reg.ctypes.data) == 0
+
+
 def test_interference_clip_counter(pkg, synth):
     """a tone of level 72 (crests of +-36 700) on 16 channels saturates at both ends: the counter is numpy's count, and SC8's own
     counts where it always did"""

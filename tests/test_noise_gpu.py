@@ -1,4 +1,4 @@
-"""Receiver noise on the GPU (include/gpsbb.h gpsbb_noise_t, k_noise_iq): every host-bound path that takes noise — the drop-in fill
+"""Receiver noise on the GPU (include/gpsbb.h gpsbb_noise_t, k_impair_iq<FMT, true, false>): every host-bound path that takes noise — the drop-in fill
 (pageable and registered), the streaming ring, gpsbb_device_noise, the node driver in every layout and gpsbb-sim — bit for bit
 against apply_noise and pack_iq (the numpy restatement) of the noiseless render of the same stream.  The clip counter must be
 numpy's count; every refusal leaves the handle, stream and node working."""
