@@ -612,6 +612,115 @@ struct DevBuf {
     }
 };
 
+/* release() of every buffer named (DevBuf, or a struct of them) */
+template <class... B>
+static void release_all(B &...b)
+{
+    (b.release(), ...);
+}
+
+/* The lap-parallel pre-pass's device scratch (gpsbb_laps.hip.h: what LapDev points at): one per table set of a batch, one for
+ * gpsbb_chain_carrier. */
+struct LapScratch {
+    DevBuf<LapBC> bc;
+    DevBuf<uint32_t> lane0, cnt, chunk_bad;
+    DevBuf<LapRec> rec;
+    DevBuf<LapAgg> agg;
+    DevBuf<double> chunk_m;
+    /* room for `chunks` chunks of laps over nbc = nblocks * nch block-channels; `room`: a quarter more of what grows with the laps
+     * on a first allocation (a ring slot, whose pushes see different Dopplers: DevBuf::reserve) */
+    int reserve(size_t nbc, size_t nch, size_t nblocks, size_t chunks, bool room)
+    {
+        const size_t more = room ? chunks / 4 : 0;
+        int e = bc.reserve(2 * nbc); /* (each step only if the ones before it succeeded: hipSuccess is 0) */
+        e = e ? e : lane0.reserve(2 * nch * (nblocks + 1));
+        e = e ? e : cnt.reserve(4 * GPSBB_MAX_CHAN);
+        e = e ? e : rec.reserve(chunks * LAP_WG, room ? chunks * LAP_WG / 4 : 0);
+        e = e ? e : agg.reserve(chunks, more);
+        e = e ? e : chunk_m.reserve(chunks, more);
+        return e ? e : chunk_bad.reserve(chunks, more);
+    }
+    void release() { release_all(bc, lane0, cnt, chunk_bad, rec, agg, chunk_m); }
+    void dev(LapDev &L) const
+    {
+        L.bc = bc.p;
+        L.lane0 = lane0.p;
+        L.nlaps = cnt.p;
+        L.nbad = cnt.p + 2 * GPSBB_MAX_CHAN;
+        L.rec = rec.p;
+        L.agg = agg.p;
+        L.chunk_m = chunk_m.p;
+        L.chunk_bad = chunk_bad.p;
+    }
+};
+
+/* k_chain_fix_par's hand-off between its chunks (BatchDev::fix_end, fix_flag, fix_epoch): a batch has one, cut into a piece per
+ * table set, gpsbb_chain_carrier another. */
+struct FixScratch {
+    DevBuf<unsigned long long> end;
+    DevBuf<int> flag;
+    bool flags_zeroed = false; /* `flag` has been cleared since it was last (re)allocated */
+    int epoch = 0;             /* the last number handed to k_chain_fix_par */
+    /* flags are compared with a launch number, never cleared: zeroed once, when the buffer is (re)allocated */
+    hipError_t reserve(size_t nflags, hipStream_t stream)
+    {
+        if (nflags <= flag.cap && end.cap >= flag.cap && flags_zeroed)
+            return hipSuccess;
+        /* (all three steps or none: a set-up that failed half-way must not leave flags that were never zeroed, or no
+         * buffer for the end phases, behind a capacity that says "nothing to do") */
+        flags_zeroed = false;
+        hipError_t e = (hipError_t)flag.reserve(nflags);
+        e = e ? e : (hipError_t)end.reserve(flag.cap);
+        e = e ? e : hipMemsetAsync(flag.p, 0, flag.cap * sizeof(int), stream);
+        if (e != hipSuccess)
+            return e;
+        epoch = 0;
+        flags_zeroed = true;
+        return hipSuccess;
+    }
+    void release() { release_all(end, flag); }
+};
+
+/* A stream's two events (gpsbb_batch::ev_prefix, ev_fix), or none: a batch that continues no push.  They order what touches the
+ * stream's carry (ChainCarryDev) across pushes, which take the handle's pre-pass streams in turn. */
+struct CarryEvents {
+    hipEvent_t prefix = nullptr, fix = nullptr;
+    static hipError_t wait(hipStream_t ss, hipEvent_t e) { return e ? hipStreamWaitEvent(ss, e, 0) : hipSuccess; }
+    static hipError_t record(hipStream_t ss, hipEvent_t e) { return e ? hipEventRecord(e, ss) : hipSuccess; }
+    /* The lap-parallel pre-pass: the carry is read by a push's carrier plan and written by its repair (exact_end AND approx_end):
+     * ordered behind every writer of the push before — lap-parallel or row walks — and ahead of every reader of the next, whichever
+     * pre-pass that push takes: both events waited for, both recorded */
+    hipError_t wait_both(hipStream_t ss) const
+    {
+        const hipError_t e = wait(ss, fix);
+        return e ? e : wait(ss, prefix);
+    }
+    hipError_t record_both(hipStream_t ss) const
+    {
+        const hipError_t e = record(ss, fix);
+        return e ? e : record(ss, prefix);
+    }
+};
+
+/* What a batch owns per table set: the tables a pre-pass leaves and a synthesis kernel reads, the pre-pass's scratch, and when
+ * the set is free again. */
+struct TableSet {
+    DevBuf<NcoRow> rows;
+    DevBuf<int32_t> tile_row;
+    DevBuf<int32_t> row_cnt;
+    DevBuf<gpsbb_chan_state_t> end;
+    /* breakpoint kernel (ev): exact tile-start states instead of rows + tile index */
+    DevBuf<double> tile_x;
+    DevBuf<uint32_t> tile_nav;
+    /* GPSBB_CHAIN_CARRIER resolved on the device by the row walks (gpsbb_walk.hip.h) */
+    DevBuf<ChainAux> aux;
+    DevBuf<SynRow> prefix;
+    LapScratch lap; /* the lap-parallel pre-pass (gpsbb_laps.hip.h): one lane per lap of every chain */
+    hipEvent_t synth_done_ref = nullptr; /* not owned: ev[3] of the run that last read this set */
+    bool synth_pending = false;
+    void release() { release_all(rows, tile_row, row_cnt, end, tile_x, tile_nav, aux, prefix, lap); }
+};
+
 /* Table sets of a batch.  Run k uses set k % nsets and its pre-pass may start as soon as the synthesis kernel
  * that last read that set has finished.  Three sets, and consecutive runs seed on alternating streams: a
  * pre-pass is as long as its longest chain whatever the batch size — longer than the synthesis it feeds — so
@@ -639,11 +748,8 @@ struct gpsbb_batch {
     uint64_t total_rows = 0;
     DevBuf<gpsbb_chan_t> d_ch;
     DevBuf<uint64_t> d_row_off;
-    /* row tables / tile index / end states exist twice: run k uses set k&1, so that the seeding
-     * pre-pass of run k+1 overlaps the synthesis kernel of run k (different streams) */
-    DevBuf<NcoRow> d_rows[NSETS];
-    DevBuf<int32_t> d_tile_row[NSETS];
-    DevBuf<int32_t> d_row_cnt[NSETS];
+    /* run k uses set k % nsets, so that the seeding pre-pass of run k+1 overlaps the synthesis kernel of run k (different streams) */
+    TableSet sets[NSETS];
     DevBuf<int32_t> d_tile_ctr;
     DevBuf<int32_t> d_seed_order; /* lane -> chain plan of k_seed (see BatchDev) */
     DevBuf<uint32_t> d_kph0; /* fixed-point carrier variant: start phase and step per (block, channel) */
@@ -653,11 +759,8 @@ struct gpsbb_batch {
     std::vector<int32_t> h_kstep;
     const int *fixed_prev_prn = nullptr;      /* stream chaining of the fixed-point carrier (host side) */
     const uint32_t *fixed_prev_phase = nullptr;
-    DevBuf<gpsbb_chan_state_t> d_end[NSETS];
-    /* breakpoint kernel (ev): exact tile-start states instead of rows + tile index, and per-channel constants */
+    /* breakpoint kernel (ev): exact tile-start states instead of rows + tile index (TableSet), and per-channel constants */
     bool ev = false;
-    DevBuf<double> d_tile_x[NSETS];
-    DevBuf<uint32_t> d_tile_nav[NSETS];
     DevBuf<EvConst> d_evc;
     std::vector<EvConst> h_evc;
     double *hs_tile_x = nullptr;
@@ -670,31 +773,22 @@ struct gpsbb_batch {
     bool chain_starts = false; /* ... with the per-sample kernel: the chain kernels only fix the blocks' start phases */
     DevBuf<int32_t> d_chain_order; /* chain_starts: the carrier chains, as k_walk's passes take them */
     int chain_lanes = 0;
-    DevBuf<ChainAux> d_aux[NSETS];
-    DevBuf<SynRow> d_prefix[NSETS];
     DevBuf<ChainDesc> d_cd;      /* what the chain kernels read of the descriptors (24 B per block-channel) */
     DevBuf<double> d_start0;     /* rough start phases: where pass A walks from */
     std::vector<ChainDesc> h_cd;
     std::vector<double> h_start0;
     int nseg = 1, seg_tiles = 0; /* the device-side chain cuts every block into nseg segments (BatchDev::nseg) */
-    DevBuf<unsigned long long> d_fix_end; /* k_chain_fix_par: the hand-off between its chunks (BatchDev::fix_end) */
-    DevBuf<int> d_fix_flag;
-    int fix_epoch = 0, fix_chunks = 0, fix_wg = FIXP_WG_BATCH;
-    bool fix_flags_zeroed = false; /* d_fix_flag has been cleared since it was last (re)allocated */
+    FixScratch fix;              /* k_chain_fix_par: the hand-off between its chunks, one piece per table set */
+    int fix_chunks = 0, fix_wg = FIXP_WG_BATCH;
     bool chain_indep = false;    /* the chain machinery runs on a batch whose blocks are independent: only the segments of a block are chained */
     bool chain_model = false;    /* pass B starts from the host's drift model of the carrier (no pass A, no k_chain_prefix) */
     bool chain_fix_seq = false;  /* k_chain_fix (blocks in order) instead of k_chain_fix_par: GPSBB_OPT_CHAIN_WHERE 2 */
     bool host_seed = false;      /* the NCO tables of this batch are built on host threads: decided at set-up, like the
                                     chain (a run never re-reads the handle's options) */
     int carr_lanes = 0; /* lanes of the seed plan that walk carrier chains (they come first) */
-    /* the lap-parallel pre-pass (gpsbb_laps.hip.h): one lane per lap of every chain; scratch per table set */
+    /* the lap-parallel pre-pass (gpsbb_laps.hip.h): one lane per lap of every chain; scratch per table set (TableSet::lap) */
     bool laps = false;
     uint32_t lap_chunk0[2][GPSBB_MAX_CHAN + 1] = {};
-    DevBuf<LapBC> d_lap_bc[NSETS];
-    DevBuf<uint32_t> d_lap_lane0[NSETS], d_lap_cnt[NSETS], d_lap_chunk_bad[NSETS];
-    DevBuf<LapRec> d_lap_rec[NSETS];
-    DevBuf<LapAgg> d_lap_agg[NSETS];
-    DevBuf<double> d_lap_chunk_m[NSETS];
     /* a stream's slot: the carrier continues from the push before (set by gpsbb_stream_push around set-up / launch) */
     ChainCarryDev *d_carry = nullptr;
     const int *carry_prn = nullptr;        /* in: prn per channel in the last block pushed before */
@@ -707,9 +801,7 @@ struct gpsbb_batch {
     char *stage = nullptr;
     size_t stage_cap = 0, stage_used = 0;
     unsigned stream_turn = 0; /* the stream's push count */
-    hipEvent_t synth_done_ref[NSETS] = {}; /* not owned: the run's ev[3] */
     hipEvent_t last_done = nullptr;
-    bool synth_pending[NSETS] = {};
     hipEvent_t upload_done = nullptr; /* descriptors and plans of the last set-up are on the device */
     hipStream_t upload_stream = nullptr; /* ... the stream that carried them */
     int nsets = 2;                    /* table sets in use: run k works on set k % nsets */
@@ -1330,16 +1422,17 @@ static int batch_setup(gpsbb_batch *b, const gpsbb_chan_t *ch, int nblocks, int 
     b->nsets = b->nsets < 2 ? 2 : (b->nsets > NSETS ? NSETS : b->nsets);
     b->nsets = b->nsets > b->max_sets ? b->max_sets : b->nsets;
     for (int set = 0; set < b->nsets; set++) {
-        HIPCHK(h, (hipError_t)b->d_end[set].reserve(nbc));
+        TableSet &ts = b->sets[set];
+        HIPCHK(h, (hipError_t)ts.end.reserve(nbc));
         if (b->ev) {
-            HIPCHK(h, (hipError_t)b->d_tile_x[set].reserve(2 * nbc * (size_t)b->nstates));
-            HIPCHK(h, (hipError_t)b->d_tile_nav[set].reserve(nbc * (size_t)b->nstates));
-            HIPCHK(h, (hipError_t)b->d_rows[set].reserve(b->total_rows + 4, b->max_sets == 1 ? (size_t)(b->total_rows / 2) : 0));
-            HIPCHK(h, (hipError_t)b->d_row_cnt[set].reserve(nbc + nvbc));
+            HIPCHK(h, (hipError_t)ts.tile_x.reserve(2 * nbc * (size_t)b->nstates));
+            HIPCHK(h, (hipError_t)ts.tile_nav.reserve(nbc * (size_t)b->nstates));
+            HIPCHK(h, (hipError_t)ts.rows.reserve(b->total_rows + 4, b->max_sets == 1 ? (size_t)(b->total_rows / 2) : 0));
+            HIPCHK(h, (hipError_t)ts.row_cnt.reserve(nbc + nvbc));
         } else {
-            HIPCHK(h, (hipError_t)b->d_rows[set].reserve(b->total_rows + 4)); /* + slack: k_synth prefetches one row past a chain */
-            HIPCHK(h, (hipError_t)b->d_tile_row[set].reserve(2 * nbc * ((size_t)b->ntiles + 1)));
-            HIPCHK(h, (hipError_t)b->d_row_cnt[set].reserve(2 * nbc));
+            HIPCHK(h, (hipError_t)ts.rows.reserve(b->total_rows + 4)); /* + slack: k_synth prefetches one row past a chain */
+            HIPCHK(h, (hipError_t)ts.tile_row.reserve(2 * nbc * ((size_t)b->ntiles + 1)));
+            HIPCHK(h, (hipError_t)ts.row_cnt.reserve(2 * nbc));
         }
     }
     if (b->ev) {
@@ -1381,15 +1474,8 @@ static int batch_setup(gpsbb_batch *b, const gpsbb_chan_t *ch, int nblocks, int 
          * channels of its first block go on from the push before (the exact phase is on the device) */
         lap_bound(ch, nblocks, nch, delt, nsamp, fixed, b->lap_chunk0);
         const size_t chunks = (size_t)b->lap_chunk0[1][nch];
-        for (int set = 0; set < b->nsets; set++) {
-            HIPCHK(h, (hipError_t)b->d_lap_bc[set].reserve(2 * nbc));
-            HIPCHK(h, (hipError_t)b->d_lap_lane0[set].reserve(2 * (size_t)nch * ((size_t)nblocks + 1)));
-            HIPCHK(h, (hipError_t)b->d_lap_cnt[set].reserve(4 * GPSBB_MAX_CHAN));
-            HIPCHK(h, (hipError_t)b->d_lap_rec[set].reserve(chunks * LAP_WG, b->max_sets == 1 ? chunks * LAP_WG / 4 : 0));
-            HIPCHK(h, (hipError_t)b->d_lap_agg[set].reserve(chunks, b->max_sets == 1 ? chunks / 4 : 0));
-            HIPCHK(h, (hipError_t)b->d_lap_chunk_m[set].reserve(chunks, b->max_sets == 1 ? chunks / 4 : 0));
-            HIPCHK(h, (hipError_t)b->d_lap_chunk_bad[set].reserve(chunks, b->max_sets == 1 ? chunks / 4 : 0));
-        }
+        for (int set = 0; set < b->nsets; set++)
+            HIPCHK(h, (hipError_t)b->sets[set].lap.reserve(nbc, (size_t)nch, (size_t)nblocks, chunks, b->max_sets == 1));
         if (b->chain_dev && b->d_carry && b->carry_prn)
             for (int i = 0; i < nch; i++)
                 if (ch[i].prn > 0 && ch[i].prn == b->carry_prn[i])
@@ -1441,30 +1527,17 @@ static int batch_setup(gpsbb_batch *b, const gpsbb_chan_t *ch, int nblocks, int 
         }
         /* the chain's scratch (ChainAux) needs no initial image: every field is written by the pass that owns it */
         for (int set = 0; set < b->nsets; set++) {
-            HIPCHK(h, (hipError_t)b->d_aux[set].reserve(nvbc));
+            HIPCHK(h, (hipError_t)b->sets[set].aux.reserve(nvbc));
             if (!b->chain_starts)
-                HIPCHK(h, (hipError_t)b->d_prefix[set].reserve(nvbc * (size_t)CHAIN_PREFIX_CAP));
+                HIPCHK(h, (hipError_t)b->sets[set].prefix.reserve(nvbc * (size_t)CHAIN_PREFIX_CAP));
         }
         HIPCHK(h, (hipError_t)b->d_cd.reserve(nvbc));
         HIPCHK(h, (hipError_t)b->d_start0.reserve(nvbc));
-        {
-            /* flags are compared with a launch number, never cleared: zeroed once, when the buffer is (re)allocated */
-            /* long chains (thousands of segments per channel): fewer, larger chunks — fewer hand-offs */
-            b->fix_wg = nblocks * b->nseg >= 2048 ? FIXP_WG_ALONE : FIXP_WG_BATCH;
-            b->fix_chunks = (nblocks * b->nseg + b->fix_wg - 1) / b->fix_wg;
-            /* one set of flags per table set: runs of a resident batch overlap, each on its own table set */
-            const size_t nf = (size_t)NSETS * GPSBB_MAX_CHAN * b->fix_chunks;
-            if (nf > b->d_fix_flag.cap || b->d_fix_end.cap < b->d_fix_flag.cap || !b->fix_flags_zeroed) {
-                /* (all three steps or none: a set-up that failed half-way must not leave flags that were never zeroed, or no
-                 * buffer for the end phases, behind a capacity that says "nothing to do") */
-                b->fix_flags_zeroed = false;
-                HIPCHK(h, (hipError_t)b->d_fix_flag.reserve(nf));
-                HIPCHK(h, (hipError_t)b->d_fix_end.reserve(b->d_fix_flag.cap));
-                HIPCHK(h, hipMemsetAsync(b->d_fix_flag.p, 0, b->d_fix_flag.cap * sizeof(int), upload_stream));
-                b->fix_epoch = 0;
-                b->fix_flags_zeroed = true;
-            }
-        }
+        /* long chains (thousands of segments per channel): fewer, larger chunks — fewer hand-offs */
+        b->fix_wg = nblocks * b->nseg >= 2048 ? FIXP_WG_ALONE : FIXP_WG_BATCH;
+        b->fix_chunks = (nblocks * b->nseg + b->fix_wg - 1) / b->fix_wg;
+        /* one set of flags per table set: runs of a resident batch overlap, each on its own table set */
+        HIPCHK(h, b->fix.reserve((size_t)NSETS * GPSBB_MAX_CHAN * b->fix_chunks, upload_stream));
         HIPCHK(h, stage_upload(b, b->d_cd.p, b->h_cd.data(), nvbc * sizeof(ChainDesc), upload_stream));
         HIPCHK(h, stage_upload(b, b->d_start0.p, b->h_start0.data(), nvbc * sizeof(double), upload_stream));
     }
@@ -1671,37 +1744,12 @@ extern "C" void gpsbb_batch_destroy(gpsbb_batch_t *b)
         return;
     (void)hipSetDevice(b->h->device);
     (void)drain_streams(b->h); /* its tables, its output and its events: pre-pass, synthesis and copy streams may all hold work on them */
-    b->d_ch.release();
-    b->d_row_off.release();
+    release_all(b->d_ch, b->d_row_off);
     if (b->upload_done)
         (void)hipEventDestroy(b->upload_done);
-    for (int k = 0; k < NSETS; k++) {
-        b->d_rows[k].release();
-        b->d_tile_row[k].release();
-        b->d_row_cnt[k].release();
-        b->d_tile_ctr.release();
-        b->d_seed_order.release();
-        b->d_kph0.release();
-        b->d_kstep.release();
-        b->d_end[k].release();
-        b->d_tile_x[k].release();
-        b->d_tile_nav[k].release();
-        b->d_aux[k].release();
-        b->d_cd.release();
-        b->d_start0.release();
-        b->d_fix_end.release();
-        b->d_fix_flag.release();
-        b->d_prefix[k].release();
-        b->d_lap_bc[k].release();
-        b->d_lap_lane0[k].release();
-        b->d_lap_cnt[k].release();
-        b->d_lap_chunk_bad[k].release();
-        b->d_lap_rec[k].release();
-        b->d_lap_agg[k].release();
-        b->d_lap_chunk_m[k].release();
-        b->d_chain_order.release();
-        b->d_evc.release();
-    }
+    for (TableSet &ts : b->sets)
+        ts.release();
+    release_all(b->d_tile_ctr, b->d_seed_order, b->d_kph0, b->d_kstep, b->d_cd, b->d_start0, b->fix, b->d_chain_order, b->d_evc);
     if (b->hs_rows)
         (void)hipHostFree(b->hs_rows);
     if (b->hs_tile_row)
@@ -1714,10 +1762,7 @@ extern "C" void gpsbb_batch_destroy(gpsbb_batch_t *b)
         (void)hipHostFree(b->hs_tile_x);
     if (b->hs_tile_nav)
         (void)hipHostFree(b->hs_tile_nav);
-    b->d_iq.release();
-    b->d_dig.release();
-    b->d_ds.release();
-    b->d_ds_ctr.release();
+    release_all(b->d_iq, b->d_dig, b->d_ds, b->d_ds_ctr);
     for (auto &e : b->ds_ev)
         if (e)
             (void)hipEventDestroy(e);
@@ -1961,7 +2006,7 @@ static bool host_seeding_wanted(const gpsbb_batch *b)
 }
 
 /* Build the tables of one run on host threads and queue their upload on the seeding stream. */
-static int host_seed_run(gpsbb_batch *b, int set, hipStream_t stream)
+static int host_seed_run(gpsbb_batch *b, const TableSet &ts, hipStream_t stream)
 {
     gpsbb *h = b->h;
     const size_t nbc = (size_t)b->nblocks * b->nch;
@@ -2000,18 +2045,19 @@ static int host_seed_run(gpsbb_batch *b, int set, hipStream_t stream)
             return GPSBB_E_INTERNAL;
     }
     if (b->ev) {
-        HIPCHK(h, hipMemcpyAsync(b->d_tile_x[set].p, b->hs_tile_x, tx_n * sizeof(double), hipMemcpyHostToDevice, stream));
-        HIPCHK(h, hipMemcpyAsync(b->d_tile_nav[set].p, b->hs_tile_nav, tn_n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        HIPCHK(h, hipMemcpyAsync(ts.tile_x.p, b->hs_tile_x, tx_n * sizeof(double), hipMemcpyHostToDevice, stream));
+        HIPCHK(h, hipMemcpyAsync(ts.tile_nav.p, b->hs_tile_nav, tn_n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     } else {
-        HIPCHK(h, hipMemcpyAsync(b->d_rows[set].p, b->hs_rows, b->total_rows * sizeof(SynRow), hipMemcpyHostToDevice, stream));
-        HIPCHK(h, hipMemcpyAsync(b->d_tile_row[set].p, b->hs_tile_row, tr_n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        HIPCHK(h, hipMemcpyAsync(ts.rows.p, b->hs_rows, b->total_rows * sizeof(SynRow), hipMemcpyHostToDevice, stream));
+        HIPCHK(h, hipMemcpyAsync(ts.tile_row.p, b->hs_tile_row, tr_n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
     }
-    HIPCHK(h, hipMemcpyAsync(b->d_end[set].p, b->hs_end, nbc * sizeof(gpsbb_chan_state_t), hipMemcpyHostToDevice, stream));
+    HIPCHK(h, hipMemcpyAsync(ts.end.p, b->hs_end, nbc * sizeof(gpsbb_chan_state_t), hipMemcpyHostToDevice, stream));
     return GPSBB_OK;
 }
 
-static BatchDev batch_dev(const gpsbb_batch *b, int set)
+static BatchDev batch_dev(const gpsbb_batch *b, const TableSet &ts)
 {
+    const size_t set = (size_t)(&ts - b->sets);
     BatchDev p;
     memset(&p, 0, sizeof p); /* (every field has a value, also the ones a later round adds) */
     p.ch = b->d_ch.p;
@@ -2025,14 +2071,14 @@ static BatchDev batch_dev(const gpsbb_batch *b, int set)
     p.flags = b->flags;
     p.tabs = b->h->d_tabs;
     p.ca_bits = b->h->d_ca;
-    p.rows = reinterpret_cast<SynRow *>(b->d_rows[set].p);
+    p.rows = reinterpret_cast<SynRow *>(ts.rows.p);
     p.row_off = b->d_row_off.p;
-    p.tile_row = b->d_tile_row[set].p;
-    p.row_cnt = b->d_row_cnt[set].p;
-    p.tile_ctr = b->d_tile_ctr.p + (size_t)set * ((size_t)b->nblocks + 1);
+    p.tile_row = ts.tile_row.p;
+    p.row_cnt = ts.row_cnt.p;
+    p.tile_ctr = b->d_tile_ctr.p + set * ((size_t)b->nblocks + 1);
     p.kph0 = (b->flags & GPSBB_FIXED_CARRIER) ? b->d_kph0.p : nullptr;
     p.kstep = (b->flags & GPSBB_FIXED_CARRIER) ? b->d_kstep.p : nullptr;
-    p.end = b->d_end[set].p;
+    p.end = ts.end.p;
     p.status = b->h->d_status;
     p.hazards = b->h->d_hz;
     p.digest = b->want_digest ? b->d_dig.p : nullptr;
@@ -2049,111 +2095,165 @@ static BatchDev batch_dev(const gpsbb_batch *b, int set)
         ev_chunk--;
     p.ev_chunk = ev_chunk < 1 ? 1 : ev_chunk;
     p.pd_danger = (uint32_t)GPSBB_KNOB_LONG("GPSBB_PD_DANGER", 2u * PD_BAND); /* (larger: more lanes take the exact path; a test aid) */
-    p.tile_x = b->d_tile_x[set].p;
-    p.tile_nav = b->d_tile_nav[set].p;
+    p.tile_x = ts.tile_x.p;
+    p.tile_nav = ts.tile_nav.p;
     p.evc = b->d_evc.p;
     p.chain_dev = b->chain_dev ? 1 : 0;
     p.chain_starts = b->chain_starts ? 1 : 0;
-    p.aux = b->chain_dev ? b->d_aux[set].p : nullptr;
+    p.aux = b->chain_dev ? ts.aux.p : nullptr;
     p.nseg = b->nseg;
     p.seg_tiles = b->seg_tiles;
     p.nvb = b->nblocks * b->nseg;
-    p.fix_end = b->d_fix_end.p ? b->d_fix_end.p + (size_t)set * GPSBB_MAX_CHAN * b->fix_chunks : nullptr;
-    p.fix_flag = b->d_fix_flag.p ? b->d_fix_flag.p + (size_t)set * GPSBB_MAX_CHAN * b->fix_chunks : nullptr;
-    p.fix_epoch = b->fix_epoch;
+    p.fix_end = b->fix.end.p ? b->fix.end.p + set * GPSBB_MAX_CHAN * b->fix_chunks : nullptr;
+    p.fix_flag = b->fix.flag.p ? b->fix.flag.p + set * GPSBB_MAX_CHAN * b->fix_chunks : nullptr;
+    p.fix_epoch = b->fix.epoch;
     p.fix_chunks = b->fix_chunks;
     p.model_start = b->chain_model ? 1 : 0;
     p.cd = b->chain_dev ? b->d_cd.p : nullptr;
     p.start0 = b->chain_dev ? b->d_start0.p : nullptr;
-    p.prefix_rows = b->chain_dev && !b->chain_starts ? b->d_prefix[set].p : nullptr;
+    p.prefix_rows = b->chain_dev && !b->chain_starts ? ts.prefix.p : nullptr;
     p.carry = b->chain_dev ? b->d_carry : nullptr;
     p.cont0_mask = b->cont0_mask;
     p.lap_end = nullptr;
     return p;
 }
 
-static LapDev lap_dev(const gpsbb_batch *b, int set)
+/* what a LapDev holds besides its scratch (LapScratch::dev), for a batch of nbc block-channels */
+static void lap_dev_plan(LapDev &L, const uint32_t chunk0[2][GPSBB_MAX_CHAN + 1], bool chained, size_t nbc)
 {
-    LapDev L;
-    L.bc = b->d_lap_bc[set].p;
-    L.lane0 = b->d_lap_lane0[set].p;
-    L.nlaps = b->d_lap_cnt[set].p;
-    L.nbad = b->d_lap_cnt[set].p + 2 * GPSBB_MAX_CHAN;
-    L.rec = b->d_lap_rec[set].p;
-    L.agg = b->d_lap_agg[set].p;
-    L.chunk_m = b->d_lap_chunk_m[set].p;
-    L.chunk_bad = b->d_lap_chunk_bad[set].p;
-    memcpy(L.chunk0, b->lap_chunk0, sizeof L.chunk0);
-    L.chained = b->chain_dev ? 1 : 0;
+    memcpy(L.chunk0, chunk0, sizeof L.chunk0);
+    L.chained = chained ? 1 : 0;
     L.jitter = (uint32_t)GPSBB_KNOB_LONG("GPSBB_LAP_JITTER", 0);
     L.burst = GPSBB_KNOB_SET("GPSBB_LAP_NO_BURST") ? 0 : (int)GPSBB_KNOB_LONG("GPSBB_LAP_BURST_SHARE", LAP_BURST_SHARE);
-    L.unit[NCO_CODE] = lap_unit(NCO_CODE, (size_t)b->nblocks * b->nch);
-    L.unit[NCO_CARR] = lap_unit(NCO_CARR, (size_t)b->nblocks * b->nch);
+    L.unit[NCO_CODE] = lap_unit(NCO_CODE, nbc);
+    L.unit[NCO_CARR] = lap_unit(NCO_CARR, nbc);
+}
+
+static LapDev lap_dev(const gpsbb_batch *b, const TableSet &ts)
+{
+    LapDev L;
+    ts.lap.dev(L);
+    lap_dev_plan(L, b->lap_chunk0, b->chain_dev, (size_t)b->nblocks * b->nch);
     return L;
 }
 
-static int batch_launch(gpsbb_batch *b, int16_t *d_iq)
+/* The lap-parallel pre-pass of one kind of chain (gpsbb_laps.hip.h): plan, reference walks, scan, true walks, repair. */
+template <int KIND>
+static void lap_chain_kind(hipStream_t ss, const BatchDev &p, const LapDev &L, int nch, LapKernelFn pass2)
+{
+    const unsigned chunks = L.chunk0[KIND][nch] - L.chunk0[KIND][0];
+    hipLaunchKernelGGL(k_lap_plan<KIND>, dim3(nch), dim3(64), 0, ss, p, L);
+    hipLaunchKernelGGL(k_lap_pass1<KIND>, dim3(chunks), dim3(LAP_WG), 0, ss, p, L);
+    hipLaunchKernelGGL(k_lap_scan<KIND>, dim3(nch), dim3(64), 0, ss, p, L);
+    hipLaunchKernelGGL(pass2, dim3(chunks), dim3(LAP_WG), 0, ss, p, L);
+    hipLaunchKernelGGL(k_lap_repair<KIND>, dim3(nch), dim3(64), 0, ss, p, L);
+}
+
+/* ... of the chains of `kind` (NCO_CODE, NCO_CARR), or of both in one grid per step (kind -1: the *_2 kernels); pass2 is
+ * lap_pass2_kernel's instance for that kind */
+static void lap_chain_launch(hipStream_t ss, const BatchDev &p, const LapDev &L, int nch, int kind, LapKernelFn pass2)
+{
+    if (kind == NCO_CODE) {
+        lap_chain_kind<NCO_CODE>(ss, p, L, nch, pass2);
+    } else if (kind == NCO_CARR) {
+        lap_chain_kind<NCO_CARR>(ss, p, L, nch, pass2);
+    } else {
+        const unsigned chunks = L.chunk0[NCO_CODE][nch] - L.chunk0[NCO_CODE][0] + (L.chunk0[NCO_CARR][nch] - L.chunk0[NCO_CARR][0]);
+        hipLaunchKernelGGL(k_lap_plan2, dim3(2 * nch), dim3(64), 0, ss, p, L);
+        hipLaunchKernelGGL(k_lap_pass1_2, dim3(chunks), dim3(LAP_WG), 0, ss, p, L);
+        hipLaunchKernelGGL(k_lap_scan2, dim3(2 * nch), dim3(64), 0, ss, p, L);
+        hipLaunchKernelGGL(pass2, dim3(chunks), dim3(LAP_WG), 0, ss, p, L);
+        hipLaunchKernelGGL(k_lap_repair2, dim3(2 * nch), dim3(64), 0, ss, p, L);
+    }
+}
+
+/* The carrier chain by the row walks (gpsbb_walk.hip.h): pass A over the first carr_lanes lanes of p's plan (the carrier chains:
+ * they come first) and the prefix — unless pass B starts from the host's drift model of every segment's start (batch_setup:
+ * chain_model) —, pass B (k_walk<pass_b>: 2 leaves rows, 3 the blocks' start phases only) over all p.seed_lanes, and the fix-up:
+ * k_chain_fix_par in workgroups of fix_wg lanes, or (fix_wg 0) k_chain_fix, the blocks in order.  A stream: this push's prefix /
+ * fix-up follow the ones of the push before (other seeding stream). */
+static hipError_t walk_chain_launch(hipStream_t ss, const BatchDev &p, int carr_lanes, bool pass_a, int pass_b, int fix_wg,
+                                    const CarryEvents &ce)
+{
+    hipError_t e;
+    if (pass_a) {
+        BatchDev pa = p;
+        pa.seed_lanes = carr_lanes;
+        hipLaunchKernelGGL(k_walk<1>, dim3((carr_lanes + GPSBB_WALK_WG - 1) / GPSBB_WALK_WG), dim3(GPSBB_WALK_WG), 0, ss, pa);
+        if ((e = CarryEvents::wait(ss, ce.prefix)) != hipSuccess)
+            return e;
+        hipLaunchKernelGGL(k_chain_prefix, dim3(p.nch), dim3(PREFIX_WG), 0, ss, p);
+        if ((e = CarryEvents::record(ss, ce.prefix)) != hipSuccess)
+            return e;
+    }
+    const dim3 wg_all((p.seed_lanes + GPSBB_WALK_WG - 1) / GPSBB_WALK_WG);
+    if (pass_b == 2)
+        hipLaunchKernelGGL(k_walk<2>, wg_all, dim3(GPSBB_WALK_WG), 0, ss, p);
+    else
+        hipLaunchKernelGGL(k_walk<3>, wg_all, dim3(GPSBB_WALK_WG), 0, ss, p);
+    if ((e = CarryEvents::wait(ss, ce.fix)) != hipSuccess)
+        return e;
+    if (fix_wg == 0)
+        hipLaunchKernelGGL(k_chain_fix, dim3(1), dim3(64), 0, ss, p);
+    else if (fix_wg == FIXP_WG_ALONE)
+        hipLaunchKernelGGL(k_chain_fix_par<FIXP_WG_ALONE>, dim3(p.nch, p.fix_chunks), dim3(FIXP_WG_ALONE), 0, ss, p);
+    else
+        hipLaunchKernelGGL(k_chain_fix_par<FIXP_WG_BATCH>, dim3(p.nch, p.fix_chunks), dim3(FIXP_WG_BATCH), 0, ss, p);
+    return CarryEvents::record(ss, ce.fix);
+}
+
+/* The timing events of this launch: seed start/end (pre-pass stream), synth start/end (synthesis stream). */
+static int launch_events(gpsbb_batch *b, hipEvent_t **ev)
 {
     gpsbb *h = b->h;
-    const int set = (int)(b->run_count % (unsigned)b->nsets);
-    b->fix_epoch++; /* a number no earlier launch of this batch handed to k_chain_fix_par */
-    if (b->want_digest)
-        HIPCHK(h, (hipError_t)b->d_dig.reserve((size_t)b->nblocks));
-    const BatchDev p = batch_dev(b, set);
-    const int lanes = (int)b->h_seed_order.size();
     /* (the drop-in call's scratch batch, everything on one stream and waited for before the call returns: no events — each record
      * is a packet between two kernels, 5 us of nothing on a call of 140) */
-    const bool timed = !b->one_stream;
-    if (!timed && b->evs.empty()) {
-        gpsbb_batch::Ev4 t = {{nullptr, nullptr, nullptr, nullptr}};
-        b->evs.push_back(t);
-    }
-    if (!timed) {
+    gpsbb_batch::Ev4 t = {{nullptr, nullptr, nullptr, nullptr}};
+    if (b->one_stream) {
+        if (b->evs.empty())
+            b->evs.push_back(t);
         b->ev_used = 0;
-    } else if (b->ev_used == b->evs.size()) {
+        *ev = b->evs[0].e;
+        return GPSBB_OK;
+    }
+    if (b->ev_used == b->evs.size()) {
         if (b->evs.size() >= 4096) {
             b->ev_used = 0; /* wrap: only the most recent runs are kept */
         } else {
-            gpsbb_batch::Ev4 t = {{nullptr, nullptr, nullptr, nullptr}};
             for (auto &e : t.e)
                 HIPCHK(h, hipEventCreate(&e));
             b->evs.push_back(t);
         }
     }
-    hipEvent_t *ev = timed ? b->evs[b->ev_used++].e : b->evs[0].e;
-    PUSH_MARK("l_ev");
+    *ev = b->evs[b->ev_used++].e;
+    return GPSBB_OK;
+}
 
-    /* The pre-pass runs on a seeding stream of its own: it may start as soon as the synthesis kernel that last
-     * read this table set has finished, i.e. it overlaps the synthesis of the runs before it.  With three sets
-     * consecutive runs take the handle's two seeding streams in turn, so that two pre-passes are in flight. */
-    hipStream_t ss = nullptr;
-    HIPCHK(h, batch_prepass_stream(b, b->chain_dev, &ss));
-    /* (a push's set-up uploaded on this very stream: in order already, and no wait packet ahead of the plan kernel) */
-    if (b->upload_done && b->upload_stream != ss)
-        HIPCHK(h, hipStreamWaitEvent(ss, b->upload_done, 0));
-    if (b->synth_pending[set])
-        HIPCHK(h, hipStreamWaitEvent(ss, b->synth_done_ref[set], 0));
-    if (timed)
-        HIPCHK(h, hipEventRecord(ev[0], ss));
-    bool ctr_reset_by_prepass = false;
+/* The pre-pass of one run into table set `set`, on stream ss.  *ctr_reset: it zeroes the set's tile counters itself. */
+static int prepass_launch(gpsbb_batch *b, int set, const BatchDev &p, hipStream_t ss, bool *ctr_reset)
+{
+    gpsbb *h = b->h;
+    const TableSet &ts = b->sets[set];
+    const int lanes = (int)b->h_seed_order.size();
+    const CarryEvents ce = {b->d_carry ? b->ev_prefix : nullptr, b->d_carry ? b->ev_fix : nullptr};
+    const int fix_wg = b->chain_fix_seq ? 0 : b->fix_wg;
+    *ctr_reset = false;
     if (h->opt_skip_seed && b->run_count >= (unsigned)b->nsets) {
         /* measurement hook: time the synthesis kernel alone on tables already built */
     } else if (b->host_seed) {
         /* the previous user of the pinned images (this batch's last run) has been copied out: its upload was
-         * followed by the synthesis kernel, which synth_done[] of that set covers */
-        const int prev = (set + b->nsets - 1) % b->nsets;
-        if (b->synth_pending[prev])
-            HIPCHK(h, hipEventSynchronize(b->synth_done_ref[prev]));
-        const int rc = host_seed_run(b, set, ss);
+         * followed by the synthesis kernel, which that set's synth_done_ref covers */
+        const TableSet &prev = b->sets[(set + b->nsets - 1) % b->nsets];
+        if (prev.synth_pending)
+            HIPCHK(h, hipEventSynchronize(prev.synth_done_ref));
+        const int rc = host_seed_run(b, ts, ss);
         if (rc != GPSBB_OK)
             return rc;
     } else if (b->ev && b->laps) {
         /* the lap-parallel pre-pass (gpsbb_laps.hip.h): plan, reference walks, scan, true walks, repair — the code chains
          * first (nothing of theirs waits for another push), then the carriers: a stream's push starts from the exact phase the
          * push before it left on the device, so its plan follows that push's repair kernel */
-        const LapDev L = lap_dev(b, set);
-        const unsigned cc = b->lap_chunk0[NCO_CODE][b->nch] - b->lap_chunk0[NCO_CODE][0];
-        const unsigned ck = b->lap_chunk0[NCO_CARR][b->nch] - b->lap_chunk0[NCO_CARR][0];
+        const LapDev L = lap_dev(b, ts);
         /* a batch that continues nothing (no stream carry: the drop-in call's block, resident batches): both kinds in one grid
          * per step, five launches instead of ten — the chain of small launches IS the latency of a small batch's pre-pass (one
          * block of the reference's geometry: 98 -> 50 us), and a big batch's two plan kernels (16 wavefronts each, 0.1 - 0.2 ms)
@@ -2163,91 +2263,35 @@ static int batch_launch(gpsbb_batch *b, int16_t *d_iq)
          * 1023 chips / (1.023e6 * delt) samples) — k_lap_pass2<., true>; at the reference's 2.6 MS/s a period is 2.5 tiles and the
          * plain loop is the faster one */
         const bool wide = GPSBB_KNOB_LONG("GPSBB_LAP_WIDE", b->delt <= 1.0 / 8.0e6 ? 1 : 0) != 0;
-        const bool merged = !p.kph0 && (!(b->d_carry && b->ev_fix) || GPSBB_KNOB_LONG("GPSBB_LAP_MERGE", 0) == 1) &&
+        const bool merged = !p.kph0 && (!ce.fix || GPSBB_KNOB_LONG("GPSBB_LAP_MERGE", 0) == 1) &&
                             GPSBB_KNOB_LONG("GPSBB_LAP_MERGE", 0) != 2;
-        /* a stream's carry (ChainCarryDev) is read by this push's carrier plan and written by its repair (exact_end AND approx_end):
-         * ordered behind every writer of the push before — lap-parallel or row walks — and ahead of every reader of the next, whichever
-         * pre-pass that push takes: both events waited for, both recorded */
-        const auto carry_wait = [&]() -> hipError_t {
-            hipError_t e = hipSuccess;
-            if (b->d_carry && b->ev_fix)
-                e = hipStreamWaitEvent(ss, b->ev_fix, 0);
-            if (e == hipSuccess && b->d_carry && b->ev_prefix)
-                e = hipStreamWaitEvent(ss, b->ev_prefix, 0);
-            return e;
-        };
-        const auto carry_done = [&]() -> hipError_t {
-            hipError_t e = hipSuccess;
-            if (b->d_carry && b->ev_fix)
-                e = hipEventRecord(b->ev_fix, ss);
-            if (e == hipSuccess && b->d_carry && b->ev_prefix)
-                e = hipEventRecord(b->ev_prefix, ss);
-            return e;
-        };
         if (merged) {
-            HIPCHK(h, carry_wait());
-            hipLaunchKernelGGL(k_lap_plan2, dim3(2 * b->nch), dim3(64), 0, ss, p, L);
-            hipLaunchKernelGGL(k_lap_pass1_2, dim3(cc + ck), dim3(LAP_WG), 0, ss, p, L);
-            hipLaunchKernelGGL(k_lap_scan2, dim3(2 * b->nch), dim3(64), 0, ss, p, L);
-            hipLaunchKernelGGL(lap_pass2_kernel(-1, wide, p.st_log2), dim3(cc + ck), dim3(LAP_WG), 0, ss, p, L);
-            hipLaunchKernelGGL(k_lap_repair2, dim3(2 * b->nch), dim3(64), 0, ss, p, L);
-            HIPCHK(h, carry_done());
+            HIPCHK(h, ce.wait_both(ss));
+            lap_chain_launch(ss, p, L, b->nch, -1, lap_pass2_kernel(-1, wide, p.st_log2));
+            HIPCHK(h, ce.record_both(ss));
         } else {
-            hipLaunchKernelGGL(k_lap_plan<NCO_CODE>, dim3(b->nch), dim3(64), 0, ss, p, L);
-            hipLaunchKernelGGL(k_lap_pass1<NCO_CODE>, dim3(cc), dim3(LAP_WG), 0, ss, p, L);
-            hipLaunchKernelGGL(k_lap_scan<NCO_CODE>, dim3(b->nch), dim3(64), 0, ss, p, L);
-            hipLaunchKernelGGL(lap_pass2_kernel(NCO_CODE, wide, p.st_log2), dim3(cc), dim3(LAP_WG), 0, ss, p, L);
-            hipLaunchKernelGGL(k_lap_repair<NCO_CODE>, dim3(b->nch), dim3(64), 0, ss, p, L);
+            lap_chain_launch(ss, p, L, b->nch, NCO_CODE, lap_pass2_kernel(NCO_CODE, wide, p.st_log2));
             if (p.kph0) {
                 /* fixed-point carrier: no chain to walk; the plan kernel leaves the end states, the tile states are a closed form */
                 hipLaunchKernelGGL(k_lap_plan<NCO_CARR>, dim3(b->nch), dim3(64), 0, ss, p, L);
                 hipLaunchKernelGGL(k_lap_fixed_tiles, dim3(b->nblocks * b->nch), dim3(256), 0, ss, p);
             } else {
-                HIPCHK(h, carry_wait());
-                hipLaunchKernelGGL(k_lap_plan<NCO_CARR>, dim3(b->nch), dim3(64), 0, ss, p, L);
-                hipLaunchKernelGGL(k_lap_pass1<NCO_CARR>, dim3(ck), dim3(LAP_WG), 0, ss, p, L);
-                hipLaunchKernelGGL(k_lap_scan<NCO_CARR>, dim3(b->nch), dim3(64), 0, ss, p, L);
-                hipLaunchKernelGGL(lap_pass2_kernel(NCO_CARR, wide, p.st_log2), dim3(ck), dim3(LAP_WG), 0, ss, p, L);
-                hipLaunchKernelGGL(k_lap_repair<NCO_CARR>, dim3(b->nch), dim3(64), 0, ss, p, L);
-                HIPCHK(h, carry_done());
+                HIPCHK(h, ce.wait_both(ss));
+                lap_chain_launch(ss, p, L, b->nch, NCO_CARR, lap_pass2_kernel(NCO_CARR, wide, p.st_log2));
+                HIPCHK(h, ce.record_both(ss));
             }
         }
-        ctr_reset_by_prepass = true; /* k_lap_plan zeroes the set's tile counters */
+        *ctr_reset = true; /* k_lap_plan zeroes the set's tile counters */
     } else if (b->ev) {
-        const bool old_seed = GPSBB_KNOB_SET("GPSBB_EV_KSEED"); /* experiment: the one-kernel pre-pass */
-        if (old_seed) {
+        if (GPSBB_KNOB_SET("GPSBB_EV_KSEED")) { /* experiment: the one-kernel pre-pass */
             hipLaunchKernelGGL(k_seed<true>, dim3((lanes + GPSBB_SEED_WG - 1) / GPSBB_SEED_WG), dim3(GPSBB_SEED_WG), 0, ss, p);
         } else {
-            const dim3 wg_all((lanes + GPSBB_WALK_WG - 1) / GPSBB_WALK_WG);
-            if (b->chain_dev) {
-                if (!b->chain_model) {
-                    BatchDev pa = p; /* pass A: the carrier chains only (they come first in the plan) */
-                    pa.seed_lanes = b->carr_lanes;
-                    hipLaunchKernelGGL(k_walk<1>, dim3((b->carr_lanes + GPSBB_WALK_WG - 1) / GPSBB_WALK_WG), dim3(GPSBB_WALK_WG), 0, ss, pa);
-                    /* a stream: this push's prefix / fix-up follow the ones of the push before (other seeding stream) */
-                    if (b->d_carry && b->ev_prefix)
-                        HIPCHK(h, hipStreamWaitEvent(ss, b->ev_prefix, 0));
-                    hipLaunchKernelGGL(k_chain_prefix, dim3(b->nch), dim3(PREFIX_WG), 0, ss, p);
-                    if (b->d_carry && b->ev_prefix)
-                        HIPCHK(h, hipEventRecord(b->ev_prefix, ss));
-                } /* else: pass B walks from the host's drift model of every segment's start (batch_setup) */
-                hipLaunchKernelGGL(k_walk<2>, wg_all, dim3(GPSBB_WALK_WG), 0, ss, p);
-                if (b->d_carry && b->ev_fix)
-                    HIPCHK(h, hipStreamWaitEvent(ss, b->ev_fix, 0));
-                if (b->chain_fix_seq)
-                    hipLaunchKernelGGL(k_chain_fix, dim3(1), dim3(64), 0, ss, p);
-                else
-                    if (b->fix_wg == FIXP_WG_ALONE)
-                        hipLaunchKernelGGL(k_chain_fix_par<FIXP_WG_ALONE>, dim3(b->nch, b->fix_chunks), dim3(FIXP_WG_ALONE), 0, ss, p);
-                    else
-                        hipLaunchKernelGGL(k_chain_fix_par<FIXP_WG_BATCH>, dim3(b->nch, b->fix_chunks), dim3(FIXP_WG_BATCH), 0, ss, p);
-                if (b->d_carry && b->ev_fix)
-                    HIPCHK(h, hipEventRecord(b->ev_fix, ss));
-            } else {
-                hipLaunchKernelGGL(k_walk<0>, wg_all, dim3(GPSBB_WALK_WG), 0, ss, p);
-            }
+            if (b->chain_dev)
+                HIPCHK(h, walk_chain_launch(ss, p, b->carr_lanes, !b->chain_model, 2, fix_wg, ce));
+            else
+                hipLaunchKernelGGL(k_walk<0>, dim3((lanes + GPSBB_WALK_WG - 1) / GPSBB_WALK_WG), dim3(GPSBB_WALK_WG), 0, ss, p);
             hipLaunchKernelGGL(k_tiles, dim3((1 + b->nseg) * b->nblocks * b->nch), dim3(GPSBB_TILES_WG), 0, ss, p);
-            ctr_reset_by_prepass = true; /* k_tiles zeroes the set's tile counters */
+            *ctr_reset = true; /* k_tiles zeroes the set's tile counters */
         }
     } else {
         if (b->chain_starts) {
@@ -2256,55 +2300,19 @@ static int batch_launch(gpsbb_batch *b, int16_t *d_iq)
             BatchDev pc = p;
             pc.seed_order = b->d_chain_order.p;
             pc.seed_lanes = b->chain_lanes;
-            const dim3 wg_c((b->chain_lanes + GPSBB_WALK_WG - 1) / GPSBB_WALK_WG);
-            hipLaunchKernelGGL(k_walk<1>, wg_c, dim3(GPSBB_WALK_WG), 0, ss, pc);
-            if (b->d_carry && b->ev_prefix)
-                HIPCHK(h, hipStreamWaitEvent(ss, b->ev_prefix, 0));
-            hipLaunchKernelGGL(k_chain_prefix, dim3(b->nch), dim3(PREFIX_WG), 0, ss, pc);
-            if (b->d_carry && b->ev_prefix)
-                HIPCHK(h, hipEventRecord(b->ev_prefix, ss));
-            hipLaunchKernelGGL(k_walk<3>, wg_c, dim3(GPSBB_WALK_WG), 0, ss, pc);
-            if (b->d_carry && b->ev_fix)
-                HIPCHK(h, hipStreamWaitEvent(ss, b->ev_fix, 0));
-            if (b->chain_fix_seq)
-                hipLaunchKernelGGL(k_chain_fix, dim3(1), dim3(64), 0, ss, pc);
-            else
-                if (b->fix_wg == FIXP_WG_ALONE)
-                    hipLaunchKernelGGL(k_chain_fix_par<FIXP_WG_ALONE>, dim3(b->nch, b->fix_chunks), dim3(FIXP_WG_ALONE), 0, ss, pc);
-                else
-                    hipLaunchKernelGGL(k_chain_fix_par<FIXP_WG_BATCH>, dim3(b->nch, b->fix_chunks), dim3(FIXP_WG_BATCH), 0, ss, pc);
-            if (b->d_carry && b->ev_fix)
-                HIPCHK(h, hipEventRecord(b->ev_fix, ss));
+            HIPCHK(h, walk_chain_launch(ss, pc, b->chain_lanes, true, 3, fix_wg, ce));
         }
         hipLaunchKernelGGL(k_seed<false>, dim3((lanes + GPSBB_SEED_WG - 1) / GPSBB_SEED_WG), dim3(GPSBB_SEED_WG), 0, ss, p);
     }
-    HIPCHK(h, hipGetLastError());
-    if (timed)
-        HIPCHK(h, hipEventRecord(ev[1], ss));
-    h->last_prepass = b->host_seed ? 2 : (b->ev && b->laps ? 3 : 1);
-    PUSH_MARK("l_pre");
+    return GPSBB_OK;
+}
 
-    /* off by default: +2 % on a stream of pushes, but overlapping kernels make the per-launch time (the roofline figure)
-     * meaningless and re-runs of a resident batch get slower */
-    const bool one_cs = !GPSBB_KNOB_SET("GPSBB_TWO_COMPUTE_STREAMS");
-    /* consecutive launches take the two synthesis streams in turn — they work on different table sets (or, slots of
-     * a ring, different batches) — except re-runs of a batch that has a single table set */
-    hipStream_t sc = h->s_compute;
-    if (!one_cs && !b->one_stream && (b->nsets >= 2 || b->max_sets == 1) && ((h->compute_turn++) & 1u)) {
-        if (!h->s_compute2)
-            HIPCHK(h, hipStreamCreateWithFlags(&h->s_compute2, hipStreamNonBlocking));
-        sc = h->s_compute2;
-    }
-    b->last_cs = sc;
-    if (sc != ss)
-        HIPCHK(h, hipStreamWaitEvent(sc, ev[1], 0));
-    if (!ctr_reset_by_prepass)
-        HIPCHK(h, hipMemsetAsync(p.tile_ctr, 0, ((size_t)b->nblocks + 1) * sizeof(int32_t), sc));
-    if (timed)
-        HIPCHK(h, hipEventRecord(ev[2], sc));
-    if (b->want_digest)
-        HIPCHK(h, hipMemsetAsync(b->d_dig.p, 0, (size_t)b->nblocks * sizeof(unsigned long long), sc));
+/* The synthesis kernel of one run on stream sc, and the blocks' digests behind it where no variant leaves them itself. */
+static int synth_launch(gpsbb_batch *b, const BatchDev &p, hipStream_t sc, int16_t *d_iq)
+{
+    gpsbb *h = b->h;
     bool digest_fused = false;
+    h->last_chain_dev = b->chain_dev && !b->chain_indep ? 1 : 0;
     if (b->ev) {
         /* One workgroup of EV_WG lanes fits a CU (its LDS image takes ~140 - 156 KB).  Grid = the blocks' primaries, then the
          * helpers (ev_pick_block: a helper joins one of the blocks that still have tiles to hand out, chosen when it starts):
@@ -2346,11 +2354,9 @@ static int batch_launch(gpsbb_batch *b, int16_t *d_iq)
         /* (the same order as the launches above; a digest-fused instantiation is the same variant) */
         h->last_variant = b->ev_all_dense ? (b->nch <= PD_WIDE_CHAN ? GPSBB_VARIANT_PD_WIDE : GPSBB_VARIANT_PD_NARROW)
                           : (b->ev_dense ? GPSBB_VARIANT_EV_DENSE : (p.kph0 ? GPSBB_VARIANT_EV_FIXED : GPSBB_VARIANT_EV));
-        h->last_chain_dev = b->chain_dev && !b->chain_indep ? 1 : 0;
     } else {
         h->last_kernel = 1;
         h->last_variant = GPSBB_VARIANT_SYNTH;
-        h->last_chain_dev = b->chain_dev && !b->chain_indep ? 1 : 0;
         /* Workgroups per block: enough of them to oversubscribe the chip ~3x (tiles are handed out
          * dynamically in chunks, so the tail is short), never more than there are chunks; the per-block
          * LDS tables (amplitude LUT, chips, nav words) are then built few times per block. */
@@ -2371,13 +2377,78 @@ static int batch_launch(gpsbb_batch *b, int16_t *d_iq)
         hipLaunchKernelGGL(k_block_digest, dim3((unsigned)chunks, (unsigned)b->nblocks), dim3(256), 0, sc, (const uint32_t *)d_iq, b->nsamp, b->d_dig.p);
     }
     HIPCHK(h, hipGetLastError());
+    return GPSBB_OK;
+}
+
+/* One run of a batch: its timing events, the pre-pass on a pre-pass stream, the synthesis on a synthesis stream behind it. */
+static int batch_launch(gpsbb_batch *b, int16_t *d_iq)
+{
+    gpsbb *h = b->h;
+    const int set = (int)(b->run_count % (unsigned)b->nsets);
+    TableSet &ts = b->sets[set];
+    b->fix.epoch++; /* a number no earlier launch of this batch handed to k_chain_fix_par */
+    if (b->want_digest)
+        HIPCHK(h, (hipError_t)b->d_dig.reserve((size_t)b->nblocks));
+    const BatchDev p = batch_dev(b, ts);
+    const bool timed = !b->one_stream;
+    hipEvent_t *ev = nullptr;
+    int rc = launch_events(b, &ev);
+    if (rc != GPSBB_OK)
+        return rc;
+    PUSH_MARK("l_ev");
+
+    /* The pre-pass runs on a seeding stream of its own: it may start as soon as the synthesis kernel that last
+     * read this table set has finished, i.e. it overlaps the synthesis of the runs before it.  With three sets
+     * consecutive runs take the handle's two seeding streams in turn, so that two pre-passes are in flight. */
+    hipStream_t ss = nullptr;
+    HIPCHK(h, batch_prepass_stream(b, b->chain_dev, &ss));
+    /* (a push's set-up uploaded on this very stream: in order already, and no wait packet ahead of the plan kernel) */
+    if (b->upload_done && b->upload_stream != ss)
+        HIPCHK(h, hipStreamWaitEvent(ss, b->upload_done, 0));
+    if (ts.synth_pending)
+        HIPCHK(h, hipStreamWaitEvent(ss, ts.synth_done_ref, 0));
+    if (timed)
+        HIPCHK(h, hipEventRecord(ev[0], ss));
+    bool ctr_reset_by_prepass = false;
+    rc = prepass_launch(b, set, p, ss, &ctr_reset_by_prepass);
+    if (rc != GPSBB_OK)
+        return rc;
+    HIPCHK(h, hipGetLastError());
+    if (timed)
+        HIPCHK(h, hipEventRecord(ev[1], ss));
+    h->last_prepass = b->host_seed ? 2 : (b->ev && b->laps ? 3 : 1);
+    PUSH_MARK("l_pre");
+
+    /* off by default: +2 % on a stream of pushes, but overlapping kernels make the per-launch time (the roofline figure)
+     * meaningless and re-runs of a resident batch get slower */
+    const bool one_cs = !GPSBB_KNOB_SET("GPSBB_TWO_COMPUTE_STREAMS");
+    /* consecutive launches take the two synthesis streams in turn — they work on different table sets (or, slots of
+     * a ring, different batches) — except re-runs of a batch that has a single table set */
+    hipStream_t sc = h->s_compute;
+    if (!one_cs && !b->one_stream && (b->nsets >= 2 || b->max_sets == 1) && ((h->compute_turn++) & 1u)) {
+        if (!h->s_compute2)
+            HIPCHK(h, hipStreamCreateWithFlags(&h->s_compute2, hipStreamNonBlocking));
+        sc = h->s_compute2;
+    }
+    b->last_cs = sc;
+    if (sc != ss)
+        HIPCHK(h, hipStreamWaitEvent(sc, ev[1], 0));
+    if (!ctr_reset_by_prepass)
+        HIPCHK(h, hipMemsetAsync(p.tile_ctr, 0, ((size_t)b->nblocks + 1) * sizeof(int32_t), sc));
+    if (timed)
+        HIPCHK(h, hipEventRecord(ev[2], sc));
+    if (b->want_digest)
+        HIPCHK(h, hipMemsetAsync(b->d_dig.p, 0, (size_t)b->nblocks * sizeof(unsigned long long), sc));
+    rc = synth_launch(b, p, sc, d_iq);
+    if (rc != GPSBB_OK)
+        return rc;
     if (timed)
         HIPCHK(h, hipEventRecord(ev[3], sc));
     /* the run's end-of-synthesis event doubles as "this table set is free again" and as what a stream's copy stream
      * waits for: every further record on the synthesis stream is another packet between two kernels */
-    b->synth_done_ref[set] = ev[3];
+    ts.synth_done_ref = ev[3];
     b->last_done = ev[3];
-    b->synth_pending[set] = timed;
+    ts.synth_pending = timed;
     b->last_set = set;
     b->run_count++;
     b->ran = true;
@@ -2431,7 +2502,7 @@ extern "C" int gpsbb_batch_read(gpsbb_batch_t *b, int16_t *iq_out, gpsbb_chan_st
         HIPCHK(h, hipMemcpy(iq_out, src, gpsbb_batch_iq_bytes(b), hipMemcpyDeviceToHost));
     }
     if (end_state)
-        HIPCHK(h, hipMemcpy(end_state, b->d_end[b->last_set].p, (size_t)b->nblocks * b->nch * sizeof(gpsbb_chan_state_t),
+        HIPCHK(h, hipMemcpy(end_state, b->sets[b->last_set].end.p, (size_t)b->nblocks * b->nch * sizeof(gpsbb_chan_state_t),
                             hipMemcpyDeviceToHost));
     return GPSBB_OK;
 }
@@ -3262,7 +3333,7 @@ static int batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, 
     hipStream_t cs = h->s_compute;
     HIPCHK(h, hipMemsetAsync(b->d_ds.p, 0, (nsum + 1) * sizeof(unsigned long long), cs));
     HIPCHK(h, hipMemsetAsync(b->d_ds_ctr.p, 0, (size_t)b->nblocks * sizeof(int32_t), cs));
-    const BatchDev p = batch_dev(b, b->last_set);
+    const BatchDev p = batch_dev(b, b->sets[b->last_set]);
     DsArgs a;
     memset(&a, 0, sizeof a);
     a.iq = reinterpret_cast<const uint32_t *>(src);
@@ -3339,11 +3410,11 @@ static int fill_block_finish(gpsbb_t *h, gpsbb_batch *b, int nch, int nsamp, int
     *st = 0xffffffffu;
     if (GPSBB_KNOB_LONG("GPSBB_FILL_TAIL_KERNEL", 1) != 0) {
         static_assert(sizeof(gpsbb_chan_state_t) % 4 == 0, "copied as 32-bit words");
-        hipLaunchKernelGGL(k_fill_tail, dim3(1), dim3(256), 0, cs, end_state ? b->d_end[b->last_set].p : nullptr, h->d_status, h->h_fill, nch, st);
+        hipLaunchKernelGGL(k_fill_tail, dim3(1), dim3(256), 0, cs, end_state ? b->sets[b->last_set].end.p : nullptr, h->d_status, h->h_fill, nch, st);
         HIPCHK(h, hipGetLastError());
     } else {
         if (end_state)
-            HIPCHK(h, hipMemcpyAsync(h->h_fill, b->d_end[b->last_set].p, (size_t)nch * sizeof(gpsbb_chan_state_t), hipMemcpyDeviceToHost, cs));
+            HIPCHK(h, hipMemcpyAsync(h->h_fill, b->sets[b->last_set].end.p, (size_t)nch * sizeof(gpsbb_chan_state_t), hipMemcpyDeviceToHost, cs));
         HIPCHK(h, hipMemcpyAsync(st, h->d_status, 4, hipMemcpyDeviceToHost, cs));
     }
     PUSH_MARK("tail");
@@ -4032,7 +4103,7 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
         /* end states (40 B each: a multiple of 16 bytes for any even count; odd counts are rounded up into the
          * allocation's slack) + the self-check word, by a small kernel: see k_end_states_to_host */
         const size_t bytes = (size_t)s->bps * s->nch * sizeof(gpsbb_chan_state_t);
-        hipLaunchKernelGGL(k_end_states_to_host, dim3(64), dim3(256), 0, cs, (const uint4 *)b->d_end[b->last_set].p,
+        hipLaunchKernelGGL(k_end_states_to_host, dim3(64), dim3(256), 0, cs, (const uint4 *)b->sets[b->last_set].end.p,
                            (uint4 *)sl.h_end, (bytes + 15) / 16, h->d_status, (uint32_t *)((char *)sl.h_end + ((bytes + 15) & ~(size_t)15)));
         HIPCHK(h, hipGetLastError());
     }
@@ -4226,19 +4297,12 @@ struct ChainOnly {
     DevBuf<ChainAux> d_aux;
     ChainCarryDev *d_carry = nullptr;
     uint32_t *d_status = nullptr; /* a self-check word of its own: the handle's may belong to a push still in flight */
-    DevBuf<unsigned long long> d_fix_end;
-    DevBuf<int> d_fix_flag;
-    bool fix_flags_zeroed = false;
-    int fix_epoch = 0;
+    FixScratch fix;
     std::vector<ChainDesc> h_cd;
     std::vector<double> h_start0;
     /* the lap-parallel chain (gpsbb_laps.hip.h with nothing to emit): the phase after every block, scratch of the lap kernels */
     DevBuf<double> d_lap_end;
-    DevBuf<LapBC> d_lap_bc;
-    DevBuf<uint32_t> d_lap_lane0, d_lap_cnt, d_lap_chunk_bad;
-    DevBuf<LapRec> d_lap_rec;
-    DevBuf<LapAgg> d_lap_agg;
-    DevBuf<double> d_lap_chunk_m;
+    LapScratch lap;
     unsigned long long *d_hz_scratch = nullptr; /* (a chain alone counts no hazards: the render of those blocks does) */
     std::vector<double> h_lap_end;
 };
@@ -4250,27 +4314,60 @@ static void chain_only_free(gpsbb *h)
     ChainOnly *c = h->chain_only;
     if (!c)
         return;
-    c->d_cd.release();
-    c->d_start0.release();
-    c->d_aux.release();
-    c->d_lap_end.release();
-    c->d_lap_bc.release();
-    c->d_lap_lane0.release();
-    c->d_lap_cnt.release();
-    c->d_lap_chunk_bad.release();
-    c->d_lap_rec.release();
-    c->d_lap_agg.release();
-    c->d_lap_chunk_m.release();
+    release_all(c->d_cd, c->d_start0, c->d_aux, c->d_lap_end, c->lap, c->fix);
     if (c->d_hz_scratch)
         (void)hipFree(c->d_hz_scratch);
-    c->d_fix_end.release();
-    c->d_fix_flag.release();
     if (c->d_carry)
         (void)hipFree(c->d_carry);
     if (c->d_status)
         (void)hipFree(c->d_status);
     delete c;
     h->chain_only = nullptr;
+}
+
+/* What the chain kernels see of the sub-batch of nb blocks from block b0 on, whichever pre-pass walks it: the chain descriptors
+ * alone, the carry from the sub-batch before, and which channels of its first block go on from the block before it. */
+static BatchDev chain_only_dev(const ChainOnly *c, int b0, int nb, int nch, double delt, int nsamp, unsigned long long *hazards)
+{
+    BatchDev p;
+    memset(&p, 0, sizeof p);
+    p.nblocks = nb;
+    p.nch = nch;
+    p.nsamp = nsamp;
+    p.ntiles = (nsamp + TILE - 1) / TILE;
+    p.nstates = p.ntiles;
+    p.delt = delt;
+    p.flags = GPSBB_CHAIN_CARRIER;
+    p.status = c->d_status;
+    p.hazards = hazards;
+    p.chain_dev = 1;
+    p.nseg = 1;
+    p.nvb = nb;
+    p.cd = c->d_cd.p;
+    p.carry = c->d_carry;
+    const size_t k0 = (size_t)b0 * nch;
+    if (b0 > 0)
+        for (int i = 0; i < nch; i++) {
+            const int prn = c->h_cd[k0 + i].prn;
+            if (prn > 0 && prn == c->h_cd[k0 - nch + i].prn)
+                p.cont0_mask |= 1u << i;
+        }
+    return p;
+}
+
+/* ... and what the call brings back once its last sub-batch is done: the exact phase after the last block, the self-check word */
+static int chain_only_finish(gpsbb *h, const ChainOnly *c, size_t nbc_all, int nch, double *carr_phase_end)
+{
+    if (carr_phase_end) {
+        ChainCarryDev cc;
+        HIPCHK(h, hipMemcpy(&cc, c->d_carry, sizeof cc, hipMemcpyDeviceToHost));
+        for (int i = 0; i < nch; i++)
+            carr_phase_end[i] = c->h_cd[nbc_all - nch + i].prn > 0 ? cc.exact_end[i] : 0.0;
+    }
+    h->last_chain_dev = 1;
+    uint32_t st = 0;
+    HIPCHK(h, hipMemcpy(&st, c->d_status, 4, hipMemcpyDeviceToHost));
+    return st ? GPSBB_E_INTERNAL : GPSBB_OK;
 }
 
 extern "C" int gpsbb_chain_carrier(gpsbb_t *h, const gpsbb_chan_t *ch, int nblocks, int nch, double delt, int nsamp,
@@ -4384,63 +4481,18 @@ extern "C" int gpsbb_chain_carrier(gpsbb_t *h, const gpsbb_chan_t *ch, int nbloc
                 nb++;
             }
             const size_t nbc = (size_t)nb * nch, k0 = (size_t)b0 * nch;
-            LapDev L;
-            memset(&L, 0, sizeof L);
-            lap_bound(ch + k0, nb, nch, delt, nsamp, false, L.chunk0, true);
-            const size_t chunks = L.chunk0[1][nch];
+            uint32_t chunk0[2][GPSBB_MAX_CHAN + 1];
+            lap_bound(ch + k0, nb, nch, delt, nsamp, false, chunk0, true);
             HIPCHK(h, (hipError_t)c->d_cd.reserve(nbc));
             HIPCHK(h, (hipError_t)c->d_lap_end.reserve(nbc));
-            HIPCHK(h, (hipError_t)c->d_lap_bc.reserve(2 * nbc));
-            HIPCHK(h, (hipError_t)c->d_lap_lane0.reserve(2 * (size_t)nch * ((size_t)nb + 1)));
-            HIPCHK(h, (hipError_t)c->d_lap_cnt.reserve(4 * GPSBB_MAX_CHAN));
-            HIPCHK(h, (hipError_t)c->d_lap_rec.reserve(chunks * LAP_WG));
-            HIPCHK(h, (hipError_t)c->d_lap_agg.reserve(chunks));
-            HIPCHK(h, (hipError_t)c->d_lap_chunk_m.reserve(chunks));
-            HIPCHK(h, (hipError_t)c->d_lap_chunk_bad.reserve(chunks));
+            HIPCHK(h, (hipError_t)c->lap.reserve(nbc, (size_t)nch, (size_t)nb, chunk0[1][nch], false));
             HIPCHK(h, hipMemcpyAsync(c->d_cd.p, c->h_cd.data() + k0, nbc * sizeof(ChainDesc), hipMemcpyHostToDevice, ss));
-            L.bc = c->d_lap_bc.p;
-            L.lane0 = c->d_lap_lane0.p;
-            L.nlaps = c->d_lap_cnt.p;
-            L.nbad = c->d_lap_cnt.p + 2 * GPSBB_MAX_CHAN;
-            L.rec = c->d_lap_rec.p;
-            L.agg = c->d_lap_agg.p;
-            L.chunk_m = c->d_lap_chunk_m.p;
-            L.chunk_bad = c->d_lap_chunk_bad.p;
-            L.chained = 1;
-            L.jitter = (uint32_t)GPSBB_KNOB_LONG("GPSBB_LAP_JITTER", 0);
-            L.burst = GPSBB_KNOB_SET("GPSBB_LAP_NO_BURST") ? 0 : (int)GPSBB_KNOB_LONG("GPSBB_LAP_BURST_SHARE", LAP_BURST_SHARE);
-            L.unit[NCO_CODE] = lap_unit(NCO_CODE, (size_t)nb * nch);
-            L.unit[NCO_CARR] = lap_unit(NCO_CARR, (size_t)nb * nch);
-            BatchDev p;
-            memset(&p, 0, sizeof p);
-            p.nblocks = nb;
-            p.nch = nch;
-            p.nsamp = nsamp;
-            p.ntiles = (nsamp + TILE - 1) / TILE;
-            p.nstates = p.ntiles;
-            p.delt = delt;
-            p.flags = GPSBB_CHAIN_CARRIER;
-            p.status = c->d_status;
-            p.hazards = c->d_hz_scratch;
-            p.chain_dev = 1;
-            p.nseg = 1;
-            p.nvb = nb;
-            p.cd = c->d_cd.p;
-            p.carry = c->d_carry;
+            LapDev L;
+            c->lap.dev(L);
+            lap_dev_plan(L, chunk0, true, nbc);
+            BatchDev p = chain_only_dev(c, b0, nb, nch, delt, nsamp, c->d_hz_scratch);
             p.lap_end = c->d_lap_end.p;
-            p.cont0_mask = 0;
-            if (b0 > 0)
-                for (int i = 0; i < nch; i++) {
-                    const int prn = c->h_cd[k0 + i].prn;
-                    if (prn > 0 && prn == c->h_cd[k0 - nch + i].prn)
-                        p.cont0_mask |= 1u << i;
-                }
-            const unsigned ck = L.chunk0[NCO_CARR][nch] - L.chunk0[NCO_CARR][0];
-            hipLaunchKernelGGL(k_lap_plan<NCO_CARR>, dim3(nch), dim3(64), 0, ss, p, L);
-            hipLaunchKernelGGL(k_lap_pass1<NCO_CARR>, dim3(ck), dim3(LAP_WG), 0, ss, p, L);
-            hipLaunchKernelGGL(k_lap_scan<NCO_CARR>, dim3(nch), dim3(64), 0, ss, p, L);
-            hipLaunchKernelGGL(k_lap_pass2<NCO_CARR>, dim3(ck), dim3(LAP_WG), 0, ss, p, L);
-            hipLaunchKernelGGL(k_lap_repair<NCO_CARR>, dim3(nch), dim3(64), 0, ss, p, L);
+            lap_chain_launch(ss, p, L, nch, NCO_CARR, lap_pass2_kernel(NCO_CARR, false, 0));
             HIPCHK(h, hipGetLastError());
             if (carr_phase_seed)
                 HIPCHK(h, hipMemcpyAsync(c->h_lap_end.data() + k0, c->d_lap_end.p, nbc * sizeof(double), hipMemcpyDeviceToHost, ss));
@@ -4458,16 +4510,7 @@ extern "C" int gpsbb_chain_carrier(gpsbb_t *h, const gpsbb_chan_t *ch, int nbloc
                         v = (blk > 0 && c->h_cd[k - nch].prn == d.prn) ? c->h_lap_end[k - nch] : d.carr_phase;
                     carr_phase_seed[k] = v;
                 }
-        if (carr_phase_end) {
-            ChainCarryDev cc;
-            HIPCHK(h, hipMemcpy(&cc, c->d_carry, sizeof cc, hipMemcpyDeviceToHost));
-            for (int i = 0; i < nch; i++)
-                carr_phase_end[i] = c->h_cd[nbc_all - nch + i].prn > 0 ? cc.exact_end[i] : 0.0;
-        }
-        h->last_chain_dev = 1;
-        uint32_t st = 0;
-        HIPCHK(h, hipMemcpy(&st, c->d_status, 4, hipMemcpyDeviceToHost));
-        return st ? GPSBB_E_INTERNAL : GPSBB_OK;
+        return chain_only_finish(h, c, nbc_all, nch, carr_phase_end);
     }
     for (int b0 = 0; b0 < nblocks; b0 += CHAIN_ONLY_BLOCKS) {
         const int nb = nblocks - b0 < CHAIN_ONLY_BLOCKS ? nblocks - b0 : CHAIN_ONLY_BLOCKS;
@@ -4475,59 +4518,22 @@ extern "C" int gpsbb_chain_carrier(gpsbb_t *h, const gpsbb_chan_t *ch, int nbloc
         HIPCHK(h, (hipError_t)c->d_cd.reserve(nbc));
         HIPCHK(h, (hipError_t)c->d_start0.reserve(nbc));
         HIPCHK(h, (hipError_t)c->d_aux.reserve(nbc));
-        const int fix_chunks = (nb + FIXP_WG_ALONE - 1) / FIXP_WG_ALONE;
-        {
-            const size_t nf = (size_t)GPSBB_MAX_CHAN * ((CHAIN_ONLY_BLOCKS + FIXP_WG_ALONE - 1) / FIXP_WG_ALONE);
-            if (nf > c->d_fix_flag.cap || c->d_fix_end.cap < c->d_fix_flag.cap || !c->fix_flags_zeroed) {
-                c->fix_flags_zeroed = false;
-                HIPCHK(h, (hipError_t)c->d_fix_flag.reserve(nf));
-                HIPCHK(h, (hipError_t)c->d_fix_end.reserve(c->d_fix_flag.cap));
-                HIPCHK(h, hipMemsetAsync(c->d_fix_flag.p, 0, c->d_fix_flag.cap * sizeof(int), ss));
-                c->fix_epoch = 0;
-                c->fix_flags_zeroed = true;
-            }
-        }
+        HIPCHK(h, c->fix.reserve((size_t)GPSBB_MAX_CHAN * ((CHAIN_ONLY_BLOCKS + FIXP_WG_ALONE - 1) / FIXP_WG_ALONE), ss));
         HIPCHK(h, hipMemcpyAsync(c->d_cd.p, c->h_cd.data() + k0, nbc * sizeof(ChainDesc), hipMemcpyHostToDevice, ss));
         HIPCHK(h, hipMemcpyAsync(c->d_start0.p, c->h_start0.data() + k0, nbc * sizeof(double), hipMemcpyHostToDevice, ss));
-        BatchDev p;
-        memset(&p, 0, sizeof p);
-        p.nblocks = nb;
-        p.nch = nch;
-        p.nsamp = nsamp;
-        p.ntiles = (nsamp + TILE - 1) / TILE;
-        p.nstates = p.ntiles;
-        p.delt = delt;
-        p.flags = GPSBB_CHAIN_CARRIER;
-        p.status = c->d_status;
-        p.hazards = h->d_hz;
-        p.chain_dev = 1;
+        BatchDev p = chain_only_dev(c, b0, nb, nch, delt, nsamp, h->d_hz);
         p.chain_starts = 1;
         p.model_start = 0; /* over tens of thousands of blocks a prediction drifts too far: pass A and the prefix stay */
-        p.nseg = 1;
         p.seg_tiles = p.ntiles;
-        p.nvb = nb;
         p.aux = c->d_aux.p;
-        p.cd = c->d_cd.p;
         p.start0 = c->d_start0.p;
-        p.carry = c->d_carry;
-        p.fix_end = c->d_fix_end.p;
-        p.fix_flag = c->d_fix_flag.p;
-        p.fix_epoch = ++c->fix_epoch;
-        p.fix_chunks = fix_chunks;
-        p.cont0_mask = 0;
-        if (b0 > 0)
-            for (int i = 0; i < nch; i++) {
-                const int prn = c->h_cd[k0 + i].prn;
-                if (prn > 0 && prn == c->h_cd[k0 - nch + i].prn)
-                    p.cont0_mask |= 1u << i;
-            }
+        p.fix_end = c->fix.end.p;
+        p.fix_flag = c->fix.flag.p;
+        p.fix_epoch = ++c->fix.epoch;
+        p.fix_chunks = (nb + FIXP_WG_ALONE - 1) / FIXP_WG_ALONE;
         p.seed_order = nullptr; /* channel by channel, blocks in order (k_walk) */
         p.seed_lanes = nch * ((nb + 63) & ~63);
-        const dim3 wg((p.seed_lanes + GPSBB_WALK_WG - 1) / GPSBB_WALK_WG);
-        hipLaunchKernelGGL(k_walk<1>, wg, dim3(GPSBB_WALK_WG), 0, ss, p);
-        hipLaunchKernelGGL(k_chain_prefix, dim3(nch), dim3(PREFIX_WG), 0, ss, p);
-        hipLaunchKernelGGL(k_walk<3>, wg, dim3(GPSBB_WALK_WG), 0, ss, p);
-        hipLaunchKernelGGL(k_chain_fix_par<FIXP_WG_ALONE>, dim3(nch, fix_chunks), dim3(FIXP_WG_ALONE), 0, ss, p);
+        HIPCHK(h, walk_chain_launch(ss, p, p.seed_lanes, true, 3, FIXP_WG_ALONE, CarryEvents()));
         HIPCHK(h, hipGetLastError());
         if (carr_phase_seed) {
             /* the exact start phase of every block, as k_chain_fix_par left it in the chain descriptors */
@@ -4538,16 +4544,7 @@ extern "C" int gpsbb_chain_carrier(gpsbb_t *h, const gpsbb_chan_t *ch, int nbloc
     if (carr_phase_seed)
         for (size_t k = 0; k < nbc_all; k++)
             carr_phase_seed[k] = c->h_cd[k].prn > 0 ? c->h_cd[k].carr_phase : 0.0;
-    if (carr_phase_end) {
-        ChainCarryDev cc;
-        HIPCHK(h, hipMemcpy(&cc, c->d_carry, sizeof cc, hipMemcpyDeviceToHost));
-        for (int i = 0; i < nch; i++)
-            carr_phase_end[i] = c->h_cd[nbc_all - nch + i].prn > 0 ? cc.exact_end[i] : 0.0;
-    }
-    h->last_chain_dev = 1;
-    uint32_t st = 0;
-    HIPCHK(h, hipMemcpy(&st, c->d_status, 4, hipMemcpyDeviceToHost));
-    return st ? GPSBB_E_INTERNAL : GPSBB_OK;
+    return chain_only_finish(h, c, nbc_all, nch, carr_phase_end);
 }
 
 #ifdef GPSBB_EXPERIMENTS
@@ -4657,7 +4654,7 @@ extern "C" int gpsbb_test_model_err(gpsbb_batch_t *b, double *maxima, unsigned l
     const int rc = gpsbb_sync(h);
     if (rc != GPSBB_OK)
         return rc;
-    const BatchDev p = batch_dev(b, b->last_set);
+    const BatchDev p = batch_dev(b, b->sets[b->last_set]);
     double *d_mx = nullptr;
     unsigned long long *d_cnt = nullptr;
     const size_t mx_bytes = sizeof(double) * GPSBB_MAX_CHAN * ME_NQ, cnt_bytes = sizeof(unsigned long long) * GPSBB_MAX_CHAN * MEC_NQ;
@@ -4700,7 +4697,7 @@ extern "C" int gpsbb_test_table_digest(gpsbb_batch_t *b, unsigned long long out[
     const int rc = gpsbb_sync(h);
     if (rc != GPSBB_OK)
         return rc;
-    const BatchDev p = batch_dev(b, b->last_set);
+    const BatchDev p = batch_dev(b, b->sets[b->last_set]);
     auto mix = [](unsigned long long z) { z ^= z >> 31; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 29; return z; };
     const size_t nst = (size_t)b->nstates;
     const size_t nx = (size_t)b->nblocks * 2 * b->nch * nst, nn = (size_t)b->nblocks * b->nch * nst, ne = (size_t)b->nblocks * b->nch;

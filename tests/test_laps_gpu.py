@@ -311,3 +311,27 @@ def test_a_carrier_without_doppler_stays_on_the_laps(pkg, fresh, oracle):
     iq, st1 = s.fill_block(ch[0], 1 / fs, nsamp)
     assert s.info(pkg.INFO_PREPASS) == 3 and (iq == one_iq[0]).all() and st1["carr_phase"].tobytes() == one_st["carr_phase"][0].tobytes()
     s.hazards(reset=True)   # (the channel on phase 1.0 counted: the session's handle goes on clean)
+
+
+def test_a_long_chain_on_the_row_walks(pkg, fresh, oracle):
+    """The other pre-pass asked for (GPSBB_OPT_SEED_WHERE 1) on a chained batch of 2048 blocks or more: from there on a batch's
+    fix-up takes the large workgroups gpsbb_chain_carrier always takes (k_chain_fix_par<FIXP_WG_ALONE>: nblocks * nseg >= 2048,
+    one segment per block at this length) — behind pass B from the host's model, behind pass A and the prefix
+    (GPSBB_OPT_CHAIN_WHERE 3), and for the per-sample kernel, where the chain only fixes the blocks' start phases.  Bit for bit."""
+    s = fresh
+    fs, nsamp, nb, nch = 25e6, 2100, 2100, 3
+    ch = pkg.synth_descriptors(nb, nch=nch, seed=2048)
+    ch["prn"][700:, 1] = 29
+    ch["prn"][1500:1503, 2] = 0
+    want_iq, want_st, _ = oracle.fill_blocks(ch, 1 / fs, nsamp, chain=True)
+    s.set_option(pkg.OPT_SEED_WHERE, 1)
+    for kernel, chain_where in ((0, 0), (0, 3), (1, 0)):
+        s.set_option(pkg.OPT_SYNTH_KERNEL, kernel)
+        s.set_option(pkg.OPT_CHAIN_WHERE, chain_where)
+        b = s.batch(ch, 1 / fs, nsamp, flags=pkg.CHAIN_CARRIER)
+        b.run(); s.sync()
+        iq, st = b.read(); b.close()
+        assert s.info(pkg.INFO_PREPASS) == 1 and s.info(pkg.INFO_CHAIN_ON_DEVICE) == 1, (kernel, chain_where)
+        assert s.info(pkg.INFO_LAST_KERNEL) == (1 if kernel else 2), (kernel, chain_where)
+        assert (iq == want_iq).all(), (kernel, chain_where)
+        assert st["carr_phase"].tobytes() == want_st["carr_phase"].tobytes(), (kernel, chain_where)
