@@ -140,8 +140,9 @@ struct EvLdsT {
     double tstate[EV_WAVES][2][2 * GPSBB_MAX_CHAN]; /* per wavefront.  [0]: the tile's exact states in guard format with the
                                                     channel's bias (2^20 + W + state), column 2*channel = code phase,
                                                     2*channel+1 = carrier phase*512 (512 - that for a falling carrier): written
-                                                    at the top of every tile from registers — one buffer is enough, a
-                                                    wavefront's LDS operations execute in order.  [1]: EvConst::tK0, tC0 of
+                                                    from registers in the epilogue of the tile before (synth_ev_body,
+                                                    stage_tile) — one buffer is enough, a wavefront's LDS operations
+                                                    execute in order.  [1]: EvConst::tK0, tC0 of
                                                     the block's channels, the addends of the two position fmas, 256 bytes
                                                     behind the states of the same channel.  A VALU instruction of gfx9 reads
                                                     ONE scalar register pair, and fma(-fraction, 1 / step, constant) has two
@@ -149,6 +150,10 @@ struct EvLdsT {
                                                     into a vector pair first (a v_mov_b64 per fma); out of LDS — a second
                                                     broadcast ds_read_b128 off the same address register — it arrives where
                                                     the fma wants it */
+    double tstep[2 * GPSBB_MAX_CHAN];            /* the block's chain steps (column 2*channel: sc, 2*channel+1: |S|), staged once per
+                                                    workgroup: what takes a granule's state to the anchor of its tile r > 0
+                                                    (synth_ev_body).  The kernel has no register to keep its lane's step in, and
+                                                    out of global memory the read put a vector-memory wait at the top of every tile */
     uint16_t chip2[GPSBB_MAX_CHAN][CHIP_LEN];    /* low byte: 0 where codeCA of chip c mod 1023 is +1, 0xff where -1;
                                                     high byte: the same for chip c+1 */
 };
@@ -750,6 +755,8 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
             L.tstate[tid >> 6][1][2 * l] = kb[l].tC0;     /* beside the code state */
             L.tstate[tid >> 6][1][2 * l + 1] = kb[l].tK0; /* beside the carrier state */
         }
+        if (SG && tid < 2 * p.nch) /* the chain steps (see EvLds::tstep) */
+            L.tstep[tid] = (tid & 1) ? kb[tid >> 1].S : kb[tid >> 1].sc;
     }
     __syncthreads();
 #ifdef GPSBB_WG_TRACE
@@ -778,11 +785,10 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
     constexpr int sg = SG; /* == p.st_log2 (the host launches the instance of its batch's granule) */
     const int nst = SG ? p.nstates : ntw;
     const double *__restrict__ txb = p.tile_x + (size_t)b * nst * nch2;
-    /* (a scalar base and a 32-bit element offset per lane, not a 64-bit pointer per lane: the kernel is short of registers — what
-     * it spills goes to HBM, DESIGN.md 3 — and a running pointer per lane is what the compiler spilled first) */
-    const uint32_t tx_off = (uint32_t)(chain_lane ? lane : 0) * (uint32_t)nst;
+    /* (a scalar base and a 32-bit element offset per lane — lane * nst, worked out where a granule's state is fetched — not a 64-bit
+     * pointer per lane: the kernel is short of registers — what it spills goes to HBM, DESIGN.md 3 — and a running pointer per
+     * lane is what the compiler spilled first) */
     const uint32_t *__restrict__ tnb = p.tile_nav + (size_t)b * p.nch * nst;
-    const uint32_t tn_off = (uint32_t)(lane < p.nch ? lane : 0) * (uint32_t)nst;
     const double off = (double)(lane * SPT);
     /* this lane's chain in guard format, biased (the fixed-point carrier's index is exact: no bias, see ev_first) */
     const double guard_w = EV_GUARD + ((chain_lane && !(FIXED && (lane & 1))) ? kb[lane >> 1].W : 0.0);
@@ -797,7 +803,7 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
     uint32_t drow = (uint32_t)lane * 4u; /* ev_d_add's address register: byte 0 = this lane's column, byte 1 rewritten per difference */
 
     /* chunks of EV_CHUNK consecutive tiles from a per-block counter; the next chunk is asked for while the
-     * current one is worked on, and a tile's states are fetched while the previous tile is worked on */
+     * current one is worked on, and a granule's states are fetched while the tile before its first is worked on */
     int base = 0;
     if (lane == 0)
         base = atomicAdd(&p.tile_ctr[b], p.ev_chunk);
@@ -809,15 +815,19 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
                                     and the host can check it (GPSBB_INFO_TILES_RENDERED) */
     double ts_v = 0.0;
     uint32_t nav_v = 0;
-    if (base < ntw) {
-        ts_v = chain_lane ? txb[tx_off + (uint32_t)(base >> sg)] : 0.0;
-        nav_v = lane < p.nch ? tnb[tn_off + (uint32_t)(base >> sg)] : 0u;
-    }
-    while (base < ntw) {
-        const int wt = base + pos;
-        const int r = wt & ((1 << sg) - 1); /* the tile's place in its granule */
-        /* the tile's states -> this wavefront's LDS slot, its data bits -> scalar masks */
-        bool rolled_over = false; /* (the code lane of a channel whose anchor has passed its granule's roll-over) */
+    /* A tile's states go into this wavefront's LDS slot and its data bits into scalar masks in the epilogue of the tile BEFORE it
+     * (and ahead of the loop for a wavefront's first): by then the channel loops have read the slot for the last time and the
+     * prefetched granule state has been on its way for a tile's time, so that the top of a tile waits for no vector memory —
+     * loads and stores share one counter, and a wait for the state up there was also a wait for the previous tile's IQ stores.
+     * Every tile is derived from its granule's state on its own: which tiles a wavefront gets, and in what order, is the claim
+     * protocol's business. */
+    const auto stage_tile = [&](int t, uint32_t &dbits, uint32_t &dnext) {
+        const int r = t & ((1 << sg) - 1); /* the tile's place in its granule */
+        bool rolled_over = false;          /* (the code lane of a channel whose anchor has passed its granule's roll-over) */
+        /* (what depends on the lane alone is worked out from an opaque copy of it here, once per tile, and not kept across the
+         * channel loops: the kernel is short of registers — DESIGN.md 3 — and what it spills goes to HBM) */
+        uint32_t ln = (uint32_t)lane;
+        asm volatile("" : "+v"(ln));
         if (chain_lane) {
             double v = (mirror ? mirror_at - ts_v : ts_v) + guard_w; /* one rounding, half a unit of 2^-32 */
             if (sg) {
@@ -827,41 +837,65 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
                  * chip 1024 on, a whole chip clear of the model's error: the truth has certainly had the granule's roll-over, the data
                  * bit after it is in force, and (at most one roll-over per granule: ev_state_log2) none follows in this tile.  One in
                  * [1023, 1024) stays as it is, and the tile is rendered as one in which the roll-over is due (chip index below
-                 * 1024 + 1040 * 0.0646 < EV_CHIP_LEN_SHORT). */
-                /* the chain's step (code: sc, carrier: |S|), read here: the kernel has no register to keep it in (its address made
-                 * opaque, so that the compiler does not keep that instead) */
-                uint32_t lane_now = (uint32_t)lane;
-                asm volatile("" : "+v"(lane_now));
-                const double st = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(kb) + (lane_now >> 1) * sizeof(EvConst) +
-                                                                    ((lane_now & 1u) ? offsetof(EvConst, S) : offsetof(EvConst, sc)));
-                v = __fma_rn((double)(r * TILE), st, v);
+                 * 1024 + 1040 * 0.0646 < EV_CHIP_LEN_SHORT).
+                 * Tile 0 of a granule IS the granule's state: fma(0, step, v) == v, so it takes neither the step nor the fma; only
+                 * the reduction (a mirrored carrier phase of exactly 512) is left of it, and its code lane never rolls over. */
+                if (r) /* (wave-uniform) */
+                    v = __fma_rn(SG == 1 ? (double)TILE : (double)(r * TILE), L.tstep[ln], v);
                 const uint32_t ip = (uint32_t)__double2hiint(v) - EV_GUARD_HI; /* the integer part */
-                const uint32_t red = (lane & 1) ? (ip & ~511u) : (ip >= (uint32_t)GPSBB_CA_LEN + 1u ? (uint32_t)GPSBB_CA_LEN : 0u);
+                const uint32_t red = (ln & 1u) ? (ip & ~511u) : (ip >= (uint32_t)GPSBB_CA_LEN + 1u ? (uint32_t)GPSBB_CA_LEN : 0u);
                 v -= (double)red;
-                rolled_over = !(lane & 1) && red != 0u;
+                rolled_over = !(ln & 1u) && red != 0u;
             }
-            L.tstate[wave][0][lane] = v;
+            L.tstate[wave][0][ln] = v;
         }
-        uint32_t nav_t = nav_v; /* the tile's data bits as the model sees them */
-        if (sg) {
-            const unsigned long long rolled = __ballot(rolled_over); /* bit 2 i: channel i */
-            if (lane < p.nch && ((rolled >> (2 * lane)) & 1ull))
-                nav_t = ((nav_v >> 1) & 1u) | (nav_v & 2u); /* past the granule's roll-over: the next bit, no further one in the tile */
+        /* the tile's data bits as the model sees them (bit i: channel i), merged in scalar registers: a channel past its granule's
+         * roll-over (r > 0 only: bit 2 i of the ballot is its code lane) has the next bit in force and no further roll-over in
+         * the tile */
+        dbits = (uint32_t)__ballot(nav_v & 1u);
+        dnext = (uint32_t)__ballot(nav_v & 2u);
+        if (sg && r) {
+            uint32_t ro = (uint32_t)__ballot(rolled_over) & 0x55555555u; /* at most 32 chain lanes */
+            ro = (ro | (ro >> 1)) & 0x33333333u;
+            ro = (ro | (ro >> 2)) & 0x0f0f0f0fu;
+            ro = (ro | (ro >> 4)) & 0x00ff00ffu;
+            ro = (ro | (ro >> 8)) & 0x0000ffffu; /* bit i: channel i */
+            dbits = (dbits & ~ro) | (dnext & ro);
         }
+    };
+    uint32_t t_dbits = 0u, t_dnext = 0u; /* of the tile being worked on */
+    /* (the other lanes' ts_v and nav_v stay zero for good: only the loads write them — a move into a register that a load may
+     * still be on its way to would be one more wait for everything in flight, the previous tile's stores included) */
+    const auto fetch_granule = [&](int g) { /* the exact state and the data bits of granule g, on their way */
+        uint32_t ln = (uint32_t)lane;
+        asm volatile("" : "+v"(ln));
+        const uint32_t at = ln * (uint32_t)nst + (uint32_t)g;
+        if (chain_lane)
+            ts_v = txb[at];
+        if (lane < p.nch)
+            nav_v = tnb[at];
+    };
+    if (base < ntw) {
+        fetch_granule(base >> sg);
+        stage_tile(base, t_dbits, t_dnext);
+    }
+    while (base < ntw) {
+        const int wt = base + pos;
+        const int r = wt & ((1 << sg) - 1); /* the tile's place in its granule */
         EvTile T;
         T.ts = L.tstate[wave][0];
         T.tile_x = sg ? txb : txb + wt;
         T.ntiles = ntw;
         T.wt = wt;
         T.sg = sg;
-        T.dbits = (uint32_t)__ballot(nav_t & 1u);
-        T.dnext = (uint32_t)__ballot(nav_t & 2u);
+        T.dbits = t_dbits;
+        T.dnext = t_dnext;
         EvFixed fx;
         fx.ph = FIXED ? p.kph0 + (size_t)b * p.nch : nullptr;
         fx.st = FIXED ? p.kstep + (size_t)b * p.nch : nullptr;
         fx.n0 = (wt - r) * TILE;
         const uint32_t dflip = T.dbits ^ T.dnext;
-        /* which tile comes next, and its states on their way */
+        /* which tile comes next, and its granule's states on their way (taken up after the channel loops: stage_tile) */
         if (pos == 0 && lane == 0) {
             /* the next chunk (see GPSBB_EV_SETTLE_CLAIM) */
             pending = __hip_atomic_fetch_add(p.tile_ctr + b, p.ev_chunk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -873,10 +907,8 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
             next_pos = 0;
         }
         const int wt_next = next_base + next_pos;
-        if (wt_next < ntw && (wt_next >> sg) != (wt >> sg)) { /* (a granule's tiles share its states) */
-            ts_v = chain_lane ? txb[tx_off + (uint32_t)(wt_next >> sg)] : 0.0;
-            nav_v = lane < p.nch ? tnb[tn_off + (uint32_t)(wt_next >> sg)] : 0u;
-        }
+        if (wt_next < ntw && (wt_next >> sg) != (wt >> sg)) /* (a granule's tiles share its states) */
+            fetch_granule(wt_next >> sg);
 
         const int n0 = wt * TILE + lane * SPT;
         const int nvalid = p.nsamp - n0 < SPT ? p.nsamp - n0 : SPT;
@@ -911,6 +943,10 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
             }
         }
         asm volatile("" ::: "memory");
+        /* ---- the next tile's states and data bits (stage_tile), ahead of this tile's stores ---- */
+        uint32_t n_dbits = 0u, n_dnext = 0u;
+        if (wt_next < ntw)
+            stage_tile(wt_next, n_dbits, n_dnext);
 #pragma unroll
         for (int j = 0; j < SPT; j++) {
             if (j)
@@ -988,6 +1024,8 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
         asm volatile("" ::: "memory");
         base = next_base;
         pos = next_pos;
+        t_dbits = n_dbits;
+        t_dnext = n_dnext;
         tiles_rendered++;
     }
     if (lane == 0 && tiles_rendered)
