@@ -76,6 +76,36 @@ int gpsfe_feed_back(gpsfe_t *fe, const gpsbb_chan_state_t *end_state);
  * descriptors, bit for bit, as nblocks calls of gpsfe_next_block. */
 int gpsfe_generate(gpsfe_t *fe, int nblocks, gpsbb_chan_t *ch);
 
+/*
+ * Multipath: up to GPSFE_MAX_ECHOES echoes, each a channel of its own in the reference's arithmetic — the PRN and data
+ * words of its satellite, code phase and bit counters of a longer range, a carrier phase of its own, a scaled gain.
+ *   slots     echo j owns slot max_chan + j; allocation never sees these slots, so slots 0 .. max_chan-1 hold, bit for bit,
+ *             what they hold without echoes.  After the call gpsfe_next_block and gpsfe_generate write gpsfe_block_chans()
+ *             descriptors per block and gpsfe_feed_back reads as many end states; gpsfe_max_chan keeps its meaning.
+ *   lifetime  live exactly while its PRN holds a direct channel: born in the call that allocates that channel, freed in
+ *             the call that frees it; an idle echo's slot has prn = 0, like any free slot.
+ *   path      e(k) = extra_m + rate_mps * (k / 10.0) at the start of block k, counted from the scenario's first block.
+ *   NCOs      computeCodePhase (c:1754-1787) on the direct channel's two ranges with range + e(k) and range + e(k+1) in
+ *             their place: code phase, iword/ibit/icode, f_carr and f_code all come out of that one function; dwrd is
+ *             the direct channel's.
+ *   carrier   at birth (2 r_ref - (r_xyz + e)) / lambda + phase_cyc, reduced as c:1956-1967 reduces it for both carrier
+ *             variants; afterwards the slot chains (or is fed back) like any channel.
+ *   gain      the direct channel's (c:2677-2685) * pow(10.0, -atten_db / 20.0).
+ * GPSFE_E_BADARG: a prn outside 1..32, extra_m negative, not finite or above 30 000 m (0.1 ms), a rate, attenuation or
+ * phase that is not finite, n outside 0..GPSFE_MAX_ECHOES, max_chan + n > GPSBB_MAX_CHAN, a call after the first block.
+ * Two echoes of one PRN are allowed; a later call before the first block replaces the earlier one's echoes.
+ */
+#define GPSFE_MAX_ECHOES 8
+typedef struct gpsfe_echo {
+    int prn;          /* 1..32: the satellite this echo belongs to                                   */
+    double extra_m;   /* extra path at scenario start, metres, >= 0                                  */
+    double rate_mps;  /* d(extra path)/dt, m/s: the echo's Doppler offset is -rate_mps / lambda      */
+    double atten_db;  /* echo gain = direct gain * 10^(-atten_db / 20)                               */
+    double phase_cyc; /* added to the echo's initial carrier phase, cycles (reflection)              */
+} gpsfe_echo_t;
+int gpsfe_set_echoes(gpsfe_t *fe, const gpsfe_echo_t *e, int n);
+int gpsfe_block_chans(const gpsfe_t *fe); /* max_chan + n: descriptors per block from now on */
+
 /* threads gpsfe_generate uses: 0 = the machine's cores up to 16 (default), 1 = none (the reference's one generator thread,
  * c:2286-2289), up to 32 */
 int gpsfe_set_threads(gpsfe_t *fe, int nthreads);

@@ -190,7 +190,7 @@ API_SYMBOLS = [
     "gpsbb_fill_block_noise", "gpsbb_stream_set_noise", "gpsbb_device_noise", "gpsbb_noise_sigma", "gpsbb_noise_table",
     "gpsbb_despread_segments", "gpsbb_batch_despread", "gpsbb_cn0_estimate",
     "gpsbb_interf_make", "gpsbb_interf_eval", "gpsbb_fill_block_impair", "gpsbb_stream_set_interf", "gpsbb_device_impair",
-    "gpsbb_batch_despread_impaired",
+    "gpsbb_batch_despread_impaired", "gpsbb_batch_despread_lags",
     "gpsbb_device_level", "gpsbb_level_clips", "gpsbb_level_choose", "gpsbb_level_rms", "gpsbb_stream_pop_level",
 ]
 # ... and include/gpsbb_node.h
@@ -307,6 +307,8 @@ def lib():
             L.gpsbb_device_impair.argtypes = [vp, vp, vp, C.c_long, i, vp, vp]
             L.gpsbb_batch_despread_impaired.argtypes = [vp, vp, u, vp, vp, i, vp]
             L.gpsbb_node_set_interf.argtypes = [vp, vp]
+        if hasattr(L, "gpsbb_batch_despread_lags"):  # (an older build loaded for an A/B: tools/ab_lib.sh)
+            L.gpsbb_batch_despread_lags.argtypes = [vp, vp, u, vp, vp, i, vp, i, vp]
         if hasattr(L, "gpsbb_device_level"):  # the level calls, as a group (an older build loaded for an A/B: tools/ab_lib.sh)
             L.gpsbb_device_level.argtypes = [vp, vp, C.c_long, i, vp, vp, vp]
             L.gpsbb_level_clips.argtypes = [vp, C.c_long, i, u, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -633,6 +635,18 @@ class Batch:
             return out
         _chk(lib().gpsbb_batch_despread(self._b, None if d_iq is None else C.c_void_p(int(d_iq)), view,
                                         None if nz is None else C.byref(nz), seg_tiles, out.ctypes.data), "gpsbb_batch_despread")
+        return out
+
+    def despread_lags(self, lags, seg_tiles=1, view=OUT_SC16, noise=None, interf=None, d_iq=None):
+        """gpsbb_batch_despread_lags: despread's sums with the view taken `lags[l]` samples later than the replica (within
+        the block: zero outside it) -> int64 [nblocks, nch, nseg, nlags, 2]; the column of a lag 0 is despread's result"""
+        lg = np.ascontiguousarray(lags, np.int32).reshape(-1)
+        nseg = despread_segments(self.nsamp, seg_tiles)
+        out = np.zeros((self.nblocks, self.nch, nseg, lg.size, 2), np.int64)
+        nz = _as_noise(noise)
+        js = _as_interf(interf)
+        _chk(lib().gpsbb_batch_despread_lags(self._b, None if d_iq is None else C.c_void_p(int(d_iq)), view, _ref(nz), _ref(js),
+                                             seg_tiles, lg.ctypes.data, lg.size, out.ctypes.data), "gpsbb_batch_despread_lags")
         return out
 
 
@@ -1226,6 +1240,20 @@ def despread_host(u, replicas, seg_tiles):
     return out
 
 
+def despread_lags_host(u, replicas, seg_tiles, lags):
+    """gpsbb_batch_despread_lags in numpy: despread_host with the view taken lags[l] samples later than the replica, u padded
+    with zeros on either side (a block does not see its neighbours) -> int64 [nblocks, nch, nseg, nlags, 2]"""
+    u = np.asarray(u, np.int64)
+    lg = [int(v) for v in np.asarray(lags).reshape(-1)]
+    if u.ndim != 3 or u.shape[-1] != 2:
+        raise ValueError("u [nblocks, nsamp, 2] wanted, got %r" % (u.shape,))
+    nsamp = u.shape[1]
+    pad = max([abs(v) for v in lg] + [0])
+    up = np.zeros((u.shape[0], nsamp + 2 * pad, 2), np.int64)
+    up[:, pad:pad + nsamp] = u
+    return np.stack([despread_host(up[:, pad + v:pad + v + nsamp], replicas, seg_tiles) for v in lg], axis=3)
+
+
 def block_digest_host(iq):
     """gpsbb_device_digest's number for blocks in host memory: iq int16 [..., nsamp, 2] -> uint64 [...]"""
     a = np.ascontiguousarray(iq, np.int16)
@@ -1420,6 +1448,18 @@ class _FeConfig(C.Structure):
                 ("fixed_carrier", C.c_int)]
 
 
+class Echo(C.Structure):
+    """gpsfe_echo_t: one multipath echo of satellite prn (include/gpsfe.h)"""
+    _fields_ = [("prn", C.c_int), ("extra_m", C.c_double), ("rate_mps", C.c_double), ("atten_db", C.c_double),
+                ("phase_cyc", C.c_double)]
+
+    def __init__(self, prn=0, extra_m=0.0, atten_db=0.0, phase_cyc=0.0, rate_mps=0.0):
+        super().__init__(int(prn), float(extra_m), float(rate_mps), float(atten_db), float(phase_cyc))
+
+
+MAX_ECHOES = 8
+
+
 def build_frontend(force=False):
     hostdir = os.path.join(HERE, "host")
     sim = os.path.join(HERE, "gpsbb-sim")
@@ -1447,6 +1487,8 @@ def fe_lib():
         L.gpsfe_set_threads.argtypes = [C.c_void_p, C.c_int]
         L.gpsfe_time.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double)]
         L.gpsfe_channel_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)] + [C.POINTER(C.c_double)] * 4
+        L.gpsfe_set_echoes.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.gpsfe_block_chans.argtypes = [C.c_void_p]
         _fe_lib = L
     return _fe_lib
 
@@ -1496,15 +1538,29 @@ class FrontEnd:
         if rc != 0:
             raise RuntimeError("gpsfe_set_threads: %d" % rc)
 
+    def set_echoes(self, echoes):
+        """gpsfe_set_echoes, before the first block: Echo objects, dicts of Echo's arguments, or tuples in gpsbb-sim -M's
+        order (prn, extra_m, atten_db[, phase_cyc[, rate_mps]]); every block has block_chans descriptors afterwards"""
+        es = [e if isinstance(e, Echo) else Echo(**e) if isinstance(e, dict) else Echo(*e) for e in echoes]
+        arr = (Echo * max(len(es), 1))(*es)
+        rc = fe_lib().gpsfe_set_echoes(self._fe, arr, len(es))
+        if rc != 0:
+            raise RuntimeError("gpsfe_set_echoes: %s (%d)" % (fe_lib().gpsfe_strerror(rc).decode(), rc))
+
+    @property
+    def block_chans(self):
+        """gpsfe_block_chans: max_chan plus the echoes' slots"""
+        return fe_lib().gpsfe_block_chans(self._fe)
+
     def generate(self, nblocks):
-        ch = np.zeros((nblocks, self.max_chan), CHAN_DTYPE)
+        ch = np.zeros((nblocks, self.block_chans), CHAN_DTYPE)
         rc = fe_lib().gpsfe_generate(self._fe, nblocks, ch.ctypes.data)
         if rc != 0:
             raise RuntimeError("gpsfe_generate: %d" % rc)
         return ch
 
     def next_block(self):
-        ch = np.zeros(self.max_chan, CHAN_DTYPE)
+        ch = np.zeros(self.block_chans, CHAN_DTYPE)
         rc = fe_lib().gpsfe_next_block(self._fe, ch.ctypes.data)
         if rc != 0:
             raise RuntimeError("gpsfe_next_block: %d" % rc)

@@ -30,6 +30,7 @@
 #include "gpsbb_events.hip.h"
 #include "gpsbb_dense.hip.h"
 #include "gpsbb_despread.hip.h"
+#include "gpsbb_despread_lags.hip.h"
 #include "gpsbb_walk.hip.h"
 #include "gpsbb_laps.hip.h"
 #include "gpsbb_nco.h"
@@ -3282,23 +3283,25 @@ static DsKernelFn ds_kernel_interf(int view, bool noise, int g)
     return k[view][noise ? 1 : 0][g];
 }
 
-static int batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, const gpsbb_noise_t *nz, const gpsbb_interf_set_t *set,
-                          int seg_tiles, gpsbb_corr_t *out);
-
-extern "C" int gpsbb_batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, const gpsbb_noise_t *nz, int seg_tiles,
-                                    gpsbb_corr_t *out)
+/* ... at lags (gpsbb_batch_despread_lags) */
+typedef void (*DslKernelFn)(BatchDev, DslArgs);
+static DslKernelFn dsl_kernel(int view, bool noise, int g, bool interf)
 {
-    return batch_despread(b, d_iq, view, nz, nullptr, seg_tiles, out);
+#define GPSBB_DSL_ROW(V, N, J) {k_despread_lags<V, N, 0, J>, k_despread_lags<V, N, 1, J>, k_despread_lags<V, N, 2, J>}
+#define GPSBB_DSL_SET(J)                                                                                               \
+    {{GPSBB_DSL_ROW(DS_SC16, false, J), GPSBB_DSL_ROW(DS_SC16, true, J)},                                               \
+     {GPSBB_DSL_ROW(PACK_SC8, false, J), GPSBB_DSL_ROW(PACK_SC8, true, J)},                                             \
+     {GPSBB_DSL_ROW(PACK_SC1, false, J), GPSBB_DSL_ROW(PACK_SC1, true, J)}}
+    static const DslKernelFn k[2][3][2][EV_STATE_LOG2_MAX + 1] = {GPSBB_DSL_SET(false), GPSBB_DSL_SET(true)};
+#undef GPSBB_DSL_SET
+#undef GPSBB_DSL_ROW
+    return k[interf ? 1 : 0][view][noise ? 1 : 0][g];
 }
 
-extern "C" int gpsbb_batch_despread_impaired(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, const gpsbb_noise_t *nz,
-                                             const gpsbb_interf_set_t *set, int seg_tiles, gpsbb_corr_t *out)
-{
-    return batch_despread(b, d_iq, view, nz, set, seg_tiles, out);
-}
-
+/* the checks, scratch, chunking, launch and copy-back of every despreading call.  lags == nullptr: the prompt sums by k_despread,
+ * out [nblocks][nch][nseg]; otherwise k_despread_lags at lags[0 .. nlags), out [nblocks][nch][nseg][nlags] */
 static int batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, const gpsbb_noise_t *nz, const gpsbb_interf_set_t *set,
-                          int seg_tiles, gpsbb_corr_t *out)
+                          int seg_tiles, const int *lags, int nlags, gpsbb_corr_t *out)
 {
     if (!b)
         return GPSBB_E_BADARG;
@@ -3311,6 +3314,14 @@ static int batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, 
     const int fmt = (view & ~(GPSBB_OUT_FORMAT_MASK | GPSBB_OUT_SHIFT_MASK)) ? -1 : out_format(view, 4, &shift8);
     if (!out || seg_tiles < 1 || fmt < 0 || ((uintptr_t)d_iq & 3))
         return GPSBB_E_BADARG;
+    DslArgs al;
+    memset(&al, 0, sizeof al);
+    for (int l = 0; lags && l < nlags; l++) {
+        al.lags[l] = lags[l];
+        al.halo_lo |= lags[l] < 0;
+        al.halo_hi |= lags[l] > 0;
+    }
+    al.nlags = nlags;
     if (!b->ran)
         return GPSBB_E_STATE;
     /* the two limits of this call: the accumulator's batches, and runs of the per-sample kernel, which leave rows and no
@@ -3327,15 +3338,14 @@ static int batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, 
     if (nz)
         HIPCHK(h, noise_ready(h));
     const long nseg = gpsbb_despread_segments(b->nsamp, seg_tiles);
-    const size_t nsum = (size_t)b->nblocks * b->nch * (size_t)nseg * 2;
+    const size_t nsum = (size_t)b->nblocks * b->nch * (size_t)nseg * (size_t)(lags ? nlags : 1) * 2;
     HIPCHK(h, (hipError_t)b->d_ds.reserve(nsum + 1));
     HIPCHK(h, (hipError_t)b->d_ds_ctr.reserve((size_t)b->nblocks));
     hipStream_t cs = h->s_compute;
     HIPCHK(h, hipMemsetAsync(b->d_ds.p, 0, (nsum + 1) * sizeof(unsigned long long), cs));
     HIPCHK(h, hipMemsetAsync(b->d_ds_ctr.p, 0, (size_t)b->nblocks * sizeof(int32_t), cs));
     const BatchDev p = batch_dev(b, b->sets[b->last_set]);
-    DsArgs a;
-    memset(&a, 0, sizeof a);
+    DsArgs &a = al.d;
     a.iq = reinterpret_cast<const uint32_t *>(src);
     a.out = b->d_ds.p;
     a.n_exact = b->d_ds.p + nsum;
@@ -3364,7 +3374,11 @@ static int batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, 
             HIPCHK(h, hipEventCreate(&e));
     HIPCHK(h, hipEventRecord(b->ds_ev[0], cs));
 #endif
-    hipLaunchKernelGGL(set ? ds_kernel_interf(fmt, nz != nullptr, p.st_log2) : ds_kernel(fmt, nz != nullptr, p.st_log2), dim3((unsigned)(want * b->nblocks)), dim3(DS_WG), 0, cs, p, a);
+    const dim3 grid((unsigned)(want * b->nblocks));
+    if (lags)
+        hipLaunchKernelGGL(dsl_kernel(fmt, nz != nullptr, p.st_log2, set != nullptr), grid, dim3(DS_WG), 0, cs, p, al);
+    else
+        hipLaunchKernelGGL(set ? ds_kernel_interf(fmt, nz != nullptr, p.st_log2) : ds_kernel(fmt, nz != nullptr, p.st_log2), grid, dim3(DS_WG), 0, cs, p, a);
     HIPCHK(h, hipGetLastError());
 #ifdef GPSBB_EXPERIMENTS
     HIPCHK(h, hipEventRecord(b->ds_ev[1], cs));
@@ -3373,6 +3387,29 @@ static int batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, 
     HIPCHK(h, hipMemcpyAsync(&b->ds_last_exact, b->d_ds.p + nsum, sizeof(unsigned long long), hipMemcpyDeviceToHost, cs));
     HIPCHK(h, hipStreamSynchronize(cs));
     return GPSBB_OK;
+}
+
+extern "C" int gpsbb_batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, const gpsbb_noise_t *nz, int seg_tiles,
+                                    gpsbb_corr_t *out)
+{
+    return batch_despread(b, d_iq, view, nz, nullptr, seg_tiles, nullptr, 0, out);
+}
+
+extern "C" int gpsbb_batch_despread_impaired(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, const gpsbb_noise_t *nz,
+                                             const gpsbb_interf_set_t *set, int seg_tiles, gpsbb_corr_t *out)
+{
+    return batch_despread(b, d_iq, view, nz, set, seg_tiles, nullptr, 0, out);
+}
+
+extern "C" int gpsbb_batch_despread_lags(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, const gpsbb_noise_t *nz,
+                                         const gpsbb_interf_set_t *set, int seg_tiles, const int *lags, int nlags, gpsbb_corr_t *out)
+{
+    if (!lags || nlags < 1 || nlags > GPSBB_DESPREAD_MAX_LAGS)
+        return GPSBB_E_BADARG;
+    for (int l = 0; l < nlags; l++)
+        if (lags[l] < -GPSBB_DESPREAD_MAX_LAG || lags[l] > GPSBB_DESPREAD_MAX_LAG)
+            return GPSBB_E_BADARG;
+    return batch_despread(b, d_iq, view, nz, set, seg_tiles, lags, nlags, out);
 }
 
 extern "C" double gpsbb_cn0_estimate(const gpsbb_corr_t *p, long n, long stride, double seg_seconds)

@@ -192,6 +192,36 @@ static int parse_interf(const char *arg, double delt, gpsbb_interf_t *e)
                              duty, delt) == GPSBB_OK;
 }
 
+/* one -M argument, prn,extra_m,atten_db[,phase_cyc[,rate_mps]], into *e; 0 if it is not well formed (gpsfe_set_echoes checks
+ * the numbers) */
+static int parse_echo(const char *arg, gpsfe_echo_t *e)
+{
+    double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    int n = 0;
+    for (;;) {
+        char *end = NULL;
+        if (n == 5)
+            return 0;
+        v[n] = strtod(arg, &end);
+        if (end == arg || !isfinite(v[n]))
+            return 0;
+        n++;
+        if (*end == 0)
+            break;
+        if (*end != ',')
+            return 0;
+        arg = end + 1;
+    }
+    if (n < 3 || v[0] < 1.0 || v[0] > 32.0 || v[0] != (double)(int)v[0] || v[1] < 0.0 || v[1] > 30000.0)
+        return 0;
+    e->prn = (int)v[0];
+    e->extra_m = v[1];
+    e->atten_db = v[2];
+    e->phase_cyc = v[3];
+    e->rate_mps = v[4];
+    return 1;
+}
+
 static void report_clipped(gpsbb_t *bb, int bits, int noise)
 {
     uint64_t clipped = 0;
@@ -204,20 +234,22 @@ static void report_clipped(gpsbb_t *bb, int bits, int noise)
 /* -A: the first K blocks of the scenario rendered as a resident batch on `gpu`, measured with the run's noise and emitters from
  * position 0, and the shifts chosen for clip_ppm.  The front end is opened a second time for it: the run's own starts afresh. */
 static int agc_choose(const gpsfe_config_t *cfg, int gpu, double delt, long nsamp, long nblocks, unsigned oflags, double clip_ppm,
-                      const gpsbb_noise_t *noise, const gpsbb_interf_set_t *interf, int *a_out, int *q_out)
+                      const gpsbb_noise_t *noise, const gpsbb_interf_set_t *interf, const gpsfe_echo_t *echo, int necho, int *a_out,
+                      int *q_out)
 {
+    const int nchan = cfg->max_chan + necho;
     const int K = nblocks < 10 ? (int)(nblocks > 0 ? nblocks : 1) : 10;
     gpsfe_t *fe = NULL;
     gpsbb_t *bb = NULL;
     gpsbb_batch_t *bt = NULL;
-    gpsbb_chan_t *ch = malloc((size_t)K * cfg->max_chan * sizeof *ch);
+    gpsbb_chan_t *ch = malloc((size_t)K * nchan * sizeof *ch);
     gpsbb_level_t *lv = malloc((size_t)K * sizeof *lv);
-    int ok = ch && lv && gpsfe_open(cfg, &fe) == GPSFE_OK;
+    int ok = ch && lv && gpsfe_open(cfg, &fe) == GPSFE_OK && gpsfe_set_echoes(fe, echo, necho) == GPSFE_OK;
     int rc = GPSBB_OK;
     if (ok) {
         gpsfe_generate(fe, K, ch);
         rc = gpsbb_create(&bb, gpu);
-        if (rc == GPSBB_OK) rc = gpsbb_batch_create(bb, ch, K, cfg->max_chan, delt, (int)nsamp, GPSBB_CHAIN_CARRIER, &bt);
+        if (rc == GPSBB_OK) rc = gpsbb_batch_create(bb, ch, K, nchan, delt, (int)nsamp, GPSBB_CHAIN_CARRIER, &bt);
         if (rc == GPSBB_OK) rc = gpsbb_batch_run(bt, NULL);
         if (rc == GPSBB_OK) rc = gpsbb_sync(bb);
         if (rc == GPSBB_OK) rc = gpsbb_device_level(bb, gpsbb_batch_device_iq(bt), K, (int)nsamp, noise, interf, lv);
@@ -258,6 +290,9 @@ static void usage(void)
                     "                 [-P usec_per_block] [-Q device_queue_blocks] [-S stats.json] [-k keep,blocks] [-b 1|8|16] [-q shift]\n"
                     "                 [-W cn0_dbhz[,shift]] [-w seed]\n"
                     "                 [-J cw,js_db,f_hz[,period_s,duty]] [-J chirp,js_db,f0_hz,f1_hz,sweep_s[,period_s,duty]] [-j shift]\n"
+                    "                 [-M prn,extra_m,atten_db[,phase_cyc[,rate_mps]]]   a multipath echo of satellite prn (up to 8 times;\n"
+                    "                                 channels + echoes <= 16): extra path in metres (0..30000), attenuation in dB, reflection\n"
+                    "                                 phase in cycles, path rate in m/s\n"
                     "                 [-A clip_ppm]   choose the -W/-j shift and -q from the level of the first second (up to 10 blocks),\n"
                     "                                 once: a later power change shows in the clip counters, not in the scale;\n"
                     "                                 not together with -q, -j or a shift inside -W cn0,shift\n"
@@ -294,8 +329,10 @@ int main(int argc, char **argv)
     const char *interf_arg[GPSBB_INTERF_MAX + 1];
     int ninterf = 0;
     const char *interf_shift_arg = NULL;
+    const char *echo_arg[GPSFE_MAX_ECHOES + 1];
+    int nechoarg = 0;
 
-    while ((opt = getopt(argc, argv, "e:u:c:l:s:Tt:in:N:d:o:g:3FG:P:S:k:Q:ICRb:q:W:w:J:j:A:")) != -1) {
+    while ((opt = getopt(argc, argv, "e:u:c:l:s:Tt:in:N:d:o:g:3FG:P:S:k:Q:ICRb:q:W:w:J:j:A:M:")) != -1) {
         switch (opt) {
         case 'e': cfg.navfile = optarg; break;
         case 'u': cfg.motion_file = optarg; break;
@@ -357,6 +394,10 @@ int main(int argc, char **argv)
             ninterf++;
             break;
         case 'j': interf_shift_arg = optarg; break;
+        case 'M':
+            echo_arg[nechoarg < GPSFE_MAX_ECHOES ? nechoarg : GPSFE_MAX_ECHOES] = optarg;
+            nechoarg++;
+            break;
         default: usage(); return 1;
         }
     }
@@ -439,10 +480,25 @@ int main(int argc, char **argv)
         fprintf(stderr, "interference: %d emitter%s, shift %d\n", jset.n, jset.n == 1 ? "" : "s", jset.shift);
     }
 
+    /* -M: the echoes, checked here as well */
+    gpsfe_echo_t echo[GPSFE_MAX_ECHOES];
+    memset(echo, 0, sizeof echo);
+    {
+        int ok = nechoarg == 0 || (nechoarg <= GPSFE_MAX_ECHOES && cfg.max_chan >= 1 && cfg.max_chan + nechoarg <= GPSBB_MAX_CHAN);
+        for (int k = 0; ok && k < nechoarg; k++)
+            ok = parse_echo(echo_arg[k], &echo[k]);
+        if (!ok) {
+            fprintf(stderr, "ERROR: -M wants prn,extra_m,atten_db[,phase_cyc[,rate_mps]], at most %d times and channels + echoes <= %d: "
+                            "a prn of 1..32, an extra path of 0..30000 m\n", GPSFE_MAX_ECHOES, GPSBB_MAX_CHAN);
+            return 1;
+        }
+    }
+    const int necho = nechoarg;
+
     if (agc_arg) {
         /* -A: both shifts from the level of the first blocks; from here on the run is the one of the explicit options */
         int a = 0, q = 0;
-        if (!agc_choose(&cfg, nshards > 0 && ndev > 0 ? devs[0] : gpu, delt, nsamp, nblocks, oflags, agc_ppm, noise, interf, &a, &q))
+        if (!agc_choose(&cfg, nshards > 0 && ndev > 0 ? devs[0] : gpu, delt, nsamp, nblocks, oflags, agc_ppm, noise, interf, echo, necho, &a, &q))
             return 1;
         nz.shift = a;
         jset.shift = a;
@@ -457,6 +513,13 @@ int main(int argc, char **argv)
         fprintf(stderr, "ERROR: %s\n", gpsfe_strerror(rc));
         return 1;
     }
+    if (necho > 0 && (rc = gpsfe_set_echoes(fe, echo, necho)) != GPSFE_OK) {
+        fprintf(stderr, "ERROR: -M: %s\n", gpsfe_strerror(rc));
+        return 1;
+    }
+    const int nchan = gpsfe_block_chans(fe); /* the channel count of every call below: the satellites' slots and the echoes' */
+    if (necho > 0)
+        fprintf(stderr, "echoes: %d, %d descriptors per block\n", necho, nchan);
     if (nshards > 0) {
         /* the whole descriptor sequence first (the host range solver runs ahead of everything: 296 bytes per block-channel),
          * then N time shards on N handles into one output */
@@ -473,7 +536,7 @@ int main(int argc, char **argv)
         const int bps = nblocks < 16 ? (int)nblocks : 16;
         contiguous = contiguous || interleaved;
         const long chunk = contiguous ? nblocks : (long)bps * nshards * 2;
-        gpsbb_chan_t *all = malloc((size_t)chunk * cfg.max_chan * sizeof *all);
+        gpsbb_chan_t *all = malloc((size_t)chunk * nchan * sizeof *all);
         FILE *fo = strcmp(out_path, "-") ? fopen(out_path, "wb") : stdout;
         if (!all || !fo) {
             fprintf(stderr, "ERROR: cannot allocate the descriptors / open %s\n", out_path);
@@ -485,7 +548,7 @@ int main(int argc, char **argv)
             o.fd = fileno(fo); /* a regular file: blocks are placed by index as they complete, from every shard at once */
             nflags |= GPSBB_NODE_INDEXED | GPSBB_NODE_CONCURRENT;
         }
-        gpsbb_node_config_t nc = {nshards, devs, cfg.max_chan, delt, (int)nsamp, bps, 3, nflags | oflags};
+        gpsbb_node_config_t nc = {nshards, devs, nchan, delt, (int)nsamp, bps, 3, nflags | oflags};
         gpsbb_node_t *node = NULL;
         gpsbb_node_stats_t ns;
         rc = gpsbb_node_create(&node, &nc);
@@ -539,8 +602,8 @@ int main(int argc, char **argv)
         /* offline generation: slots of up to 16 blocks through the ring, three in flight */
         const int bps = nblocks < 16 ? (int)(nblocks > 0 ? nblocks : 1) : 16, depth = 3;
         gpsbb_stream_t *st = NULL;
-        gpsbb_chan_t *slot = malloc((size_t)bps * cfg.max_chan * sizeof *slot);
-        rc = slot ? gpsbb_stream_create(bb, cfg.max_chan, delt, (int)nsamp, bps, depth, GPSBB_CHAIN_CARRIER | oflags, &st) : GPSBB_E_NOMEM;
+        gpsbb_chan_t *slot = malloc((size_t)bps * nchan * sizeof *slot);
+        rc = slot ? gpsbb_stream_create(bb, nchan, delt, (int)nsamp, bps, depth, GPSBB_CHAIN_CARRIER | oflags, &st) : GPSBB_E_NOMEM;
         if (rc == GPSBB_OK && noise)
             rc = gpsbb_stream_set_noise(st, noise); /* from block 0: every push moves the position on by its blocks */
         if (rc == GPSBB_OK && interf)
@@ -606,7 +669,7 @@ int main(int argc, char **argv)
              * before the consumer's clock starts.  A fill has no side effects besides its outputs ... */
             int16_t *scratch = malloc((size_t)nsamp * 4);
             for (int w = 0; scratch && w < 2; w++)
-                (void)gpsbb_fill_block(bb, ch, cfg.max_chan, delt, (int)nsamp, scratch, NULL);
+                (void)gpsbb_fill_block(bb, ch, nchan, delt, (int)nsamp, scratch, NULL);
             free(scratch);
             /* ... besides the handle's hazard counters: block 0 must count once in the note at the end, not three times */
             gpsbb_hazards_t warm;
@@ -619,12 +682,12 @@ int main(int argc, char **argv)
         clock_gettime(CLOCK_MONOTONIC, &ta);
         if (interf) {
             nz.sample0 = jset.sample0 = (uint64_t)blk * (uint64_t)nsamp;
-            rc = gpsbb_fill_block_impair(bb, ch, cfg.max_chan, delt, (int)nsamp, oflags, noise, &jset, iq, st);
+            rc = gpsbb_fill_block_impair(bb, ch, nchan, delt, (int)nsamp, oflags, noise, &jset, iq, st);
         } else if (noise) {
             nz.sample0 = (uint64_t)blk * (uint64_t)nsamp;
-            rc = gpsbb_fill_block_noise(bb, ch, cfg.max_chan, delt, (int)nsamp, oflags, &nz, iq, st);
+            rc = gpsbb_fill_block_noise(bb, ch, nchan, delt, (int)nsamp, oflags, &nz, iq, st);
         } else {
-            rc = gpsbb_fill_block_ex(bb, ch, cfg.max_chan, delt, (int)nsamp, oflags, iq, st); /* replaces c:2690-2756 */
+            rc = gpsbb_fill_block_ex(bb, ch, nchan, delt, (int)nsamp, oflags, iq, st); /* replaces c:2690-2756 */
         }
         clock_gettime(CLOCK_MONOTONIC, &tb);
         lat_ms[blk] = ts_ms(&tb, &ta);
@@ -665,7 +728,7 @@ int main(int argc, char **argv)
             fprintf(sf, "{\"blocks\": %ld, \"nsamp\": %ld, \"channels\": %d, \"fs_hz\": %ld, \"period_us\": %.1f, \"device_queue_blocks\": %d, "
                         "\"fill_block_ms\": {\"mean\": %.4f, \"p50\": %.4f, \"p90\": %.4f, \"p99\": %.4f, \"p999\": %.4f, \"max\": %.4f}, "
                         "\"underruns\": %ld, \"worst_late_ms\": %.4f, \"delivered\": %ld, \"blocks_over_2ms\": %d, \"first_slow_blocks\": [%s]}\n",
-                    blk, nsamp, cfg.max_chan, fs_hz, (double)paced.period_ns / 1e3, paced.queue, sum / (double)blk, lat_ms[blk / 2],
+                    blk, nsamp, nchan, fs_hz, (double)paced.period_ns / 1e3, paced.queue, sum / (double)blk, lat_ms[blk / 2],
                     lat_ms[(long)((double)blk * 0.9)], lat_ms[(long)((double)blk * 0.99)], lat_ms[(long)((double)blk * 0.999)],
                     lat_ms[blk - 1], paced.underruns, paced.worst_late_ms, paced.seen, nslow, slow);
             fclose(sf);

@@ -83,6 +83,7 @@ typedef struct {  /* the host-side part of channel_t h:152-174 */
     double azel[2];
     range_t rho0;
     double gain;
+    double r_xyz_ini, r_ref_ini; /* the two ranges the initial carrier phase was made of (c:1956-1957): an echo's birth reads them */
 } chan_t;
 
 struct gpsfe {
@@ -104,6 +105,11 @@ struct gpsfe {
     gtime_t *span_grx;     /* gpsfe_generate's scratch of a span (block times, position indices, ranges): kept between calls */
     int *span_ipos;
     range_t *span_rho;
+    /* multipath echoes (gpsfe_set_echoes): echo j owns slot max_chan + j, outside what allocate_channels sees */
+    int necho;
+    long blk;                                /* blocks handed out so far: block k starts with the extra path e(k) */
+    gpsfe_echo_t echo[GPSFE_MAX_ECHOES];
+    double echo_phase[GPSFE_MAX_ECHOES];     /* carr_phase of the echo's slot: set at birth, then fed back like a channel's */
 };
 
 /* receiver antenna attenuation in dB for boresight angle 0:5:180 deg (c:164-169) */
@@ -624,6 +630,23 @@ static int sat_visible(const eph_t *e, gtime_t g, const double *xyz, double mask
     return (azel[1] * K_R2D > mask_deg) ? 1 : 0;
 }
 
+/* the extra path of an echo at the start of block k (one division: every path to it computes the same double) */
+static double echo_extra(const gpsfe_echo_t *e, long k) { return e->extra_m + e->rate_mps * ((double)k / 10.0); }
+
+/* an echo's initial carrier phase, from the ranges its direct channel was born with and the extra path at that time:
+ * c:1956-1967 with r_xyz + e in r_xyz's place and the reflection's phase added */
+static void echo_birth(gpsfe_t *fe, int j, const chan_t *c, long k)
+{
+    const gpsfe_echo_t *e = &fe->echo[j];
+    double phase_ini = (2.0 * c->r_ref_ini - (c->r_xyz_ini + echo_extra(e, k))) / K_LAMBDA + e->phase_cyc;
+    if (!fe->fixed_carrier) {
+        fe->echo_phase[j] = phase_ini - floor(phase_ini);
+    } else {
+        phase_ini -= floor(phase_ini);
+        fe->echo_phase[j] = (double)(unsigned int)(512.0 * 65536.0 * phase_ini);
+    }
+}
+
 /* allocateChannel c:1918-1989 (the elevation mask is hard-wired to 0 there) */
 static int allocate_channels(gpsfe_t *fe, const eph_t *eph, gtime_t grx, const double *xyz)
 {
@@ -651,6 +674,11 @@ static int allocate_channels(gpsfe_t *fe, const eph_t *eph, gtime_t grx, const d
                     const double r_xyz = rho.range;
                     pseudorange(&rho, &eph[sv], &fe->iono, grx, origin);
                     const double r_ref = rho.range;
+                    c->r_xyz_ini = r_xyz;
+                    c->r_ref_ini = r_ref;
+                    for (int j = 0; j < fe->necho; j++) /* born with its direct channel, for the block that starts now */
+                        if (fe->echo[j].prn == c->prn)
+                            echo_birth(fe, j, c, fe->blk + 1);
                     double phase_ini = (2.0 * r_ref - r_xyz) / K_LAMBDA;
                     if (!fe->fixed_carrier) {
                         c->carr_phase = phase_ini - floor(phase_ini);
@@ -1106,6 +1134,7 @@ static void end_of_block(gpsfe_t *fe, const double *xyz)
     fe->grx = gps_add(fe->grx, 0.1); /* c:2800 */
     if (++fe->iumd >= fe->numd)      /* c:2802-2805 */
         fe->iumd = 0;
+    fe->blk++;
 }
 
 static void fill_descriptor(gpsbb_chan_t *d, const chan_t *c, const nco_seed_t *s, double gain)
@@ -1122,11 +1151,50 @@ static void fill_descriptor(gpsbb_chan_t *d, const chan_t *c, const nco_seed_t *
     memcpy(d->dwrd, c->dwrd, sizeof d->dwrd);
 }
 
+/* the descriptor of echo j in block k: a channel of its own whose ranges are the direct channel's (rho0 at the block's
+ * start, rho1 at its end) plus the extra path.  Everything of the NCOs comes out of seed_ncos, as for any channel. */
+static void fill_echo(const gpsfe_t *fe, int j, long k, const chan_t *c, const range_t *rho0, const range_t *rho1, gpsbb_chan_t *d)
+{
+    const gpsfe_echo_t *e = &fe->echo[j];
+    range_t r0 = *rho0, r1 = *rho1;
+    r0.range = rho0->range + echo_extra(e, k);
+    r1.range = rho1->range + echo_extra(e, k + 1);
+    const nco_seed_t s = seed_ncos(&r0, &r1, c->g0, 0.1);
+    fill_descriptor(d, c, &s, channel_gain(fe, rho1) * pow(10.0, -e->atten_db / 20.0));
+    d->carr_phase = fe->echo_phase[j];
+}
+
+int gpsfe_block_chans(const gpsfe_t *fe) { return fe ? fe->max_chan + fe->necho : 0; }
+
+int gpsfe_set_echoes(gpsfe_t *fe, const gpsfe_echo_t *e, int n)
+{
+    if (!fe || n < 0 || n > GPSFE_MAX_ECHOES || (n > 0 && !e) || fe->blk != 0 || fe->max_chan + n > GPSBB_MAX_CHAN)
+        return GPSFE_E_BADARG;
+    for (int j = 0; j < n; j++)
+        if (e[j].prn < 1 || e[j].prn > N_SAT || !isfinite(e[j].extra_m) || e[j].extra_m < 0.0 || e[j].extra_m > 30000.0 ||
+            !isfinite(e[j].rate_mps) || !isfinite(e[j].atten_db) || !isfinite(e[j].phase_cyc))
+            return GPSFE_E_BADARG;
+    fe->necho = n;
+    for (int j = 0; j < n; j++) {
+        fe->echo[j] = e[j];
+        fe->echo_phase[j] = 0.0;
+        fe->emitted_prn[fe->max_chan + j] = 0;
+        const int i = fe->sat_chan[e[j].prn - 1];
+        if (i >= 0) /* its satellite was allocated when the scenario opened: born there, with e(0) */
+            echo_birth(fe, j, &fe->chan[i], 0);
+    }
+    return GPSFE_OK;
+}
+
 int gpsfe_next_block(gpsfe_t *fe, gpsbb_chan_t *ch)
 {
     if (!fe || !ch)
         return GPSFE_E_BADARG;
     const double *xyz = fe->static_mode ? fe->xyz[0] : fe->xyz[fe->iumd];
+    for (int j = 0; j < fe->necho; j++) { /* an echo is live exactly while its PRN holds a direct channel */
+        memset(&ch[fe->max_chan + j], 0, sizeof *ch);
+        fe->emitted_prn[fe->max_chan + j] = fe->sat_chan[fe->echo[j].prn - 1] >= 0 ? fe->echo[j].prn : 0;
+    }
 
     /* refresh code phase, counters, frequencies and gain of every allocated channel (c:2656-2687) */
     for (int i = 0; i < fe->max_chan; i++) {
@@ -1140,6 +1208,9 @@ int gpsfe_next_block(gpsfe_t *fe, gpsbb_chan_t *ch)
         pseudorange(&rho, &fe->eph[fe->ieph][c->prn - 1], &fe->iono, fe->grx, xyz);
         c->azel[0] = rho.azel[0];
         c->azel[1] = rho.azel[1];
+        for (int j = 0; j < fe->necho; j++) /* (before the channel moves on to the block's end) */
+            if (fe->echo[j].prn == c->prn)
+                fill_echo(fe, j, fe->blk, c, &c->rho0, &rho, &ch[fe->max_chan + j]);
         seed_code_phase(c, &rho, 0.1);
         c->gain = channel_gain(fe, &rho);
         const nco_seed_t s = {c->f_carr, c->f_code, c->code_phase, c->iword, c->ibit, c->icode};
@@ -1160,6 +1231,11 @@ int gpsfe_feed_back(gpsfe_t *fe, const gpsbb_chan_state_t *end_state)
     for (int i = 0; i < fe->max_chan; i++)
         if (fe->chan[i].prn > 0 && fe->chan[i].prn == fe->emitted_prn[i] && end_state[i].dataBit != 0)
             fe->chan[i].carr_phase = end_state[i].carr_phase;
+    for (int j = 0; j < fe->necho; j++) { /* an echo's slot by the same rule: still live, and it was in the block */
+        const int i = fe->max_chan + j;
+        if (fe->sat_chan[fe->echo[j].prn - 1] >= 0 && fe->echo[j].prn == fe->emitted_prn[i] && end_state[i].dataBit != 0)
+            fe->echo_phase[j] = end_state[i].carr_phase;
+    }
     return GPSFE_OK;
 }
 
@@ -1281,7 +1357,8 @@ typedef struct {
     const gtime_t *grx;       /* [n] block times */
     const int *ipos;          /* [n] index into fe->xyz */
     range_t *rho;             /* [n][max_chan] */
-    gpsbb_chan_t *ch;         /* [n][max_chan] out */
+    gpsbb_chan_t *ch;         /* [n][max_chan + necho] out */
+    long blk0;                /* the span's first block, counted from the scenario's first */
     nco_seed_t last[GPSBB_MAX_CHAN]; /* what the last block left in chan[] */
     double last_gain[GPSBB_MAX_CHAN];
 } span_job_t;
@@ -1290,7 +1367,7 @@ static void span_work(void *v, int tid, int nthr, pthread_barrier_t *bar)
 {
     span_job_t *j = v;
     const gpsfe_t *fe = j->fe;
-    const int mc = fe->max_chan;
+    const int mc = fe->max_chan, bc = mc + fe->necho;
     const int k0 = (int)((long)j->n * tid / nthr), k1 = (int)((long)j->n * (tid + 1) / nthr);
     for (int k = k0; k < k1; k++)
         for (int i = 0; i < mc; i++) {
@@ -1302,7 +1379,7 @@ static void span_work(void *v, int tid, int nthr, pthread_barrier_t *bar)
     for (int k = k0; k < k1; k++)
         for (int i = 0; i < mc; i++) {
             const chan_t *c = &fe->chan[i];
-            gpsbb_chan_t *d = &j->ch[(size_t)k * mc + i];
+            gpsbb_chan_t *d = &j->ch[(size_t)k * bc + i];
             memset(d, 0, sizeof *d);
             if (c->prn <= 0)
                 continue;
@@ -1315,6 +1392,16 @@ static void span_work(void *v, int tid, int nthr, pthread_barrier_t *bar)
                 j->last[i] = s;
                 j->last_gain[i] = gain;
             }
+        }
+    for (int k = k0; k < k1; k++)
+        for (int e = 0; e < fe->necho; e++) {
+            gpsbb_chan_t *d = &j->ch[(size_t)k * bc + mc + e];
+            memset(d, 0, sizeof *d);
+            const int i = fe->sat_chan[fe->echo[e].prn - 1];
+            if (i < 0)
+                continue;
+            const range_t *r0 = k ? &j->rho[(size_t)(k - 1) * mc + i] : &fe->chan[i].rho0;
+            fill_echo(fe, e, j->blk0 + k, &fe->chan[i], r0, &j->rho[(size_t)k * mc + i], d);
         }
 }
 
@@ -1358,7 +1445,7 @@ int gpsfe_generate(gpsfe_t *fe, int nblocks, gpsbb_chan_t *ch)
     int b = 0;
     while (b < nblocks) {
         if (!parallel) {
-            const int rc = gpsfe_next_block(fe, ch + (size_t)b * fe->max_chan);
+            const int rc = gpsfe_next_block(fe, ch + (size_t)b * (fe->max_chan + fe->necho));
             if (rc != GPSFE_OK)
                 return rc;
             b++;
@@ -1385,7 +1472,8 @@ int gpsfe_generate(gpsfe_t *fe, int nblocks, gpsbb_chan_t *ch)
         job.grx = grx;
         job.ipos = ipos;
         job.rho = rho;
-        job.ch = ch + (size_t)b * fe->max_chan;
+        job.ch = ch + (size_t)b * (fe->max_chan + fe->necho);
+        job.blk0 = fe->blk;
         fe_pool_run(fe->pool, span_work, &job);
         /* the state the sequential loop would be in before the maintenance of the span's last block */
         for (int i = 0; i < fe->max_chan; i++) {
@@ -1405,6 +1493,9 @@ int gpsfe_generate(gpsfe_t *fe, int nblocks, gpsbb_chan_t *ch)
             c->rho0 = *r;
             c->gain = job.last_gain[i];
         }
+        for (int j = 0; j < fe->necho; j++)
+            fe->emitted_prn[fe->max_chan + j] = fe->sat_chan[fe->echo[j].prn - 1] >= 0 ? fe->echo[j].prn : 0;
+        fe->blk += n - 1;
         fe->grx = grx[n - 1];
         fe->iumd = ipos[n - 1];
         end_of_block(fe, fe->xyz[ipos[n - 1]]);
