@@ -347,8 +347,39 @@ def exp_lib():
         L.gpsbb_test_despread_exact.restype = C.c_ulonglong
         L.gpsbb_test_despread_ms.argtypes = [vp]
         L.gpsbb_test_despread_ms.restype = C.c_float
+        if hasattr(L, "gpsbb_test_plan"):  # (an older build loaded for an A/B: tools/ab_lib.sh)
+            L.gpsbb_test_plan.argtypes = [vp, i, i, d, i, u, vp, i, vp, vp, vp, vp, vp]
         _exp_lib = L
     return _exp_lib
+
+
+PLAN_FIELDS = ("nblocks", "nch", "nsamp", "ntiles", "delt", "flags", "ev", "ev_dense", "ev_all_dense", "laps", "host_seed", "st_log2",
+               "nstates", "chain_dev", "chain_starts", "chain_indep", "chain_model", "chain_fix_seq", "nseg", "seg_tiles", "fix_wg",
+               "fix_chunks", "nsets", "total_rows", "carr_lanes", "chain_lanes", "cont0_mask", "lap_chunk0", "h_ch", "h_evc", "row_off",
+               "h_kph0", "h_kstep", "h_cd", "h_start0", "h_seed_order", "h_chain_order", "carry_phase")
+
+
+def plan(ch, delt, nsamp, flags=0, seed_where=0, synth_kernel=0, chain_where=0, skip_seed=0, max_sets=6, carry_prn=None,
+         carry_phase=None, fixed_prev_prn=None, fixed_prev_phase=None):
+    """gpsbb_test_plan (csrc/gpsbb_testhooks.h): what set-up would decide for these descriptors, without a handle or a GPU.  Returns
+    (rc, values): values = PLAN_FIELDS -> the BatchPlan scalar, or the 64-bit FNV-1a of the image (0: the plan defines none; `delt`
+    is hashed too).  carry_prn / carry_phase (float64, advanced in place): the stream lends its carry; fixed_prev_*: the
+    accumulator's chaining state."""
+    ch = _as_chan(ch)
+    nb, nch = ch.shape
+    opt = np.array([seed_where, synth_kernel, skip_seed, chain_where, max_sets], np.int32)
+    out = np.zeros(len(PLAN_FIELDS), np.uint64)
+
+    def ptr(a, dtype):
+        if a is None:
+            return None
+        assert a.dtype == dtype and a.flags.c_contiguous and a.size >= nch
+        return a.ctypes.data
+
+    rc = exp_lib().gpsbb_test_plan(ch.ctypes.data, nb, nch, delt, nsamp, flags, opt.ctypes.data, int(carry_prn is not None),
+                                   ptr(carry_prn, np.int32), ptr(carry_phase, np.float64), ptr(fixed_prev_prn, np.int32),
+                                   ptr(fixed_prev_phase, np.uint32), out.ctypes.data)
+    return rc, ({f: int(v) for f, v in zip(PLAN_FIELDS, out)} if rc == 0 else None)
 
 
 def _chk(rc, what):

@@ -472,7 +472,7 @@ struct WorkPool {
 };
 
 constexpr int SEED_STREAMS_MAX = 8;
-constexpr int CHAIN_SEG_ROWS = 1750;    /* rows of a carrier chain per segment of the device-side chain, about (see batch_setup) */
+constexpr int CHAIN_SEG_ROWS = 1750;    /* rows of a carrier chain per segment of the device-side chain, about (see plan_segments) */
 constexpr int CHAIN_SEG_MIN_TILES = 16; /* ... but no segment shorter than this many tiles */
 constexpr int CHAIN_SEG_MAX = 8;        /* segments per block at most */
 constexpr int CHAIN_INDEP_MIN_TILES = 1024; /* independent blocks of at least this many tiles are cut into segments as well */
@@ -729,6 +729,55 @@ struct TableSet {
  * three streams, where the carrier is chained on the device (two walks and the fix-up per run). */
 constexpr int NSETS = 6;
 
+/* GPSBB_PUSH_TRACE=<ms>: where the host time of a stream push goes, printed for pushes that take longer than <ms> */
+struct PushTrace {
+    double limit_ms = -1.0;
+    int n = 0;
+    const char *what[32];
+    std::chrono::steady_clock::time_point t[32];
+    PushTrace()
+    {
+#ifdef GPSBB_EXPERIMENTS
+        const char *e = getenv("GPSBB_PUSH_TRACE");
+        if (e)
+            limit_ms = atof(e);
+#endif
+    }
+    void start() { n = 0; mark("start"); }
+    void mark(const char *w)
+    {
+        if (limit_ms < 0.0 || n >= 32)
+            return;
+        what[n] = w;
+        t[n++] = std::chrono::steady_clock::now();
+    }
+    void end()
+    {
+        if (limit_ms < 0.0 || n < 2)
+            return;
+        mark("end");
+        const double tot = std::chrono::duration<double, std::milli>(t[n - 1] - t[0]).count();
+        if (tot < limit_ms)
+            return;
+        fprintf(stderr, "[gpsbb push %.3f ms]", tot);
+        for (int i = 1; i < n; i++)
+            fprintf(stderr, " %s %.3f", what[i], std::chrono::duration<double, std::milli>(t[i] - t[i - 1]).count());
+        fprintf(stderr, "\n");
+    }
+};
+static thread_local PushTrace g_push_trace;
+#define PUSH_MARK(w) g_push_trace.mark(w)
+
+/* carry[i] = {prn, phase} of channel i after the previous call (in) / after this one (out); may be NULL */
+struct ChainCarry {
+    int prn[GPSBB_MAX_CHAN];
+    double phase[GPSBB_MAX_CHAN];
+};
+static void chain_carrier_host(const gpsbb_chan_t *ch, int nblocks, int nch, double delt, int nsamp, double *seed,
+                               int nthreads, ChainCarry *carry);
+
+#include "gpsbb_plan.h"
+
 struct gpsbb_batch {
     gpsbb *h = nullptr;
     /* the handle's seeding stream, or (odd slots of a ring) its second one: the pre-passes of two consecutive
@@ -736,92 +785,59 @@ struct gpsbb_batch {
      * 6.6e9 -> 7.3e9 samples/s at depth 3, 8.4e9 at depth 4).  Two, not one per slot: with the compute and
      * copy streams that makes four, and streams beyond the hardware queues share them. */
     hipStream_t seed_stream = nullptr;
-    hipStream_t last_cs = nullptr; /* the synthesis stream of the last launch */
-    bool want_digest = false;      /* this launch also leaves every block's digest in d_dig (GPSBB_PUSH_DIGEST): by the synthesis kernel
-                                      itself where there is a variant that does (k_synth_ev_digest), by k_block_digest behind it otherwise */
-    DevBuf<unsigned long long> d_dig;
     bool one_stream = false;       /* the drop-in call's scratch batch: upload, pre-pass and synthesis on the synthesis stream (a
                                       hop from stream to stream is 16 us of nothing for a call that takes 150: gpsbb_fill_block_ex) */
-    int nblocks = 0, nch = 0, nsamp = 0, ntiles = 0;
-    int st_log2 = 0, nstates = 0;  /* the state granule of the tile tables (BatchDev::st_log2, ev_state_log2) */
-    double delt = 0.0;
-    unsigned flags = 0;
-    uint64_t total_rows = 0;
+    int max_sets = NSETS;
+    BatchPlan plan;  /* written by batch_setup alone, once plan_batch has succeeded */
+    PlanImages img;  /* ... with it */
+    StreamLink link; /* a stream's, for the length of one push */
+
+    /* device buffers */
     DevBuf<gpsbb_chan_t> d_ch;
     DevBuf<uint64_t> d_row_off;
     /* run k uses set k % nsets, so that the seeding pre-pass of run k+1 overlaps the synthesis kernel of run k (different streams) */
     TableSet sets[NSETS];
     DevBuf<int32_t> d_tile_ctr;
-    DevBuf<int32_t> d_seed_order; /* lane -> chain plan of k_seed (see BatchDev) */
-    DevBuf<uint32_t> d_kph0; /* fixed-point carrier variant: start phase and step per (block, channel) */
+    DevBuf<int32_t> d_seed_order;
+    DevBuf<uint32_t> d_kph0;
     DevBuf<int32_t> d_kstep;
-    std::vector<int32_t> h_seed_order;
-    std::vector<uint32_t> h_kph0;
-    std::vector<int32_t> h_kstep;
-    const int *fixed_prev_prn = nullptr;      /* stream chaining of the fixed-point carrier (host side) */
-    const uint32_t *fixed_prev_phase = nullptr;
-    /* breakpoint kernel (ev): exact tile-start states instead of rows + tile index (TableSet), and per-channel constants */
-    bool ev = false;
     DevBuf<EvConst> d_evc;
-    std::vector<EvConst> h_evc;
-    double *hs_tile_x = nullptr;
-    uint32_t *hs_tile_nav = nullptr;
-    size_t hs_tx_cap = 0, hs_tn_cap = 0;
-    /* GPSBB_CHAIN_CARRIER resolved on the device (gpsbb_walk.hip.h: k_chain_prefix / k_chain_fix) */
-    bool ev_dense = false; /* some channel is evaluated per sample: k_synth_ev<true> */
-    bool ev_all_dense = false; /* every active channel is: k_synth_pd */
-    bool chain_dev = false;
-    bool chain_starts = false; /* ... with the per-sample kernel: the chain kernels only fix the blocks' start phases */
-    DevBuf<int32_t> d_chain_order; /* chain_starts: the carrier chains, as k_walk's passes take them */
-    int chain_lanes = 0;
-    DevBuf<ChainDesc> d_cd;      /* what the chain kernels read of the descriptors (24 B per block-channel) */
-    DevBuf<double> d_start0;     /* rough start phases: where pass A walks from */
-    std::vector<ChainDesc> h_cd;
-    std::vector<double> h_start0;
-    int nseg = 1, seg_tiles = 0; /* the device-side chain cuts every block into nseg segments (BatchDev::nseg) */
+    DevBuf<int32_t> d_chain_order;
+    DevBuf<ChainDesc> d_cd;
+    DevBuf<double> d_start0;
     FixScratch fix;              /* k_chain_fix_par: the hand-off between its chunks, one piece per table set */
-    int fix_chunks = 0, fix_wg = FIXP_WG_BATCH;
-    bool chain_indep = false;    /* the chain machinery runs on a batch whose blocks are independent: only the segments of a block are chained */
-    bool chain_model = false;    /* pass B starts from the host's drift model of the carrier (no pass A, no k_chain_prefix) */
-    bool chain_fix_seq = false;  /* k_chain_fix (blocks in order) instead of k_chain_fix_par: GPSBB_OPT_CHAIN_WHERE 2 */
-    bool host_seed = false;      /* the NCO tables of this batch are built on host threads: decided at set-up, like the
-                                    chain (a run never re-reads the handle's options) */
-    int carr_lanes = 0; /* lanes of the seed plan that walk carrier chains (they come first) */
-    /* the lap-parallel pre-pass (gpsbb_laps.hip.h): one lane per lap of every chain; scratch per table set (TableSet::lap) */
-    bool laps = false;
-    uint32_t lap_chunk0[2][GPSBB_MAX_CHAN + 1] = {};
-    /* a stream's slot: the carrier continues from the push before (set by gpsbb_stream_push around set-up / launch) */
-    ChainCarryDev *d_carry = nullptr;
-    const int *carry_prn = nullptr;        /* in: prn per channel in the last block pushed before */
-    double *carry_phase = nullptr;         /* in/out: the host's rough idea of the phase there / after this push */
-    uint32_t cont0_mask = 0;
-    hipEvent_t ev_prefix = nullptr, ev_fix = nullptr; /* the stream's: order k_chain_prefix / k_chain_fix across pushes */
-    int max_sets = NSETS;
+    DevBuf<int16_t> d_iq;
+    DevBuf<unsigned long long> d_dig;
     /* pinned staging arena of the uploads of one set-up: hipMemcpyAsync from pageable memory is not asynchronous
      * (it waits for the stream's earlier work — the previous push's pre-pass — before it returns) */
     char *stage = nullptr;
     size_t stage_cap = 0, stage_used = 0;
-    unsigned stream_turn = 0; /* the stream's push count */
-    hipEvent_t last_done = nullptr;
     hipEvent_t upload_done = nullptr; /* descriptors and plans of the last set-up are on the device */
     hipStream_t upload_stream = nullptr; /* ... the stream that carried them */
-    int nsets = 2;                    /* table sets in use: run k works on set k % nsets */
+
+    /* per-launch state */
+    bool want_digest = false;      /* this launch also leaves every block's digest in d_dig (GPSBB_PUSH_DIGEST): by the synthesis kernel
+                                      itself where there is a variant that does (k_synth_ev_digest), by k_block_digest behind it otherwise */
+    hipStream_t last_cs = nullptr; /* the synthesis stream of the last launch */
+    hipEvent_t last_done = nullptr;
     unsigned run_count = 0;
     int last_set = 0;
-    DevBuf<int16_t> d_iq;
-    /* seeding on the host (small batches): pinned images of the row pool, tile index and end states */
-    SynRow *hs_rows = nullptr;
-    int32_t *hs_tile_row = nullptr;
-    gpsbb_chan_state_t *hs_end = nullptr;
-    size_t hs_rows_cap = 0, hs_tr_cap = 0, hs_end_cap = 0;
-    std::vector<uint64_t> row_off;
-    std::vector<gpsbb_chan_t> h_ch; /* library-owned copy: the caller's array may go away after the call */
     struct Ev4 { hipEvent_t e[4]; }; /* seed start/end (seed stream), synth start/end (compute stream) */
     std::vector<Ev4> evs; /* one set per run since the last timing reset */
     size_t ev_used = 0;
     bool ran = false;
     int16_t *last_iq = nullptr;
     int16_t *last_ext_iq = nullptr; /* the caller's device buffer of the last run, if it used one */
+
+    /* seeding on the host (small batches): pinned images of the row pool, tile index and end states, or (ev) of the tile states */
+    SynRow *hs_rows = nullptr;
+    int32_t *hs_tile_row = nullptr;
+    gpsbb_chan_state_t *hs_end = nullptr;
+    size_t hs_rows_cap = 0, hs_tr_cap = 0, hs_end_cap = 0;
+    double *hs_tile_x = nullptr;
+    uint32_t *hs_tile_nav = nullptr;
+    size_t hs_tx_cap = 0, hs_tn_cap = 0;
+
     /* gpsbb_batch_despread's scratch, kept between calls: the sums (and behind them the count of samples that took the exact
      * path), the tile counters */
     DevBuf<unsigned long long> d_ds;
@@ -1138,16 +1154,6 @@ extern "C" int gpsbb_create(gpsbb_t **out, int device)
     return GPSBB_OK;
 }
 
-/* carry[i] = {prn, phase} of channel i after the previous call (in) / after this one (out); may be NULL */
-struct ChainCarry {
-    int prn[GPSBB_MAX_CHAN];
-    double phase[GPSBB_MAX_CHAN];
-};
-static void chain_carrier_host(const gpsbb_chan_t *ch, int nblocks, int nch, double delt, int nsamp, double *seed,
-                               int nthreads, ChainCarry *carry);
-
-static bool host_seeding_wanted(const gpsbb_batch *b);
-
 /* the instance of k_lap_pass2 (kind NCO_CODE / NCO_CARR) or k_lap_pass2_2 (kind -1: both) for a state granule of 2^g tiles */
 typedef void (*LapKernelFn)(BatchDev, LapDev);
 static LapKernelFn lap_pass2_kernel(int kind, bool wide, int g)
@@ -1169,66 +1175,7 @@ static EvKernelFn ev_kernel(int g, bool digest)
     return k[digest ? 1 : 0][g];
 }
 
-/* The state granule of a batch's tile tables (BatchDev::st_log2): one exact state per 2^g tiles where the breakpoint kernel proper
- * (k_synth_ev, k_synth_ev_digest) renders behind the lap-parallel pre-pass; one per tile for every other kernel and pre-pass.  The
- * tile anchors k_synth_ev derives from a granule's state (gpsbb_events.hip.h) assume at most one code roll-over from a granule's
- * first sample to its last: 1023 chips take at least 15 800 samples at the steps that kernel admits (sc < 1 / 15.5), against 4 096
- * — checked here for every channel all the same. */
-static int ev_state_log2(const gpsbb_batch *b, bool fixed)
-{
-    if (!b->ev || !b->laps || b->ev_dense || fixed)
-        return 0;
-    long g = GPSBB_KNOB_LONG("GPSBB_EV_STATE_LOG2", GPSBB_EV_STATE_LOG2);
-    g = g < 0 ? 0 : (g > EV_STATE_LOG2_MAX ? EV_STATE_LOG2_MAX : g);
-    while (g > 0 && !ev_granule_fits((int)g)) /* (a variant build's smaller budget: make r3budgets) */
-        g--;
-    const size_t nbc = (size_t)b->nblocks * b->nch;
-    for (size_t k = 0; k < nbc && g > 0; k++)
-        if (!(b->h_evc[k].sc * (double)((TILE << g) + SPT) < (double)(GPSBB_CA_LEN - 1)))
-            return 0;
-    return (int)g;
-}
-
 /* upload `bytes` from pageable `src` through the batch's pinned arena (grown at the start of a set-up) */
-/* GPSBB_PUSH_TRACE=<ms>: where the host time of a stream push goes, printed for pushes that take longer than <ms> */
-struct PushTrace {
-    double limit_ms = -1.0;
-    int n = 0;
-    const char *what[32];
-    std::chrono::steady_clock::time_point t[32];
-    PushTrace()
-    {
-#ifdef GPSBB_EXPERIMENTS
-        const char *e = getenv("GPSBB_PUSH_TRACE");
-        if (e)
-            limit_ms = atof(e);
-#endif
-    }
-    void start() { n = 0; mark("start"); }
-    void mark(const char *w)
-    {
-        if (limit_ms < 0.0 || n >= 32)
-            return;
-        what[n] = w;
-        t[n++] = std::chrono::steady_clock::now();
-    }
-    void end()
-    {
-        if (limit_ms < 0.0 || n < 2)
-            return;
-        mark("end");
-        const double tot = std::chrono::duration<double, std::milli>(t[n - 1] - t[0]).count();
-        if (tot < limit_ms)
-            return;
-        fprintf(stderr, "[gpsbb push %.3f ms]", tot);
-        for (int i = 1; i < n; i++)
-            fprintf(stderr, " %s %.3f", what[i], std::chrono::duration<double, std::milli>(t[i] - t[i - 1]).count());
-        fprintf(stderr, "\n");
-    }
-};
-static thread_local PushTrace g_push_trace;
-#define PUSH_MARK(w) g_push_trace.mark(w)
-
 static hipError_t stage_upload(gpsbb_batch *b, void *dst, const void *src, size_t bytes, hipStream_t stream)
 {
     const size_t at = (b->stage_used + 63) & ~(size_t)63;
@@ -1239,421 +1186,120 @@ static hipError_t stage_upload(gpsbb_batch *b, void *dst, const void *src, size_
     return hipMemcpyAsync(dst, b->stage + at, bytes, hipMemcpyHostToDevice, stream);
 }
 
-/* ---- batch planning -------------------------------------------------------------------------------- */
+/* ---- batch set-up: plan, then stage ---------------------------------------------------------------- */
 
-static int batch_setup(gpsbb_batch *b, const gpsbb_chan_t *ch, int nblocks, int nch, double delt,
-                       int nsamp, unsigned flags, hipStream_t upload_stream)
+/* The pinned arena of one set-up's uploads, with room to spare: descriptors, plans, per-channel constants, chain scratch. */
+static int stage_arena(gpsbb_batch *b, size_t nbc)
 {
     gpsbb *h = b->h;
-    if (!ch || nblocks < 1 || nblocks > 65535 || nch < 1 || nch > GPSBB_MAX_CHAN || nsamp < 1 ||
-        !(delt > 0.0) || !std::isfinite(delt) || (flags & ~(GPSBB_CHAIN_CARRIER | GPSBB_FIXED_CARRIER)))
-        return GPSBB_E_BADARG;
-    const size_t nbc = (size_t)nblocks * nch;
-    const bool fixed = (flags & GPSBB_FIXED_CARRIER) != 0;
-    for (size_t k = 0; k < nbc; k++)
-        if (!chan_ok(ch[k], delt, fixed))
-            return GPSBB_E_BADCHAN;
-
-    {
-        /* everything a set-up uploads, with room to spare: descriptors, plans, per-channel constants, chain scratch */
-        const size_t need = nbc * (sizeof(gpsbb_chan_t) + sizeof(EvConst) + 8 + 2 * 4 + 5 * 4 +
-                                   (size_t)CHAIN_SEG_MAX * (sizeof(ChainDesc) + 8 + 8 + 2 * 4)) + 64 * 1024;
-        if (b->upload_done) /* the previous set-up's copies out of the arena are long done; make sure */
-            HIPCHK(h, hipEventSynchronize(b->upload_done));
-        PUSH_MARK("arena");
-        if (need > b->stage_cap) {
-            if (b->stage)
-                (void)hipHostFree(b->stage);
-            b->stage = nullptr;
-            b->stage_cap = 0;
-            HIPCHK(h, hipHostMalloc((void **)&b->stage, need + need / 4, hipHostMallocDefault));
-            b->stage_cap = need + need / 4;
-        }
-        b->stage_used = 0;
+    const size_t need = nbc * (sizeof(gpsbb_chan_t) + sizeof(EvConst) + 8 + 2 * 4 + 5 * 4 +
+                               (size_t)CHAIN_SEG_MAX * (sizeof(ChainDesc) + 8 + 8 + 2 * 4)) + 64 * 1024;
+    if (b->upload_done) /* the previous set-up's copies out of the arena are long done; make sure */
+        HIPCHK(h, hipEventSynchronize(b->upload_done));
+    PUSH_MARK("arena");
+    if (need > b->stage_cap) {
+        if (b->stage)
+            (void)hipHostFree(b->stage);
+        b->stage = nullptr;
+        b->stage_cap = 0;
+        HIPCHK(h, hipHostMalloc((void **)&b->stage, need + need / 4, hipHostMallocDefault));
+        b->stage_cap = need + need / 4;
     }
-    b->nblocks = nblocks;
-    b->nch = nch;
-    b->nsamp = nsamp;
-    b->delt = delt;
-    b->flags = flags;
-    b->ntiles = (nsamp + TILE - 1) / TILE;
-    if (2ull * nbc * ((unsigned long long)b->ntiles + 1) >= (1ull << 32))
-        return GPSBB_E_NOMEM; /* the tile index is addressed with 32-bit element offsets (16 GiB of it) */
+    b->stage_used = 0;
+    return GPSBB_OK;
+}
 
-    /* Which synthesis kernel: the breakpoint kernel (gpsbb_events.hip.h) where every run of SPT samples holds
-     * at most one chip change and at most EV_KC_MAX table-index changes and the I sums stay below 2^15. */
-    b->ev = h->opt_synth_kernel != 1 && ev_plan(ch, nblocks, nch, delt, b->h_evc, fixed);
-    b->ev_dense = false;
-    b->ev_all_dense = b->ev;
-    if (b->ev)
-        for (size_t k = 0; k < nbc; k++) {
-            b->ev_dense = b->ev_dense || b->h_evc[k].kc == EV_KC_DENSE;
-            b->ev_all_dense = b->ev_all_dense && (ch[k].prn <= 0 || b->h_evc[k].kc == EV_KC_DENSE);
-        }
-    b->ev_all_dense = b->ev_all_dense && b->ev_dense;
-    if (fixed && b->ev_dense && !b->ev_all_dense) {
-        /* The fixed-point carrier has no mixed kernel: k_synth_ev_dense is the IEEE body (a falling phase mirrored as 512 - y,
-         * biased change positions), not the accumulator's (512 - 2^-16 - y, exact).  A batch whose channels straddle the
-         * one-chip-change-per-run limit (fs within ~50 Hz of 15.5 * 1.023e6 once the code Doppler is in) goes to the stepped
-         * kernel. */
-        b->ev = false;
-        b->ev_dense = b->ev_all_dense = false;
-    }
-    PUSH_MARK("ev_plan");
-
-    /* where the pre-pass runs and where the carrier chain is resolved: decided here, once, for all runs of the batch */
-    /* on the device: lap-parallel (gpsbb_laps.hip.h) wherever the model kernels render and no step is tiny; the row walks
-     * (k_walk and the chain kernels) for the rest and where GPSBB_OPT_SEED_WHERE / _CHAIN_WHERE ask for them.  The lap-parallel
-     * pre-pass takes 0.1 ms whatever the size of the batch — less than host threads need for one block (tools/fill_latency.py:
-     * 0.25 against 0.33 ms per gpsbb_fill_block of the reference's geometry) — so where it is eligible the size decides nothing. */
-    const bool lap_ok = b->ev && h->opt_seed_where != 1 && h->opt_seed_where != 2 && h->opt_chain_where != 2 && h->opt_chain_where != 3 &&
-                        !GPSBB_KNOB_SET("GPSBB_NO_LAPS") && lap_eligible(ch, nbc, delt, fixed);
-    /* (a stream's push that was promised the device-side chain — b->d_carry: decided in gpsbb_stream_push on what it can see of
-     * the descriptors, before the kernel plan exists — stays on the device whatever the size: the row walks where the laps
-     * decline, e.g. a rate only the per-sample kernel renders) */
-    b->host_seed = !lap_ok && !b->d_carry && host_seeding_wanted(b);
-    b->laps = lap_ok;
-    b->st_log2 = ev_state_log2(b, fixed);
-    b->nstates = (b->ntiles + (1 << b->st_log2) - 1) >> b->st_log2;
-    const bool chained = !fixed && (flags & GPSBB_CHAIN_CARRIER) && (nblocks > 1 || b->d_carry);
-    b->chain_dev = chained && h->opt_chain_where != 1 && !b->host_seed;
-    b->chain_fix_seq = h->opt_chain_where == 2;
-    b->chain_starts = b->chain_dev && !b->ev;
-    b->chain_model = false; /* decided below, once the number of segments is known */
-    b->chain_indep = false;
-    /* The device-side chain cuts blocks into SEGMENTS that are chained like blocks: a walk takes as long as its chain
-     * whatever the batch (0.47 us per row; a 5 kHz carrier has 7 000 rows per 0.1 s of signal, at any sample rate), so
-     * segments of about CHAIN_SEG_ROWS rows make the two walks of a pre-pass that many times shorter.  (Tried for batches
-     * of independent blocks as well, every block's first segment starting a chain: the five dependent kernels of the
-     * chain cost more than the shorter walks save — M1 geometry 1.77e11 -> 1.45e11 samples/s — so those keep k_walk<0>.) */
-    b->nseg = 1;
-    /* Batches of INDEPENDENT blocks go through the same machinery where the model of the carrier serves (no pass A): every
-     * block's first segment starts a chain from its descriptor's phase, the walks are as many times shorter, and the three
-     * kernels that follow cost less than a walk of whole blocks — for long blocks (25 MS/s, 2.5 M samples: 4.08e11 ->
-     * 4.26e11 samples/s on a resident batch); for the reference's 300 000-sample blocks the fix-up over four thousand short
-     * segments costs more than the walks save (1.72e11 -> 1.61e11): those keep k_walk<0>. */
-    const bool indep_ok = !chained && !b->d_carry && b->ev && !fixed && !b->host_seed && h->opt_chain_where == 0 &&
-                          b->ntiles >= (int)GPSBB_KNOB_LONG("GPSBB_INDEP_MIN_TILES", CHAIN_INDEP_MIN_TILES);
-    if (!b->laps && ((b->chain_dev && !b->chain_starts) || indep_ok)) { /* (k_seed, the per-sample kernel's pre-pass, walks whole blocks) */
-        double rows_max = 0.0;
-        for (size_t k = 0; k < nbc; k++)
-            if (ch[k].prn > 0) {
-                const double sa = std::fabs(ch[k].f_carr * delt);
-                const double r = sa > 0.0 ? ((double)nsamp * sa + 1.0) * (2.0 - std::log2(sa)) : 1.0;
-                rows_max = r > rows_max ? r : rows_max;
-            }
-        int n = (int)(rows_max / (double)GPSBB_KNOB_LONG("GPSBB_SEG_ROWS", CHAIN_SEG_ROWS) + 0.5);
-        const int n_cap = b->ntiles / CHAIN_SEG_MIN_TILES;
-        n = n > CHAIN_SEG_MAX ? CHAIN_SEG_MAX : n;
-        n = n > n_cap ? n_cap : n;
-        n = n < 1 ? 1 : n;
-        if (b->chain_dev) {
-            b->nseg = n;
-        } else if (n > 1 && (long)nblocks * n <= CHAIN_MODEL_MAX_SEGS) {
-            b->chain_dev = true;
-            b->chain_indep = true;
-            b->nseg = n;
-        }
-    }
-    b->seg_tiles = (b->ntiles + b->nseg - 1) / b->nseg;
-    b->nseg = (b->ntiles + b->seg_tiles - 1) / b->seg_tiles; /* no empty last segment */
-    /* Pass B's start phases from the host's drift model of the carrier (CarrDrift) instead of a first walk — where the
-     * model's error cannot pile up: it is ~6e-15 cycles per segment (partly systematic), and a start phase further than
-     * pass B's margin from the truth costs a walk of the segment (about one segment-channel in 10^5 per 1e-12 of error).  So:
-     * batches of up to CHAIN_MODEL_MAX_SEGS segments.  Not the pushes of a stream — the belief can only be re-anchored on
-     * end states that are a ring's depth of pushes old (measured: 3.3 segment walks per 400-block push, stream 4.48e11 ->
-     * 4.26e11 samples/s), and not chains over tens of thousands of blocks (gpsbb_chain_carrier): those keep pass A. */
-    b->chain_model = !b->laps && b->chain_dev && !b->chain_starts && !b->d_carry && h->opt_chain_where != 3 &&
-                     (long)nblocks * b->nseg <= CHAIN_MODEL_MAX_SEGS;
-    const size_t nvbc = nbc * (size_t)b->nseg; /* carrier chains: one per (segment, channel) */
-
-    /* row pool plan: the code chains (block*nch + channel), then the carrier chains ((block*nseg + segment)*nch + channel) */
-    b->row_off.assign(nbc + nvbc + 1, 0);
-    uint64_t off = 0;
-    for (size_t k = 0; k < nbc && !b->laps; k++) { /* (the lap-parallel pre-pass keeps no rows) */
-        b->row_off[k] = off;
-        if (ch[k].prn > 0) {
-            off += row_bound(ch[k].f_code * delt, 1023.0, 9, nsamp) + 1;
-            if (b->ev)
-                off += (uint64_t)nsamp / (uint64_t)WALK_ROW_MAX + 1; /* k_walk cuts long rows */
-        } else {
-            off += 1;
-        }
-    }
-    if (!b->laps) {
-        /* a segment's bound depends on the block-channel's step and the segment's length only: one evaluation per
-         * block-channel for the full segments, one for the (shorter) last */
-        const int full = b->seg_tiles * TILE, last = nsamp - (b->nseg - 1) * full;
-        const int ns_full = b->nseg == 1 ? nsamp : full, ns_last = b->nseg == 1 ? nsamp : last;
-        for (int blk = 0; blk < nblocks; blk++)
-            for (int sgi = 0; sgi < b->nseg; sgi++) {
-                uint64_t *ro = &b->row_off[nbc + ((size_t)blk * b->nseg + sgi) * nch];
-                const int ns = sgi == b->nseg - 1 ? ns_last : ns_full;
-                for (int i = 0; i < nch; i++) {
-                    const gpsbb_chan_t &c = ch[(size_t)blk * nch + i];
-                    ro[i] = 0; /* count first, offsets below */
-                    if (c.prn > 0 && !fixed) {
-                        if (sgi == 0 || sgi == b->nseg - 1)
-                            ro[i] = row_bound(std::fabs(c.f_carr * delt), 1.0, -1, ns) + 1 + (b->ev ? (uint64_t)ns / (uint64_t)WALK_ROW_MAX + 1 : 0);
-                        else
-                            ro[i] = b->row_off[nbc + ((size_t)blk * b->nseg) * nch + i]; /* as the block's first segment */
-                    } else {
-                        ro[i] = 1;
-                    }
-                }
-            }
-        /* (the first segments' entries are read above while later ones are filled: turn counts into offsets afterwards) */
-        for (size_t kv = 0; kv < nvbc; kv++) {
-            const uint64_t cnt = b->row_off[nbc + kv];
-            b->row_off[nbc + kv] = off;
-            off += cnt;
-        }
-    }
-    b->row_off[nbc + nvbc] = off;
-    b->total_rows = off;
-
-    /* device scratch of both table sets, sized here so that a launch never allocates (growing frees, and
-     * a free synchronises the device) */
+/* Device scratch of every table set in use, sized here so that a launch never allocates (growing frees, and a free
+ * synchronises the device), and the uploads of the plan's images on upload_stream. */
+static int stage_plan(gpsbb_batch *b, hipStream_t upload_stream)
+{
+    gpsbb *h = b->h;
+    const BatchPlan &pl = b->plan;
+    const PlanImages &img = b->img;
+    const size_t nbc = (size_t)pl.nblocks * pl.nch, nvbc = nbc * (size_t)pl.nseg;
+    const bool room = b->max_sets == 1; /* a ring slot, whose pushes see different Dopplers (DevBuf::reserve) */
     HIPCHK(h, (hipError_t)b->d_ch.reserve(nbc));
     HIPCHK(h, (hipError_t)b->d_row_off.reserve(nbc + nvbc + 1));
-    HIPCHK(h, (hipError_t)b->d_tile_ctr.reserve((size_t)NSETS * ((size_t)nblocks + 1))); /* one set of counters per table set: a block's next tile, [nblocks] the helpers' tickets (ev_pick_block) */
-    /* table sets = pre-passes in flight + 1: the pre-pass of either kernel takes longer than the synthesis it feeds
-     * (M1 geometry, per-sample kernel: two sets 6.6e10, three 7.7e10 samples/s), the chained ones longer still */
-    b->nsets = (int)GPSBB_KNOB_LONG("GPSBB_NSETS", b->chain_dev ? 4 : 3);
-    b->nsets = b->nsets < 2 ? 2 : (b->nsets > NSETS ? NSETS : b->nsets);
-    b->nsets = b->nsets > b->max_sets ? b->max_sets : b->nsets;
-    for (int set = 0; set < b->nsets; set++) {
+    HIPCHK(h, (hipError_t)b->d_tile_ctr.reserve((size_t)NSETS * ((size_t)pl.nblocks + 1))); /* one set of counters per table set: a block's next tile, [nblocks] the helpers' tickets (ev_pick_block) */
+    for (int set = 0; set < pl.nsets; set++) {
         TableSet &ts = b->sets[set];
         HIPCHK(h, (hipError_t)ts.end.reserve(nbc));
-        if (b->ev) {
-            HIPCHK(h, (hipError_t)ts.tile_x.reserve(2 * nbc * (size_t)b->nstates));
-            HIPCHK(h, (hipError_t)ts.tile_nav.reserve(nbc * (size_t)b->nstates));
-            HIPCHK(h, (hipError_t)ts.rows.reserve(b->total_rows + 4, b->max_sets == 1 ? (size_t)(b->total_rows / 2) : 0));
+        if (pl.ev) {
+            HIPCHK(h, (hipError_t)ts.tile_x.reserve(2 * nbc * (size_t)pl.nstates));
+            HIPCHK(h, (hipError_t)ts.tile_nav.reserve(nbc * (size_t)pl.nstates));
+            HIPCHK(h, (hipError_t)ts.rows.reserve(pl.total_rows + 4, room ? (size_t)(pl.total_rows / 2) : 0));
             HIPCHK(h, (hipError_t)ts.row_cnt.reserve(nbc + nvbc));
         } else {
-            HIPCHK(h, (hipError_t)ts.rows.reserve(b->total_rows + 4)); /* + slack: k_synth prefetches one row past a chain */
-            HIPCHK(h, (hipError_t)ts.tile_row.reserve(2 * nbc * ((size_t)b->ntiles + 1)));
+            HIPCHK(h, (hipError_t)ts.rows.reserve(pl.total_rows + 4)); /* + slack: k_synth prefetches one row past a chain */
+            HIPCHK(h, (hipError_t)ts.tile_row.reserve(2 * nbc * ((size_t)pl.ntiles + 1)));
             HIPCHK(h, (hipError_t)ts.row_cnt.reserve(2 * nbc));
         }
     }
-    if (b->ev) {
+    if (pl.ev) {
         HIPCHK(h, (hipError_t)b->d_evc.reserve(nbc));
-        HIPCHK(h, stage_upload(b, b->d_evc.p, b->h_evc.data(), nbc * sizeof(EvConst), upload_stream));
+        HIPCHK(h, stage_upload(b, b->d_evc.p, img.h_evc.data(), nbc * sizeof(EvConst), upload_stream));
     }
-    if (fixed) {
-        /* start phase and step of the 32-bit accumulator per (block, channel); the chain across blocks is
-         * plain modular arithmetic, resolved here (c:2675, 2748) */
-        b->h_kph0.assign(nbc, 0u);
-        b->h_kstep.assign(nbc, 0);
-        for (int i = 0; i < nch; i++) {
-            int prev_prn = b->fixed_prev_prn ? b->fixed_prev_prn[i] : 0;
-            uint32_t prev_ph = b->fixed_prev_phase ? b->fixed_prev_phase[i] : 0u;
-            for (int blk = 0; blk < nblocks; blk++) {
-                const gpsbb_chan_t &c = ch[(size_t)blk * nch + i];
-                const size_t k = (size_t)blk * nch + i;
-                if (c.prn <= 0) {
-                    prev_prn = 0;
-                    continue;
-                }
-                const volatile double scaled = 512.0 * 65536.0 * c.f_carr * delt;
-                b->h_kstep[k] = (int)std::round(scaled);
-                const bool cont = (flags & GPSBB_CHAIN_CARRIER) && c.prn == prev_prn;
-                b->h_kph0[k] = cont ? prev_ph : (uint32_t)c.carr_phase;
-                prev_ph = b->h_kph0[k] + (uint32_t)nsamp * (uint32_t)b->h_kstep[k];
-                prev_prn = c.prn;
-            }
-        }
+    if (pl.flags & GPSBB_FIXED_CARRIER) {
         HIPCHK(h, (hipError_t)b->d_kph0.reserve(nbc));
         HIPCHK(h, (hipError_t)b->d_kstep.reserve(nbc));
-        HIPCHK(h, stage_upload(b, b->d_kph0.p, b->h_kph0.data(), nbc * 4, upload_stream));
-        HIPCHK(h, stage_upload(b, b->d_kstep.p, b->h_kstep.data(), nbc * 4, upload_stream));
+        HIPCHK(h, stage_upload(b, b->d_kph0.p, img.h_kph0.data(), nbc * 4, upload_stream));
+        HIPCHK(h, stage_upload(b, b->d_kstep.p, img.h_kstep.data(), nbc * 4, upload_stream));
     }
-    b->h_ch.assign(ch, ch + nbc);
-    b->cont0_mask = 0;
-    if (b->laps) {
-        /* the lap-parallel pre-pass: room for the laps of every channel, scratch per table set; a stream's push: which
-         * channels of its first block go on from the push before (the exact phase is on the device) */
-        lap_bound(ch, nblocks, nch, delt, nsamp, fixed, b->lap_chunk0);
-        const size_t chunks = (size_t)b->lap_chunk0[1][nch];
-        for (int set = 0; set < b->nsets; set++)
-            HIPCHK(h, (hipError_t)b->sets[set].lap.reserve(nbc, (size_t)nch, (size_t)nblocks, chunks, b->max_sets == 1));
-        if (b->chain_dev && b->d_carry && b->carry_prn)
-            for (int i = 0; i < nch; i++)
-                if (ch[i].prn > 0 && ch[i].prn == b->carry_prn[i])
-                    b->cont0_mask |= 1u << i;
-    }
-    if (b->chain_dev && !b->laps) {
-        /* The carrier chain is resolved exactly on the device, in parallel over the blocks (k_walk pass A,
-         * k_chain_prefix, k_walk pass B, k_chain_fix).  All the host contributes is a rough start phase per block:
-         * the descriptor's phase carried forward by nsamp*step in plain double arithmetic (good to ~1e-7 cycles
-         * after a few hundred blocks; pass A takes it from there). */
-        b->h_cd.resize(nvbc);
-        b->h_start0.resize(nvbc);
-        for (int i = 0; i < nch; i++) {
-            double x = b->d_carry && b->carry_phase ? b->carry_phase[i] : 0.0;
-            int prev_prn = b->d_carry && b->carry_prn ? b->carry_prn[i] : 0;
-            for (int blk = 0; blk < nblocks; blk++) {
-                const gpsbb_chan_t &c = ch[(size_t)blk * nch + i];
-                const volatile double sk = c.f_carr * delt;
-                const CarrDrift drift(b->chain_model && c.prn > 0 ? (double)sk : 0.0);
-                if (c.prn > 0) {
-                    if (c.prn != prev_prn || b->chain_indep)
-                        x = c.carr_phase;
-                    else if (blk == 0)
-                        b->cont0_mask |= 1u << i;
-                }
-                for (int sgi = 0; sgi < b->nseg; sgi++) {
-                    const size_t kv = ((size_t)blk * b->nseg + sgi) * nch + i;
-                    ChainDesc &cd = b->h_cd[kv];
-                    cd.f_carr = c.f_carr;
-                    cd.carr_phase = c.carr_phase; /* read for a block's first segment only (one that starts a chain) */
-                    cd.prn = c.prn;
-                    cd.start = (b->chain_indep && sgi == 0) ? 1 : 0;
-                    b->h_start0[kv] = c.prn > 0 ? x : 0.0;
-                    if (c.prn > 0) {
-                        const int left = nsamp - sgi * b->seg_tiles * TILE, full = b->seg_tiles * TILE;
-                        const int ns = b->nseg == 1 ? nsamp : (left < full ? left : full);
-                        if (b->chain_model && x < 1.0) {
-                            x = drift.advance(x, ns, sk);
-                        } else {
-                            x = x + (double)ns * sk;
-                            x -= std::floor(x);
-                        }
-                    }
-                }
-                prev_prn = c.prn > 0 ? c.prn : 0;
-            }
-            if (b->d_carry && b->carry_phase)
-                b->carry_phase[i] = x;
-        }
+    if (pl.laps) /* the lap-parallel pre-pass: scratch per table set */
+        for (int set = 0; set < pl.nsets; set++)
+            HIPCHK(h, (hipError_t)b->sets[set].lap.reserve(nbc, (size_t)pl.nch, (size_t)pl.nblocks, (size_t)pl.lap_chunk0[1][pl.nch], room));
+    if (pl.chain_dev && !pl.laps) {
         /* the chain's scratch (ChainAux) needs no initial image: every field is written by the pass that owns it */
-        for (int set = 0; set < b->nsets; set++) {
+        for (int set = 0; set < pl.nsets; set++) {
             HIPCHK(h, (hipError_t)b->sets[set].aux.reserve(nvbc));
-            if (!b->chain_starts)
+            if (!pl.chain_starts)
                 HIPCHK(h, (hipError_t)b->sets[set].prefix.reserve(nvbc * (size_t)CHAIN_PREFIX_CAP));
         }
         HIPCHK(h, (hipError_t)b->d_cd.reserve(nvbc));
         HIPCHK(h, (hipError_t)b->d_start0.reserve(nvbc));
-        /* long chains (thousands of segments per channel): fewer, larger chunks — fewer hand-offs */
-        b->fix_wg = nblocks * b->nseg >= 2048 ? FIXP_WG_ALONE : FIXP_WG_BATCH;
-        b->fix_chunks = (nblocks * b->nseg + b->fix_wg - 1) / b->fix_wg;
         /* one set of flags per table set: runs of a resident batch overlap, each on its own table set */
-        HIPCHK(h, b->fix.reserve((size_t)NSETS * GPSBB_MAX_CHAN * b->fix_chunks, upload_stream));
-        HIPCHK(h, stage_upload(b, b->d_cd.p, b->h_cd.data(), nvbc * sizeof(ChainDesc), upload_stream));
-        HIPCHK(h, stage_upload(b, b->d_start0.p, b->h_start0.data(), nvbc * sizeof(double), upload_stream));
-    }
-    if ((flags & GPSBB_CHAIN_CARRIER) && !fixed && nblocks > 1 && !b->chain_dev) {
-        /* blocks consecutive in time: resolve the carrier phase at the start of every block here, exactly
-         * (same jump-ahead as the device, one host thread per channel), so that the device's chains are all
-         * independent.  Walking the blocks in order on the device would serialise the whole pre-pass. */
-        std::vector<double> seeds(nbc);
-        chain_carrier_host(ch, nblocks, nch, delt, nsamp, seeds.data(), 0, nullptr);
-        for (size_t k = 0; k < nbc; k++)
-            if (b->h_ch[k].prn > 0)
-                b->h_ch[k].carr_phase = seeds[k];
+        HIPCHK(h, b->fix.reserve((size_t)NSETS * GPSBB_MAX_CHAN * pl.fix_chunks, upload_stream));
+        HIPCHK(h, stage_upload(b, b->d_cd.p, img.h_cd.data(), nvbc * sizeof(ChainDesc), upload_stream));
+        HIPCHK(h, stage_upload(b, b->d_start0.p, img.h_start0.data(), nvbc * sizeof(double), upload_stream));
     }
     PUSH_MARK("aux");
-    HIPCHK(h, stage_upload(b, b->d_ch.p, b->h_ch.data(), nbc * sizeof(gpsbb_chan_t), upload_stream));
+    HIPCHK(h, stage_upload(b, b->d_ch.p, img.h_ch.data(), nbc * sizeof(gpsbb_chan_t), upload_stream));
     PUSH_MARK("up_ch");
-    if (!b->laps)
-        HIPCHK(h, stage_upload(b, b->d_row_off.p, b->row_off.data(), (nbc + nvbc + 1) * 8, upload_stream));
-    if (b->laps) {
-        b->h_seed_order.clear();
-        b->carr_lanes = 0;
-    } else {
-        /* which chain each lane of k_seed walks (BatchDev::seed_order).  k_seed takes as long as its slowest
-         * wavefront: rows of its longest chain x the time of one turn of the loop, which grows with the
-         * number of lanes that are out of step.  Measured (400 x 16 chains, |f_carr| uniform up to 5 kHz):
-         * 6.3 ms in block order, 6.1 ms with the carrier chains by descending |f_carr|, 5.3 ms with the
-         * longest of them in wavefronts of few lanes.  (16 chains per wavefront throughout does not help
-         * small batches: 16-block ring slots 6.0e9 vs 6.6e9 samples/s.) */
-        /* carrier chains: one per (segment, channel), kv = (block*nseg + segment)*nch + channel (nseg = 1: per block) */
-        const size_t nvbc = nbc * (size_t)b->nseg;
-        const int nseg = b->nseg;
-        std::vector<int32_t> carr(nvbc);
-        const gpsbb_chan_t *hc = b->h_ch.data();
-        const bool by_sign = b->ev; /* k_walk runs the two directions in separate loops: keep them in separate wavefronts */
-        {
-            /* By direction (rising first), then by descending |f_carr| — a wavefront runs as long as its longest chain —
-             * in CARR_BUCKETS classes of |f_carr| (a counting sort: the plan of a 400-block push with four segments per
-             * block orders 25 600 chains, and a comparison sort of them cost more than everything else in the push). */
-            constexpr int CARR_BUCKETS = 512;
-            double fmax = 0.0;
-            for (size_t k = 0; k < nbc; k++)
-                if (hc[k].prn > 0 && std::fabs(hc[k].f_carr) > fmax)
-                    fmax = std::fabs(hc[k].f_carr);
-            const double scale = fmax > 0.0 ? (CARR_BUCKETS - 1) / fmax : 0.0;
-            std::vector<uint16_t> key(nbc);
-            std::vector<uint32_t> head(2 * CARR_BUCKETS + 2, 0u);
-            for (size_t k = 0; k < nbc; k++) {
-                unsigned kk;
-                if (hc[k].prn <= 0) {
-                    kk = 2 * CARR_BUCKETS; /* idle channels last */
-                } else {
-                    const unsigned q = (unsigned)(CARR_BUCKETS - 1) - (unsigned)(std::fabs(hc[k].f_carr) * scale);
-                    kk = (by_sign && std::signbit(hc[k].f_carr) ? CARR_BUCKETS : 0) + (q < (unsigned)CARR_BUCKETS ? q : CARR_BUCKETS - 1);
-                }
-                key[k] = (uint16_t)kk;
-                head[kk + 1] += (uint32_t)nseg;
-            }
-            for (size_t j = 1; j < head.size(); j++)
-                head[j] += head[j - 1];
-            for (size_t vb = 0; vb < (size_t)nblocks * nseg; vb++)
-                for (int i = 0; i < nch; i++)
-                    carr[head[key[(vb / nseg) * nch + i]]++] = (int32_t)(vb * nch + i);
-        }
-        std::vector<int32_t> &order = b->h_seed_order;
-        order.clear();
-        auto waves_of = [&](const int32_t *chains, size_t n, size_t per_wave, int32_t add) {
-            for (size_t c = 0; c < n; c += per_wave)
-                for (size_t l = 0; l < 64; l++)
-                    order.push_back(l < per_wave && c + l < n ? chains[c + l] + add : -1);
-        };
-        std::vector<int32_t> code(nbc);
-        for (size_t k = 0; k < nbc; k++)
-            code[k] = (int32_t)k;
-        if (b->ev) {
-            /* k_walk keeps the lanes of a wavefront in lockstep: a turn of its loop costs the same however many
-             * lanes take part, so wavefronts are full, the carrier chains by descending |f_carr| (a wavefront runs
-             * as long as its longest chain) and the longest ones first */
-            const size_t lanes_per_wave = (size_t)GPSBB_KNOB_LONG("GPSBB_WALK_LANES", 64);
-            waves_of(carr.data(), nvbc, lanes_per_wave, (int32_t)nbc);
-            b->carr_lanes = (int)order.size();
-            waves_of(code.data(), nbc, 64, 0);
-        } else {
-            waves_of(code.data(), nbc, 64, 0);
-            /* the longest 8 % in wavefronts of 8, the next 16 % in wavefronts of 16, the next 32 % in wavefronts of 32 */
-            const size_t n8 = nbc * 8 / 100 / 8 * 8, n16 = nbc * 16 / 100 / 16 * 16, n32 = nbc * 32 / 100 / 32 * 32;
-            waves_of(carr.data(), n8, 8, (int32_t)nbc);
-            waves_of(carr.data() + n8, n16, 16, (int32_t)nbc);
-            waves_of(carr.data() + n8 + n16, n32, 32, (int32_t)nbc);
-            waves_of(carr.data() + n8 + n16 + n32, nbc - n8 - n16 - n32, 64, (int32_t)nbc);
-        }
-        HIPCHK(h, (hipError_t)b->d_seed_order.reserve(order.size()));
-        PUSH_MARK("order");
-        HIPCHK(h, stage_upload(b, b->d_seed_order.p, order.data(), order.size() * 4, upload_stream));
-        if (b->chain_starts) {
-            /* the chain's two walks take the carrier chains alone, in lockstep: by direction, then by |f_carr| (nseg = 1
-             * here: chains are blocks) */
-            std::stable_sort(carr.begin(), carr.end(), [hc](int32_t x, int32_t y) {
-                const bool nx = hc[x].prn > 0 && std::signbit(hc[x].f_carr), ny = hc[y].prn > 0 && std::signbit(hc[y].f_carr);
-                return nx != ny && ny;
-            });
-            std::vector<int32_t> co;
-            for (size_t c = 0; c < nbc; c += 64)
-                for (size_t l = 0; l < 64; l++)
-                    co.push_back(c + l < nbc ? carr[c + l] + (int32_t)nbc : -1);
-            b->chain_lanes = (int)co.size();
-            HIPCHK(h, (hipError_t)b->d_chain_order.reserve(co.size()));
-            HIPCHK(h, stage_upload(b, b->d_chain_order.p, co.data(), co.size() * 4, upload_stream));
+    if (!pl.laps) {
+        HIPCHK(h, stage_upload(b, b->d_row_off.p, img.row_off.data(), (nbc + nvbc + 1) * 8, upload_stream));
+        HIPCHK(h, (hipError_t)b->d_seed_order.reserve(img.h_seed_order.size()));
+        HIPCHK(h, stage_upload(b, b->d_seed_order.p, img.h_seed_order.data(), img.h_seed_order.size() * 4, upload_stream));
+        if (pl.chain_starts) {
+            HIPCHK(h, (hipError_t)b->d_chain_order.reserve(img.h_chain_order.size()));
+            HIPCHK(h, stage_upload(b, b->d_chain_order.p, img.h_chain_order.data(), img.h_chain_order.size() * 4, upload_stream));
         }
     }
     if (!b->upload_done)
         HIPCHK(h, hipEventCreateWithFlags(&b->upload_done, hipEventDisableTiming));
     HIPCHK(h, hipEventRecord(b->upload_done, upload_stream));
     b->upload_stream = upload_stream;
-    b->ran = false;
     return GPSBB_OK;
+}
+
+/* Set a batch up for its descriptors: plan (plan_batch, or plan_finish behind a plan_begin the caller has run into `begun` and the
+ * batch's images), then stage.  A plan that fails leaves the batch's plan as it was. */
+static int batch_setup(gpsbb_batch *b, const PlanIn &in, const PlanOpts &o, hipStream_t upload_stream, const BatchPlan *begun = nullptr)
+{
+    BatchPlan pl;
+    if (begun) {
+        pl = *begun;
+        plan_finish(pl, b->img, in, o, b->link);
+    } else {
+        const int rc = plan_batch(pl, b->img, in, o, b->link);
+        if (rc != GPSBB_OK)
+            return rc;
+    }
+    b->plan = pl;
+    int rc = stage_arena(b, (size_t)in.nblocks * in.nch);
+    rc = rc != GPSBB_OK ? rc : stage_plan(b, upload_stream);
+    if (rc == GPSBB_OK)
+        b->ran = false;
+    return rc;
 }
 
 static gpsbb_batch *batch_new(gpsbb *h)
@@ -1719,7 +1365,7 @@ static hipError_t use_second_seed_stream(gpsbb_batch *b)
  * turn, so that two pre-passes are in flight beside the synthesis:
  *  - a batch with three or more table sets: run by run (two streams however many sets: a third pre-pass in flight bought nothing,
  *    tools/sweep_seed_streams.sh, and would want a fifth hardware queue);
- *  - a stream's slot with the device-side chain (b->d_carry set by the push, one table set): push by push (a pre-pass is a chain
+ *  - a stream's slot with the device-side chain (b->link.d_carry set by the push, one table set): push by push (a pre-pass is a chain
  *    of latency-bound kernels, and the ring delivers one push per (that / streams));
  *  - anything else: the stream the batch was given when it was created (every other batch, every other slot). */
 static hipError_t batch_prepass_stream(gpsbb_batch *b, bool chain_on_device, hipStream_t *out)
@@ -1728,13 +1374,13 @@ static hipError_t batch_prepass_stream(gpsbb_batch *b, bool chain_on_device, hip
     *out = b->one_stream ? h->s_compute : b->seed_stream;
     if (b->one_stream)
         return hipSuccess;
-    if (b->nsets > 2) {
+    if (b->plan.nsets > 2) {
         const unsigned base = b->seed_stream == h->s_seed ? 0u : 1u;
-        return seed_stream_at(h, (base + b->run_count) % std::min((unsigned)(b->nsets - 1), STREAM_SEED_STREAMS), out);
+        return seed_stream_at(h, (base + b->run_count) % std::min((unsigned)(b->plan.nsets - 1), STREAM_SEED_STREAMS), out);
     }
-    if (b->d_carry && chain_on_device) {
+    if (b->link.d_carry && chain_on_device) {
         const unsigned nseed = (unsigned)GPSBB_KNOB_LONG("GPSBB_STREAM_SEED_STREAMS", STREAM_SEED_STREAMS);
-        return seed_stream_at(h, b->stream_turn % (nseed >= 1 && nseed <= (unsigned)SEED_STREAMS_MAX ? nseed : STREAM_SEED_STREAMS), out);
+        return seed_stream_at(h, b->link.stream_turn % (nseed >= 1 && nseed <= (unsigned)SEED_STREAMS_MAX ? nseed : STREAM_SEED_STREAMS), out);
     }
     return hipSuccess;
 }
@@ -1792,7 +1438,7 @@ extern "C" int gpsbb_batch_create(gpsbb_t *h, const gpsbb_chan_t *ch, int nblock
             return e2 == hipErrorOutOfMemory ? GPSBB_E_NOMEM : GPSBB_E_HIP;
         }
     }
-    int rc = batch_setup(b, ch, nblocks, nch, delt, nsamp, flags, b->seed_stream);
+    int rc = batch_setup(b, PlanIn{ch, nblocks, nch, delt, nsamp, flags}, plan_opts(h, b->max_sets), b->seed_stream);
     if (rc != GPSBB_OK) {
         gpsbb_batch_destroy(b);
         return rc;
@@ -1804,7 +1450,7 @@ extern "C" int gpsbb_batch_create(gpsbb_t *h, const gpsbb_chan_t *ch, int nblock
 
 extern "C" size_t gpsbb_batch_iq_bytes(const gpsbb_batch_t *b)
 {
-    return b ? (size_t)b->nblocks * (size_t)b->nsamp * 4 : 0;
+    return b ? (size_t)b->plan.nblocks * (size_t)b->plan.nsamp * 4 : 0;
 }
 
 /* ---- seeding on the host --------------------------------------------------------------------------
@@ -1813,8 +1459,6 @@ extern "C" size_t gpsbb_batch_iq_bytes(const gpsbb_batch_t *b)
  * the same chains with the same code (gpsbb_nco.h) an order of magnitude faster per row, and the tables
  * (a few MB) are uploaded instead.  Same rows, same tile index, same end states as the kernel writes. */
 namespace {
-
-constexpr size_t HOST_SEED_MAX_CHANNELS = 64; /* blocks x channels up to which the host seeds */
 
 struct HostRowSink {
     SynRow *rows;
@@ -1890,10 +1534,12 @@ struct HostRowSink {
  * seed_carr_chain / seed_carr_fixed do on the device.  Returns false on a row-pool overflow. */
 bool host_seed_chain(const gpsbb_batch *b, int kind, size_t k, unsigned long long *dwrd_oob, unsigned long long *itable_512)
 {
-    const gpsbb_chan_t &c = b->h_ch[k];
+    const BatchPlan &pl = b->plan;
+    const PlanImages &img = b->img;
+    const gpsbb_chan_t &c = img.h_ch[k];
     gpsbb_chan_state_t &e = b->hs_end[k];
-    const size_t nbc = (size_t)b->nblocks * b->nch;
-    const bool fixed = (b->flags & GPSBB_FIXED_CARRIER) != 0;
+    const size_t nbc = (size_t)pl.nblocks * pl.nch;
+    const bool fixed = (pl.flags & GPSBB_FIXED_CARRIER) != 0;
     if (c.prn <= 0) {
         if (kind == 0) {
             e.code_phase = 0.0;
@@ -1904,25 +1550,25 @@ bool host_seed_chain(const gpsbb_batch *b, int kind, size_t k, unsigned long lon
         }
         return true;
     }
-    const size_t blk = k / (size_t)b->nch, i = k % (size_t)b->nch;
+    const size_t blk = k / (size_t)pl.nch, i = k % (size_t)pl.nch;
     if (kind == 1 && fixed) {
-        e.carr_phase = (double)(uint32_t)(b->h_kph0[k] + (uint32_t)b->nsamp * (uint32_t)b->h_kstep[k]);
-        if (b->ev) {
+        e.carr_phase = (double)(uint32_t)(img.h_kph0[k] + (uint32_t)pl.nsamp * (uint32_t)img.h_kstep[k]);
+        if (pl.ev) {
             /* k_synth_pd: the table index at every tile start, in closed form (what k_tiles writes on the device) */
-            double *tx = b->hs_tile_x + (blk * (2 * (size_t)b->nch) + 2 * i + 1) * (size_t)b->ntiles;
-            for (int t = 0; t < b->ntiles; t++)
-                tx[t] = fixed_tile_index(b->h_kph0[k], b->h_kstep[k], t);
+            double *tx = b->hs_tile_x + (blk * (2 * (size_t)pl.nch) + 2 * i + 1) * (size_t)pl.ntiles;
+            for (int t = 0; t < pl.ntiles; t++)
+                tx[t] = fixed_tile_index(img.h_kph0[k], img.h_kstep[k], t);
         }
         return true;
     }
-    if (b->ev) {
+    if (pl.ev) {
         /* breakpoint kernel: tile-start states instead of rows (what k_seed<true> writes) */
         uint32_t nav = kind == 0 ? nav_pack(c.icode, c.ibit, c.iword) : 0u;
-        TileSink sink = make_tile_sink(b->hs_tile_x, b->hs_tile_nav, b->nch, b->ntiles, (int)blk, (int)i, kind,
+        TileSink sink = make_tile_sink(b->hs_tile_x, b->hs_tile_nav, pl.nch, pl.ntiles, (int)blk, (int)i, kind,
                                        kind == 0 ? c.dwrd : nullptr, nav, nullptr);
         if (kind == 0) {
-            const double s = mul_rn(c.f_code, b->delt);
-            const double x = build_rows_f64<NCO_CODE>(c.code_phase, s, nav, b->nsamp, sink);
+            const double s = mul_rn(c.f_code, pl.delt);
+            const double x = build_rows_f64<NCO_CODE>(c.code_phase, s, nav, pl.nsamp, sink);
             sink.finish();
             e.code_phase = x;
             e.iword = nav_iword(nav);
@@ -1933,8 +1579,8 @@ bool host_seed_chain(const gpsbb_batch *b, int kind, size_t k, unsigned long lon
             e.codeCA = (int)((b->h->h_ca[(size_t)c.prn * 32 + (ci >> 5)] >> (ci & 31)) & 1u) * 2 - 1;
             e._pad = 0;
         } else {
-            const double s = mul_rn(c.f_carr, b->delt);
-            e.carr_phase = build_rows_f64<NCO_CARR>(c.carr_phase, s, nav, b->nsamp, sink);
+            const double s = mul_rn(c.f_carr, pl.delt);
+            e.carr_phase = build_rows_f64<NCO_CARR>(c.carr_phase, s, nav, pl.nsamp, sink);
             sink.finish();
         }
         *itable_512 += sink.hz_local[0];
@@ -1943,8 +1589,8 @@ bool host_seed_chain(const gpsbb_batch *b, int kind, size_t k, unsigned long lon
     }
     const size_t chain = (size_t)kind * nbc + k;
     HostRowSink sink;
-    sink.rows = b->hs_rows + b->row_off[chain];
-    sink.cap = (uint32_t)(b->row_off[chain + 1] - b->row_off[chain] - 1);
+    sink.rows = b->hs_rows + img.row_off[chain];
+    sink.cap = (uint32_t)(img.row_off[chain + 1] - img.row_off[chain] - 1);
     sink.cnt = 0;
     sink.overflow = false;
     sink.dwrd_oob = 0;
@@ -1952,14 +1598,14 @@ bool host_seed_chain(const gpsbb_batch *b, int kind, size_t k, unsigned long lon
     sink.dwrd = kind == 0 ? c.dwrd : nullptr;
     uint32_t nav = kind == 0 ? nav_pack(c.icode, c.ibit, c.iword) : 0u;
     sink.dbit = kind == 0 && nav_bit(c.dwrd, nav) < 0 ? 0x80000000u : 0u;
-    sink.tr = b->hs_tile_row + (blk * ((size_t)b->ntiles + 1)) * (2 * (size_t)b->nch) + 2 * i + (size_t)kind;
-    sink.tstride = 2 * (size_t)b->nch;
+    sink.tr = b->hs_tile_row + (blk * ((size_t)pl.ntiles + 1)) * (2 * (size_t)pl.nch) + 2 * i + (size_t)kind;
+    sink.tstride = 2 * (size_t)pl.nch;
     sink.tile_t = 0;
-    sink.ntiles = b->ntiles;
+    sink.ntiles = pl.ntiles;
     sink.wrap_pend = 0;
     if (kind == 0) {
-        const double s = mul_rn(c.f_code, b->delt);
-        const double x = build_rows_f64<NCO_CODE>(c.code_phase, s, nav, b->nsamp, sink);
+        const double s = mul_rn(c.f_code, pl.delt);
+        const double x = build_rows_f64<NCO_CODE>(c.code_phase, s, nav, pl.nsamp, sink);
         sink.finish();
         e.code_phase = x;
         e.iword = nav_iword(nav);
@@ -1970,8 +1616,8 @@ bool host_seed_chain(const gpsbb_batch *b, int kind, size_t k, unsigned long lon
         e.codeCA = (int)((b->h->h_ca[(size_t)c.prn * 32 + (ci >> 5)] >> (ci & 31)) & 1u) * 2 - 1;
         e._pad = 0;
     } else {
-        const double s = mul_rn(c.f_carr, b->delt);
-        e.carr_phase = build_rows_f64<NCO_CARR>(c.carr_phase, s, nav, b->nsamp, sink);
+        const double s = mul_rn(c.f_carr, pl.delt);
+        e.carr_phase = build_rows_f64<NCO_CARR>(c.carr_phase, s, nav, pl.nsamp, sink);
         sink.finish();
     }
     *dwrd_oob += sink.dwrd_oob;
@@ -1996,28 +1642,19 @@ int host_pinned_reserve(void **p, size_t *cap, size_t bytes)
 
 } /* namespace */
 
-/* where the NCO tables of a run are built: by size (default), or as GPSBB_OPT_SEED_WHERE says (tests run both ways) */
-static bool host_seeding_wanted(const gpsbb_batch *b)
-{
-    const bool off = GPSBB_KNOB_SET("GPSBB_DEVICE_SEED_ONLY");
-    const size_t lim = (size_t)GPSBB_KNOB_LONG("GPSBB_HOST_SEED_MAX", HOST_SEED_MAX_CHANNELS);
-    if (b->h->opt_seed_where)
-        return b->h->opt_seed_where == 2;
-    return !off && (size_t)b->nblocks * b->nch <= lim;
-}
-
 /* Build the tables of one run on host threads and queue their upload on the seeding stream. */
 static int host_seed_run(gpsbb_batch *b, const TableSet &ts, hipStream_t stream)
 {
+    const BatchPlan &pl = b->plan;
     gpsbb *h = b->h;
-    const size_t nbc = (size_t)b->nblocks * b->nch;
-    const size_t tr_n = 2 * nbc * ((size_t)b->ntiles + 1);
-    const size_t tx_n = 2 * nbc * (size_t)b->ntiles, tn_n = nbc * (size_t)b->ntiles;
-    if (b->ev) {
+    const size_t nbc = (size_t)pl.nblocks * pl.nch;
+    const size_t tr_n = 2 * nbc * ((size_t)pl.ntiles + 1);
+    const size_t tx_n = 2 * nbc * (size_t)pl.ntiles, tn_n = nbc * (size_t)pl.ntiles;
+    if (pl.ev) {
         HIPCHK(h, (hipError_t)host_pinned_reserve((void **)&b->hs_tile_x, &b->hs_tx_cap, tx_n * sizeof(double)));
         HIPCHK(h, (hipError_t)host_pinned_reserve((void **)&b->hs_tile_nav, &b->hs_tn_cap, tn_n * sizeof(uint32_t)));
     } else {
-        HIPCHK(h, (hipError_t)host_pinned_reserve((void **)&b->hs_rows, &b->hs_rows_cap, (b->total_rows + 4) * sizeof(SynRow)));
+        HIPCHK(h, (hipError_t)host_pinned_reserve((void **)&b->hs_rows, &b->hs_rows_cap, (pl.total_rows + 4) * sizeof(SynRow)));
         HIPCHK(h, (hipError_t)host_pinned_reserve((void **)&b->hs_tile_row, &b->hs_tr_cap, tr_n * sizeof(int32_t)));
     }
     HIPCHK(h, (hipError_t)host_pinned_reserve((void **)&b->hs_end, &b->hs_end_cap, nbc * sizeof(gpsbb_chan_state_t)));
@@ -2045,11 +1682,11 @@ static int host_seed_run(gpsbb_batch *b, const TableSet &ts, hipStream_t stream)
         if (!ok[t])
             return GPSBB_E_INTERNAL;
     }
-    if (b->ev) {
+    if (pl.ev) {
         HIPCHK(h, hipMemcpyAsync(ts.tile_x.p, b->hs_tile_x, tx_n * sizeof(double), hipMemcpyHostToDevice, stream));
         HIPCHK(h, hipMemcpyAsync(ts.tile_nav.p, b->hs_tile_nav, tn_n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     } else {
-        HIPCHK(h, hipMemcpyAsync(ts.rows.p, b->hs_rows, b->total_rows * sizeof(SynRow), hipMemcpyHostToDevice, stream));
+        HIPCHK(h, hipMemcpyAsync(ts.rows.p, b->hs_rows, pl.total_rows * sizeof(SynRow), hipMemcpyHostToDevice, stream));
         HIPCHK(h, hipMemcpyAsync(ts.tile_row.p, b->hs_tile_row, tr_n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
     }
     HIPCHK(h, hipMemcpyAsync(ts.end.p, b->hs_end, nbc * sizeof(gpsbb_chan_state_t), hipMemcpyHostToDevice, stream));
@@ -2058,63 +1695,64 @@ static int host_seed_run(gpsbb_batch *b, const TableSet &ts, hipStream_t stream)
 
 static BatchDev batch_dev(const gpsbb_batch *b, const TableSet &ts)
 {
+    const BatchPlan &pl = b->plan;
     const size_t set = (size_t)(&ts - b->sets);
     BatchDev p;
     memset(&p, 0, sizeof p); /* (every field has a value, also the ones a later round adds) */
     p.ch = b->d_ch.p;
-    p.nblocks = b->nblocks;
-    p.nch = b->nch;
-    p.nsamp = b->nsamp;
-    p.ntiles = b->ntiles;
-    p.st_log2 = b->st_log2;
-    p.nstates = b->nstates;
-    p.delt = b->delt;
-    p.flags = b->flags;
+    p.nblocks = pl.nblocks;
+    p.nch = pl.nch;
+    p.nsamp = pl.nsamp;
+    p.ntiles = pl.ntiles;
+    p.st_log2 = pl.st_log2;
+    p.nstates = pl.nstates;
+    p.delt = pl.delt;
+    p.flags = pl.flags;
     p.tabs = b->h->d_tabs;
     p.ca_bits = b->h->d_ca;
     p.rows = reinterpret_cast<SynRow *>(ts.rows.p);
     p.row_off = b->d_row_off.p;
     p.tile_row = ts.tile_row.p;
     p.row_cnt = ts.row_cnt.p;
-    p.tile_ctr = b->d_tile_ctr.p + set * ((size_t)b->nblocks + 1);
-    p.kph0 = (b->flags & GPSBB_FIXED_CARRIER) ? b->d_kph0.p : nullptr;
-    p.kstep = (b->flags & GPSBB_FIXED_CARRIER) ? b->d_kstep.p : nullptr;
+    p.tile_ctr = b->d_tile_ctr.p + set * ((size_t)pl.nblocks + 1);
+    p.kph0 = (pl.flags & GPSBB_FIXED_CARRIER) ? b->d_kph0.p : nullptr;
+    p.kstep = (pl.flags & GPSBB_FIXED_CARRIER) ? b->d_kstep.p : nullptr;
     p.end = ts.end.p;
     p.status = b->h->d_status;
     p.hazards = b->h->d_hz;
     p.digest = b->want_digest ? b->d_dig.p : nullptr;
     p.seed_order = b->d_seed_order.p;
-    p.seed_lanes = (int)b->h_seed_order.size();
-    p.ev = b->ev ? 1 : 0;
-    int ev_chunk = b->ev_all_dense ? (int)GPSBB_KNOB_LONG("GPSBB_PD_CHUNK", PD_CHUNK) : (int)GPSBB_KNOB_LONG("GPSBB_EV_CHUNK", EV_CHUNK);
+    p.seed_lanes = (int)b->img.h_seed_order.size();
+    p.ev = pl.ev ? 1 : 0;
+    int ev_chunk = pl.ev_all_dense ? (int)GPSBB_KNOB_LONG("GPSBB_PD_CHUNK", PD_CHUNK) : (int)GPSBB_KNOB_LONG("GPSBB_EV_CHUNK", EV_CHUNK);
     /* a batch too small to give every CU a workgroup's worth of chunks (the drop-in call's one block: 293 tiles) hands its tiles out
      * in smaller chunks, down to one at a time: twice the workgroups, half the tiles each (0.116 -> 0.110 ms for the reference's
      * block rendered into a registered buffer) */
     const long cus = b->h->sm_count > 0 ? b->h->sm_count : 256;
     while (ev_chunk > 1 && GPSBB_KNOB_LONG("GPSBB_SMALL_CHUNKS", 1) != 0 &&
-           (long)b->nblocks * (((long)b->ntiles + ev_chunk - 1) / ev_chunk) < cus * EV_WAVES)
+           (long)pl.nblocks * (((long)pl.ntiles + ev_chunk - 1) / ev_chunk) < cus * EV_WAVES)
         ev_chunk--;
     p.ev_chunk = ev_chunk < 1 ? 1 : ev_chunk;
     p.pd_danger = (uint32_t)GPSBB_KNOB_LONG("GPSBB_PD_DANGER", 2u * PD_BAND); /* (larger: more lanes take the exact path; a test aid) */
     p.tile_x = ts.tile_x.p;
     p.tile_nav = ts.tile_nav.p;
     p.evc = b->d_evc.p;
-    p.chain_dev = b->chain_dev ? 1 : 0;
-    p.chain_starts = b->chain_starts ? 1 : 0;
-    p.aux = b->chain_dev ? ts.aux.p : nullptr;
-    p.nseg = b->nseg;
-    p.seg_tiles = b->seg_tiles;
-    p.nvb = b->nblocks * b->nseg;
-    p.fix_end = b->fix.end.p ? b->fix.end.p + set * GPSBB_MAX_CHAN * b->fix_chunks : nullptr;
-    p.fix_flag = b->fix.flag.p ? b->fix.flag.p + set * GPSBB_MAX_CHAN * b->fix_chunks : nullptr;
+    p.chain_dev = pl.chain_dev ? 1 : 0;
+    p.chain_starts = pl.chain_starts ? 1 : 0;
+    p.aux = pl.chain_dev ? ts.aux.p : nullptr;
+    p.nseg = pl.nseg;
+    p.seg_tiles = pl.seg_tiles;
+    p.nvb = pl.nblocks * pl.nseg;
+    p.fix_end = b->fix.end.p ? b->fix.end.p + set * GPSBB_MAX_CHAN * pl.fix_chunks : nullptr;
+    p.fix_flag = b->fix.flag.p ? b->fix.flag.p + set * GPSBB_MAX_CHAN * pl.fix_chunks : nullptr;
     p.fix_epoch = b->fix.epoch;
-    p.fix_chunks = b->fix_chunks;
-    p.model_start = b->chain_model ? 1 : 0;
-    p.cd = b->chain_dev ? b->d_cd.p : nullptr;
-    p.start0 = b->chain_dev ? b->d_start0.p : nullptr;
-    p.prefix_rows = b->chain_dev && !b->chain_starts ? ts.prefix.p : nullptr;
-    p.carry = b->chain_dev ? b->d_carry : nullptr;
-    p.cont0_mask = b->cont0_mask;
+    p.fix_chunks = pl.fix_chunks;
+    p.model_start = pl.chain_model ? 1 : 0;
+    p.cd = pl.chain_dev ? b->d_cd.p : nullptr;
+    p.start0 = pl.chain_dev ? b->d_start0.p : nullptr;
+    p.prefix_rows = pl.chain_dev && !pl.chain_starts ? ts.prefix.p : nullptr;
+    p.carry = pl.chain_dev ? b->link.d_carry : nullptr;
+    p.cont0_mask = pl.cont0_mask;
     p.lap_end = nullptr;
     return p;
 }
@@ -2132,9 +1770,10 @@ static void lap_dev_plan(LapDev &L, const uint32_t chunk0[2][GPSBB_MAX_CHAN + 1]
 
 static LapDev lap_dev(const gpsbb_batch *b, const TableSet &ts)
 {
+    const BatchPlan &pl = b->plan;
     LapDev L;
     ts.lap.dev(L);
-    lap_dev_plan(L, b->lap_chunk0, b->chain_dev, (size_t)b->nblocks * b->nch);
+    lap_dev_plan(L, pl.lap_chunk0, pl.chain_dev, (size_t)pl.nblocks * pl.nch);
     return L;
 }
 
@@ -2169,7 +1808,7 @@ static void lap_chain_launch(hipStream_t ss, const BatchDev &p, const LapDev &L,
 }
 
 /* The carrier chain by the row walks (gpsbb_walk.hip.h): pass A over the first carr_lanes lanes of p's plan (the carrier chains:
- * they come first) and the prefix — unless pass B starts from the host's drift model of every segment's start (batch_setup:
+ * they come first) and the prefix — unless pass B starts from the host's drift model of every segment's start (plan_segments:
  * chain_model) —, pass B (k_walk<pass_b>: 2 leaves rows, 3 the blocks' start phases only) over all p.seed_lanes, and the fix-up:
  * k_chain_fix_par in workgroups of fix_wg lanes, or (fix_wg 0) k_chain_fix, the blocks in order.  A stream: this push's prefix /
  * fix-up follow the ones of the push before (other seeding stream). */
@@ -2233,24 +1872,25 @@ static int launch_events(gpsbb_batch *b, hipEvent_t **ev)
 /* The pre-pass of one run into table set `set`, on stream ss.  *ctr_reset: it zeroes the set's tile counters itself. */
 static int prepass_launch(gpsbb_batch *b, int set, const BatchDev &p, hipStream_t ss, bool *ctr_reset)
 {
+    const BatchPlan &pl = b->plan;
     gpsbb *h = b->h;
     const TableSet &ts = b->sets[set];
-    const int lanes = (int)b->h_seed_order.size();
-    const CarryEvents ce = {b->d_carry ? b->ev_prefix : nullptr, b->d_carry ? b->ev_fix : nullptr};
-    const int fix_wg = b->chain_fix_seq ? 0 : b->fix_wg;
+    const int lanes = (int)b->img.h_seed_order.size();
+    const CarryEvents ce = {b->link.d_carry ? b->link.ev_prefix : nullptr, b->link.d_carry ? b->link.ev_fix : nullptr};
+    const int fix_wg = pl.chain_fix_seq ? 0 : pl.fix_wg;
     *ctr_reset = false;
-    if (h->opt_skip_seed && b->run_count >= (unsigned)b->nsets) {
+    if (h->opt_skip_seed && b->run_count >= (unsigned)pl.nsets) {
         /* measurement hook: time the synthesis kernel alone on tables already built */
-    } else if (b->host_seed) {
+    } else if (pl.host_seed) {
         /* the previous user of the pinned images (this batch's last run) has been copied out: its upload was
          * followed by the synthesis kernel, which that set's synth_done_ref covers */
-        const TableSet &prev = b->sets[(set + b->nsets - 1) % b->nsets];
+        const TableSet &prev = b->sets[(set + pl.nsets - 1) % pl.nsets];
         if (prev.synth_pending)
             HIPCHK(h, hipEventSynchronize(prev.synth_done_ref));
         const int rc = host_seed_run(b, ts, ss);
         if (rc != GPSBB_OK)
             return rc;
-    } else if (b->ev && b->laps) {
+    } else if (pl.ev && pl.laps) {
         /* the lap-parallel pre-pass (gpsbb_laps.hip.h): plan, reference walks, scan, true walks, repair — the code chains
          * first (nothing of theirs waits for another push), then the carriers: a stream's push starts from the exact phase the
          * push before it left on the device, so its plan follows that push's repair kernel */
@@ -2263,45 +1903,45 @@ static int prepass_launch(gpsbb_batch *b, int set, const BatchDev &p, hipStream_
         /* pass 2 writes the tile states in 32- / 16-byte pieces where the geometry has them (several tiles per lap: a code period is
          * 1023 chips / (1.023e6 * delt) samples) — k_lap_pass2<., true>; at the reference's 2.6 MS/s a period is 2.5 tiles and the
          * plain loop is the faster one */
-        const bool wide = GPSBB_KNOB_LONG("GPSBB_LAP_WIDE", b->delt <= 1.0 / 8.0e6 ? 1 : 0) != 0;
+        const bool wide = GPSBB_KNOB_LONG("GPSBB_LAP_WIDE", pl.delt <= 1.0 / 8.0e6 ? 1 : 0) != 0;
         const bool merged = !p.kph0 && (!ce.fix || GPSBB_KNOB_LONG("GPSBB_LAP_MERGE", 0) == 1) &&
                             GPSBB_KNOB_LONG("GPSBB_LAP_MERGE", 0) != 2;
         if (merged) {
             HIPCHK(h, ce.wait_both(ss));
-            lap_chain_launch(ss, p, L, b->nch, -1, lap_pass2_kernel(-1, wide, p.st_log2));
+            lap_chain_launch(ss, p, L, pl.nch, -1, lap_pass2_kernel(-1, wide, p.st_log2));
             HIPCHK(h, ce.record_both(ss));
         } else {
-            lap_chain_launch(ss, p, L, b->nch, NCO_CODE, lap_pass2_kernel(NCO_CODE, wide, p.st_log2));
+            lap_chain_launch(ss, p, L, pl.nch, NCO_CODE, lap_pass2_kernel(NCO_CODE, wide, p.st_log2));
             if (p.kph0) {
                 /* fixed-point carrier: no chain to walk; the plan kernel leaves the end states, the tile states are a closed form */
-                hipLaunchKernelGGL(k_lap_plan<NCO_CARR>, dim3(b->nch), dim3(64), 0, ss, p, L);
-                hipLaunchKernelGGL(k_lap_fixed_tiles, dim3(b->nblocks * b->nch), dim3(256), 0, ss, p);
+                hipLaunchKernelGGL(k_lap_plan<NCO_CARR>, dim3(pl.nch), dim3(64), 0, ss, p, L);
+                hipLaunchKernelGGL(k_lap_fixed_tiles, dim3(pl.nblocks * pl.nch), dim3(256), 0, ss, p);
             } else {
                 HIPCHK(h, ce.wait_both(ss));
-                lap_chain_launch(ss, p, L, b->nch, NCO_CARR, lap_pass2_kernel(NCO_CARR, wide, p.st_log2));
+                lap_chain_launch(ss, p, L, pl.nch, NCO_CARR, lap_pass2_kernel(NCO_CARR, wide, p.st_log2));
                 HIPCHK(h, ce.record_both(ss));
             }
         }
         *ctr_reset = true; /* k_lap_plan zeroes the set's tile counters */
-    } else if (b->ev) {
+    } else if (pl.ev) {
         if (GPSBB_KNOB_SET("GPSBB_EV_KSEED")) { /* experiment: the one-kernel pre-pass */
             hipLaunchKernelGGL(k_seed<true>, dim3((lanes + GPSBB_SEED_WG - 1) / GPSBB_SEED_WG), dim3(GPSBB_SEED_WG), 0, ss, p);
         } else {
-            if (b->chain_dev)
-                HIPCHK(h, walk_chain_launch(ss, p, b->carr_lanes, !b->chain_model, 2, fix_wg, ce));
+            if (pl.chain_dev)
+                HIPCHK(h, walk_chain_launch(ss, p, pl.carr_lanes, !pl.chain_model, 2, fix_wg, ce));
             else
                 hipLaunchKernelGGL(k_walk<0>, dim3((lanes + GPSBB_WALK_WG - 1) / GPSBB_WALK_WG), dim3(GPSBB_WALK_WG), 0, ss, p);
-            hipLaunchKernelGGL(k_tiles, dim3((1 + b->nseg) * b->nblocks * b->nch), dim3(GPSBB_TILES_WG), 0, ss, p);
+            hipLaunchKernelGGL(k_tiles, dim3((1 + pl.nseg) * pl.nblocks * pl.nch), dim3(GPSBB_TILES_WG), 0, ss, p);
             *ctr_reset = true; /* k_tiles zeroes the set's tile counters */
         }
     } else {
-        if (b->chain_starts) {
+        if (pl.chain_starts) {
             /* the carrier chained on the device for the per-sample kernel: pass A, prefix, pass B without rows and the
              * fix-up put the exact start phase of every block into its descriptor; k_seed then sees independent blocks */
             BatchDev pc = p;
             pc.seed_order = b->d_chain_order.p;
-            pc.seed_lanes = b->chain_lanes;
-            HIPCHK(h, walk_chain_launch(ss, pc, b->chain_lanes, true, 3, fix_wg, ce));
+            pc.seed_lanes = pl.chain_lanes;
+            HIPCHK(h, walk_chain_launch(ss, pc, pl.chain_lanes, true, 3, fix_wg, ce));
         }
         hipLaunchKernelGGL(k_seed<false>, dim3((lanes + GPSBB_SEED_WG - 1) / GPSBB_SEED_WG), dim3(GPSBB_SEED_WG), 0, ss, p);
     }
@@ -2311,36 +1951,37 @@ static int prepass_launch(gpsbb_batch *b, int set, const BatchDev &p, hipStream_
 /* The synthesis kernel of one run on stream sc, and the blocks' digests behind it where no variant leaves them itself. */
 static int synth_launch(gpsbb_batch *b, const BatchDev &p, hipStream_t sc, int16_t *d_iq)
 {
+    const BatchPlan &pl = b->plan;
     gpsbb *h = b->h;
     bool digest_fused = false;
-    h->last_chain_dev = b->chain_dev && !b->chain_indep ? 1 : 0;
-    if (b->ev) {
+    h->last_chain_dev = pl.chain_dev && !pl.chain_indep ? 1 : 0;
+    if (pl.ev) {
         /* One workgroup of EV_WG lanes fits a CU (its LDS image takes ~140 - 156 KB).  Grid = the blocks' primaries, then the
          * helpers (ev_pick_block: a helper joins one of the blocks that still have tiles to hand out, chosen when it starts):
          * as many as can be useful when there are few blocks (never more workgroups per block than there are chunks of tiles
          * per wavefront), else enough to keep every CU busy through the end of the launch — the last round of blocks and then
          * what is left of it take the CUs twice over. */
         const long wg_slots = (long)(h->sm_count > 0 ? h->sm_count : 256);
-        const long chunks = ((long)b->ntiles + p.ev_chunk - 1) / p.ev_chunk;
+        const long chunks = ((long)pl.ntiles + p.ev_chunk - 1) / p.ev_chunk;
         const long max_useful = (chunks + EV_WAVES - 1) / EV_WAVES;
         const long oversub = GPSBB_KNOB_LONG("GPSBB_EV_HELPERS", 2);
-        long helpers = (long)b->nblocks * (max_useful - 1);
+        long helpers = (long)pl.nblocks * (max_useful - 1);
         if (helpers > wg_slots * oversub)
             helpers = wg_slots * oversub;
         if (helpers < 0)
             helpers = 0;
-        const dim3 grid((unsigned)(b->nblocks + helpers));
-        if (b->ev_all_dense && b->want_digest) {
-            if (b->nch <= PD_WIDE_CHAN)
+        const dim3 grid((unsigned)(pl.nblocks + helpers));
+        if (pl.ev_all_dense && b->want_digest) {
+            if (pl.nch <= PD_WIDE_CHAN)
                 hipLaunchKernelGGL((k_synth_pd<true, true>), grid, dim3(EV_WG), sizeof(PdLds<true>) + EV_PICK_LDS, sc, p, d_iq);
             else
                 hipLaunchKernelGGL((k_synth_pd<false, true>), grid, dim3(EV_WG), sizeof(PdLds<false>) + EV_PICK_LDS, sc, p, d_iq);
             digest_fused = true;
-        } else if (b->ev_all_dense && b->nch <= PD_WIDE_CHAN)
+        } else if (pl.ev_all_dense && pl.nch <= PD_WIDE_CHAN)
             hipLaunchKernelGGL(k_synth_pd<true>, grid, dim3(EV_WG), sizeof(PdLds<true>) + EV_PICK_LDS, sc, p, d_iq);
-        else if (b->ev_all_dense)
+        else if (pl.ev_all_dense)
             hipLaunchKernelGGL(k_synth_pd<false>, grid, dim3(EV_WG), sizeof(PdLds<false>) + EV_PICK_LDS, sc, p, d_iq);
-        else if (b->ev_dense)
+        else if (pl.ev_dense)
             hipLaunchKernelGGL(k_synth_ev_dense, grid, dim3(EV_WG), sizeof(EvLds) + EV_PICK_LDS, sc, p, d_iq);
         else if (p.kph0)
             hipLaunchKernelGGL(k_synth_ev_fixed, grid, dim3(EV_WG), sizeof(EvLdsLean) + EV_PICK_LDS, sc, p, d_iq);
@@ -2353,8 +1994,8 @@ static int synth_launch(gpsbb_batch *b, const BatchDev &p, hipStream_t sc, int16
                                sizeof(EvLdsLean) + EV_PICK_LDS, sc, p, d_iq);
         h->last_kernel = 2;
         /* (the same order as the launches above; a digest-fused instantiation is the same variant) */
-        h->last_variant = b->ev_all_dense ? (b->nch <= PD_WIDE_CHAN ? GPSBB_VARIANT_PD_WIDE : GPSBB_VARIANT_PD_NARROW)
-                          : (b->ev_dense ? GPSBB_VARIANT_EV_DENSE : (p.kph0 ? GPSBB_VARIANT_EV_FIXED : GPSBB_VARIANT_EV));
+        h->last_variant = pl.ev_all_dense ? (pl.nch <= PD_WIDE_CHAN ? GPSBB_VARIANT_PD_WIDE : GPSBB_VARIANT_PD_NARROW)
+                          : (pl.ev_dense ? GPSBB_VARIANT_EV_DENSE : (p.kph0 ? GPSBB_VARIANT_EV_FIXED : GPSBB_VARIANT_EV));
     } else {
         h->last_kernel = 1;
         h->last_variant = GPSBB_VARIANT_SYNTH;
@@ -2362,20 +2003,20 @@ static int synth_launch(gpsbb_batch *b, const BatchDev &p, hipStream_t sc, int16
          * dynamically in chunks, so the tail is short), never more than there are chunks; the per-block
          * LDS tables (amplitude LUT, chips, nav words) are then built few times per block. */
         const long wg_slots = (long)(h->sm_count > 0 ? h->sm_count : 256) * 2;
-        const long chunks = ((long)b->ntiles + TILE_CHUNK - 1) / TILE_CHUNK;
+        const long chunks = ((long)pl.ntiles + TILE_CHUNK - 1) / TILE_CHUNK;
         const long max_useful = (chunks + WAVES_PER_WG - 1) / WAVES_PER_WG;
         const long oversub = GPSBB_KNOB_LONG("GPSBB_OVERSUB", 12);
-        long want = (wg_slots * oversub + b->nblocks - 1) / b->nblocks;
+        long want = (wg_slots * oversub + pl.nblocks - 1) / pl.nblocks;
         want = want < 1 ? 1 : (want > max_useful ? max_useful : want);
         const int gx = (int)want;
-        hipLaunchKernelGGL(k_synth, dim3(gx, b->nblocks), dim3(TILE_THREADS), sizeof(SynthLds), sc, p, d_iq);
+        hipLaunchKernelGGL(k_synth, dim3(gx, pl.nblocks), dim3(TILE_THREADS), sizeof(SynthLds), sc, p, d_iq);
     }
     if (b->want_digest && !digest_fused) {
         /* a synthesis kernel without a digesting variant: the blocks read back behind it, on its stream */
-        long chunks = (2048 + b->nblocks - 1) / b->nblocks;
-        const long max_chunks = ((long)b->nsamp + 1023) / 1024;
+        long chunks = (2048 + pl.nblocks - 1) / pl.nblocks;
+        const long max_chunks = ((long)pl.nsamp + 1023) / 1024;
         chunks = chunks > max_chunks ? max_chunks : (chunks < 1 ? 1 : chunks);
-        hipLaunchKernelGGL(k_block_digest, dim3((unsigned)chunks, (unsigned)b->nblocks), dim3(256), 0, sc, (const uint32_t *)d_iq, b->nsamp, b->d_dig.p);
+        hipLaunchKernelGGL(k_block_digest, dim3((unsigned)chunks, (unsigned)pl.nblocks), dim3(256), 0, sc, (const uint32_t *)d_iq, pl.nsamp, b->d_dig.p);
     }
     HIPCHK(h, hipGetLastError());
     return GPSBB_OK;
@@ -2384,12 +2025,13 @@ static int synth_launch(gpsbb_batch *b, const BatchDev &p, hipStream_t sc, int16
 /* One run of a batch: its timing events, the pre-pass on a pre-pass stream, the synthesis on a synthesis stream behind it. */
 static int batch_launch(gpsbb_batch *b, int16_t *d_iq)
 {
+    const BatchPlan &pl = b->plan;
     gpsbb *h = b->h;
-    const int set = (int)(b->run_count % (unsigned)b->nsets);
+    const int set = (int)(b->run_count % (unsigned)pl.nsets);
     TableSet &ts = b->sets[set];
     b->fix.epoch++; /* a number no earlier launch of this batch handed to k_chain_fix_par */
     if (b->want_digest)
-        HIPCHK(h, (hipError_t)b->d_dig.reserve((size_t)b->nblocks));
+        HIPCHK(h, (hipError_t)b->d_dig.reserve((size_t)pl.nblocks));
     const BatchDev p = batch_dev(b, ts);
     const bool timed = !b->one_stream;
     hipEvent_t *ev = nullptr;
@@ -2402,7 +2044,7 @@ static int batch_launch(gpsbb_batch *b, int16_t *d_iq)
      * read this table set has finished, i.e. it overlaps the synthesis of the runs before it.  With three sets
      * consecutive runs take the handle's two seeding streams in turn, so that two pre-passes are in flight. */
     hipStream_t ss = nullptr;
-    HIPCHK(h, batch_prepass_stream(b, b->chain_dev, &ss));
+    HIPCHK(h, batch_prepass_stream(b, pl.chain_dev, &ss));
     /* (a push's set-up uploaded on this very stream: in order already, and no wait packet ahead of the plan kernel) */
     if (b->upload_done && b->upload_stream != ss)
         HIPCHK(h, hipStreamWaitEvent(ss, b->upload_done, 0));
@@ -2417,7 +2059,7 @@ static int batch_launch(gpsbb_batch *b, int16_t *d_iq)
     HIPCHK(h, hipGetLastError());
     if (timed)
         HIPCHK(h, hipEventRecord(ev[1], ss));
-    h->last_prepass = b->host_seed ? 2 : (b->ev && b->laps ? 3 : 1);
+    h->last_prepass = pl.host_seed ? 2 : (pl.ev && pl.laps ? 3 : 1);
     PUSH_MARK("l_pre");
 
     /* off by default: +2 % on a stream of pushes, but overlapping kernels make the per-launch time (the roofline figure)
@@ -2426,7 +2068,7 @@ static int batch_launch(gpsbb_batch *b, int16_t *d_iq)
     /* consecutive launches take the two synthesis streams in turn — they work on different table sets (or, slots of
      * a ring, different batches) — except re-runs of a batch that has a single table set */
     hipStream_t sc = h->s_compute;
-    if (!one_cs && !b->one_stream && (b->nsets >= 2 || b->max_sets == 1) && ((h->compute_turn++) & 1u)) {
+    if (!one_cs && !b->one_stream && (pl.nsets >= 2 || b->max_sets == 1) && ((h->compute_turn++) & 1u)) {
         if (!h->s_compute2)
             HIPCHK(h, hipStreamCreateWithFlags(&h->s_compute2, hipStreamNonBlocking));
         sc = h->s_compute2;
@@ -2435,11 +2077,11 @@ static int batch_launch(gpsbb_batch *b, int16_t *d_iq)
     if (sc != ss)
         HIPCHK(h, hipStreamWaitEvent(sc, ev[1], 0));
     if (!ctr_reset_by_prepass)
-        HIPCHK(h, hipMemsetAsync(p.tile_ctr, 0, ((size_t)b->nblocks + 1) * sizeof(int32_t), sc));
+        HIPCHK(h, hipMemsetAsync(p.tile_ctr, 0, ((size_t)pl.nblocks + 1) * sizeof(int32_t), sc));
     if (timed)
         HIPCHK(h, hipEventRecord(ev[2], sc));
     if (b->want_digest)
-        HIPCHK(h, hipMemsetAsync(b->d_dig.p, 0, (size_t)b->nblocks * sizeof(unsigned long long), sc));
+        HIPCHK(h, hipMemsetAsync(b->d_dig.p, 0, (size_t)pl.nblocks * sizeof(unsigned long long), sc));
     rc = synth_launch(b, p, sc, d_iq);
     if (rc != GPSBB_OK)
         return rc;
@@ -2463,7 +2105,7 @@ extern "C" int gpsbb_batch_run(gpsbb_batch_t *b, int16_t *d_iq)
     gpsbb *h = b->h;
     HIPCHK(h, hipSetDevice(h->device));
     if (!d_iq) {
-        HIPCHK(h, (hipError_t)b->d_iq.reserve((size_t)b->nblocks * b->nsamp * 2));
+        HIPCHK(h, (hipError_t)b->d_iq.reserve((size_t)b->plan.nblocks * b->plan.nsamp * 2));
         d_iq = b->d_iq.p;
         b->last_iq = d_iq;
     } else {
@@ -2503,7 +2145,7 @@ extern "C" int gpsbb_batch_read(gpsbb_batch_t *b, int16_t *iq_out, gpsbb_chan_st
         HIPCHK(h, hipMemcpy(iq_out, src, gpsbb_batch_iq_bytes(b), hipMemcpyDeviceToHost));
     }
     if (end_state)
-        HIPCHK(h, hipMemcpy(end_state, b->sets[b->last_set].end.p, (size_t)b->nblocks * b->nch * sizeof(gpsbb_chan_state_t),
+        HIPCHK(h, hipMemcpy(end_state, b->sets[b->last_set].end.p, (size_t)b->plan.nblocks * b->plan.nch * sizeof(gpsbb_chan_state_t),
                             hipMemcpyDeviceToHost));
     return GPSBB_OK;
 }
@@ -3306,9 +2948,10 @@ static int batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, 
     if (!b)
         return GPSBB_E_BADARG;
     gpsbb *h = b->h;
+    const BatchPlan &pl = b->plan;
     int shift8 = 0;
     ImpairCall ic;
-    if (!impair_make(nz, set, (uint64_t)b->nblocks * (uint64_t)b->nsamp, &ic))
+    if (!impair_make(nz, set, (uint64_t)pl.nblocks * (uint64_t)pl.nsamp, &ic))
         return GPSBB_E_BADARG;
     /* (nothing is packed here, so SC1 takes any nsamp: the format is looked up for a length it accepts) */
     const int fmt = (view & ~(GPSBB_OUT_FORMAT_MASK | GPSBB_OUT_SHIFT_MASK)) ? -1 : out_format(view, 4, &shift8);
@@ -3326,7 +2969,7 @@ static int batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, 
         return GPSBB_E_STATE;
     /* the two limits of this call: the accumulator's batches, and runs of the per-sample kernel, which leave rows and no
      * tile states */
-    if ((b->flags & GPSBB_FIXED_CARRIER) || !b->ev)
+    if ((pl.flags & GPSBB_FIXED_CARRIER) || !pl.ev)
         return GPSBB_E_BADARG;
     const int16_t *src = d_iq ? d_iq : b->last_iq;
     if (!src)
@@ -3337,13 +2980,13 @@ static int batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, 
         return rc;
     if (nz)
         HIPCHK(h, noise_ready(h));
-    const long nseg = gpsbb_despread_segments(b->nsamp, seg_tiles);
-    const size_t nsum = (size_t)b->nblocks * b->nch * (size_t)nseg * (size_t)(lags ? nlags : 1) * 2;
+    const long nseg = gpsbb_despread_segments(pl.nsamp, seg_tiles);
+    const size_t nsum = (size_t)pl.nblocks * pl.nch * (size_t)nseg * (size_t)(lags ? nlags : 1) * 2;
     HIPCHK(h, (hipError_t)b->d_ds.reserve(nsum + 1));
-    HIPCHK(h, (hipError_t)b->d_ds_ctr.reserve((size_t)b->nblocks));
+    HIPCHK(h, (hipError_t)b->d_ds_ctr.reserve((size_t)pl.nblocks));
     hipStream_t cs = h->s_compute;
     HIPCHK(h, hipMemsetAsync(b->d_ds.p, 0, (nsum + 1) * sizeof(unsigned long long), cs));
-    HIPCHK(h, hipMemsetAsync(b->d_ds_ctr.p, 0, (size_t)b->nblocks * sizeof(int32_t), cs));
+    HIPCHK(h, hipMemsetAsync(b->d_ds_ctr.p, 0, (size_t)pl.nblocks * sizeof(int32_t), cs));
     const BatchDev p = batch_dev(b, b->sets[b->last_set]);
     DsArgs &a = al.d;
     a.iq = reinterpret_cast<const uint32_t *>(src);
@@ -3355,12 +2998,12 @@ static int batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, 
     /* a chunk never spans more segments than it must, and small batches hand their tiles out one at a time */
     const long cus = h->sm_count > 0 ? h->sm_count : 256;
     int chunk = seg_tiles < DS_CHUNK ? seg_tiles : DS_CHUNK;
-    while (chunk > 1 && (long)b->nblocks * (((long)b->ntiles + chunk - 1) / chunk) < cus * 8 * DS_WAVES)
+    while (chunk > 1 && (long)pl.nblocks * (((long)pl.ntiles + chunk - 1) / chunk) < cus * 8 * DS_WAVES)
         chunk--;
     a.chunk = chunk;
-    const long chunks = ((long)b->ntiles + chunk - 1) / chunk;
+    const long chunks = ((long)pl.ntiles + chunk - 1) / chunk;
     const long max_useful = (chunks + DS_WAVES - 1) / DS_WAVES;
-    long want = (cus * 16 + b->nblocks - 1) / b->nblocks;
+    long want = (cus * 16 + pl.nblocks - 1) / pl.nblocks;
     want = want < 1 ? 1 : (want > max_useful ? max_useful : want);
     a.wgs_per_block = (int)want;
     a.shift8 = shift8;
@@ -3374,7 +3017,7 @@ static int batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, 
             HIPCHK(h, hipEventCreate(&e));
     HIPCHK(h, hipEventRecord(b->ds_ev[0], cs));
 #endif
-    const dim3 grid((unsigned)(want * b->nblocks));
+    const dim3 grid((unsigned)(want * pl.nblocks));
     if (lags)
         hipLaunchKernelGGL(dsl_kernel(fmt, nz != nullptr, p.st_log2, set != nullptr), grid, dim3(DS_WG), 0, cs, p, al);
     else
@@ -3557,7 +3200,7 @@ static int fill_block_impl(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, double d
         HIPCHK(h, noise_ready(h));
     g_push_trace.start();
     b->one_stream = GPSBB_KNOB_LONG("GPSBB_FILL_ONE_STREAM", 1) != 0;
-    int rc = batch_setup(b, ch, 1, nch, delt, nsamp, flags & GPSBB_FIXED_CARRIER, b->one_stream ? h->s_compute : h->s_seed);
+    int rc = batch_setup(b, PlanIn{ch, 1, nch, delt, nsamp, flags & GPSBB_FIXED_CARRIER}, plan_opts(h, b->max_sets), b->one_stream ? h->s_compute : h->s_seed);
     if (rc != GPSBB_OK)
         return rc;
     PUSH_MARK("set-up");
@@ -3973,7 +3616,11 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
      * push to push, exactly.  Where that is resolved is decided per push below (on the device: gpsbb_walk.hip.h). */
     unsigned run_flags = s->flags & (GPSBB_CHAIN_CARRIER | GPSBB_FIXED_CARRIER);
     const size_t nbc = (size_t)s->bps * s->nch;
-    b->d_carry = nullptr;
+    const PlanOpts opts = plan_opts(h, b->max_sets);
+    PlanIn in{ch, s->bps, s->nch, s->delt, s->nsamp, run_flags};
+    BatchPlan begun; /* the plan's first step, where the decision below had to take it */
+    bool have_begun = false;
+    StreamLink link; /* what this push lends the slot's batch */
     /* the host's chaining state only moves on once every enqueue of this push has succeeded */
     ChainCarry carry_next;
     bool carry_host = false;
@@ -3990,20 +3637,24 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
          * blocks, the phase carried from push to push in device memory; for either synthesis kernel), on host
          * threads — sequential per channel — for pushes small enough to be seeded on the host.  A stream may
          * change sides between pushes: the carry then moves across, which costs a synchronisation. */
-        const size_t host_lim = (size_t)GPSBB_KNOB_LONG("GPSBB_HOST_SEED_MAX", HOST_SEED_MAX_CHANNELS);
-        const bool dev_only = GPSBB_KNOB_SET("GPSBB_DEVICE_SEED_ONLY");
         /* (small pushes too where the lap-parallel pre-pass will take them: it costs less than the host threads) */
         /* (... which it only does for blocks the model kernels render: the kernel plan's own test, here, before the push is promised
          * the device-side chain — a small push of a 1 MS/s stream, which they decline, stays with the host threads instead of the
          * row walks' milliseconds) */
-        bool small_on_dev = nbc <= host_lim && h->opt_seed_where == 0 && h->opt_synth_kernel != 1 && h->opt_chain_where == 0 &&
-                            !GPSBB_KNOB_SET("GPSBB_NO_LAPS") && lap_eligible(ch, nbc, s->delt, false);
+        /* (the plan's own steps, asked once: what plan_begin leaves is handed on to batch_setup below — these conditions imply the
+         * device side, so the descriptors and flags are the ones the rest of the plan is made for) */
+        bool small_on_dev = nbc <= opts.host_seed_max && opts.seed_where == 0 && opts.synth_kernel != 1 && opts.chain_where == 0 &&
+                            plan_laps_admit(in, opts);
         if (small_on_dev) {
-            std::vector<EvConst> probe;
-            small_on_dev = ev_plan(ch, s->bps, s->nch, s->delt, probe);
+            const int rc_ = plan_begin(begun, b->img, in, opts);
+            if (rc_ != GPSBB_OK)
+                return rc_;
+            have_begun = true;
+            small_on_dev = begun.ev;
         }
-        const bool dev = h->opt_chain_where != 1 &&
-                         (h->opt_seed_where == 1 || h->opt_seed_where == 3 || (h->opt_seed_where == 0 && (dev_only || nbc > host_lim || small_on_dev)));
+        const bool dev = opts.chain_where != 1 &&
+                         (opts.seed_where == 1 || opts.seed_where == 3 ||
+                          (opts.seed_where == 0 && (opts.device_seed_only || nbc > opts.host_seed_max || small_on_dev)));
         if (!s->carry) {
             s->carry = new (std::nothrow) ChainCarry();
             if (!s->carry)
@@ -4034,12 +3685,12 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
             }
             s->carry_on_device = true;
             memcpy(rough_next, s->rough_phase, sizeof rough_next);
-            b->d_carry = s->d_carry;
-            b->carry_prn = s->last_prn;
-            b->carry_phase = rough_next;
-            b->ev_prefix = s->ev_prefix;
-            b->ev_fix = s->ev_fix;
-            b->stream_turn = (unsigned)s->head;
+            link.d_carry = s->d_carry;
+            link.carry_prn = s->last_prn;
+            link.carry_phase = rough_next;
+            link.ev_prefix = s->ev_prefix;
+            link.ev_fix = s->ev_fix;
+            link.stream_turn = (unsigned)s->head;
         } else {
             if (s->carry_on_device) {
                 /* device -> host */
@@ -4063,36 +3714,42 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
                 s->seeded[k].carr_phase = s->seeds[k];
             ch = s->seeded.data();
             run_flags &= ~GPSBB_CHAIN_CARRIER;
+            in.ch = ch; /* the plan is taken on the rewritten descriptors */
+            in.flags = run_flags;
+            have_begun = false;
         }
     }
-    if (!b->d_carry)
+    if (!link.d_carry)
         memcpy(rough_next, s->rough_phase, sizeof rough_next);
     /* the slot's previous D2H copy was waited for by the pop that freed it */
     const bool fx_chain = (s->flags & GPSBB_FIXED_CARRIER) && (s->flags & GPSBB_CHAIN_CARRIER) && s->head > 0;
-    b->fixed_prev_prn = fx_chain ? s->fx_prn : nullptr;
-    b->fixed_prev_phase = fx_chain ? s->fx_phase : nullptr;
+    link.fixed_prev_prn = fx_chain ? s->fx_prn : nullptr;
+    link.fixed_prev_phase = fx_chain ? s->fx_phase : nullptr;
+    /* the batch holds the link for the length of this push: set-up and launch read it */
+    struct Unlink {
+        gpsbb_batch *b;
+        ~Unlink() { b->link = StreamLink(); }
+    } unlink{b};
+    b->link = link;
     PUSH_MARK("plan");
     /* descriptors and plans go up on the stream that will run this push's pre-pass (a push promised the device-side chain gets it,
      * or fails below) */
     hipStream_t us = nullptr;
-    HIPCHK(h, batch_prepass_stream(b, b->d_carry != nullptr, &us));
-    int rc = batch_setup(b, ch, s->bps, s->nch, s->delt, s->nsamp, run_flags, us);
+    HIPCHK(h, batch_prepass_stream(b, b->link.d_carry != nullptr, &us));
+    int rc = batch_setup(b, in, opts, us, have_begun ? &begun : nullptr);
     PUSH_MARK("setup");
-    b->fixed_prev_prn = nullptr;
-    b->fixed_prev_phase = nullptr;
-    if (rc != GPSBB_OK) {
-        b->d_carry = nullptr;
+    if (rc != GPSBB_OK)
         return rc;
-    }
-    if (b->d_carry && !b->chain_dev) { /* the push was promised a device-side chain */
-        b->d_carry = nullptr;
+    /* The push was promised a device-side chain.  Unreachable: a carry keeps plan_placement from seeding on the host whatever
+     * the size, the carry is only lent where GPSBB_OPT_CHAIN_WHERE is not 1, and a chained IEEE batch with a carry is
+     * `chained` there — so chain_dev follows.  Kept in case a later plan step breaks that. */
+    if (link.d_carry && !b->plan.chain_dev)
         return GPSBB_E_INTERNAL;
-    }
     if (s->flags & GPSBB_FIXED_CARRIER)
         for (int i = 0; i < s->nch; i++) {
             const size_t k = (size_t)(s->bps - 1) * s->nch + i;
             fx_prn_next[i] = ch[k].prn > 0 ? ch[k].prn : 0;
-            fx_phase_next[i] = b->h_kph0[k] + (uint32_t)s->nsamp * (uint32_t)b->h_kstep[k];
+            fx_phase_next[i] = b->img.h_kph0[k] + (uint32_t)s->nsamp * (uint32_t)b->img.h_kstep[k];
         }
     b->last_iq = b->d_iq.p;
     /* From here on kernels of this push may be in the queues (with the device-side chain they advance the carry in
@@ -4110,7 +3767,6 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
     sl.has_lvl = false;
     rc = batch_launch(b, b->d_iq.p);
     PUSH_MARK("launch");
-    b->d_carry = nullptr;
     if (rc != GPSBB_OK)
         return rc;
     PUSH_MARK("rec");
@@ -4686,7 +4342,8 @@ extern "C" int gpsbb_test_model_err(gpsbb_batch_t *b, double *maxima, unsigned l
     if (!b || !maxima || !counts)
         return GPSBB_E_BADARG;
     gpsbb *h = b->h;
-    if (!b->ran || !b->ev)
+    const BatchPlan &pl = b->plan;
+    if (!b->ran || !pl.ev)
         return GPSBB_E_STATE; /* only the model kernels have a model */
     const int rc = gpsbb_sync(h);
     if (rc != GPSBB_OK)
@@ -4699,9 +4356,9 @@ extern "C" int gpsbb_test_model_err(gpsbb_batch_t *b, double *maxima, unsigned l
     HIPCHK(h, hipMalloc((void **)&d_cnt, cnt_bytes));
     HIPCHK(h, hipMemsetAsync(d_mx, 0, mx_bytes, h->s_compute));
     HIPCHK(h, hipMemsetAsync(d_cnt, 0, cnt_bytes, h->s_compute));
-    const size_t threads = (size_t)b->nblocks * b->nch * b->ntiles;
+    const size_t threads = (size_t)pl.nblocks * pl.nch * pl.ntiles;
     const dim3 grid((unsigned)((threads + 255) / 256));
-    if (b->ev_all_dense)
+    if (pl.ev_all_dense)
         hipLaunchKernelGGL(k_model_err_pd, grid, dim3(256), 0, h->s_compute, p, d_mx, d_cnt);
     else
         hipLaunchKernelGGL(k_model_err_ev, grid, dim3(256), 0, h->s_compute, p, d_mx, d_cnt);
@@ -4712,7 +4369,7 @@ extern "C" int gpsbb_test_model_err(gpsbb_batch_t *b, double *maxima, unsigned l
     (void)hipFree(d_mx);
     (void)hipFree(d_cnt);
     if (which)
-        *which = b->ev_all_dense ? 2 : 1;
+        *which = pl.ev_all_dense ? 2 : 1;
     return GPSBB_OK;
 }
 
@@ -4723,27 +4380,77 @@ extern "C" int gpsbb_test_model_err(gpsbb_batch_t *b, double *maxima, unsigned l
 /* the state granule the batch's tables were built with (BatchDev::st_log2), or a negative error */
 extern "C" int gpsbb_test_state_log2(gpsbb_batch_t *b)
 {
-    return b ? b->st_log2 : GPSBB_E_BADARG;
+    return b ? b->plan.st_log2 : GPSBB_E_BADARG;
+}
+
+/* plan_batch on its own (no handle, no GPU): the BatchPlan scalars and a 64-bit FNV-1a of every image the plan defines for that
+ * batch (0: not one of them), in the order gpsbb_testhooks.h names */
+static unsigned long long fnv1a(const void *p, size_t n)
+{
+    unsigned long long h = 0xcbf29ce484222325ull;
+    for (size_t i = 0; i < n; i++)
+        h = (h ^ ((const uint8_t *)p)[i]) * 0x100000001b3ull;
+    return h;
+}
+
+template <class T>
+static unsigned long long fnv1a(const std::vector<T> &v, bool defined = true)
+{
+    return defined ? fnv1a(v.data(), v.size() * sizeof(T)) : 0ull;
+}
+
+extern "C" int gpsbb_test_plan(const gpsbb_chan_t *ch, int nblocks, int nch, double delt, int nsamp, unsigned flags, const int opt[5],
+                               int carry, const int *carry_prn, double *carry_phase, const int *fixed_prev_prn,
+                               const uint32_t *fixed_prev_phase, unsigned long long out[GPSBB_TEST_PLAN_NQ])
+{
+    if (!opt || !out)
+        return GPSBB_E_BADARG;
+    static ChainCarryDev none; /* (a carry is present or not: the plan never looks inside) */
+    StreamLink lk;
+    lk.d_carry = carry ? &none : nullptr;
+    lk.carry_prn = carry_prn;
+    lk.carry_phase = carry_phase;
+    lk.fixed_prev_prn = fixed_prev_prn;
+    lk.fixed_prev_phase = fixed_prev_phase;
+    BatchPlan pl;
+    PlanImages img;
+    const int rc = plan_batch(pl, img, PlanIn{ch, nblocks, nch, delt, nsamp, flags}, plan_opts(opt[0], opt[1], opt[2] != 0, opt[3], opt[4]), lk);
+    if (rc != GPSBB_OK)
+        return rc;
+    const bool fixed = (pl.flags & GPSBB_FIXED_CARRIER) != 0, walks = pl.chain_dev && !pl.laps;
+    const unsigned long long v[GPSBB_TEST_PLAN_NQ] = {
+        (unsigned long long)pl.nblocks, (unsigned long long)pl.nch, (unsigned long long)pl.nsamp, (unsigned long long)pl.ntiles,
+        fnv1a(&pl.delt, sizeof pl.delt), pl.flags, pl.ev, pl.ev_dense, pl.ev_all_dense, pl.laps, pl.host_seed,
+        (unsigned long long)pl.st_log2, (unsigned long long)pl.nstates, pl.chain_dev, pl.chain_starts, pl.chain_indep, pl.chain_model,
+        pl.chain_fix_seq, (unsigned long long)pl.nseg, (unsigned long long)pl.seg_tiles, (unsigned long long)pl.fix_wg,
+        (unsigned long long)pl.fix_chunks, (unsigned long long)pl.nsets, pl.total_rows, (unsigned long long)pl.carr_lanes,
+        (unsigned long long)pl.chain_lanes, pl.cont0_mask, pl.laps ? fnv1a(pl.lap_chunk0, sizeof pl.lap_chunk0) : 0ull,
+        fnv1a(img.h_ch), fnv1a(img.h_evc, pl.ev), fnv1a(img.row_off), fnv1a(img.h_kph0, fixed), fnv1a(img.h_kstep, fixed),
+        fnv1a(img.h_cd, walks), fnv1a(img.h_start0, walks), fnv1a(img.h_seed_order), fnv1a(img.h_chain_order, pl.chain_starts),
+        carry && carry_phase ? fnv1a(carry_phase, (size_t)pl.nch * sizeof(double)) : 0ull};
+    memcpy(out, v, sizeof v);
+    return GPSBB_OK;
 }
 
 extern "C" int gpsbb_test_table_digest(gpsbb_batch_t *b, unsigned long long out[3])
 {
-    if (!b || !out || !b->ran || !b->ev)
+    if (!b || !out || !b->ran || !b->plan.ev)
         return GPSBB_E_STATE;
     gpsbb *h = b->h;
+    const BatchPlan &pl = b->plan;
     const int rc = gpsbb_sync(h);
     if (rc != GPSBB_OK)
         return rc;
     const BatchDev p = batch_dev(b, b->sets[b->last_set]);
     auto mix = [](unsigned long long z) { z ^= z >> 31; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 29; return z; };
-    const size_t nst = (size_t)b->nstates;
-    const size_t nx = (size_t)b->nblocks * 2 * b->nch * nst, nn = (size_t)b->nblocks * b->nch * nst, ne = (size_t)b->nblocks * b->nch;
+    const size_t nst = (size_t)pl.nstates;
+    const size_t nx = (size_t)pl.nblocks * 2 * pl.nch * nst, nn = (size_t)pl.nblocks * pl.nch * nst, ne = (size_t)pl.nblocks * pl.nch;
     /* The states keyed by the tile t they start: every tile's, but for a batch that k_synth_ev renders — whose tables hold one state
      * per granule behind the lap-parallel pre-pass (BatchDev::st_log2) and one per tile behind the row walks — those of the tiles that
      * start a granule of the size the lap-parallel pre-pass would use: the two pre-passes' tables digest alike where they agree, and
      * every other batch's are compared tile by tile */
-    const int dg = b->ev_dense || (b->flags & GPSBB_FIXED_CARRIER) ? 0 : (int)GPSBB_KNOB_LONG("GPSBB_EV_STATE_LOG2", GPSBB_EV_STATE_LOG2);
-    const int tstep = 1 << (dg > b->st_log2 ? dg : b->st_log2);
+    const int dg = pl.ev_dense || (pl.flags & GPSBB_FIXED_CARRIER) ? 0 : (int)GPSBB_KNOB_LONG("GPSBB_EV_STATE_LOG2", GPSBB_EV_STATE_LOG2);
+    const int tstep = 1 << (dg > pl.st_log2 ? dg : pl.st_log2);
     std::vector<unsigned long long> hx(nx);
     std::vector<uint32_t> hn(nn);
     std::vector<gpsbb_chan_state_t> he(ne);
@@ -4757,15 +4464,15 @@ extern "C" int gpsbb_test_table_digest(gpsbb_batch_t *b, unsigned long long out[
     for (size_t k = 0; k < ne; k++) {
         if (hc[k].prn <= 0)
             continue;
-        const size_t blk = k / (size_t)b->nch, i = k % (size_t)b->nch;
+        const size_t blk = k / (size_t)pl.nch, i = k % (size_t)pl.nch;
         for (int kind = 0; kind < 2; kind++)
-            for (int t = 0; t < b->ntiles; t += tstep) {
-                const size_t at = (blk * 2 * b->nch + 2 * i + kind) * (size_t)b->ntiles + t;
-                out[0] += mix(hx[(blk * 2 * b->nch + 2 * i + kind) * nst + (t >> b->st_log2)] + 0x9E3779B97F4A7C15ull * (at + 1));
+            for (int t = 0; t < pl.ntiles; t += tstep) {
+                const size_t at = (blk * 2 * pl.nch + 2 * i + kind) * (size_t)pl.ntiles + t;
+                out[0] += mix(hx[(blk * 2 * pl.nch + 2 * i + kind) * nst + (t >> pl.st_log2)] + 0x9E3779B97F4A7C15ull * (at + 1));
             }
-        for (int t = 0; t < b->ntiles; t += tstep) {
-            const size_t at = k * (size_t)b->ntiles + t;
-            out[1] += mix((unsigned long long)(hn[k * nst + (t >> b->st_log2)] & 3u) + 0x9E3779B97F4A7C15ull * (at + 1));
+        for (int t = 0; t < pl.ntiles; t += tstep) {
+            const size_t at = k * (size_t)pl.ntiles + t;
+            out[1] += mix((unsigned long long)(hn[k * nst + (t >> pl.st_log2)] & 3u) + 0x9E3779B97F4A7C15ull * (at + 1));
         }
         unsigned long long w[5];
         memcpy(w, &he[k], sizeof w);

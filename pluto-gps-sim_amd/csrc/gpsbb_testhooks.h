@@ -33,6 +33,20 @@ double gpsbb_test_carr_predict(double x0, double s, int n);
  * model kernels with GPSBB_FIXED_CARRIER */
 double gpsbb_test_fixed_tile_index(unsigned ph0, int step, int t);
 
+/* plan_batch (gpsbb.hip) on given descriptors, options and stream carry: what a batch's set-up would decide, without a handle.
+ * opt: GPSBB_OPT_SEED_WHERE, _SYNTH_KERNEL, _SKIP_SEED, _CHAIN_WHERE and the batch's table sets at most (a ring slot: 1; else 6).
+ * carry: the stream lends its carry (carry_prn, carry_phase in/out as gpsbb_stream_push passes them); fixed_prev_*: the
+ * accumulator's chaining state, or NULL.  out: nblocks, nch, nsamp, ntiles, hash(delt), flags, ev, ev_dense, ev_all_dense, laps,
+ * host_seed, st_log2, nstates, chain_dev, chain_starts, chain_indep, chain_model, chain_fix_seq, nseg, seg_tiles, fix_wg,
+ * fix_chunks, nsets, total_rows, carr_lanes, chain_lanes, cont0_mask, then the 64-bit FNV-1a (0: the plan defines none) of
+ * lap_chunk0, h_ch, h_evc, row_off, h_kph0, h_kstep, h_cd, h_start0, h_seed_order, the chain order, carry_phase afterwards.
+ * Returns GPSBB_OK or the error batch set-up would return. */
+#define GPSBB_TEST_PLAN_NQ 38
+struct gpsbb_chan;
+int gpsbb_test_plan(const struct gpsbb_chan *ch, int nblocks, int nch, double delt, int nsamp, unsigned flags, const int opt[5],
+                    int carry, const int *carry_prn, double *carry_phase, const int *fixed_prev_prn,
+                    const uint32_t *fixed_prev_phase, unsigned long long out[GPSBB_TEST_PLAN_NQ]);
+
 /* The error budgets of the model kernels, measured (gpsbb_modelerr.hip.h): the realised |model - truth| of everything
  * k_synth_ev / k_synth_pd test, over every tile of the batch's last run, per channel index.  Needs a GPU. */
 #define GPSBB_TEST_ME_NQ 11  /* maxima per channel: y0, y0/W, tk, tk/W, x0, x0/W, tc, tc/W, pure_y, pure_x, W (units of 2^-32) */

@@ -120,7 +120,7 @@ def test_every_block_matches_the_cpu_runner(fixed):
 # Rate x MAX_CHAN x carrier: block lengths that are not multiples of 1024 or 2048 (a partial last tile, a partial last state
 # granule), 302 blocks (the 30-s maintenance after block 299, and a block after the first one it seeds), and the kernel and
 # pre-pass each rate must take.  GPSBB_INFO_LAST_KERNEL tells the per-sample kernel from the model kernels only; the last
-# column names the model kernel the library's plan (batch_setup in gpsbb.hip) gives the rate: k_synth_pd where every channel
+# column names the model kernel the library's plan (plan_kernel in gpsbb_plan.h) gives the rate: k_synth_pd where every channel
 # is evaluated per sample (2.6, 3 MS/s), k_synth_ev_dense where only some are (the mixed band at 15.5 * 1.023 MS/s),
 # k_synth_ev above it, k_synth_ev_fixed for the 32-bit carrier.  The laps do not serve the per-sample kernel (1 MS/s): one
 # block of 12-16 channels is then seeded on host threads.

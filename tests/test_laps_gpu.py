@@ -232,6 +232,28 @@ def test_a_small_chained_stream_at_a_rate_the_laps_decline(pkg, fresh, oracle):
     assert (np.concatenate(got).reshape(want_iq.shape) == want_iq).all()
 
 
+def test_a_small_chained_stream_changes_sides_for_one_push(pkg, fresh, oracle):
+    """gpsbb_stream_push takes its decision from the plan's own steps (plan_laps_admit, plan_begin: csrc/gpsbb.hip) and hands what
+    they computed on to the set-up.  A small chained stream the laps keep on the device; its third push carries one channel whose
+    carrier step is not zero and below 2^-50 cycles per sample, which the laps decline: that push goes to the host threads, the
+    carry crosses to the host for it and back for the fourth.  All five pushes are the oracle's chain, IQ and end states."""
+    s = fresh
+    nch, bps, pushes, nsamp, fs = 4, 2, 5, 4096, 25e6
+    ch = pkg.synth_descriptors(bps * pushes, nch=nch, seed=93)
+    ch["f_carr"][2 * bps:3 * bps, 1] = 1e-9  # |f_carr / fs| = 4e-17 < 2^-50
+    want_iq, want_st, _ = oracle.fill_blocks(ch, 1 / fs, nsamp, chain=True)
+    st = s.stream(nch, 1 / fs, nsamp, bps, depth=2, flags=pkg.CHAIN_CARRIER)
+    for k in range(pushes):
+        st.push(ch[k * bps:(k + 1) * bps])
+        where = (s.info(pkg.INFO_PREPASS), s.info(pkg.INFO_CHAIN_ON_DEVICE))
+        assert where == ((2, 0) if k == 2 else (3, 1)), (k, where)
+        iq, es = st.pop(copy=True)
+        assert (np.asarray(iq).reshape(bps, nsamp, 2) == want_iq[k * bps:(k + 1) * bps]).all(), k
+        for f in ("carr_phase", "code_phase", "iword", "ibit", "icode"):
+            assert es[f].tobytes() == want_st[f][k * bps:(k + 1) * bps].tobytes(), (k, f)
+    st.close()
+
+
 @pytest.mark.parametrize("where", [3, 1])
 def test_the_null_stream_owns_nothing(pkg, where):
     """Round 4's race — a fresh stream's carry cleared by a null-stream memset that the library's non-blocking streams do not

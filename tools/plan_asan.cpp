@@ -1,0 +1,41 @@
+// plan_batch (csrc/gpsbb_plan.h) under the host sanitizers, on a machine without a GPU: the matrix of tests/test_batch_plan.py, as
+// `python tests/batch_plan_cases.py FILE` writes it, through gpsbb_test_plan; prints what the test compares, one line per set-up.
+//   hipcc --offload-arch=gfx950 -std=c++17 -ffp-contract=off -DGPSBB_EXPERIMENTS -Xarch_host -fsanitize=address,undefined \
+//         -Ipluto-gps-sim_amd/csrc -Iinclude tools/plan_asan.cpp pluto-gps-sim_amd/csrc/gpsbb_node.cpp -o plan_asan
+//   ./plan_asan FILE
+// Never loaded into Python, never run on a GPU: nothing here makes a HIP call.
+#include "../pluto-gps-sim_amd/csrc/gpsbb.hip"
+
+struct Record { // one set-up; `first`: the case's first push (the carry's rough phases start from zero)
+    int32_t nblocks, nch, nsamp, first, opt[5], carry, fixed_prev, carry_prn[GPSBB_MAX_CHAN], fx_prn[GPSBB_MAX_CHAN];
+    uint32_t flags, fx_phase[GPSBB_MAX_CHAN];
+    double delt;
+};
+
+int main(int argc, char **argv)
+{
+    FILE *f = argc > 1 ? fopen(argv[1], "rb") : nullptr;
+    if (!f)
+        return 2;
+    Record r;
+    double rough[GPSBB_MAX_CHAN] = {0};
+    long n = 0;
+    while (fread(&r, sizeof r, 1, f) == 1) {
+        std::vector<gpsbb_chan_t> ch((size_t)r.nblocks * r.nch);
+        if (fread(ch.data(), sizeof(gpsbb_chan_t), ch.size(), f) != ch.size())
+            return 3;
+        if (r.first)
+            memset(rough, 0, sizeof rough);
+        unsigned long long out[GPSBB_TEST_PLAN_NQ];
+        const int rc = gpsbb_test_plan(ch.data(), r.nblocks, r.nch, r.delt, r.nsamp, r.flags, r.opt, r.carry, r.carry ? r.carry_prn : nullptr,
+                                       r.carry ? rough : nullptr, r.fixed_prev ? r.fx_prn : nullptr, r.fixed_prev ? r.fx_phase : nullptr, out);
+        printf("%d", rc);
+        for (int i = 0; rc == GPSBB_OK && i < GPSBB_TEST_PLAN_NQ; i++)
+            printf(" %llx", out[i]);
+        printf("\n");
+        n++;
+    }
+    fclose(f);
+    fprintf(stderr, "plan_asan: %ld set-ups\n", n);
+    return 0;
+}
