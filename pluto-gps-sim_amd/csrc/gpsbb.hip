@@ -4382,6 +4382,11 @@ extern "C" int gpsbb_test_state_log2(gpsbb_batch_t *b)
 {
     return b ? b->plan.st_log2 : GPSBB_E_BADARG;
 }
+/* ... and the carrier rows' (ev_carr_log2 of it) */
+extern "C" int gpsbb_test_state_log2_carr(gpsbb_batch_t *b)
+{
+    return b ? ev_carr_log2(b->plan.st_log2) : GPSBB_E_BADARG;
+}
 
 /* plan_batch on its own (no handle, no GPU): the BatchPlan scalars and a 64-bit FNV-1a of every image the plan defines for that
  * batch (0: not one of them), in the order gpsbb_testhooks.h names */
@@ -4448,9 +4453,11 @@ extern "C" int gpsbb_test_table_digest(gpsbb_batch_t *b, unsigned long long out[
     /* The states keyed by the tile t they start: every tile's, but for a batch that k_synth_ev renders — whose tables hold one state
      * per granule behind the lap-parallel pre-pass (BatchDev::st_log2) and one per tile behind the row walks — those of the tiles that
      * start a granule of the size the lap-parallel pre-pass would use: the two pre-passes' tables digest alike where they agree, and
-     * every other batch's are compared tile by tile */
+     * every other batch's are compared tile by tile.  The granule is per kind: a carrier row's is ev_carr_log2 of the code's, in the
+     * tables and in the key alike */
     const int dg = pl.ev_dense || (pl.flags & GPSBB_FIXED_CARRIER) ? 0 : (int)GPSBB_KNOB_LONG("GPSBB_EV_STATE_LOG2", GPSBB_EV_STATE_LOG2);
     const int tstep = 1 << (dg > pl.st_log2 ? dg : pl.st_log2);
+    const int gc = ev_carr_log2(pl.st_log2), tstep_carr = 1 << ev_carr_log2(dg > pl.st_log2 ? dg : pl.st_log2);
     std::vector<unsigned long long> hx(nx);
     std::vector<uint32_t> hn(nn);
     std::vector<gpsbb_chan_state_t> he(ne);
@@ -4466,9 +4473,10 @@ extern "C" int gpsbb_test_table_digest(gpsbb_batch_t *b, unsigned long long out[
             continue;
         const size_t blk = k / (size_t)pl.nch, i = k % (size_t)pl.nch;
         for (int kind = 0; kind < 2; kind++)
-            for (int t = 0; t < pl.ntiles; t += tstep) {
+            for (int t = 0; t < pl.ntiles; t += kind == NCO_CARR ? tstep_carr : tstep) {
                 const size_t at = (blk * 2 * pl.nch + 2 * i + kind) * (size_t)pl.ntiles + t;
-                out[0] += mix(hx[(blk * 2 * pl.nch + 2 * i + kind) * nst + (t >> pl.st_log2)] + 0x9E3779B97F4A7C15ull * (at + 1));
+                out[0] += mix(hx[(blk * 2 * pl.nch + 2 * i + kind) * nst + (t >> (kind == NCO_CARR ? gc : pl.st_log2))] +
+                              0x9E3779B97F4A7C15ull * (at + 1));
             }
         for (int t = 0; t < pl.ntiles; t += tstep) {
             const size_t at = k * (size_t)pl.ntiles + t;

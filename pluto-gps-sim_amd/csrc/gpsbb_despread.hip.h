@@ -69,24 +69,35 @@ __device__ __forceinline__ uint32_t ds_pair(int lo, int hi) { return ((uint32_t)
 /* index (bits 0-8) and sign (bit 9: the replica is negative) of sample n after the state (xt, yt) as the reference has them
  * (c:2697-2737): the exact jump-ahead, for the samples the model cannot vouch for.  nav: bit 0 the data bit in force at the
  * state's sample is -1, bit 1 the one after the next roll-over (at most one between a state and the end of its tiles). */
-__device__ __noinline__ uint32_t ds_exact_sample(double xt, double yt, double S, double sc, uint32_t down, uint32_t nav, int n,
-                                                 const uint32_t *chips)
+__device__ __forceinline__ uint32_t ds_exact_sample_body(double xt, double yt, double S, double sc, uint32_t down, uint32_t nav, int n,
+                                                         int ny, const uint32_t *chips)
 {
     int64_t wraps = 0;
     const double x = code_jump(xt, sc, (int64_t)n, &wraps);
     const uint32_t neg = wraps > 0 ? (nav >> 1) & 1u : nav & 1u;
-    const double cp = carr_jump(yt * (1.0 / 512.0), (down ? -S : S) * (1.0 / 512.0), (int64_t)n);
+    const double cp = carr_jump(yt * (1.0 / 512.0), (down ? -S : S) * (1.0 / 512.0), (int64_t)ny);
     const int it = (int)(cp * 512.0) & 511; /* c:2697; carr_phase == 1.0: index 512 defined as 0 */
     const int ci = (int)x;                  /* c:2737 */
     const uint32_t bit = (chips[(ci >> 5) & 31] >> (ci & 31)) & 1u;
     return (uint32_t)it | (((bit ^ 1u) ^ neg) << 9);
 }
+__device__ __noinline__ uint32_t ds_exact_sample(double xt, double yt, double S, double sc, uint32_t down, uint32_t nav, int n,
+                                                 const uint32_t *chips)
+{
+    return ds_exact_sample_body(xt, yt, S, sc, down, nav, n, n, chips);
+}
+/* ... behind a carrier granule that is not the code's (ev_carr_log2): the carrier state yt lies ny samples back, the code's n */
+__device__ __noinline__ uint32_t ds_exact_sample_2g(double xt, double yt, double S, double sc, uint32_t down, uint32_t nav, int n, int ny,
+                                                    const uint32_t *chips)
+{
+    return ds_exact_sample_body(xt, yt, S, sc, down, nav, n, ny, chips);
+}
 
 /* the model's index | sign << 9 of one sample, and whether it can be trusted */
-__device__ __forceinline__ uint32_t ds_model_sample(double nn, double S, double sc, double yg, double xg, uint32_t flip, uint32_t nav,
+__device__ __forceinline__ uint32_t ds_model_sample(double nn, double nny, double S, double sc, double yg, double xg, uint32_t flip, uint32_t nav,
                                                     const uint32_t *chips, uint32_t danger, bool &bad)
 {
-    const double y = __fma_rn(nn, S, yg), x = __fma_rn(nn, sc, xg);
+    const double y = __fma_rn(nny, S, yg), x = __fma_rn(nn, sc, xg);
     bad = min((uint32_t)__double2loint(y), (uint32_t)__double2loint(x)) < danger;
     const uint32_t it = ((uint32_t)__double2hiint(y) & 511u) ^ flip;
     uint32_t c = (uint32_t)__double2hiint(x) & 0xfffffu;
@@ -222,13 +233,15 @@ __global__ __launch_bounds__(DS_WG) void k_despread(BatchDev p, DsArgs a)
                 u[j] = j * 64 < left ? ds_view<VIEW, NOISE, INTERF>(u[j], (unsigned long long)b * (unsigned long long)p.nsamp +
                                                                               (unsigned long long)(wt * TILE + j * 64 + lane), a, ntab, L.rep[0])
                                      : 0u; /* a sample that does not exist adds nothing */
-            const int g = wt >> SG;
-            const double n0 = (double)((wt & ((1 << SG) - 1)) * TILE + lane); /* samples since the state's */
+            constexpr int GC = ev_carr_log2(SG); /* the carrier's granule; SG is the code's */
+            const int g = wt >> SG, gy = wt >> GC;
+            const int ns = (wt & ((1 << SG) - 1)) * TILE + lane, nsy = GC == SG ? ns : (wt & ((1 << GC) - 1)) * TILE + lane;
+            const double n0 = (double)ns, n0y = (double)nsy; /* samples since the state's */
             for (uint32_t mk = act_mask; mk; mk &= mk - 1) {
                 const int i = __builtin_ctz(mk);
                 const double S = scalar_load(&kb[i].S), sc = scalar_load(&kb[i].sc);
                 const uint32_t down = scalar_load(&kb[i].down) != 0 ? 1u : 0u;
-                const double xt = txb[(size_t)(2 * i) * nst + g], yt = txb[(size_t)(2 * i + 1) * nst + g];
+                const double xt = txb[(size_t)(2 * i) * nst + g], yt = txb[(size_t)(2 * i + 1) * nst + gy];
                 const uint32_t nav = tnb[(size_t)i * nst + g];
                 const double yg = (down ? 512.0 - yt : yt) + guard, xg = xt + guard;
                 const uint32_t flip = down ? 511u : 0u;
@@ -238,7 +251,7 @@ __global__ __launch_bounds__(DS_WG) void k_despread(BatchDev p, DsArgs a)
 #pragma unroll
                 for (int j = 0; j < SPT; j++) {
                     bool bj;
-                    const uint32_t r = ds_model_sample(n0 + (double)(j * 64), S, sc, yg, xg, flip, nav, chips, a.danger, bj);
+                    const uint32_t r = ds_model_sample(n0 + (double)(j * 64), n0y + (double)(j * 64), S, sc, yg, xg, flip, nav, chips, a.danger, bj);
                     bad |= bj ? 1u << j : 0u;
                     const uint2 t = (&L.rep[0][0])[r];
                     pi = __builtin_amdgcn_sdot2(__builtin_bit_cast(ds_s16x2, u[j]), __builtin_bit_cast(ds_s16x2, t.x), pi, false);
@@ -255,8 +268,9 @@ __global__ __launch_bounds__(DS_WG) void k_despread(BatchDev p, DsArgs a)
                         for (int q = 0; q < SPT; q++)
                             uw = q == j ? u[q] : uw;
                         bool bj;
-                        const uint32_t rm = ds_model_sample(n0 + (double)(j * 64), S, sc, yg, xg, flip, nav, chips, a.danger, bj);
-                        const uint32_t re = ds_exact_sample(xt, yt, S, sc, down, nav, (wt & ((1 << SG) - 1)) * TILE + j * 64 + lane, chips);
+                        const uint32_t rm = ds_model_sample(n0 + (double)(j * 64), n0y + (double)(j * 64), S, sc, yg, xg, flip, nav, chips, a.danger, bj);
+                        const uint32_t re = GC == SG ? ds_exact_sample(xt, yt, S, sc, down, nav, ns + j * 64, chips)
+                                                     : ds_exact_sample_2g(xt, yt, S, sc, down, nav, ns + j * 64, nsy + j * 64, chips);
                         const uint2 tm = (&L.rep[0][0])[rm], te = (&L.rep[0][0])[re];
                         const ds_s16x2 uj = __builtin_bit_cast(ds_s16x2, uw);
                         pi += __builtin_amdgcn_sdot2(uj, __builtin_bit_cast(ds_s16x2, te.x), 0, false) -

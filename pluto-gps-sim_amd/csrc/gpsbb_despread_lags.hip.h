@@ -144,14 +144,15 @@ __global__ __launch_bounds__(DS_WG) void k_despread_lags(BatchDev p, DslArgs al)
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); /* the strip is written before any lane reads it */
             __builtin_amdgcn_wave_barrier();
             const int left = p.nsamp - wt * TILE - lane; /* samples j*64 < left exist */
-            const int g = wt >> SG;
-            const int ns = (wt & ((1 << SG) - 1)) * TILE + lane; /* samples since the state's */
-            const double n0 = (double)ns;
+            constexpr int GC = ev_carr_log2(SG); /* the carrier's granule; SG is the code's */
+            const int g = wt >> SG, gy = wt >> GC;
+            const int ns = (wt & ((1 << SG) - 1)) * TILE + lane, nsy = GC == SG ? ns : (wt & ((1 << GC) - 1)) * TILE + lane;
+            const double n0 = (double)ns, n0y = (double)nsy; /* samples since the state's */
             for (uint32_t mk = act_mask; mk; mk &= mk - 1) {
                 const int i = __builtin_ctz(mk);
                 const double S = scalar_load(&kb[i].S), sc = scalar_load(&kb[i].sc);
                 const uint32_t down = scalar_load(&kb[i].down) != 0 ? 1u : 0u;
-                const double xt = txb[(size_t)(2 * i) * nst + g], yt = txb[(size_t)(2 * i + 1) * nst + g];
+                const double xt = txb[(size_t)(2 * i) * nst + g], yt = txb[(size_t)(2 * i + 1) * nst + gy];
                 const uint32_t nav = tnb[(size_t)i * nst + g];
                 const double yg = (down ? 512.0 - yt : yt) + guard, xg = xt + guard;
                 const uint32_t flip = down ? 511u : 0u;
@@ -162,7 +163,7 @@ __global__ __launch_bounds__(DS_WG) void k_despread_lags(BatchDev p, DslArgs al)
 #pragma unroll
                 for (int j = 0; j < SPT; j++) {
                     bool bj;
-                    const uint32_t r = ds_model_sample(n0 + (double)(j * 64), S, sc, yg, xg, flip, nav, chips, a.danger, bj);
+                    const uint32_t r = ds_model_sample(n0 + (double)(j * 64), n0y + (double)(j * 64), S, sc, yg, xg, flip, nav, chips, a.danger, bj);
                     const bool is = j * 64 < left;
                     bad |= bj && is ? 1u << j : 0u;
                     const uint2 tj = (&L.rep[0][0])[r];
@@ -174,7 +175,8 @@ __global__ __launch_bounds__(DS_WG) void k_despread_lags(BatchDev p, DslArgs al)
                     for (int j = 0; j < SPT; j++) { /* (one call site, the entry put back by selects: t[] stays in registers) */
                         if (!((bad >> j) & 1u))
                             continue;
-                        const uint32_t re = ds_exact_sample(xt, yt, S, sc, down, nav, ns + j * 64, chips);
+                        const uint32_t re = GC == SG ? ds_exact_sample(xt, yt, S, sc, down, nav, ns + j * 64, chips)
+                                                     : ds_exact_sample_2g(xt, yt, S, sc, down, nav, ns + j * 64, nsy + j * 64, chips);
                         const uint2 te = (&L.rep[0][0])[re];
 #pragma unroll
                         for (int q = 0; q < SPT; q++)

@@ -113,6 +113,25 @@ constexpr bool ev_granule_fits(int g) { return ((double)(TILE << g) + (double)(S
 #ifdef GPSBB_EV_MODEL_ERR_OWN
 static_assert(ev_granule_fits(EV_STATE_LOG2_MAX), "the model of the largest state granule must stay inside the error budget");
 #endif
+/* The granule is a property of the KIND.  g (st_log2, the knob, nstates, tile_nav) is the CODE's; the CARRIER's is one step larger:
+ * its recurrence rounds to half an ulp of a number below 512 index units, 2^-45, half the code's 2^-44 chips, so 2^(g+1) tiles of
+ * carrier stand where 2^g tiles of code do — (4096 + 15) * 2^-45 = 0.50 units of 2^-32 at the default g = 1, what two tiles of
+ * code come to — and measured, the carrier's change positions at 4 tiles stay inside W / 2 where the code's do not
+ * (profiles/sg01_granule_ab.json: tk_over_W 0.4483, tc_over_W 0.5106).  A carrier row of tile_x keeps the code's stride (nstates)
+ * and uses its first ceil(ntiles / 2^gc) entries.  g = 0 is one state per tile for both, g = EV_STATE_LOG2_MAX the same granule
+ * for both. */
+constexpr bool ev_carr_granule_fits(int gc) { return ((double)(TILE << gc) + (double)(SPT - 1)) * 0x1p-45 + 1.5 * 0x1p-32 <= EV_MODEL_ERR; }
+constexpr int ev_carr_log2(int g)
+{
+    int gc = g >= 1 ? (g + 1 < EV_STATE_LOG2_MAX ? g + 1 : EV_STATE_LOG2_MAX) : 0;
+    while (gc > g && !ev_carr_granule_fits(gc)) /* (a variant build's smaller budget: make r3budgets) */
+        gc--;
+    return gc;
+}
+#ifdef GPSBB_EV_MODEL_ERR_OWN
+static_assert(ev_carr_granule_fits(EV_STATE_LOG2_MAX), "the carrier model of the largest state granule must stay inside the error budget");
+static_assert(EV_STATE_LOG2_MAX == 2, "ev_second names the one granule whose carrier's differs (ev_exact_run_2g<1>)");
+#endif
 
 /* A wavefront claims its next chunk of tiles with a returning atomic.  Rounds 2 and 3 issued it in inline assembly and did not
  * wait for it until the chunk's last tile — invisible to the compiler, which is free to copy or spill a register it believes
@@ -224,16 +243,19 @@ __device__ __forceinline__ T scalar_load(const T *p)
  * The exact recomputation of one lane's run of one channel (rare): advance both NCOs from the tile's exact
  * state by n_off genuine steps with the jump-ahead of gpsbb_nco.h, then walk the run sample by sample as the
  * reference does (c:2697-2746) and add the differences of its contributions.  Returns the contribution at
- * the run's first sample.
+ * the run's first sample.  Each NCO starts from the state of ITS kind's granule (ev_carr_log2): the code from
+ * tile_x, n_off steps back, the carrier (TWO_G; else as the code) from tile_y (its row base, as tile_x is the code's), n_off_y
+ * steps back.
  */
-template <bool FIXED, class LDS>
+template <bool FIXED, bool TWO_G = false, class LDS>
 __device__ __forceinline__ uint32_t ev_exact_run_body(LDS &L, int wave, int lane, int i, const EvConst *kbi, const double *tile_x,
-                                                      int ntiles, uint32_t nb, int n_off, uint32_t fx_phase, int32_t fx_step)
+                                                      int ntiles, uint32_t nb, int n_off, const double *tile_y, int n_off_y,
+                                                      uint32_t fx_phase, int32_t fx_step)
 {
     constexpr bool fixed = FIXED;
     const bool down = kbi->down != 0;
     const double S = down ? -kbi->S : kbi->S, sc = kbi->sc;
-    const double xt = tile_x[(size_t)(2 * i) * ntiles], yt = tile_x[(size_t)(2 * i + 1) * ntiles];
+    const double xt = tile_x[(size_t)(2 * i) * ntiles], yt = (TWO_G ? tile_y : tile_x)[(size_t)(2 * i + 1) * ntiles];
     /* code NCO: at most one roll-over between the tile start and the end of the run (checked by the host) */
     int64_t wraps = 0;
     double x = code_jump(xt, sc, (int64_t)n_off, &wraps);
@@ -241,7 +263,7 @@ __device__ __forceinline__ uint32_t ev_exact_run_body(LDS &L, int wave, int lane
     const uint32_t dbm_next = ((nb >> 1) & 1u) ? 0xffffffffu : 0u;
     /* carrier NCO in cycles (the tile state is stored scaled by 512, exactly) */
     const double s = S * (1.0 / 512.0);
-    double cp = carr_jump(yt * (1.0 / 512.0), s, (int64_t)n_off);
+    double cp = carr_jump(yt * (1.0 / 512.0), s, (int64_t)(TWO_G ? n_off_y : n_off));
     uint32_t prev = 0, first = 0;
     uint32_t ph = fx_phase + (uint32_t)n_off * (uint32_t)fx_step; /* fixed-point carrier: the accumulator at the run's first sample */
 #pragma unroll 1
@@ -276,14 +298,26 @@ template <class LDS>
 __device__ __noinline__ uint32_t ev_exact_run(LDS &L, int wave, int lane, int i, const EvConst *kbi, const double *tile_x,
                                               int ntiles, uint32_t nb, int n_off)
 {
-    return ev_exact_run_body<false>(L, wave, lane, i, kbi, tile_x, ntiles, nb, n_off, 0u, 0);
+    return ev_exact_run_body<false>(L, wave, lane, i, kbi, tile_x, ntiles, nb, n_off, nullptr, 0, 0u, 0);
+}
+/* ... behind a carrier granule that is not the code's (ev_carr_log2(SG) != SG): each NCO from the state of its kind's granule of
+ * tile wt.  tile_x: the block's first state (chain c's row at [c * nst]); wt_nb: wt << 2 | nb; off: the run's first sample in the
+ * tile.  Where the two states lie is worked out here, behind the call: its caller has no registers for it. */
+template <int SG, class LDS>
+__device__ __noinline__ uint32_t ev_exact_run_2g(LDS &L, int wave, int lane, int i, const EvConst *kbi, const double *tile_x, int nst,
+                                                 uint32_t wt_nb, int off)
+{
+    constexpr int GC = ev_carr_log2(SG);
+    const int wt = (int)(wt_nb >> 2);
+    return ev_exact_run_body<false, true>(L, wave, lane, i, kbi, tile_x + (wt >> SG), nst, wt_nb & 3u, (wt & ((1 << SG) - 1)) * TILE + off,
+                                          tile_x + (wt >> GC), (wt & ((1 << GC) - 1)) * TILE + off, 0u, 0);
 }
 /* ... with the fixed-point carrier: the accumulator at the tile's first sample and its step take the carrier NCO's place */
 template <class LDS>
 __device__ __noinline__ uint32_t ev_exact_run_fixed(LDS &L, int wave, int lane, int i, const EvConst *kbi, const double *tile_x,
                                                     int ntiles, uint32_t nb, int n_off, uint32_t fx_phase, int32_t fx_step)
 {
-    return ev_exact_run_body<true>(L, wave, lane, i, kbi, tile_x, ntiles, nb, n_off, fx_phase, fx_step);
+    return ev_exact_run_body<true>(L, wave, lane, i, kbi, tile_x, ntiles, nb, n_off, nullptr, 0, fx_phase, fx_step);
 }
 
 /* per-channel constants of the fast path (scalar registers) */
@@ -437,6 +471,8 @@ __device__ __forceinline__ EvExactAt ev_exact_at(const EvTile &T, int i)
     }
     return a;
 }
+/* (where the carrier's granule is not the code's — T.sg is a constant of the kernel — ev_exact_run_2g finds both states itself) */
+__device__ __forceinline__ bool ev_exact_2g(const EvTile &T) { return ev_carr_log2(T.sg) != T.sg; }
 
 /*
  * Second half: signs, the contribution at sample 0 (into acc0) and its changes (into D).  db / db_next: the
@@ -477,6 +513,9 @@ __device__ __forceinline__ void ev_second(LDS &L, uint32_t &drow, int wave, int 
             if (FIXED) /* the accumulator at the tile's first sample */
                 acc0 += ev_exact_run_fixed(L, wave, lane, i, kb + i, x.tile_x, x.stride, x.nb, x.n_skip + (int)off,
                                            fx.ph[i] + (uint32_t)fx.n0 * (uint32_t)fx.st[i], fx.st[i]);
+            else if (ev_exact_2g(T)) /* (only GPSBB_EV_STATE_LOG2 = 1 has two granules: EV_STATE_LOG2_MAX is 2) */
+                acc0 += ev_exact_run_2g<1>(L, wave, lane, i, kb + i, T.tile_x, (T.ntiles + 1) >> 1,
+                                           ((uint32_t)T.wt << 2) | ((T.dbits >> i) & 1u) | (((T.dnext >> i) & 1u) << 1), (int)off);
             else
                 acc0 += ev_exact_run(L, wave, lane, i, kb + i, x.tile_x, x.stride, x.nb, x.n_skip + (int)off);
             atomicAdd(n_exact, 1ull);
@@ -540,7 +579,7 @@ __device__ __forceinline__ void ev_dense(LDS &L, int wave, int lane, int i, cons
             for (int j = 0; j < SPT; j++)
                 v[j] = 0;
             const EvExactAt x = ev_exact_at(T, i);
-            acc0 += ev_exact_run(L, wave, lane, i, kb + i, x.tile_x, x.stride, x.nb, x.n_skip + (int)off);
+            acc0 += ev_exact_run(L, wave, lane, i, kb + i, x.tile_x, x.stride, x.nb, x.n_skip + (int)off); /* (sg = 0 here) */
             atomicAdd(n_exact, 1ull);
         }
     }
@@ -782,7 +821,8 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
     const bool chain_lane = lane < nch2;
     const bool mirror = chain_lane && (lane & 1) && kb[lane >> 1].down != 0;
     /* this lane's chain (state-contiguous) in the state arrays: one exact state per GRANULE of 2^sg tiles (BatchDev::st_log2) */
-    constexpr int sg = SG; /* == p.st_log2 (the host launches the instance of its batch's granule) */
+    constexpr int sg = SG; /* == p.st_log2 (the host launches the instance of its batch's granule): the code's */
+    constexpr int gc = ev_carr_log2(SG); /* the carrier's (odd chain lanes) */
     const int nst = SG ? p.nstates : ntw;
     const double *__restrict__ txb = p.tile_x + (size_t)b * nst * nch2;
     /* (a scalar base and a 32-bit element offset per lane — lane * nst, worked out where a granule's state is fetched — not a 64-bit
@@ -822,7 +862,7 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
      * Every tile is derived from its granule's state on its own: which tiles a wavefront gets, and in what order, is the claim
      * protocol's business. */
     const auto stage_tile = [&](int t, uint32_t &dbits, uint32_t &dnext) {
-        const int r = t & ((1 << sg) - 1); /* the tile's place in its granule */
+        const int r = t & ((1 << sg) - 1); /* the tile's place in its granule: the code's */
         bool rolled_over = false;          /* (the code lane of a channel whose anchor has passed its granule's roll-over) */
         /* (what depends on the lane alone is worked out from an opaque copy of it here, once per tile, and not kept across the
          * channel loops: the kernel is short of registers — DESIGN.md 3 — and what it spills goes to HBM) */
@@ -840,8 +880,14 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
                  * 1024 + 1040 * 0.0646 < EV_CHIP_LEN_SHORT).
                  * Tile 0 of a granule IS the granule's state: fma(0, step, v) == v, so it takes neither the step nor the fma; only
                  * the reduction (a mirrored carrier phase of exactly 512) is left of it, and its code lane never rolls over. */
-                if (r) /* (wave-uniform) */
-                    v = __fma_rn(SG == 1 ? (double)TILE : (double)(r * TILE), L.tstep[ln], v);
+                if (gc == sg) {
+                    if (r) /* (wave-uniform) */
+                        v = __fma_rn(SG == 1 ? (double)TILE : (double)(r * TILE), L.tstep[ln], v);
+                } else if (t & ((1 << gc) - 1)) { /* (wave-uniform: some kind's r is not 0) */
+                    /* each lane by the place in ITS kind's granule; fma(0, step, v) == v, so a lane whose r is 0 may take it */
+                    const uint32_t rk = (uint32_t)t & ((ln & 1u) ? (1u << gc) - 1u : (1u << sg) - 1u);
+                    v = __fma_rn((double)(rk * (uint32_t)TILE), L.tstep[ln], v);
+                }
                 const uint32_t ip = (uint32_t)__double2hiint(v) - EV_GUARD_HI; /* the integer part */
                 const uint32_t red = (ln & 1u) ? (ip & ~511u) : (ip >= (uint32_t)GPSBB_CA_LEN + 1u ? (uint32_t)GPSBB_CA_LEN : 0u);
                 v -= (double)red;
@@ -870,8 +916,8 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
         uint32_t ln = (uint32_t)lane;
         asm volatile("" : "+v"(ln));
         const uint32_t at = ln * (uint32_t)nst + (uint32_t)g;
-        if (chain_lane)
-            ts_v = txb[at];
+        if (chain_lane) /* (a carrier lane reads its granule's state again where only the code's granule is new) */
+            ts_v = txb[gc == sg ? at : at - ((ln & 1u) ? (uint32_t)g - ((uint32_t)g >> (gc - sg)) : 0u)];
         if (lane < p.nch)
             nav_v = tnb[at];
     };

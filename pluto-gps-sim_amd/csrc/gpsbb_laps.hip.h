@@ -57,6 +57,7 @@
 #define GPSBB_LAPS_HIP_H
 
 #include "gpsbb_walk.hip.h"
+#include "gpsbb_events.hip.h"
 
 namespace gpsbb_impl {
 
@@ -456,7 +457,23 @@ __device__ __forceinline__ void lap_enter_block(const BatchDev &p, const LapDev 
  * time, they were more than half of what the pre-pass writes to HBM (a sector of 32 bytes per word: WRITE_SIZE).  Tiles
  * [w.navt, the first tile whose first sample is n_excl or later). */
 /* SG (here and in lap_emit_row, lap_run, lap_walk): the batch's state granule BatchDev::st_log2 as a constant (pass 2: what
- * costs registers as a variable shift), or -1: read it from p (the repair) */
+ * costs registers as a variable shift), or -1: read it from p (the repair).  It is the CODE's granule; a carrier chain leaves a
+ * state per 2^ev_carr_log2(SG) tiles (gpsbb_events.hip.h), into the same row with the same stride p.nstates: lap_tsl is the log2 of
+ * the samples per state of a kind, lap_nstates the states a row of the kind holds. */
+template <int KIND, int SG>
+__device__ __forceinline__ uint32_t lap_tsl(const BatchDev &p)
+{
+    const int g = SG >= 0 ? SG : p.st_log2;
+    return (uint32_t)__builtin_ctz(TILE) + (uint32_t)(KIND == NCO_CARR ? ev_carr_log2(g) : g);
+}
+template <int KIND, int SG>
+__device__ __forceinline__ int lap_nstates(const BatchDev &p)
+{
+    if (KIND != NCO_CARR || (SG >= 0 && ev_carr_log2(SG) == SG))
+        return p.nstates;
+    const int gc = ev_carr_log2(SG >= 0 ? SG : p.st_log2);
+    return (p.ntiles + (1 << gc) - 1) >> gc;
+}
 template <int KIND, int SG = -1>
 __device__ __forceinline__ void lap_nav_out(const BatchDev &p, int i, LapLane<KIND> &w, bool on, int n_excl, uint32_t bits)
 {
@@ -496,12 +513,13 @@ __device__ __forceinline__ void lap_nav_out(const BatchDev &p, int i, LapLane<KI
 template <int KIND, bool WIDE, int SG = -1>
 __device__ __forceinline__ void lap_emit_row(const BatchDev &p, int i, bool on, int b, int n, int k, double x, double S, uint32_t bits)
 {
-    /* samples per state (BatchDev::st_log2): states at n = 0, TS, 2 TS, ... */
-    const uint32_t tsl = (uint32_t)__builtin_ctz(TILE) + (uint32_t)(SG >= 0 ? SG : p.st_log2);
+    /* samples per state of the kind (lap_tsl): states at n = 0, TS, 2 TS, ... */
+    const uint32_t tsl = lap_tsl<KIND, SG>(p);
+    const int nstates = lap_nstates<KIND, SG>(p);
     const int TS = 1 << tsl;
     int t = (int)(((uint32_t)n + (uint32_t)(TS - 1)) >> tsl);
     int t_end = (int)((uint32_t)(n + k) >> tsl) + 1; /* one past the last tile whose first sample is in the row */
-    t_end = t_end < p.nstates ? t_end : p.nstates;
+    t_end = t_end < nstates ? t_end : nstates;
     int cnt = on ? t_end - t : 0;
     cnt = cnt < 0 ? 0 : cnt;
     if (!__ballot(cnt > 0))
@@ -605,7 +623,8 @@ constexpr int LAP_BURST = 16;
 template <int KIND, bool SNEG, bool EMIT, bool TIES, bool WIDE, int SG = -1>
 __device__ __forceinline__ void lap_run(const BatchDev &p, int i, LapLane<KIND> &w, const bool was, const int L_burst)
 {
-    const uint32_t tsl = (uint32_t)__builtin_ctz(TILE) + (uint32_t)(SG >= 0 ? SG : p.st_log2);
+    const uint32_t tsl = lap_tsl<KIND, SG>(p);
+    const int nstates = lap_nstates<KIND, SG>(p);
     const int TS = 1 << tsl;
     constexpr int TOPEX = LapK<KIND>::TOPEX;
     constexpr int TOP = KIND == NCO_CARR ? 1022 : 1023 + 9; /* the top binade: [0.5, 1) / [512, 1024) */
@@ -629,7 +648,7 @@ __device__ __forceinline__ void lap_run(const BatchDev &p, int i, LapLane<KIND> 
                 const int k = still && nmax > n ? nmax - n : 0;
                 if (EMIT && p.tile_x) {
                     const int t0 = (int)(((uint32_t)n + (uint32_t)(TS - 1)) >> tsl);
-                    if (__ballot(still && (t0 << tsl) <= n + k && t0 < p.nstates))
+                    if (__ballot(still && (t0 << tsl) <= n + k && t0 < nstates))
                         lap_emit_row<KIND, WIDE, SG>(p, i, still, w.b, n, k, x, 0.0, w.bits);
                 }
                 if (still) {
@@ -731,7 +750,7 @@ __device__ __forceinline__ void lap_run(const BatchDev &p, int i, LapLane<KIND> 
         if (EMIT && p.tile_x) { /* (no tile states where only the chain is wanted: gpsbb_chain_carrier) */
             /* does a tile start inside the row (samples n .. n1)? */
             const int t0 = (int)(((uint32_t)n + (uint32_t)(TS - 1)) >> tsl);
-            if (__ballot(go && (t0 << tsl) <= n1 && t0 < p.nstates))
+            if (__ballot(go && (t0 << tsl) <= n1 && t0 < nstates))
                 lap_emit_row<KIND, WIDE, SG>(p, i, go, w.b, n, k, x, S, w.bits);
         }
         const bool step = go && n1 < nmax;

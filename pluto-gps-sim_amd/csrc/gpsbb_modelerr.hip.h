@@ -234,10 +234,10 @@ __global__ __launch_bounds__(256) void k_model_err_ev(BatchDev p, double *mx, un
     if (p.ch[b * p.nch + i].prn <= 0)
         return;
     const EvConst kb = p.evc[b * p.nch + i];
-    /* the tile's granule (BatchDev::st_log2) and its place in it */
-    const int sg = p.st_log2, nst = p.nstates, r = wt & ((1 << sg) - 1);
+    /* the tile's granules (BatchDev::st_log2 is the code's, ev_carr_log2 of it the carrier's) and its place in each */
+    const int sg = p.st_log2, gc = ev_carr_log2(sg), nst = p.nstates, r = wt & ((1 << sg) - 1), ry_t = wt & ((1 << gc) - 1);
     const double *txb = p.tile_x + b * (size_t)nst * 2 * p.nch;
-    const double ts_x_g = txb[(size_t)(2 * i) * nst + (wt >> sg)], ts_y = txb[(size_t)(2 * i + 1) * nst + (wt >> sg)];
+    const double ts_x_g = txb[(size_t)(2 * i) * nst + (wt >> sg)], ts_y = txb[(size_t)(2 * i + 1) * nst + (wt >> gc)];
     const bool down = kb.down != 0;
     /* exactly what synth_ev_body puts into EvLds::tstate (IEEE carrier) */
     const bool fixed = p.kph0 != nullptr; /* k_synth_ev_fixed: the carrier lanes carry no bias, a falling phase is mirrored bit by bit */
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(256) void k_model_err_ev(BatchDev p, double *mx, un
     int red_laps = 0, red_wraps = 0;
     double ts_y_m = ts_y_g, ts_x = ts_x_g; /* where the plain linear model starts (ME_PURE_*): the tile's exact state */
     if (sg) {
-        ytg = __fma_rn((double)(r * TILE), kb.S, ytg);
+        ytg = __fma_rn((double)(ry_t * TILE), kb.S, ytg);
         xtg = __fma_rn((double)(r * TILE), kb.sc, xtg);
         const uint32_t iy = (uint32_t)__double2hiint(ytg) - EV_GUARD_HI, ix = (uint32_t)__double2hiint(xtg) - EV_GUARD_HI;
         const uint32_t ry = iy & ~511u, rx = ix >= (uint32_t)GPSBB_CA_LEN + 1u ? (uint32_t)GPSBB_CA_LEN : 0u;
@@ -267,7 +267,13 @@ __global__ __launch_bounds__(256) void k_model_err_ev(BatchDev p, double *mx, un
     T.fixed = fixed;
     T.st = fixed ? (uint32_t)p.kstep[b * p.nch + i] : 0u;
     T.ph = fixed ? p.kph0[b * p.nch + i] + (uint32_t)(wt - r) * (uint32_t)TILE * T.st : 0u;
-    /* the truth from the granule's first sample to the tile's, then counted from the anchor's period on */
+    /* the truth from each granule's first sample to the tile's (the carrier's granule starts first: its steps alone, with a step
+     * of zero for the code, until the code's granule starts), then counted from the anchor's period on */
+    T.sc = 0.0;
+    for (int n = 0; n < (ry_t - r) * TILE; n++)
+        T.step();
+    T.sc = kb.sc;
+    T.wraps = 0;
     for (int n = 0; n < r * TILE; n++)
         T.step();
     T.laps -= red_laps;

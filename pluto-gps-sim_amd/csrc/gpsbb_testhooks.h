@@ -57,6 +57,10 @@ int gpsbb_test_model_err(struct gpsbb_batch *b, double *maxima, unsigned long lo
 unsigned long long gpsbb_test_despread_exact(struct gpsbb_batch *b);
 /* ... and what its kernel took, by HIP events on the synthesis stream, in ms (-1: none yet) */
 float gpsbb_test_despread_ms(struct gpsbb_batch *b);
+/* the state granule of the batch's tile tables as log2 of its tiles: the code rows' (BatchDev::st_log2) and the carrier rows'
+ * (ev_carr_log2 of it, gpsbb_events.hip.h) */
+int gpsbb_test_state_log2(struct gpsbb_batch *b);
+int gpsbb_test_state_log2_carr(struct gpsbb_batch *b);
 void gpsbb_test_budgets(double out[3]); /* EV_MODEL_ERR, EV_T_EPS, PD_BAND of this build, in units of 2^-32 */
 
 #ifdef __cplusplus
