@@ -174,6 +174,28 @@ class Level(C.Structure):
 assert LEVEL_DTYPE.itemsize == 536 and C.sizeof(Level) == 536
 
 
+# blind acquisition (include/gpsbb.h gpsbb_device_acquire): the search over PRN, Doppler bin and code delay
+ACQ_MAX_BINS, ACQ_PRNS = 64, 32
+ACQ_ROW_DTYPE = np.dtype([("peak", "<u8"), ("sum_lo", "<u8"), ("sum_hi", "<u8"), ("lag", "<i4"), ("_pad", "<i4")])
+
+
+class AcqCfg(C.Structure):
+    """gpsbb_acq_cfg_t: prn_mask (bit p-1: PRN p), nbins, step[64] (2^-32 turns per sample), code_step (2^-32 chips per sample),
+    ncoh (N), nlags (P), nnc, shift"""
+    _fields_ = [("prn_mask", C.c_uint32), ("nbins", C.c_int32), ("step", C.c_int32 * ACQ_MAX_BINS), ("code_step", C.c_uint64),
+                ("ncoh", C.c_int32), ("nlags", C.c_int32), ("nnc", C.c_int32), ("shift", C.c_int32)]
+
+    def copy(self, **fields):
+        """the same configuration with some fields replaced"""
+        c = AcqCfg.from_buffer_copy(self)
+        for k, v in fields.items():
+            setattr(c, k, v)
+        return c
+
+
+assert ACQ_ROW_DTYPE.itemsize == 32 and C.sizeof(AcqCfg) == 288
+
+
 ERRORS = {0: "GPSBB_OK", -1: "GPSBB_E_BADARG", -2: "GPSBB_E_BADCHAN", -3: "GPSBB_E_HIP", -4: "GPSBB_E_NOMEM",
           -5: "GPSBB_E_INTERNAL", -6: "GPSBB_E_NODEVICE", -7: "GPSBB_E_STATE"}
 
@@ -192,6 +214,7 @@ API_SYMBOLS = [
     "gpsbb_interf_make", "gpsbb_interf_eval", "gpsbb_fill_block_impair", "gpsbb_stream_set_interf", "gpsbb_device_impair",
     "gpsbb_batch_despread_impaired", "gpsbb_batch_despread_lags",
     "gpsbb_device_level", "gpsbb_level_clips", "gpsbb_level_choose", "gpsbb_level_rms", "gpsbb_stream_pop_level",
+    "gpsbb_device_acquire", "gpsbb_acq_min_shift", "gpsbb_acq_make", "gpsbb_acq_best",
 ]
 # ... and include/gpsbb_node.h
 NODE_API_SYMBOLS = ["gpsbb_node_create", "gpsbb_node_run", "gpsbb_node_run_digest", "gpsbb_node_slot_digests", "gpsbb_node_destroy", "gpsbb_node_plan", "gpsbb_node_begin", "gpsbb_node_feed", "gpsbb_node_end",
@@ -316,6 +339,11 @@ def lib():
             L.gpsbb_level_rms.argtypes = [vp, C.c_long, i]
             L.gpsbb_level_rms.restype = d
             L.gpsbb_stream_pop_level.argtypes = [vp, C.POINTER(vp), vp, vp]
+        if hasattr(L, "gpsbb_device_acquire"):  # the acquisition calls, as a group (an older build loaded for an A/B: tools/ab_lib.sh)
+            L.gpsbb_device_acquire.argtypes = [vp, vp, C.c_long, u, vp, vp, vp, vp, vp]
+            L.gpsbb_acq_min_shift.argtypes = [u, i, i]
+            L.gpsbb_acq_make.argtypes = [vp, d, d, d, i, d, i, i, u]
+            L.gpsbb_acq_best.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_uint64), C.POINTER(d)]
         _lib = L
     return _lib
 
@@ -511,6 +539,16 @@ class Synth:
         _chk(lib().gpsbb_device_level(self._h, C.c_void_p(int(d_ptr)), nblocks, nsamp, _ref(nz), _ref(js), out.ctypes.data),
              "gpsbb_device_level")
         return out
+
+    def device_acquire(self, d_ptr, nsamp, cfg, view=OUT_SC16, noise=None, interf=None, want_grid=False):
+        """gpsbb_device_acquire: the search of nsamp int16 I/Q pairs in device memory -> rows ACQ_ROW_DTYPE [32, nbins], or
+        (rows, grid uint64 [32, nbins, nlags]) with want_grid (acquire_host is the same in numpy)"""
+        nz, js = _as_noise(noise), _as_interf(interf)
+        rows = np.zeros((ACQ_PRNS, max(int(cfg.nbins), 0)), ACQ_ROW_DTYPE)
+        grid = np.zeros((ACQ_PRNS, max(int(cfg.nbins), 0), max(int(cfg.nlags), 0)), np.uint64) if want_grid else None
+        _chk(lib().gpsbb_device_acquire(self._h, C.c_void_p(int(d_ptr)), int(nsamp), view, _ref(nz), _ref(js), C.byref(cfg),
+                                        rows.ctypes.data, None if grid is None else grid.ctypes.data), "gpsbb_device_acquire")
+        return (rows, grid) if want_grid else rows
 
     def device_noise(self, d_src, nblocks, nsamp, noise, d_dst=None):
         """gpsbb_device_noise: nblocks blocks of int16 IQ in device memory at d_src, with noise, into d_dst (default: in place)"""
@@ -1283,6 +1321,98 @@ def despread_lags_host(u, replicas, seg_tiles, lags):
     up = np.zeros((u.shape[0], nsamp + 2 * pad, 2), np.int64)
     up[:, pad:pad + nsamp] = u
     return np.stack([despread_host(up[:, pad + v:pad + v + nsamp], replicas, seg_tiles) for v in lg], axis=3)
+
+
+def acq_min_shift(view, ncoh, nnc):
+    """gpsbb_acq_min_shift: the smallest shift the overflow rule allows"""
+    a = lib().gpsbb_acq_min_shift(view, int(ncoh), int(nnc))
+    _chk(a if a < 0 else 0, "gpsbb_acq_min_shift")
+    return a
+
+
+def acq_make(delt, f_min_hz, f_step_hz, nbins, coh_s, nlags=0, nnc=1, view=OUT_SC16):
+    """gpsbb_acq_make: an AcqCfg from physical units (nlags <= 0: one code period)"""
+    cfg = AcqCfg()
+    _chk(lib().gpsbb_acq_make(C.byref(cfg), float(delt), float(f_min_hz), float(f_step_hz), int(nbins), float(coh_s), int(nlags), int(nnc),
+                              view), "gpsbb_acq_make")
+    return cfg
+
+
+def acq_best(rows, cfg, prn):
+    """gpsbb_acq_best: (bin, lag, peak, ratio) of PRN prn's rows"""
+    r = np.ascontiguousarray(rows, ACQ_ROW_DTYPE)
+    if r.shape != (ACQ_PRNS, cfg.nbins):
+        raise ValueError("rows [32, nbins] wanted, got %r" % (r.shape,))
+    b, l, pk, ratio = C.c_int(), C.c_int(), C.c_uint64(), C.c_double()
+    _chk(lib().gpsbb_acq_best(r.ctypes.data, C.byref(cfg), int(prn), C.byref(b), C.byref(l), C.byref(pk), C.byref(ratio)), "gpsbb_acq_best")
+    return b.value, l.value, pk.value, ratio.value
+
+
+def acq_chips(cfg, prns):
+    """the replica of the definition: int64 [len(prns), nnc * ncoh], +1 where chip ((code_step * m) >> 32) mod 1023 is 1, else -1"""
+    m = np.arange(int(cfg.nnc) * int(cfg.ncoh), dtype=np.uint64)
+    c = ((np.uint64(cfg.code_step) * m) >> np.uint64(32)) % np.uint64(1023)
+    return np.stack([2 * codegen(p).astype(np.int64)[c.astype(np.int64)] - 1 for p in prns]) if len(prns) else np.zeros((0, m.size), np.int64)
+
+
+def acq_mix(u, step):
+    """the mixed signal of one bin: u int64 [nsamp, 2] (view_host's) -> (yI, yQ) int64 [nsamp], w * conj(carrier) with the table
+    index ((uint32)(step * n)) >> 23"""
+    sin512, cos512 = sincos_tables()
+    n = np.arange(u.shape[0], dtype=np.uint64)
+    idx = (((np.uint64(int(step) & 0xFFFFFFFF) * n) & np.uint64(0xFFFFFFFF)) >> np.uint64(23)).astype(np.int64)
+    c, s = cos512.astype(np.int64)[idx], sin512.astype(np.int64)[idx]
+    return u[:, 0] * c + u[:, 1] * s, u[:, 1] * c - u[:, 0] * s
+
+
+def acquire_host(u, cfg, blas=None):
+    """gpsbb_device_acquire in numpy: u int64 [nsamp, 2] (view_host's output of the buffer) -> (rows ACQ_ROW_DTYPE [32, nbins], grid
+    uint64 [32, nbins, nlags]); PRNs outside cfg.prn_mask are left zero (and cost nothing).  Per bin and interval the coherent
+    sums are the chips [PRN, N] times the sliding-window matrix y[m + L] [N, nlags].  blas=False forms them in int64, one PRN at
+    a time (np.correlate: the same sums without the matrix); blas=True as one float64 product, which is the same numbers: every
+    term and every partial sum, in any order, is an integer below N * Wmax * 1024 <= 2^45 < 2^53.  None: float64 for more than
+    four PRNs.  Shift, squares and sums are int64 / uint64 / Python integers either way."""
+    u = np.asarray(u, np.int64)
+    if u.ndim != 2 or u.shape[1] != 2:
+        raise ValueError("u [nsamp, 2] wanted, got %r" % (u.shape,))
+    N, P, nnc, a, nbins = int(cfg.ncoh), int(cfg.nlags), int(cfg.nnc), int(cfg.shift), int(cfg.nbins)
+    if u.shape[0] < nnc * N + P - 1:
+        raise ValueError("nsamp < nnc * ncoh + nlags - 1")
+    prns = [p for p in range(1, ACQ_PRNS + 1) if (int(cfg.prn_mask) >> (p - 1)) & 1]
+    blas = len(prns) > 4 if blas is None else blas
+    x = acq_chips(cfg, prns)
+    xm = x.astype(np.float64) if blas else x
+    grid = np.zeros((ACQ_PRNS, nbins, P), np.uint64)
+    rows = np.zeros((ACQ_PRNS, nbins), ACQ_ROW_DTYPE)
+    if not prns:
+        return rows, grid
+    lc = max(1, min(P, (1 << 23) // max(N, 1)))   # delays per product: the window matrix stays near 64 MB
+    pi = np.array(prns) - 1
+    for k in range(nbins):
+        y = acq_mix(u, cfg.step[k])
+        m = np.zeros((len(prns), P), np.uint64)
+        for i in range(nnc):
+            for l0 in range(0, P, lc if blas else P):
+                l1 = min(P, l0 + lc) if blas else P
+                for yc in y:
+                    seg = yc[i * N + l0:i * N + N + l1 - 1]
+                    if blas:
+                        w = np.lib.stride_tricks.sliding_window_view(seg, l1 - l0)   # [N, delays]
+                        sc = (xm[:, i * N:(i + 1) * N] @ w.astype(np.float64)).astype(np.int64)
+                    else:
+                        sc = np.stack([np.correlate(seg, xp[i * N:(i + 1) * N], "valid") for xp in xm])
+                        assert sc.dtype == np.int64
+                    t = (sc >> a).astype(np.uint64)
+                    m[:, l0:l1] += t * t
+        grid[pi, k] = m
+    rows["peak"] = grid.max(axis=2)
+    rows["lag"] = grid.argmax(axis=2)
+    hi32, lo32 = (grid >> np.uint64(32)).sum(axis=2), (grid & np.uint64(0xFFFFFFFF)).sum(axis=2)   # nlags <= 2^15: below 2^47
+    for p in range(ACQ_PRNS):
+        for k in range(nbins):
+            tot = (int(hi32[p, k]) << 32) + int(lo32[p, k])
+            rows["sum_lo"][p, k], rows["sum_hi"][p, k] = tot & 0xFFFFFFFFFFFFFFFF, tot >> 64
+    return rows, grid
 
 
 def block_digest_host(iq):

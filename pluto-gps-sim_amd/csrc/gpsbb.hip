@@ -31,6 +31,7 @@
 #include "gpsbb_dense.hip.h"
 #include "gpsbb_despread.hip.h"
 #include "gpsbb_despread_lags.hip.h"
+#include "gpsbb_acq.hip.h"
 #include "gpsbb_walk.hip.h"
 #include "gpsbb_laps.hip.h"
 #include "gpsbb_nco.h"
@@ -553,6 +554,13 @@ struct gpsbb {
             return e;
         }
     } d_digest;
+#ifdef GPSBB_EXPERIMENTS
+    hipEvent_t acq_ev[2] = {}; /* around the last gpsbb_device_acquire's kernels, gpsbb_test_acquire_ms */
+#endif
+    DigestBuf d_acq_chips, d_acq_rows; /* gpsbb_device_acquire's scratch, kept between calls (in 8-byte words): the expanded chips; the
+                                          tiles' partials with the rows behind them */
+    DigestBuf d_acq_grid;              /* ... and the grid where wanted (up to 512 MiB, for tests and plots): freed when the call
+                                          that asked for it has copied it out, here only while that call runs or after it failed */
 };
 
 /* every stream the handle has created, in no particular order */
@@ -1018,6 +1026,14 @@ extern "C" void gpsbb_destroy(gpsbb_t *h)
         (void)hipFree(h->d_digest.p);
     if (h->d_level)
         (void)hipFree(h->d_level);
+#ifdef GPSBB_EXPERIMENTS
+    for (hipEvent_t e : h->acq_ev)
+        if (e)
+            (void)hipEventDestroy(e);
+#endif
+    for (gpsbb::DigestBuf *b : {&h->d_acq_chips, &h->d_acq_rows, &h->d_acq_grid})
+        if (b->p)
+            (void)hipFree(b->p);
     delete h->pool;
     h->pool = nullptr;
     for_each_stream(h, [](hipStream_t st) { (void)hipStreamDestroy(st); });
@@ -3055,6 +3071,114 @@ extern "C" int gpsbb_batch_despread_lags(gpsbb_batch_t *b, const int16_t *d_iq, 
     return batch_despread(b, d_iq, view, nz, set, seg_tiles, lags, nlags, out);
 }
 
+/* ---- blind acquisition (include/gpsbb.h gpsbb_device_acquire; gpsbb_acq.h, gpsbb_acq.hip.h) ---- */
+
+static_assert(sizeof(gpsbb_acq_cfg_t) == 288 && sizeof(gpsbb_acq_row_t) == 32, "gpsbb_acq_cfg_t / gpsbb_acq_row_t layout");
+
+extern "C" int gpsbb_acq_min_shift(unsigned view, int ncoh, int nnc) { return acq_min_shift(view, ncoh, nnc); }
+
+extern "C" int gpsbb_acq_make(gpsbb_acq_cfg_t *cfg, double delt, double f_min_hz, double f_step_hz, int nbins, double coh_s, int nlags,
+                              int nnc, unsigned view)
+{
+    return acq_make(cfg, delt, f_min_hz, f_step_hz, nbins, coh_s, nlags, nnc, view);
+}
+
+extern "C" int gpsbb_acq_best(const gpsbb_acq_row_t *rows, const gpsbb_acq_cfg_t *cfg, int prn, int *bin, int *lag, uint64_t *peak,
+                              double *ratio)
+{
+    return acq_best(rows, cfg, prn, bin, lag, peak, ratio);
+}
+
+typedef void (*AcqKernelFn)(AcqArgs);
+static AcqKernelFn acq_kernel(int fmt, bool noise, bool interf)
+{
+#define GPSBB_AQ_ROW(V) {{k_acq<V, false, false>, k_acq<V, false, true>}, {k_acq<V, true, false>, k_acq<V, true, true>}}
+    static const AcqKernelFn k[3][2][2] = {GPSBB_AQ_ROW(DS_SC16), GPSBB_AQ_ROW(PACK_SC8), GPSBB_AQ_ROW(PACK_SC1)};
+#undef GPSBB_AQ_ROW
+    return k[fmt][noise ? 1 : 0][interf ? 1 : 0];
+}
+
+extern "C" int gpsbb_device_acquire(gpsbb_t *h, const int16_t *d_iq, long nsamp, unsigned view, const gpsbb_noise_t *nz,
+                                    const gpsbb_interf_set_t *set, const gpsbb_acq_cfg_t *cfg, gpsbb_acq_row_t *rows, uint64_t *grid)
+{
+    int shift8 = 0;
+    const int fmt = acq_view_format(view, &shift8);
+    ImpairCall ic;
+    if (!h || !d_iq || !cfg || !rows || ((uintptr_t)d_iq & 3) || nsamp < 1 || !acq_cfg_ok(cfg, fmt, nsamp) ||
+        !impair_make(nz, set, (uint64_t)nsamp, &ic))
+        return GPSBB_E_BADARG;
+    static_assert(DS_SC16 == 0 && PACK_SC8 == 1 && PACK_SC1 == 2, "acq_view_format's numbers are the kernels'");
+    HIPCHK(h, hipSetDevice(h->device));
+    const int rc = gpsbb_sync(h); /* as gpsbb_device_level: whatever the handle was rendering into d_iq is there */
+    if (rc != GPSBB_OK)
+        return rc;
+    if (nz)
+        HIPCHK(h, noise_ready(h));
+    AcqArgs a;
+    memset(&a, 0, sizeof a);
+    a.nbins = cfg->nbins;
+    a.ncoh = cfg->ncoh;
+    a.npad = (cfg->ncoh + 31) & ~31;
+    a.nlags = cfg->nlags;
+    a.nnc = cfg->nnc;
+    a.shift = cfg->shift;
+    a.ntiles = (cfg->nlags + 31) / 32;
+    a.nsamp = nsamp;
+    memcpy(a.step, cfg->step, sizeof a.step);
+    const size_t nrows = (size_t)ACQ_PRNS * (size_t)a.nbins;
+    const size_t chip_words = ((size_t)a.nnc * ACQ_PRNS * (size_t)a.npad + 7) / 8;
+    const size_t row_words = nrows * ((size_t)a.ntiles + 1) * (sizeof(gpsbb_acq_row_t) / 8);
+    const size_t grid_words = grid ? nrows * (size_t)a.nlags : 0;
+    HIPCHK(h, (hipError_t)h->d_acq_chips.reserve(chip_words));
+    HIPCHK(h, (hipError_t)h->d_acq_rows.reserve(row_words));
+    if (grid)
+        HIPCHK(h, (hipError_t)h->d_acq_grid.reserve(grid_words));
+    hipStream_t cs = h->s_compute;
+    gpsbb_acq_row_t *d_part = reinterpret_cast<gpsbb_acq_row_t *>(h->d_acq_rows.p);
+    gpsbb_acq_row_t *d_rows = d_part + nrows * (size_t)a.ntiles;
+    HIPCHK(h, hipMemsetAsync(h->d_acq_rows.p, 0, row_words * 8, cs));
+    if (grid)
+        HIPCHK(h, hipMemsetAsync(h->d_acq_grid.p, 0, grid_words * 8, cs));
+    a.d.iq = reinterpret_cast<const uint32_t *>(d_iq);
+    a.d.shift8 = shift8;
+    a.d.nz = ic.a.nz;
+    a.d.ntab = h->d_noise_tab;
+    a.d.it = ic.a.it;
+    a.tabs = h->d_tabs;
+    a.chips = reinterpret_cast<const int8_t *>(h->d_acq_chips.p);
+    a.grid = grid ? h->d_acq_grid.p : nullptr;
+    a.part = d_part;
+    const long long nchip = (long long)a.nnc * a.npad;
+#ifdef GPSBB_EXPERIMENTS
+    for (auto &e : h->acq_ev)
+        if (!e)
+            HIPCHK(h, hipEventCreate(&e));
+    HIPCHK(h, hipEventRecord(h->acq_ev[0], cs));
+#endif
+    hipLaunchKernelGGL(k_acq_chips, dim3((unsigned)((nchip + 255) / 256)), dim3(256), 0, cs, h->d_ca, reinterpret_cast<int8_t *>(h->d_acq_chips.p),
+                       cfg->prn_mask, (unsigned long long)cfg->code_step, a.ncoh, a.npad, a.nnc);
+    HIPCHK(h, hipGetLastError());
+    /* x: runs of four delay tiles (at most 256), y: the bins (at most 64) */
+    hipLaunchKernelGGL(acq_kernel(fmt, nz != nullptr, set != nullptr), dim3((unsigned)((a.ntiles + AQ_WAVES - 1) / AQ_WAVES), (unsigned)a.nbins),
+                       dim3(AQ_WG), 0, cs, a);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(k_acq_fold, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, cs, d_part, d_rows, (int)nrows, a.ntiles);
+    HIPCHK(h, hipGetLastError());
+#ifdef GPSBB_EXPERIMENTS
+    HIPCHK(h, hipEventRecord(h->acq_ev[1], cs));
+#endif
+    HIPCHK(h, hipMemcpyAsync(rows, d_rows, nrows * sizeof(gpsbb_acq_row_t), hipMemcpyDeviceToHost, cs));
+    if (grid)
+        HIPCHK(h, hipMemcpyAsync(grid, h->d_acq_grid.p, grid_words * 8, hipMemcpyDeviceToHost, cs));
+    HIPCHK(h, hipStreamSynchronize(cs));
+    if (grid) { /* the grid is not kept: it can be half a gigabyte, and the next call may not want one */
+        (void)hipFree(h->d_acq_grid.p);
+        h->d_acq_grid.p = nullptr;
+        h->d_acq_grid.cap = 0;
+    }
+    return GPSBB_OK;
+}
+
 extern "C" double gpsbb_cn0_estimate(const gpsbb_corr_t *p, long n, long stride, double seg_seconds)
 {
     if (!p || n < 2 || stride < 1 || !(seg_seconds > 0.0) || !std::isfinite(seg_seconds))
@@ -4531,6 +4655,14 @@ extern "C" float gpsbb_test_despread_ms(gpsbb_batch *b)
 {
     float ms = -1.0f;
     if (!b || !b->ds_ev[0] || !b->ds_ev[1] || hipEventElapsedTime(&ms, b->ds_ev[0], b->ds_ev[1]) != hipSuccess)
+        return -1.0f;
+    return ms;
+}
+
+extern "C" float gpsbb_test_acquire_ms(gpsbb *h)
+{
+    float ms = -1.0f;
+    if (!h || !h->acq_ev[0] || !h->acq_ev[1] || hipEventElapsedTime(&ms, h->acq_ev[0], h->acq_ev[1]) != hipSuccess)
         return -1.0f;
     return ms;
 }
