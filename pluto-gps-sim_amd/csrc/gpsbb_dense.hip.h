@@ -566,12 +566,12 @@ __global__ __launch_bounds__(EV_WG) __attribute__((amdgpu_waves_per_eu(5, 5))) v
         if (__builtin_expect(p.nsamp - wt * TILE >= TILE, 1)) {
 #pragma unroll
             for (int j = 0; j < SPT; j++)
-                out[j * 64] = __builtin_amdgcn_perm(__float_as_uint(acc[j].y), __float_as_uint(acc[j].x), 0x05040100u);
+                iq_store<(GPSBB_IQ_NT_PD != 0)>(out + j * 64, __builtin_amdgcn_perm(__float_as_uint(acc[j].y), __float_as_uint(acc[j].x), 0x05040100u));
         } else {
 #pragma unroll
             for (int j = 0; j < SPT; j++)
                 if (j * 64 < left)
-                    out[j * 64] = __builtin_amdgcn_perm(__float_as_uint(acc[j].y), __float_as_uint(acc[j].x), 0x05040100u);
+                    iq_store<(GPSBB_IQ_NT_PD != 0)>(out + j * 64, __builtin_amdgcn_perm(__float_as_uint(acc[j].y), __float_as_uint(acc[j].x), 0x05040100u));
         }
         base = next_base;
         pos = next_pos;

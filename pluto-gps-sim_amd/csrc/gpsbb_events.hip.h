@@ -203,6 +203,25 @@ __device__ __forceinline__ void lds_write_at(uint32_t a, T v)
     *(__attribute__((address_space(3))) T *)(uintptr_t)a = v;
 }
 
+/* The L2 retention policy of the IQ stream.  Nobody on the device reads a push's 4 GB of IQ again while it is rendered, and
+ * plain stores of it evict what is read again: the kernel's own spill slots, the pass-2 tile states, the granule states.
+ * GPSBB_IQ_NT 1 stores IQ non-temporally (`nt` on the instruction), 0 as any other store: both forms build from one tree
+ * (make EXTRA=-DGPSBB_IQ_NT=0) for the A/B of DESIGN.md 3; GPSBB_IQ_NT_PD is the same for k_synth_pd. */
+#ifndef GPSBB_IQ_NT
+#define GPSBB_IQ_NT 1
+#endif
+#ifndef GPSBB_IQ_NT_PD
+#define GPSBB_IQ_NT_PD GPSBB_IQ_NT
+#endif
+template <bool NT = (GPSBB_IQ_NT != 0), class T>
+__device__ __forceinline__ void iq_store(T *p, T v)
+{
+    if (NT)
+        __builtin_nontemporal_store(v, p);
+    else
+        *p = v;
+}
+
 constexpr uint32_t EV_SAT_HI_C = 0x4130000fu; /* the high word of a position clamped to 15.5 (row 15: discard) */
 #define EV_SAT_HI EV_SAT_HI_C
 
@@ -1055,7 +1074,7 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
             ev_u32x4 *g = reinterpret_cast<ev_u32x4 *>(tile_out) + lane_now;
 #pragma unroll
             for (int k = 0; k < 4; k++)
-                g[k * 64] = v[k]; /* 1 KB of consecutive addresses per instruction */
+                iq_store(g + k * 64, v[k]); /* 1 KB of consecutive addresses per instruction */
         } else {
             /* the block's last, partial tile (or a block that does not start on a 16-byte boundary): from the registers */
 #pragma unroll
@@ -1065,7 +1084,7 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
 #pragma unroll
             for (int j = 0; j < SPT; j++)
                 if (j < nvalid)
-                    out[j] = o[j];
+                    iq_store(out + j, o[j]);
         }
         asm volatile("" ::: "memory");
         base = next_base;
