@@ -377,6 +377,8 @@ def exp_lib():
         L.gpsbb_test_despread_ms.restype = C.c_float
         if hasattr(L, "gpsbb_test_plan"):  # (an older build loaded for an A/B: tools/ab_lib.sh)
             L.gpsbb_test_plan.argtypes = [vp, i, i, d, i, u, vp, i, vp, vp, vp, vp, vp]
+        if hasattr(L, "gpsbb_test_push_side"):  # (an older build loaded for an A/B: tools/ab_lib.sh)
+            L.gpsbb_test_push_side.argtypes = [vp, i, i, d, i, u, vp, vp]
         _exp_lib = L
     return _exp_lib
 
@@ -408,6 +410,21 @@ def plan(ch, delt, nsamp, flags=0, seed_where=0, synth_kernel=0, chain_where=0, 
                                    ptr(carry_prn, np.int32), ptr(carry_phase, np.float64), ptr(fixed_prev_prn, np.int32),
                                    ptr(fixed_prev_phase, np.uint32), out.ctypes.data)
     return rc, ({f: int(v) for f, v in zip(PLAN_FIELDS, out)} if rc == 0 else None)
+
+
+PUSH_CHAIN_NONE, PUSH_CHAIN_HOST, PUSH_CHAIN_DEVICE = 0, 1, 2
+
+
+def push_side(ch, delt, nsamp, flags=0, seed_where=0, synth_kernel=0, chain_where=0, skip_seed=0, max_sets=1):
+    """gpsbb_test_push_side (csrc/gpsbb_testhooks.h): on which side a ring with these flags would chain the carrier of this push,
+    without a handle or a GPU.  Returns (rc, values): values = {"chain": PUSH_CHAIN_*, "begun": the decision took the plan's first
+    step}."""
+    ch = _as_chan(ch)
+    nb, nch = ch.shape
+    opt = np.array([seed_where, synth_kernel, skip_seed, chain_where, max_sets], np.int32)
+    out = np.zeros(2, np.int32)
+    rc = exp_lib().gpsbb_test_push_side(ch.ctypes.data, nb, nch, delt, nsamp, flags, opt.ctypes.data, out.ctypes.data)
+    return rc, ({"chain": int(out[0]), "begun": int(out[1])} if rc == 0 else None)
 
 
 def _chk(rc, what):

@@ -3463,6 +3463,28 @@ extern "C" int gpsbb_fill_block_ref_fixed(gpsbb_t *h, void *chan, const gpsbb_re
 /* time-sharded streaming with pinned host gather                                                     */
 /* ================================================================================================== */
 
+/* A ring's carrier chain from one push to the next.  A push works on a copy and commits it with one assignment once every enqueue
+ * has succeeded; only a move of the carry between the sides — the same state, told the other way — is committed on the spot. */
+struct StreamChain {
+    ChainCarry carry = {};                     /* IEEE carrier chained on the host across pushes: prn and exact phase */
+    /* ... or on the device (gpsbb_stream::d_carry), and then the host keeps: */
+    int last_prn[GPSBB_MAX_CHAN] = {0};        /* prn per channel in the last block pushed */
+    double rough_phase[GPSBB_MAX_CHAN] = {0};  /* its rough idea of the carrier phase after it */
+    bool on_device = false;                    /* where the authoritative carry is right now */
+    int fx_prn[GPSBB_MAX_CHAN] = {0};          /* fixed-point carrier: channel state after the last push */
+    uint32_t fx_phase[GPSBB_MAX_CHAN] = {0};
+    /* The next push does not continue the one before: every channel of its first block starts from its descriptor's phase, as if
+     * it had just been allocated (c:1956-1964) — "no satellite was here before" is all the chain has to be told.  phases_too: a
+     * ring that starts a new stream (gpsbb_stream_reset) forgets where the old one stood as well. */
+    void forget(bool phases_too)
+    {
+        if (phases_too)
+            *this = StreamChain();
+        for (int i = 0; i < GPSBB_MAX_CHAN; i++)
+            last_prn[i] = fx_prn[i] = carry.prn[i] = 0;
+    }
+};
+
 struct gpsbb_stream {
     gpsbb *h = nullptr;
     int nch = 0, nsamp = 0, bps = 0, depth = 0;
@@ -3486,17 +3508,11 @@ struct gpsbb_stream {
     };
     std::vector<Slot> slots;
     uint64_t head = 0, tail = 0; /* pushes / pops so far */
-    ChainCarry *carry = nullptr;               /* IEEE carrier chained on the host across pushes */
-    /* ... or on the device (gpsbb_walk.hip.h): the exact phase never leaves it */
-    ChainCarryDev *d_carry = nullptr;
+    StreamChain chain;           /* where the carrier chain stands after the last push */
+    ChainCarryDev *d_carry = nullptr; /* the carry while it is on the device (gpsbb_walk.hip.h): the exact phase never leaves it */
     hipEvent_t ev_prefix = nullptr, ev_fix = nullptr;
-    int last_prn[GPSBB_MAX_CHAN] = {0};        /* prn per channel in the last block pushed */
-    double rough_phase[GPSBB_MAX_CHAN] = {0};  /* the host's rough idea of the carrier phase after it */
-    bool carry_on_device = false;              /* where the authoritative carry is right now */
-    std::vector<gpsbb_chan_t> seeded;
+    std::vector<gpsbb_chan_t> seeded; /* a host-side push: its descriptors with every block's start phase */
     std::vector<double> seeds;
-    int fx_prn[GPSBB_MAX_CHAN] = {0};          /* fixed-point carrier: channel state after the last push */
-    uint32_t fx_phase[GPSBB_MAX_CHAN] = {0};
     bool poisoned = false; /* a push failed after part of it had been enqueued: the chain's state on the device has
                               moved on without the host's; nothing more can be pushed or popped */
 };
@@ -3507,7 +3523,6 @@ extern "C" void gpsbb_stream_destroy(gpsbb_stream_t *s)
         return;
     (void)hipSetDevice(s->h->device);
     (void)drain_streams(s->h); /* the carry, the pinned slots and the events: pre-pass, synthesis and copy streams hold work on them */
-    delete s->carry;
     if (s->d_carry)
         (void)hipFree(s->d_carry);
     if (s->ev_prefix)
@@ -3594,15 +3609,7 @@ extern "C" int gpsbb_stream_reset(gpsbb_stream_t *s)
         return rc;
     if (s->d_carry)
         HIPCHK(h, zero_now(h, s->d_carry, sizeof(ChainCarryDev)));
-    if (s->carry)
-        memset(s->carry, 0, sizeof *s->carry);
-    s->carry_on_device = false;
-    for (int i = 0; i < GPSBB_MAX_CHAN; i++) {
-        s->last_prn[i] = 0;
-        s->rough_phase[i] = 0.0;
-        s->fx_prn[i] = 0;
-        s->fx_phase[i] = 0;
-    }
+    s->chain.forget(true);
     s->head = s->tail = 0;
     s->out_pos = s->noise_on || !s->interf_on ? s->impair.nz.sample0 : s->impair.it.sample0;
     return GPSBB_OK;
@@ -3701,203 +3708,92 @@ static bool stream_impair(const gpsbb_stream *s, ImpairCall *c)
     return impair_at(c, s->out_pos, (uint64_t)s->bps * (uint64_t)s->nsamp);
 }
 
-static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain, bool want_digest, bool want_level)
+/* GPSBB_PUSH_LEVEL: what k_level will be given is checked, and its memory made, before anything of the push exists */
+static int push_level_memory(gpsbb_stream *s, const ImpairCall &ic)
 {
-    if (!s || !ch)
+    if (!level_fits(ic.a, ic.noise, s->nsamp))
         return GPSBB_E_BADARG;
-    if (s->poisoned || s->head - s->tail >= (uint64_t)s->depth)
-        return GPSBB_E_STATE; /* ring full: pop first */
-    ImpairCall ic; /* the one value the gather and k_level are both given */
-    if (!stream_impair(s, &ic))
-        return GPSBB_E_BADARG; /* the push would reach position 2^63 */
-    if (want_level) {
-        /* GPSBB_PUSH_LEVEL: what k_level will be given is checked, and its memory made, before anything of the push exists */
-        if (!level_fits(ic.a, ic.noise, s->nsamp))
-            return GPSBB_E_BADARG;
-        auto &lsl = s->slots[s->head % s->depth];
-        HIPCHK(s->h, hipSetDevice(s->h->device));
-        if (!lsl.d_lvl)
-            HIPCHK(s->h, hipMalloc((void **)&lsl.d_lvl, (size_t)s->bps * sizeof(LevelOut)));
-        if (!lsl.h_lvl)
-            HIPCHK(s->h, hipHostMalloc((void **)&lsl.h_lvl, (size_t)s->bps * sizeof(LevelOut), hipHostMallocDefault));
-    }
-    if (new_chain) {
-        /* this push does not continue the one before: every channel of its first block starts from its descriptor's phase,
-         * as if it had just been allocated (c:1956-1964) — "no satellite was here before" is all the chain has to be told */
-        for (int i = 0; i < GPSBB_MAX_CHAN; i++) {
-            s->last_prn[i] = 0;
-            s->fx_prn[i] = 0;
-            if (s->carry)
-                s->carry->prn[i] = 0;
-        }
-    }
-    gpsbb *h = s->h;
-    g_push_trace.start();
-    HIPCHK(h, hipSetDevice(h->device));
     auto &sl = s->slots[s->head % s->depth];
-    gpsbb_batch *b = sl.batch;
-    /* Blocks consecutive in time with the IEEE carrier: the carrier phase carries over from block to block and from
-     * push to push, exactly.  Where that is resolved is decided per push below (on the device: gpsbb_walk.hip.h). */
-    unsigned run_flags = s->flags & (GPSBB_CHAIN_CARRIER | GPSBB_FIXED_CARRIER);
-    const size_t nbc = (size_t)s->bps * s->nch;
-    const PlanOpts opts = plan_opts(h, b->max_sets);
-    PlanIn in{ch, s->bps, s->nch, s->delt, s->nsamp, run_flags};
-    BatchPlan begun; /* the plan's first step, where the decision below had to take it */
-    bool have_begun = false;
-    StreamLink link; /* what this push lends the slot's batch */
-    /* the host's chaining state only moves on once every enqueue of this push has succeeded */
-    ChainCarry carry_next;
-    bool carry_host = false;
-    double rough_next[GPSBB_MAX_CHAN]; /* taken from s->rough_phase below, once the carry is where this push wants it */
-    int fx_prn_next[GPSBB_MAX_CHAN];
-    uint32_t fx_phase_next[GPSBB_MAX_CHAN];
-    memcpy(fx_prn_next, s->fx_prn, sizeof fx_prn_next);
-    memcpy(fx_phase_next, s->fx_phase, sizeof fx_phase_next);
-    if ((s->flags & GPSBB_CHAIN_CARRIER) && !(s->flags & GPSBB_FIXED_CARRIER)) {
-        for (size_t k = 0; k < nbc; k++)
-            if (!chan_ok(ch[k], s->delt))
-                return GPSBB_E_BADCHAN;
-        /* Where the carrier is chained: on the device wherever the pre-pass runs there (exactly, in parallel over the
-         * blocks, the phase carried from push to push in device memory; for either synthesis kernel), on host
-         * threads — sequential per channel — for pushes small enough to be seeded on the host.  A stream may
-         * change sides between pushes: the carry then moves across, which costs a synchronisation. */
-        /* (small pushes too where the lap-parallel pre-pass will take them: it costs less than the host threads) */
-        /* (... which it only does for blocks the model kernels render: the kernel plan's own test, here, before the push is promised
-         * the device-side chain — a small push of a 1 MS/s stream, which they decline, stays with the host threads instead of the
-         * row walks' milliseconds) */
-        /* (the plan's own steps, asked once: what plan_begin leaves is handed on to batch_setup below — these conditions imply the
-         * device side, so the descriptors and flags are the ones the rest of the plan is made for) */
-        bool small_on_dev = nbc <= opts.host_seed_max && opts.seed_where == 0 && opts.synth_kernel != 1 && opts.chain_where == 0 &&
-                            plan_laps_admit(in, opts);
-        if (small_on_dev) {
-            const int rc_ = plan_begin(begun, b->img, in, opts);
-            if (rc_ != GPSBB_OK)
-                return rc_;
-            have_begun = true;
-            small_on_dev = begun.ev;
-        }
-        const bool dev = opts.chain_where != 1 &&
-                         (opts.seed_where == 1 || opts.seed_where == 3 ||
-                          (opts.seed_where == 0 && (opts.device_seed_only || nbc > opts.host_seed_max || small_on_dev)));
-        if (!s->carry) {
-            s->carry = new (std::nothrow) ChainCarry();
-            if (!s->carry)
-                return GPSBB_E_NOMEM;
-            memset(s->carry, 0, sizeof *s->carry);
-        }
-        if (dev) {
-            if (!s->d_carry) {
-                HIPCHK(h, hipMalloc((void **)&s->d_carry, sizeof(ChainCarryDev)));
-                HIPCHK(h, zero_now(h, s->d_carry, sizeof(ChainCarryDev)));
-                HIPCHK(h, hipEventCreateWithFlags(&s->ev_prefix, hipEventDisableTiming));
-                HIPCHK(h, hipEventCreateWithFlags(&s->ev_fix, hipEventDisableTiming));
-            }
-            if (!s->carry_on_device && s->head > 0) {
-                /* host -> device: the exact phases as both the prediction and the truth */
-                ChainCarryDev c;
-                for (int i = 0; i < GPSBB_MAX_CHAN; i++)
-                    c.approx_end[i] = c.exact_end[i] = s->carry->phase[i];
-                const int rc_ = gpsbb_sync(h);
-                if (rc_ != GPSBB_OK)
-                    return rc_;
-                HIPCHK(h, hipMemcpy(s->d_carry, &c, sizeof c, hipMemcpyHostToDevice));
-                HIPCHK(h, hipStreamSynchronize(nullptr)); /* (see zero_now) */
-                for (int i = 0; i < s->nch; i++) {
-                    s->last_prn[i] = s->carry->prn[i];
-                    s->rough_phase[i] = s->carry->phase[i];
-                }
-            }
-            s->carry_on_device = true;
-            memcpy(rough_next, s->rough_phase, sizeof rough_next);
-            link.d_carry = s->d_carry;
-            link.carry_prn = s->last_prn;
-            link.carry_phase = rough_next;
-            link.ev_prefix = s->ev_prefix;
-            link.ev_fix = s->ev_fix;
-            link.stream_turn = (unsigned)s->head;
-        } else {
-            if (s->carry_on_device) {
-                /* device -> host */
-                ChainCarryDev c;
-                const int rc_ = gpsbb_sync(h);
-                if (rc_ != GPSBB_OK)
-                    return rc_;
-                HIPCHK(h, hipMemcpy(&c, s->d_carry, sizeof c, hipMemcpyDeviceToHost));
-                for (int i = 0; i < s->nch; i++) {
-                    s->carry->prn[i] = s->last_prn[i];
-                    s->carry->phase[i] = c.exact_end[i];
-                }
-                s->carry_on_device = false;
-            }
-            s->seeded.assign(ch, ch + nbc);
-            s->seeds.resize(nbc);
-            carry_next = *s->carry; /* committed only when the push has been enqueued in full */
-            carry_host = true;
-            chain_carrier_host(ch, s->bps, s->nch, s->delt, s->nsamp, s->seeds.data(), 0, &carry_next);
-            for (size_t k = 0; k < nbc; k++)
-                s->seeded[k].carr_phase = s->seeds[k];
-            ch = s->seeded.data();
-            run_flags &= ~GPSBB_CHAIN_CARRIER;
-            in.ch = ch; /* the plan is taken on the rewritten descriptors */
-            in.flags = run_flags;
-            have_begun = false;
+    HIPCHK(s->h, hipSetDevice(s->h->device));
+    if (!sl.d_lvl)
+        HIPCHK(s->h, hipMalloc((void **)&sl.d_lvl, (size_t)s->bps * sizeof(LevelOut)));
+    if (!sl.h_lvl)
+        HIPCHK(s->h, hipHostMalloc((void **)&sl.h_lvl, (size_t)s->bps * sizeof(LevelOut), hipHostMallocDefault));
+    return GPSBB_OK;
+}
+
+/* A device-side push: the carry in device memory, made on the first such push, moved there behind a host-side one; `next` follows. */
+static int push_carry_to_device(gpsbb_stream *s, StreamChain &next)
+{
+    gpsbb *h = s->h;
+    StreamChain &at = s->chain;
+    if (!s->d_carry) {
+        HIPCHK(h, hipMalloc((void **)&s->d_carry, sizeof(ChainCarryDev)));
+        HIPCHK(h, zero_now(h, s->d_carry, sizeof(ChainCarryDev)));
+        HIPCHK(h, hipEventCreateWithFlags(&s->ev_prefix, hipEventDisableTiming));
+        HIPCHK(h, hipEventCreateWithFlags(&s->ev_fix, hipEventDisableTiming));
+    }
+    if (!at.on_device && s->head > 0) {
+        /* host -> device: the exact phases as both the prediction and the truth */
+        ChainCarryDev c;
+        for (int i = 0; i < GPSBB_MAX_CHAN; i++)
+            c.approx_end[i] = c.exact_end[i] = at.carry.phase[i];
+        const int rc = gpsbb_sync(h);
+        if (rc != GPSBB_OK)
+            return rc;
+        HIPCHK(h, hipMemcpy(s->d_carry, &c, sizeof c, hipMemcpyHostToDevice));
+        HIPCHK(h, hipStreamSynchronize(nullptr)); /* (see zero_now) */
+        for (int i = 0; i < s->nch; i++) {
+            at.last_prn[i] = at.carry.prn[i];
+            at.rough_phase[i] = at.carry.phase[i];
         }
     }
-    if (!link.d_carry)
-        memcpy(rough_next, s->rough_phase, sizeof rough_next);
-    /* the slot's previous D2H copy was waited for by the pop that freed it */
-    const bool fx_chain = (s->flags & GPSBB_FIXED_CARRIER) && (s->flags & GPSBB_CHAIN_CARRIER) && s->head > 0;
-    link.fixed_prev_prn = fx_chain ? s->fx_prn : nullptr;
-    link.fixed_prev_phase = fx_chain ? s->fx_phase : nullptr;
-    /* the batch holds the link for the length of this push: set-up and launch read it */
-    struct Unlink {
-        gpsbb_batch *b;
-        ~Unlink() { b->link = StreamLink(); }
-    } unlink{b};
-    b->link = link;
-    PUSH_MARK("plan");
-    /* descriptors and plans go up on the stream that will run this push's pre-pass (a push promised the device-side chain gets it,
-     * or fails below) */
-    hipStream_t us = nullptr;
-    HIPCHK(h, batch_prepass_stream(b, b->link.d_carry != nullptr, &us));
-    int rc = batch_setup(b, in, opts, us, have_begun ? &begun : nullptr);
-    PUSH_MARK("setup");
-    if (rc != GPSBB_OK)
-        return rc;
-    /* The push was promised a device-side chain.  Unreachable: a carry keeps plan_placement from seeding on the host whatever
-     * the size, the carry is only lent where GPSBB_OPT_CHAIN_WHERE is not 1, and a chained IEEE batch with a carry is
-     * `chained` there — so chain_dev follows.  Kept in case a later plan step breaks that. */
-    if (link.d_carry && !b->plan.chain_dev)
-        return GPSBB_E_INTERNAL;
-    if (s->flags & GPSBB_FIXED_CARRIER)
+    at.on_device = true;
+    next = at;
+    return GPSBB_OK;
+}
+
+/* A host-side push: the carry fetched from the device behind a device-side one, the chain resolved on host threads into next.carry,
+ * and the push goes on as one of independent blocks: `in` takes descriptors that carry every block's start phase, and no plan begun. */
+static int push_carry_to_host(gpsbb_stream *s, StreamChain &next, PlanIn &in, PushSide &side)
+{
+    gpsbb *h = s->h;
+    StreamChain &at = s->chain;
+    if (at.on_device) {
+        /* device -> host */
+        ChainCarryDev c;
+        const int rc = gpsbb_sync(h);
+        if (rc != GPSBB_OK)
+            return rc;
+        HIPCHK(h, hipMemcpy(&c, s->d_carry, sizeof c, hipMemcpyDeviceToHost));
         for (int i = 0; i < s->nch; i++) {
-            const size_t k = (size_t)(s->bps - 1) * s->nch + i;
-            fx_prn_next[i] = ch[k].prn > 0 ? ch[k].prn : 0;
-            fx_phase_next[i] = b->img.h_kph0[k] + (uint32_t)s->nsamp * (uint32_t)b->img.h_kstep[k];
+            at.carry.prn[i] = at.last_prn[i];
+            at.carry.phase[i] = c.exact_end[i];
         }
-    b->last_iq = b->d_iq.p;
-    /* From here on kernels of this push may be in the queues (with the device-side chain they advance the carry in
-     * device memory): a failure leaves the host's and the device's view of the stream apart, so the stream is closed
-     * instead of letting a retry chain from the wrong phase. */
-    struct Poison {
-        gpsbb_stream *s;
-        bool armed = true;
-        ~Poison() { if (armed) s->poisoned = true; }
-    } poison{s};
-    b->want_digest = want_digest;
-    if (want_digest && !sl.h_dig)
-        HIPCHK(h, hipHostMalloc((void **)&sl.h_dig, (size_t)s->bps * sizeof(unsigned long long), hipHostMallocDefault));
-    sl.has_dig = false;
-    sl.has_lvl = false;
-    rc = batch_launch(b, b->d_iq.p);
-    PUSH_MARK("launch");
-    if (rc != GPSBB_OK)
-        return rc;
-    PUSH_MARK("rec");
+        at.on_device = false;
+    }
+    next = at;
+    const size_t nbc = (size_t)s->bps * s->nch;
+    s->seeded.assign(in.ch, in.ch + nbc);
+    s->seeds.resize(nbc);
+    chain_carrier_host(in.ch, s->bps, s->nch, s->delt, s->nsamp, s->seeds.data(), 0, &next.carry);
+    for (size_t k = 0; k < nbc; k++)
+        s->seeded[k].carr_phase = s->seeds[k];
+    in.ch = s->seeded.data();
+    in.flags &= ~GPSBB_CHAIN_CARRIER;
+    side.begun = false;
+    return GPSBB_OK;
+}
+
+/* Everything behind the synthesis of a push: the gather, the end states, the digests, the level, and the event a pop waits for. */
+static int push_outputs(gpsbb_stream *s, gpsbb_stream::Slot &sl, ImpairCall &ic, bool want_digest, bool want_level)
+{
+    gpsbb *h = s->h;
+    gpsbb_batch *b = sl.batch;
     /* Host-bound output: gather on the copy stream — pinned, asynchronous, overlaps the next push's kernels.  A device-only
      * ring has none: its end states (and digests) merely follow the synthesis, so they ride behind it on its stream, with no
      * event wait and no stream that holds one (a hardware queue whose head is a wait for a 1.5 ms kernel runs nothing that
-     * shares it until then). */
+     * shares it until then).  (The slot's previous D2H copy was waited for by the pop that freed it.) */
     hipStream_t cs = b->last_cs;
     if (sl.h_iq) {
         if (!h->s_copy)
@@ -3916,14 +3812,12 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
         }
     }
     PUSH_MARK("iq");
-    {
-        /* end states (40 B each: a multiple of 16 bytes for any even count; odd counts are rounded up into the
-         * allocation's slack) + the self-check word, by a small kernel: see k_end_states_to_host */
-        const size_t bytes = (size_t)s->bps * s->nch * sizeof(gpsbb_chan_state_t);
-        hipLaunchKernelGGL(k_end_states_to_host, dim3(64), dim3(256), 0, cs, (const uint4 *)b->sets[b->last_set].end.p,
-                           (uint4 *)sl.h_end, (bytes + 15) / 16, h->d_status, (uint32_t *)((char *)sl.h_end + ((bytes + 15) & ~(size_t)15)));
-        HIPCHK(h, hipGetLastError());
-    }
+    /* end states (40 B each: a multiple of 16 bytes for any even count; odd counts are rounded up into the
+     * allocation's slack) + the self-check word, by a small kernel: see k_end_states_to_host */
+    const size_t bytes = (size_t)s->bps * s->nch * sizeof(gpsbb_chan_state_t);
+    hipLaunchKernelGGL(k_end_states_to_host, dim3(64), dim3(256), 0, cs, (const uint4 *)b->sets[b->last_set].end.p,
+                       (uint4 *)sl.h_end, (bytes + 15) / 16, h->d_status, (uint32_t *)((char *)sl.h_end + ((bytes + 15) & ~(size_t)15)));
+    HIPCHK(h, hipGetLastError());
     if (want_digest) {
         HIPCHK(h, hipMemcpyAsync(sl.h_dig, b->d_dig.p, (size_t)s->bps * sizeof(unsigned long long), hipMemcpyDeviceToHost, cs));
         sl.has_dig = true;
@@ -3936,21 +3830,110 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
     }
     PUSH_MARK("endst");
     HIPCHK(h, hipEventRecord(sl.copied, cs));
-    /* commit */
-    if (carry_host)
-        *s->carry = carry_next;
-    if (s->carry_on_device && (s->flags & GPSBB_CHAIN_CARRIER) && !(s->flags & GPSBB_FIXED_CARRIER))
-        for (int i = 0; i < s->nch; i++) {
-            const int prn = ch[(size_t)(s->bps - 1) * s->nch + i].prn;
-            s->last_prn[i] = prn > 0 ? prn : 0;
+    return GPSBB_OK;
+}
+
+/* What ends with a push, however it ends: the slot's batch holds the link for the length of the push (set-up and launch read it).
+ * And once `queued` — kernels of the push may be in the queues; with the device-side chain they advance the carry in device
+ * memory — a failure leaves the host's and the device's view of the stream apart: the stream is closed instead of letting a retry
+ * chain from the wrong phase.  Before that a failure just returns: a NEW_CHAIN taken and a carry moved stay, nothing else does. */
+struct PushGuard {
+    gpsbb_stream *s;
+    gpsbb_batch *b;
+    bool queued = false, done = false;
+    ~PushGuard()
+    {
+        b->link = StreamLink();
+        s->poisoned = s->poisoned || (queued && !done);
+    }
+};
+
+/* Blocks consecutive in time with the IEEE carrier: the carrier phase carries over from block to block and from push to push,
+ * exactly; on which side is decided per push (plan_push_side). */
+static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain, bool want_digest, bool want_level)
+{
+    if (!s || !ch)
+        return GPSBB_E_BADARG;
+    if (s->poisoned || s->head - s->tail >= (uint64_t)s->depth)
+        return GPSBB_E_STATE; /* ring full: pop first */
+    ImpairCall ic; /* the one value the gather and k_level are both given */
+    if (!stream_impair(s, &ic))
+        return GPSBB_E_BADARG; /* the push would reach position 2^63 */
+    int rc = want_level ? push_level_memory(s, ic) : GPSBB_OK;
+    if (rc != GPSBB_OK)
+        return rc;
+    if (new_chain)
+        s->chain.forget(false);
+    gpsbb *h = s->h;
+    g_push_trace.start();
+    HIPCHK(h, hipSetDevice(h->device));
+    auto &sl = s->slots[s->head % s->depth];
+    gpsbb_batch *b = sl.batch;
+    const PlanOpts opts = plan_opts(h, b->max_sets);
+    PlanIn in{ch, s->bps, s->nch, s->delt, s->nsamp, s->flags & (GPSBB_CHAIN_CARRIER | GPSBB_FIXED_CARRIER)};
+    PushSide side;
+    rc = plan_push_side(side, b->img, in, opts);
+    if (rc != GPSBB_OK)
+        return rc;
+    StreamChain next = s->chain; /* the chain behind this push */
+    if (side.chain == PUSH_CHAIN_DEVICE)
+        rc = push_carry_to_device(s, next);
+    else if (side.chain == PUSH_CHAIN_HOST)
+        rc = push_carry_to_host(s, next, in, side);
+    if (rc != GPSBB_OK)
+        return rc;
+    /* what the push lends the batch: the carry, its events and the chain as the push found it (the rough phases in and out, in
+     * the copy); the accumulator's chaining state behind a first push */
+    PushGuard guard{s, b};
+    if (side.chain == PUSH_CHAIN_DEVICE) {
+        b->link.d_carry = s->d_carry;
+        b->link.carry_prn = s->chain.last_prn;
+        b->link.carry_phase = next.rough_phase;
+        b->link.ev_prefix = s->ev_prefix;
+        b->link.ev_fix = s->ev_fix;
+        b->link.stream_turn = (unsigned)s->head;
+    }
+    if ((s->flags & GPSBB_FIXED_CARRIER) && (s->flags & GPSBB_CHAIN_CARRIER) && s->head > 0) {
+        b->link.fixed_prev_prn = s->chain.fx_prn;
+        b->link.fixed_prev_phase = s->chain.fx_phase;
+    }
+    PUSH_MARK("plan");
+    /* descriptors and plans go up on the stream that will run this push's pre-pass */
+    hipStream_t us = nullptr;
+    HIPCHK(h, batch_prepass_stream(b, b->link.d_carry != nullptr, &us));
+    rc = batch_setup(b, in, opts, us, side.begun ? &side.plan0 : nullptr);
+    PUSH_MARK("setup");
+    if (rc != GPSBB_OK)
+        return rc;
+    for (int i = 0; i < s->nch; i++) {
+        const size_t k = (size_t)(s->bps - 1) * s->nch + i;
+        if (side.chain == PUSH_CHAIN_DEVICE)
+            next.last_prn[i] = in.ch[k].prn > 0 ? in.ch[k].prn : 0;
+        if (s->flags & GPSBB_FIXED_CARRIER) {
+            next.fx_prn[i] = in.ch[k].prn > 0 ? in.ch[k].prn : 0;
+            next.fx_phase[i] = b->img.h_kph0[k] + (uint32_t)s->nsamp * (uint32_t)b->img.h_kstep[k];
         }
-    memcpy(s->rough_phase, rough_next, sizeof rough_next);
-    memcpy(s->fx_prn, fx_prn_next, sizeof fx_prn_next);
-    memcpy(s->fx_phase, fx_phase_next, sizeof fx_phase_next);
+    }
+    b->last_iq = b->d_iq.p;
+    guard.queued = true;
+    b->want_digest = want_digest;
+    if (want_digest && !sl.h_dig)
+        HIPCHK(h, hipHostMalloc((void **)&sl.h_dig, (size_t)s->bps * sizeof(unsigned long long), hipHostMallocDefault));
+    sl.has_dig = false;
+    sl.has_lvl = false;
+    rc = batch_launch(b, b->d_iq.p);
+    PUSH_MARK("launch");
+    if (rc != GPSBB_OK)
+        return rc;
+    PUSH_MARK("rec");
+    rc = push_outputs(s, sl, ic, want_digest, want_level);
+    if (rc != GPSBB_OK)
+        return rc;
+    s->chain = next; /* every enqueue of this push has succeeded: the chain moves on */
     if (s->noise_on || s->interf_on)
         s->out_pos += (unsigned long long)s->bps * (unsigned long long)s->nsamp;
     s->head++;
-    poison.armed = false;
+    guard.done = true;
     g_push_trace.end();
     return GPSBB_OK;
 }
@@ -4559,6 +4542,20 @@ extern "C" int gpsbb_test_plan(const gpsbb_chan_t *ch, int nblocks, int nch, dou
         carry && carry_phase ? fnv1a(carry_phase, (size_t)pl.nch * sizeof(double)) : 0ull};
     memcpy(out, v, sizeof v);
     return GPSBB_OK;
+}
+
+/* plan_push_side on its own: the side (PUSH_CHAIN_*), and whether the decision took the plan's first step */
+extern "C" int gpsbb_test_push_side(const gpsbb_chan_t *ch, int nblocks, int nch, double delt, int nsamp, unsigned flags, const int opt[5],
+                                    int out[2])
+{
+    if (!ch || !opt || !out || nblocks < 1 || nch < 1 || nch > GPSBB_MAX_CHAN)
+        return GPSBB_E_BADARG;
+    PushSide side;
+    PlanImages img;
+    const int rc = plan_push_side(side, img, PlanIn{ch, nblocks, nch, delt, nsamp, flags}, plan_opts(opt[0], opt[1], opt[2] != 0, opt[3], opt[4]));
+    out[0] = (int)side.chain;
+    out[1] = side.begun;
+    return rc;
 }
 
 extern "C" int gpsbb_test_table_digest(gpsbb_batch_t *b, unsigned long long out[3])

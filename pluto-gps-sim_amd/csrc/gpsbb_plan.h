@@ -1,7 +1,8 @@
 /*
  * gpsbb_plan.h — how a batch is planned: everything batch set-up decides from the descriptors, the handle's options and a stream's
- * carry, as one pure host function (plan_batch) and the plain structs it fills.  No HIP call, neither the handle nor the batch:
- * gpsbb.hip stages what the plan says (batch_setup) and launches from it; gpsbb_test_plan runs it without a GPU.
+ * carry, as one pure host function (plan_batch) and the plain structs it fills; and, ahead of it for a ring's push, on which side
+ * the push chains its carrier (plan_push_side).  No HIP call, neither the handle nor the batch: gpsbb.hip stages what the plan says
+ * (batch_setup) and launches from it; gpsbb_test_plan and gpsbb_test_push_side run them without a GPU.
  * Included by gpsbb.hip behind the descriptor checks and kernel plans it calls (chan_ok, ev_plan, lap_eligible, lap_bound, row_bound,
  * CarrDrift) and the constants it reads (NSETS, CHAIN_*); not a translation unit of its own.
  */
@@ -167,7 +168,7 @@ static int plan_begin(BatchPlan &pl, PlanImages &img, const PlanIn &in, const Pl
 }
 
 /* What of the lap-parallel pre-pass's eligibility does not depend on the kernel choice: the options, and no step that is tiny.
- * (gpsbb_stream_push asks this first and chooses the kernel only where the answer matters.) */
+ * (plan_push_side asks this first and chooses the kernel only where the answer matters.) */
 static bool plan_laps_admit(const PlanIn &in, const PlanOpts &o)
 {
     return o.seed_where != 1 && o.seed_where != 2 && o.chain_where != 2 && o.chain_where != 3 && !o.no_laps &&
@@ -175,11 +176,52 @@ static bool plan_laps_admit(const PlanIn &in, const PlanOpts &o)
 }
 
 /* where the NCO tables of a run are built: by size (default), or as GPSBB_OPT_SEED_WHERE says (tests run both ways) */
-static bool host_seeding_wanted(const BatchPlan &pl, const PlanOpts &o)
+static bool host_seeding_wanted(size_t nbc, const PlanOpts &o)
 {
     if (o.seed_where)
         return o.seed_where == 2;
-    return !o.device_seed_only && (size_t)pl.nblocks * pl.nch <= o.host_seed_max;
+    return !o.device_seed_only && nbc <= o.host_seed_max;
+}
+
+/* On which side a ring's push chains its IEEE carrier.  NONE: the ring is not chained, or chains the accumulator.  DEVICE: exactly,
+ * in parallel over the blocks, the phase carried from push to push in device memory, for either synthesis kernel — the push is planned
+ * with the stream's carry (StreamLink::d_carry), from which plan_placement derives chain_dev and never host_seed.  HOST: on host
+ * threads, sequential per channel — the push is planned on descriptors that carry every block's start phase, without
+ * GPSBB_CHAIN_CARRIER.  A stream may change sides between pushes: the carry then moves across, which costs a synchronisation. */
+enum PushChain { PUSH_CHAIN_NONE, PUSH_CHAIN_HOST, PUSH_CHAIN_DEVICE };
+struct PushSide {
+    PushChain chain = PUSH_CHAIN_NONE;
+    bool begun = false; /* the decision took the plan's first step: plan0 (and the images it was given) hold plan_begin's result */
+    BatchPlan plan0;
+};
+
+/* The device wherever the pre-pass runs there, the host for pushes small enough to be seeded on the host — but for small pushes the
+ * lap-parallel pre-pass will take: it costs less than the host threads.  It only takes blocks the model kernels render (a small push
+ * of a 1 MS/s stream, which they decline, stays with the host threads instead of the row walks' milliseconds), so plan_begin runs
+ * here, once, where the answer hangs on it — the conditions imply the device side unless the kernels decline, so its result is the
+ * one the rest of the plan is made for (side.begun). */
+static int plan_push_side(PushSide &side, PlanImages &img, const PlanIn &in, const PlanOpts &o)
+{
+    side = PushSide();
+    if (!(in.flags & GPSBB_CHAIN_CARRIER) || (in.flags & GPSBB_FIXED_CARRIER))
+        return GPSBB_OK;
+    const size_t nbc = (size_t)in.nblocks * in.nch;
+    for (size_t k = 0; k < nbc; k++)
+        if (!chan_ok(in.ch[k], in.delt))
+            return GPSBB_E_BADCHAN;
+    bool small_on_dev = nbc <= o.host_seed_max && o.seed_where == 0 && o.synth_kernel != 1 && o.chain_where == 0 &&
+                        plan_laps_admit(in, o);
+    if (small_on_dev) {
+        const int rc = plan_begin(side.plan0, img, in, o);
+        if (rc != GPSBB_OK)
+            return rc;
+        side.begun = true;
+        small_on_dev = side.plan0.ev;
+    }
+    /* (plan_placement's own question: what it would seed on the host without a carry is chained there) */
+    const bool dev = o.chain_where != 1 && (!host_seeding_wanted(nbc, o) || small_on_dev);
+    side.chain = dev ? PUSH_CHAIN_DEVICE : PUSH_CHAIN_HOST;
+    return GPSBB_OK;
 }
 
 /* The state granule of a batch's tile tables (BatchDev::st_log2): one exact state per 2^g tiles where the breakpoint kernel proper
@@ -211,10 +253,9 @@ static void plan_placement(BatchPlan &pl, const PlanImages &img, const PlanIn &i
      * pre-pass takes 0.1 ms whatever the size of the batch — less than host threads need for one block (tools/fill_latency.py:
      * 0.25 against 0.33 ms per gpsbb_fill_block of the reference's geometry) — so where it is eligible the size decides nothing. */
     const bool lap_ok = pl.ev && plan_laps_admit(in, o);
-    /* (a stream's push that was promised the device-side chain — the carry: decided in gpsbb_stream_push, which asks
-     * plan_laps_admit and plan_begin themselves — stays on the device whatever the size: the row walks where the laps decline,
-     * e.g. a rate only the per-sample kernel renders) */
-    pl.host_seed = !lap_ok && !carry && host_seeding_wanted(pl, o);
+    /* (a stream's push on the device side — the carry: PUSH_CHAIN_DEVICE of plan_push_side — stays on the device whatever the
+     * size: the row walks where the laps decline, e.g. a rate only the per-sample kernel renders) */
+    pl.host_seed = !lap_ok && !carry && host_seeding_wanted((size_t)in.nblocks * in.nch, o);
     pl.laps = lap_ok;
     pl.st_log2 = ev_state_log2(pl, img, o);
     pl.nstates = (pl.ntiles + (1 << pl.st_log2) - 1) >> pl.st_log2;

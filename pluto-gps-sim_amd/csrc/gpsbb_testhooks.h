@@ -46,6 +46,12 @@ struct gpsbb_chan;
 int gpsbb_test_plan(const struct gpsbb_chan *ch, int nblocks, int nch, double delt, int nsamp, unsigned flags, const int opt[5],
                     int carry, const int *carry_prn, double *carry_phase, const int *fixed_prev_prn,
                     const uint32_t *fixed_prev_phase, unsigned long long out[GPSBB_TEST_PLAN_NQ]);
+/* plan_push_side (gpsbb_plan.h) on the descriptors of one push of a ring with these flags: on which side gpsbb_stream_push would
+ * chain the IEEE carrier.  opt: as above.  out[0]: 0 not at all (no GPSBB_CHAIN_CARRIER, or the accumulator), 1 on host threads,
+ * 2 on the device; out[1]: the decision ran plan_begin (its result is handed on to set-up where the side is the device).
+ * Returns GPSBB_OK or the error the push would return from there. */
+int gpsbb_test_push_side(const struct gpsbb_chan *ch, int nblocks, int nch, double delt, int nsamp, unsigned flags, const int opt[5],
+                         int out[2]);
 
 /* The error budgets of the model kernels, measured (gpsbb_modelerr.hip.h): the realised |model - truth| of everything
  * k_synth_ev / k_synth_pd test, over every tile of the batch's last run, per channel index.  Needs a GPU. */

@@ -1,5 +1,6 @@
 // plan_batch (csrc/gpsbb_plan.h) under the host sanitizers, on a machine without a GPU: the matrix of tests/test_batch_plan.py, as
-// `python tests/batch_plan_cases.py FILE` writes it, through gpsbb_test_plan; prints what the test compares, one line per set-up.
+// `python tests/batch_plan_cases.py FILE` writes it, through gpsbb_test_plan; prints what the test compares, one line per set-up —
+// and, for every set-up with GPSBB_CHAIN_CARRIER and the IEEE carrier, what plan_push_side makes of it (gpsbb_test_push_side).
 //   hipcc --offload-arch=gfx950 -std=c++17 -ffp-contract=off -DGPSBB_EXPERIMENTS -Xarch_host -fsanitize=address,undefined \
 //         -Ipluto-gps-sim_amd/csrc -Iinclude tools/plan_asan.cpp pluto-gps-sim_amd/csrc/gpsbb_node.cpp -o plan_asan
 //   ./plan_asan FILE
@@ -32,6 +33,11 @@ int main(int argc, char **argv)
         printf("%d", rc);
         for (int i = 0; rc == GPSBB_OK && i < GPSBB_TEST_PLAN_NQ; i++)
             printf(" %llx", out[i]);
+        if ((r.flags & GPSBB_CHAIN_CARRIER) && !(r.flags & GPSBB_FIXED_CARRIER)) { // as a ring's push: the side of its chain, last on the line
+            int side[2] = {0, 0};
+            const int rs = gpsbb_test_push_side(ch.data(), r.nblocks, r.nch, r.delt, r.nsamp, r.flags, r.opt, side);
+            printf(" side %d %d %d", rs, side[0], side[1]);
+        }
         printf("\n");
         n++;
     }
