@@ -379,6 +379,8 @@ def exp_lib():
             L.gpsbb_test_plan.argtypes = [vp, i, i, d, i, u, vp, i, vp, vp, vp, vp, vp]
         if hasattr(L, "gpsbb_test_push_side"):  # (an older build loaded for an A/B: tools/ab_lib.sh)
             L.gpsbb_test_push_side.argtypes = [vp, i, i, d, i, u, vp, vp]
+        if hasattr(L, "gpsbb_test_chain_plan"):  # (an older build loaded for an A/B: tools/ab_lib.sh)
+            L.gpsbb_test_chain_plan.argtypes = [vp, i, i, d, i, i, vp]
         _exp_lib = L
     return _exp_lib
 
@@ -425,6 +427,26 @@ def push_side(ch, delt, nsamp, flags=0, seed_where=0, synth_kernel=0, chain_wher
     out = np.zeros(2, np.int32)
     rc = exp_lib().gpsbb_test_push_side(ch.ctypes.data, nb, nch, delt, nsamp, flags, opt.ctypes.data, out.ctypes.data)
     return rc, ({"chain": int(out[0]), "begun": int(out[1])} if rc == 0 else None)
+
+
+CHAIN_PLAN_PIECES = 64
+
+
+def chain_plan(ch, delt, nsamp, seed_where=0, nblocks=None, nch=None):
+    """gpsbb_test_chain_plan (csrc/gpsbb_testhooks.h): what gpsbb_chain_carrier would decide for these arguments before its first
+    HIP call, without a handle or a GPU.  Returns (rc, values): values = {"laps", "npieces" (the true count), "h_cd", "h_start0"
+    (64-bit FNV-1a), "pieces": [[b0, nb, cont0_mask, FNV-1a of chunk0 or 0], ...] (the first CHAIN_PLAN_PIECES)}.  nblocks / nch:
+    the counts to pass instead of the array's (the argument checks)."""
+    ch = _as_chan(ch)
+    nb, nc = ch.shape
+    out = np.zeros(4 + 4 * CHAIN_PLAN_PIECES, np.uint64)
+    rc = exp_lib().gpsbb_test_chain_plan(ch.ctypes.data, nb if nblocks is None else nblocks, nc if nch is None else nch, delt, nsamp,
+                                         seed_where, out.ctypes.data)
+    if rc != 0:
+        return rc, None
+    n = min(int(out[1]), CHAIN_PLAN_PIECES)
+    return rc, {"laps": int(out[0]), "npieces": int(out[1]), "h_cd": int(out[2]), "h_start0": int(out[3]),
+                "pieces": [[int(v) for v in out[4 + 4 * k:8 + 4 * k]] for k in range(n)]}
 
 
 def _chk(rc, what):

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cctype>
 #include <cmath>
 #include <cstdio>
@@ -337,16 +338,22 @@ bool ev_plan(const gpsbb_chan_t *ch, int nblocks, int nch, double delt, std::vec
 /* Does the lap-parallel pre-pass take these blocks (gpsbb_laps.hip.h, Eligibility)?  It is exact for any step it walks; what is
  * excluded is what its turn of the walk does not cover: steps more than 50 binades below the state (0 < |step| < 2^-50: below
  * 2e-8 Hz at 25 MS/s).  A step of exactly zero — a carrier without Doppler — is taken: the phase stands still (round 6). */
+bool lap_carr_step_ok(double f_carr, double delt) /* the carrier's condition alone (gpsbb_chain_carrier has no code chains) */
+{
+    const volatile double sk = f_carr * delt;
+    return std::fabs(sk) >= 0x1p-50 || sk == 0.0; /* (exactly zero stands still: lap_run takes it) */
+}
+
 bool lap_eligible(const gpsbb_chan_t *ch, size_t nbc, double delt, bool fixed)
 {
     for (size_t k = 0; k < nbc; k++) {
         const gpsbb_chan_t &c = ch[k];
         if (c.prn <= 0)
             continue;
-        const volatile double sc = c.f_code * delt, sk = c.f_carr * delt;
+        const volatile double sc = c.f_code * delt;
         if (!(sc >= 0x1p-20))
             return false;
-        if (!fixed && !(std::fabs(sk) >= 0x1p-50) && sk != 0.0) /* (exactly zero stands still: lap_run takes it) */
+        if (!fixed && !lap_carr_step_ok(c.f_carr, delt))
             return false;
     }
     return true;
@@ -783,6 +790,24 @@ struct ChainCarry {
 };
 static void chain_carrier_host(const gpsbb_chan_t *ch, int nblocks, int nch, double delt, int nsamp, double *seed,
                                int nthreads, ChainCarry *carry);
+
+/* work(i0, i1) over the channels [0, nch) in nthreads equal shares, a thread each.  A thread that cannot be started (no exception
+ * may cross the C boundary) leaves its share to the caller. */
+template <class Work>
+static void channel_threads(int nch, int nthreads, const Work &work)
+{
+    std::vector<std::thread> th;
+    for (int t = 0; t < nthreads; t++) {
+        const int i0 = (int)((long)nch * t / nthreads), i1 = (int)((long)nch * (t + 1) / nthreads);
+        try {
+            th.emplace_back(work, i0, i1);
+        } catch (...) {
+            work(i0, i1);
+        }
+    }
+    for (auto &t : th)
+        t.join();
+}
 
 #include "gpsbb_plan.h"
 
@@ -4057,22 +4082,10 @@ static void chain_carrier_host(const gpsbb_chan_t *ch, int nblocks, int nch, dou
     };
     if (nthreads <= 0 || nthreads > nch)
         nthreads = nch;
-    if (nthreads == 1) {
+    if (nthreads == 1)
         work(0, nch);
-    } else {
-        /* a thread that cannot be started (no exception may cross the C boundary) leaves its share to the caller */
-        std::vector<std::thread> th;
-        for (int t = 0; t < nthreads; t++) {
-            const int i0 = (int)((long)nch * t / nthreads), i1 = (int)((long)nch * (t + 1) / nthreads);
-            try {
-                th.emplace_back(work, i0, i1);
-            } catch (...) {
-                work(i0, i1);
-            }
-        }
-        for (auto &t : th)
-            t.join();
-    }
+    else
+        channel_threads(nch, nthreads, work);
 }
 
 extern "C" int gpsbb_chain_carrier_host(const gpsbb_chan_t *ch, int nblocks, int nch, double delt, int nsamp,
@@ -4089,25 +4102,24 @@ extern "C" int gpsbb_chain_carrier_host(const gpsbb_chan_t *ch, int nblocks, int
 
 /* ---- the carrier chain alone, on the device ---------------------------------------------------------- */
 
-/* Device scratch of gpsbb_chain_carrier: 24-byte chain descriptors, rough start phases, the chain's per-block record
- * and the carry from one sub-batch to the next.  Nothing of a synthesis batch (rows, tile states, IQ) exists here. */
+/* What gpsbb_chain_carrier keeps between calls: its plan and host images (plan_chain_only), and its device scratch — 24-byte chain
+ * descriptors, rough start phases, the chain's per-block record and the carry from one sub-batch to the next.  Nothing of a
+ * synthesis batch (rows, tile states, IQ) exists here. */
 struct ChainOnly {
+    ChainOnlyPlan plan;
+    PlanImages img; /* h_cd, h_start0 of all the call's blocks; the row walks read every block's exact start phase back into h_cd */
     DevBuf<ChainDesc> d_cd;
     DevBuf<double> d_start0;
     DevBuf<ChainAux> d_aux;
     ChainCarryDev *d_carry = nullptr;
     uint32_t *d_status = nullptr; /* a self-check word of its own: the handle's may belong to a push still in flight */
     FixScratch fix;
-    std::vector<ChainDesc> h_cd;
-    std::vector<double> h_start0;
     /* the lap-parallel chain (gpsbb_laps.hip.h with nothing to emit): the phase after every block, scratch of the lap kernels */
     DevBuf<double> d_lap_end;
     LapScratch lap;
     unsigned long long *d_hz_scratch = nullptr; /* (a chain alone counts no hazards: the render of those blocks does) */
     std::vector<double> h_lap_end;
 };
-constexpr int CHAIN_ONLY_BLOCKS = 16384;
-constexpr double CHAIN_ONLY_LAPS = 6.0e6; /* laps per sub-batch of the lap-parallel chain (40 bytes of scratch each) */ /* blocks per sub-batch: 168 MB of ChainAux at 16 channels */
 
 static void chain_only_free(gpsbb *h)
 {
@@ -4125,44 +4137,135 @@ static void chain_only_free(gpsbb *h)
     h->chain_only = nullptr;
 }
 
-/* What the chain kernels see of the sub-batch of nb blocks from block b0 on, whichever pre-pass walks it: the chain descriptors
- * alone, the carry from the sub-batch before, and which channels of its first block go on from the block before it. */
-static BatchDev chain_only_dev(const ChainOnly *c, int b0, int nb, int nch, double delt, int nsamp, unsigned long long *hazards)
+/* The scratch every piece shares, cleared: the carry from piece to piece, the self-check word, the lap kernels' hazard counters. */
+static int chain_only_scratch(gpsbb *h, ChainOnly *c, size_t lap_seeds)
+{
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!c->d_carry)
+        HIPCHK(h, hipMalloc((void **)&c->d_carry, sizeof(ChainCarryDev)));
+    if (!c->d_status)
+        HIPCHK(h, hipMalloc((void **)&c->d_status, 4));
+    HIPCHK(h, hipMemsetAsync(c->d_carry, 0, sizeof(ChainCarryDev), h->s_seed));
+    HIPCHK(h, hipMemsetAsync(c->d_status, 0, 4, h->s_seed));
+    if (c->plan.laps) {
+        if (!c->d_hz_scratch)
+            HIPCHK(h, hipMalloc((void **)&c->d_hz_scratch, 64));
+        HIPCHK(h, hipMemsetAsync(c->d_hz_scratch, 0, 64, h->s_seed));
+        if (lap_seeds)
+            c->h_lap_end.resize(lap_seeds);
+    }
+    return GPSBB_OK;
+}
+
+/* What the chain kernels see of a piece, whichever pre-pass walks it: the chain descriptors alone, the carry from the piece
+ * before, and which channels of its first block go on from the block before it. */
+static BatchDev chain_only_dev(const ChainOnly *c, const ChainOnlyPiece &pc, const PlanIn &in, unsigned long long *hazards)
 {
     BatchDev p;
     memset(&p, 0, sizeof p);
-    p.nblocks = nb;
-    p.nch = nch;
-    p.nsamp = nsamp;
-    p.ntiles = (nsamp + TILE - 1) / TILE;
+    p.nblocks = pc.nb;
+    p.nch = in.nch;
+    p.nsamp = in.nsamp;
+    p.ntiles = (in.nsamp + TILE - 1) / TILE;
     p.nstates = p.ntiles;
-    p.delt = delt;
+    p.delt = in.delt;
     p.flags = GPSBB_CHAIN_CARRIER;
     p.status = c->d_status;
     p.hazards = hazards;
     p.chain_dev = 1;
     p.nseg = 1;
-    p.nvb = nb;
+    p.nvb = pc.nb;
     p.cd = c->d_cd.p;
     p.carry = c->d_carry;
-    const size_t k0 = (size_t)b0 * nch;
-    if (b0 > 0)
-        for (int i = 0; i < nch; i++) {
-            const int prn = c->h_cd[k0 + i].prn;
-            if (prn > 0 && prn == c->h_cd[k0 - nch + i].prn)
-                p.cont0_mask |= 1u << i;
-        }
+    p.cont0_mask = pc.cont0_mask;
     return p;
 }
 
-/* ... and what the call brings back once its last sub-batch is done: the exact phase after the last block, the self-check word */
-static int chain_only_finish(gpsbb *h, const ChainOnly *c, size_t nbc_all, int nch, double *carr_phase_end)
+/* One piece by the lap-parallel pre-pass (gpsbb_laps.hip.h: plan, reference walks, scan, true walks with nothing to emit but the
+ * phase after every block, repair); want_seeds: those phases brought back into h_lap_end. */
+static int chain_only_lap_piece(gpsbb *h, ChainOnly *c, const ChainOnlyPiece &pc, const PlanIn &in, bool want_seeds)
+{
+    hipStream_t ss = h->s_seed;
+    const size_t nbc = (size_t)pc.nb * in.nch, k0 = (size_t)pc.b0 * in.nch;
+    HIPCHK(h, (hipError_t)c->d_cd.reserve(nbc));
+    HIPCHK(h, (hipError_t)c->d_lap_end.reserve(nbc));
+    HIPCHK(h, (hipError_t)c->lap.reserve(nbc, (size_t)in.nch, (size_t)pc.nb, pc.chunk0[1][in.nch], false));
+    HIPCHK(h, hipMemcpyAsync(c->d_cd.p, c->img.h_cd.data() + k0, nbc * sizeof(ChainDesc), hipMemcpyHostToDevice, ss));
+    LapDev L;
+    c->lap.dev(L);
+    lap_dev_plan(L, pc.chunk0, true, nbc);
+    BatchDev p = chain_only_dev(c, pc, in, c->d_hz_scratch);
+    p.lap_end = c->d_lap_end.p;
+    lap_chain_launch(ss, p, L, in.nch, NCO_CARR, lap_pass2_kernel(NCO_CARR, false, 0));
+    HIPCHK(h, hipGetLastError());
+    if (want_seeds)
+        HIPCHK(h, hipMemcpyAsync(c->h_lap_end.data() + k0, c->d_lap_end.p, nbc * sizeof(double), hipMemcpyDeviceToHost, ss));
+    HIPCHK(h, hipStreamSynchronize(ss));
+    return GPSBB_OK;
+}
+
+/* One piece by the row walks (gpsbb_walk.hip.h: pass A, prefix, pass B, k_chain_fix_par); want_seeds: the exact start phase of
+ * every block, as k_chain_fix_par left it in the chain descriptors, brought back over the piece's part of h_cd. */
+static int chain_only_walk_piece(gpsbb *h, ChainOnly *c, const ChainOnlyPiece &pc, const PlanIn &in, bool want_seeds)
+{
+    hipStream_t ss = h->s_seed;
+    const size_t nbc = (size_t)pc.nb * in.nch, k0 = (size_t)pc.b0 * in.nch;
+    HIPCHK(h, (hipError_t)c->d_cd.reserve(nbc));
+    HIPCHK(h, (hipError_t)c->d_start0.reserve(nbc));
+    HIPCHK(h, (hipError_t)c->d_aux.reserve(nbc));
+    HIPCHK(h, c->fix.reserve((size_t)GPSBB_MAX_CHAN * ((CHAIN_ONLY_BLOCKS + FIXP_WG_ALONE - 1) / FIXP_WG_ALONE), ss));
+    HIPCHK(h, hipMemcpyAsync(c->d_cd.p, c->img.h_cd.data() + k0, nbc * sizeof(ChainDesc), hipMemcpyHostToDevice, ss));
+    HIPCHK(h, hipMemcpyAsync(c->d_start0.p, c->img.h_start0.data() + k0, nbc * sizeof(double), hipMemcpyHostToDevice, ss));
+    BatchDev p = chain_only_dev(c, pc, in, h->d_hz);
+    p.chain_starts = 1;
+    p.model_start = 0; /* over tens of thousands of blocks a prediction drifts too far: pass A and the prefix stay */
+    p.seg_tiles = p.ntiles;
+    p.aux = c->d_aux.p;
+    p.start0 = c->d_start0.p;
+    p.fix_end = c->fix.end.p;
+    p.fix_flag = c->fix.flag.p;
+    p.fix_epoch = ++c->fix.epoch;
+    p.fix_chunks = (pc.nb + FIXP_WG_ALONE - 1) / FIXP_WG_ALONE;
+    p.seed_order = nullptr; /* channel by channel, blocks in order (k_walk) */
+    p.seed_lanes = in.nch * ((pc.nb + 63) & ~63);
+    HIPCHK(h, walk_chain_launch(ss, p, p.seed_lanes, true, 3, FIXP_WG_ALONE, CarryEvents()));
+    HIPCHK(h, hipGetLastError());
+    if (want_seeds)
+        HIPCHK(h, hipMemcpyAsync(c->img.h_cd.data() + k0, c->d_cd.p, nbc * sizeof(ChainDesc), hipMemcpyDeviceToHost, ss));
+    HIPCHK(h, hipStreamSynchronize(ss)); /* the device buffers are the next piece's */
+    return GPSBB_OK;
+}
+
+/* Every block's start phase from what the lap-parallel pieces brought back: a block starts where the one before ended, or — a
+ * channel that was idle or had another prn there — from its own phase */
+static void chain_only_lap_seeds(const ChainOnly *c, const PlanIn &in, double *seed)
+{
+    for (int i = 0; i < in.nch; i++)
+        for (int blk = 0; blk < in.nblocks; blk++) {
+            const size_t k = (size_t)blk * in.nch + i;
+            const ChainDesc &d = c->img.h_cd[k];
+            double v = 0.0;
+            if (d.prn > 0)
+                v = (blk > 0 && c->img.h_cd[k - in.nch].prn == d.prn) ? c->h_lap_end[k - in.nch] : d.carr_phase;
+            seed[k] = v;
+        }
+}
+
+/* ... from what the row-walk pieces brought back */
+static void chain_only_walk_seeds(const ChainOnly *c, const PlanIn &in, double *seed)
+{
+    for (size_t k = 0; k < (size_t)in.nblocks * in.nch; k++)
+        seed[k] = c->img.h_cd[k].prn > 0 ? c->img.h_cd[k].carr_phase : 0.0;
+}
+
+/* ... and what the call brings back once its last piece is done: the exact phase after the last block, the self-check word */
+static int chain_only_finish(gpsbb *h, const ChainOnly *c, const PlanIn &in, double *carr_phase_end)
 {
     if (carr_phase_end) {
         ChainCarryDev cc;
         HIPCHK(h, hipMemcpy(&cc, c->d_carry, sizeof cc, hipMemcpyDeviceToHost));
-        for (int i = 0; i < nch; i++)
-            carr_phase_end[i] = c->h_cd[nbc_all - nch + i].prn > 0 ? cc.exact_end[i] : 0.0;
+        for (int i = 0; i < in.nch; i++)
+            carr_phase_end[i] = c->img.h_cd[(size_t)(in.nblocks - 1) * in.nch + i].prn > 0 ? cc.exact_end[i] : 0.0;
     }
     h->last_chain_dev = 1;
     uint32_t st = 0;
@@ -4175,176 +4278,22 @@ extern "C" int gpsbb_chain_carrier(gpsbb_t *h, const gpsbb_chan_t *ch, int nbloc
 {
     if (!h || !ch || nblocks < 1 || nch < 1 || nch > GPSBB_MAX_CHAN || nsamp < 1 || !(delt > 0.0) || !std::isfinite(delt))
         return GPSBB_E_BADARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!h->chain_only) {
-        h->chain_only = new (std::nothrow) ChainOnly;
-        if (!h->chain_only)
-            return GPSBB_E_NOMEM;
-    }
+    if (!h->chain_only && !(h->chain_only = new (std::nothrow) ChainOnly))
+        return GPSBB_E_NOMEM;
     ChainOnly *c = h->chain_only;
-    if (!c->d_carry)
-        HIPCHK(h, hipMalloc((void **)&c->d_carry, sizeof(ChainCarryDev)));
-    if (!c->d_status)
-        HIPCHK(h, hipMalloc((void **)&c->d_status, 4));
-    HIPCHK(h, hipMemsetAsync(c->d_carry, 0, sizeof(ChainCarryDev), h->s_seed));
-    HIPCHK(h, hipMemsetAsync(c->d_status, 0, 4, h->s_seed));
-    /* what the chain reads of a descriptor, and the rough start phases (plain double arithmetic; pass A takes it from
-     * there): one host thread per channel, the blocks in order */
-    const size_t nbc_all = (size_t)nblocks * nch;
-    c->h_cd.resize(nbc_all);
-    c->h_start0.resize(nbc_all);
-    std::vector<char> bad(nch, 0);
-    auto work = [&](int i0, int i1) {
-        for (int i = i0; i < i1; i++) {
-            double x = 0.0;
-            int prev_prn = 0;
-            for (int blk = 0; blk < nblocks; blk++) {
-                const size_t k = (size_t)blk * nch + i;
-                const gpsbb_chan_t &d = ch[k];
-                ChainDesc &cd = c->h_cd[k];
-                cd.f_carr = d.f_carr;
-                cd.carr_phase = d.carr_phase;
-                cd.prn = d.prn;
-                cd.start = 0;
-                double start0 = 0.0;
-                if (d.prn != 0) {
-                    /* the part of the descriptor contract the carrier chain depends on */
-                    if (d.prn < 0 || d.prn > 32 || !std::isfinite(d.f_carr) || !std::isfinite(d.carr_phase) ||
-                        std::signbit(d.carr_phase) || d.carr_phase > 1.0 || !(std::fabs(d.f_carr * delt) <= 0.125)) {
-                        bad[i] = 1;
-                        cd.prn = 0;
-                    } else {
-                        if (d.prn != prev_prn)
-                            x = d.carr_phase;
-                        start0 = x;
-                        const volatile double sk = d.f_carr * delt;
-                        x = x + (double)nsamp * sk;
-                        x -= std::floor(x);
-                    }
-                }
-                c->h_start0[k] = start0;
-                prev_prn = cd.prn > 0 ? cd.prn : 0;
-            }
-        }
-    };
-    {
-        std::vector<std::thread> th;
-        for (int i = 0; i < nch; i++) {
-            try {
-                th.emplace_back(work, i, i + 1);
-            } catch (...) {
-                work(i, i + 1);
-            }
-        }
-        for (auto &t : th)
-            t.join();
-    }
-    for (int i = 0; i < nch; i++)
-        if (bad[i])
-            return GPSBB_E_BADCHAN;
-
-    hipStream_t ss = h->s_seed;
-    /* Lap-parallel (gpsbb_laps.hip.h: plan, reference walks, scan, true walks with nothing to emit but the phase after every
-     * block, repair) wherever no carrier step is below 2^-50: a fraction of a millisecond per sub-batch whatever its blocks are —
-     * the row walks below take as long as their longest chain, twice (a feeder that chains every few slots of a stream, the
-     * node driver's incremental run, could not live with 8 ms per call). */
-    bool use_laps = h->opt_seed_where != 1 && !GPSBB_KNOB_SET("GPSBB_NO_LAPS");
-    for (size_t k = 0; k < nbc_all && use_laps; k++)
-        if (c->h_cd[k].prn > 0) {
-            const volatile double sk = c->h_cd[k].f_carr * delt;
-            use_laps = std::fabs(sk) >= 0x1p-50 || sk == 0.0;
-        }
-    if (use_laps) {
-        if (!c->d_hz_scratch)
-            HIPCHK(h, hipMalloc((void **)&c->d_hz_scratch, 64));
-        HIPCHK(h, hipMemsetAsync(c->d_hz_scratch, 0, 64, ss));
-        if (carr_phase_seed)
-            c->h_lap_end.resize(nbc_all);
-        int b0 = 0;
-        while (b0 < nblocks) {
-            /* as many blocks as fit the scratch: by the laps they hold */
-            double laps = 0.0;
-            int nb = 0;
-            while (b0 + nb < nblocks && nb < CHAIN_ONLY_BLOCKS) {
-                double l = 0.0;
-                /* lanes by the laps per lane a sub-batch of nb + 1 blocks would get (lap_unit grows with the batch: a block counted
-                 * with the smaller unit of a smaller batch is over-counted, never under: the scratch stays within CHAIN_ONLY_LAPS) */
-                const double unit = (double)lap_unit(NCO_CARR, (size_t)(nb + 1) * nch);
-                for (int i = 0; i < nch; i++) {
-                    const ChainDesc &d = c->h_cd[(size_t)(b0 + nb) * nch + i];
-                    if (d.prn > 0)
-                        l += std::floor((std::floor((double)nsamp * std::fabs(d.f_carr * delt)) + 1.0) / unit) + 3.0;
-                }
-                if (nb > 0 && laps + l > CHAIN_ONLY_LAPS)
-                    break;
-                laps += l;
-                nb++;
-            }
-            const size_t nbc = (size_t)nb * nch, k0 = (size_t)b0 * nch;
-            uint32_t chunk0[2][GPSBB_MAX_CHAN + 1];
-            lap_bound(ch + k0, nb, nch, delt, nsamp, false, chunk0, true);
-            HIPCHK(h, (hipError_t)c->d_cd.reserve(nbc));
-            HIPCHK(h, (hipError_t)c->d_lap_end.reserve(nbc));
-            HIPCHK(h, (hipError_t)c->lap.reserve(nbc, (size_t)nch, (size_t)nb, chunk0[1][nch], false));
-            HIPCHK(h, hipMemcpyAsync(c->d_cd.p, c->h_cd.data() + k0, nbc * sizeof(ChainDesc), hipMemcpyHostToDevice, ss));
-            LapDev L;
-            c->lap.dev(L);
-            lap_dev_plan(L, chunk0, true, nbc);
-            BatchDev p = chain_only_dev(c, b0, nb, nch, delt, nsamp, c->d_hz_scratch);
-            p.lap_end = c->d_lap_end.p;
-            lap_chain_launch(ss, p, L, nch, NCO_CARR, lap_pass2_kernel(NCO_CARR, false, 0));
-            HIPCHK(h, hipGetLastError());
-            if (carr_phase_seed)
-                HIPCHK(h, hipMemcpyAsync(c->h_lap_end.data() + k0, c->d_lap_end.p, nbc * sizeof(double), hipMemcpyDeviceToHost, ss));
-            HIPCHK(h, hipStreamSynchronize(ss));
-            b0 += nb;
-        }
-        if (carr_phase_seed)
-            /* a block starts where the one before ended, or — a channel that was idle or had another prn there — from its own phase */
-            for (int i = 0; i < nch; i++)
-                for (int blk = 0; blk < nblocks; blk++) {
-                    const size_t k = (size_t)blk * nch + i;
-                    const ChainDesc &d = c->h_cd[k];
-                    double v = 0.0;
-                    if (d.prn > 0)
-                        v = (blk > 0 && c->h_cd[k - nch].prn == d.prn) ? c->h_lap_end[k - nch] : d.carr_phase;
-                    carr_phase_seed[k] = v;
-                }
-        return chain_only_finish(h, c, nbc_all, nch, carr_phase_end);
-    }
-    for (int b0 = 0; b0 < nblocks; b0 += CHAIN_ONLY_BLOCKS) {
-        const int nb = nblocks - b0 < CHAIN_ONLY_BLOCKS ? nblocks - b0 : CHAIN_ONLY_BLOCKS;
-        const size_t nbc = (size_t)nb * nch, k0 = (size_t)b0 * nch;
-        HIPCHK(h, (hipError_t)c->d_cd.reserve(nbc));
-        HIPCHK(h, (hipError_t)c->d_start0.reserve(nbc));
-        HIPCHK(h, (hipError_t)c->d_aux.reserve(nbc));
-        HIPCHK(h, c->fix.reserve((size_t)GPSBB_MAX_CHAN * ((CHAIN_ONLY_BLOCKS + FIXP_WG_ALONE - 1) / FIXP_WG_ALONE), ss));
-        HIPCHK(h, hipMemcpyAsync(c->d_cd.p, c->h_cd.data() + k0, nbc * sizeof(ChainDesc), hipMemcpyHostToDevice, ss));
-        HIPCHK(h, hipMemcpyAsync(c->d_start0.p, c->h_start0.data() + k0, nbc * sizeof(double), hipMemcpyHostToDevice, ss));
-        BatchDev p = chain_only_dev(c, b0, nb, nch, delt, nsamp, h->d_hz);
-        p.chain_starts = 1;
-        p.model_start = 0; /* over tens of thousands of blocks a prediction drifts too far: pass A and the prefix stay */
-        p.seg_tiles = p.ntiles;
-        p.aux = c->d_aux.p;
-        p.start0 = c->d_start0.p;
-        p.fix_end = c->fix.end.p;
-        p.fix_flag = c->fix.flag.p;
-        p.fix_epoch = ++c->fix.epoch;
-        p.fix_chunks = (nb + FIXP_WG_ALONE - 1) / FIXP_WG_ALONE;
-        p.seed_order = nullptr; /* channel by channel, blocks in order (k_walk) */
-        p.seed_lanes = nch * ((nb + 63) & ~63);
-        HIPCHK(h, walk_chain_launch(ss, p, p.seed_lanes, true, 3, FIXP_WG_ALONE, CarryEvents()));
-        HIPCHK(h, hipGetLastError());
-        if (carr_phase_seed) {
-            /* the exact start phase of every block, as k_chain_fix_par left it in the chain descriptors */
-            HIPCHK(h, hipMemcpyAsync(c->h_cd.data() + k0, c->d_cd.p, nbc * sizeof(ChainDesc), hipMemcpyDeviceToHost, ss));
-        }
-        HIPCHK(h, hipStreamSynchronize(ss)); /* the host image of the next sub-batch's uploads is re-used scratch */
-    }
-    if (carr_phase_seed)
-        for (size_t k = 0; k < nbc_all; k++)
-            carr_phase_seed[k] = c->h_cd[k].prn > 0 ? c->h_cd[k].carr_phase : 0.0;
-    return chain_only_finish(h, c, nbc_all, nch, carr_phase_end);
+    const PlanIn in{ch, nblocks, nch, delt, nsamp, GPSBB_CHAIN_CARRIER};
+    int rc = plan_chain_only(c->plan, c->img, in, plan_opts(h, NSETS)); /* every error of the arguments, before any HIP call */
+    if (rc != GPSBB_OK)
+        return rc;
+    const bool want_seeds = carr_phase_seed != nullptr;
+    rc = chain_only_scratch(h, c, c->plan.laps && want_seeds ? (size_t)nblocks * nch : 0);
+    for (size_t k = 0; k < c->plan.pieces.size() && rc == GPSBB_OK; k++)
+        rc = (c->plan.laps ? chain_only_lap_piece : chain_only_walk_piece)(h, c, c->plan.pieces[k], in, want_seeds);
+    if (rc != GPSBB_OK)
+        return rc;
+    if (want_seeds)
+        (c->plan.laps ? chain_only_lap_seeds : chain_only_walk_seeds)(c, in, carr_phase_seed);
+    return chain_only_finish(h, c, in, carr_phase_end);
 }
 
 #ifdef GPSBB_EXPERIMENTS
@@ -4556,6 +4505,31 @@ extern "C" int gpsbb_test_push_side(const gpsbb_chan_t *ch, int nblocks, int nch
     out[0] = (int)side.chain;
     out[1] = side.begun;
     return rc;
+}
+
+/* plan_chain_only on its own: which pre-pass, the pieces (the first GPSBB_TEST_CHAIN_PLAN_PIECES of them), the images' hashes */
+extern "C" int gpsbb_test_chain_plan(const gpsbb_chan_t *ch, int nblocks, int nch, double delt, int nsamp, int seed_where,
+                                     unsigned long long out[GPSBB_TEST_CHAIN_PLAN_NQ])
+{
+    if (!out)
+        return GPSBB_E_BADARG;
+    ChainOnlyPlan cp;
+    PlanImages img;
+    const int rc = plan_chain_only(cp, img, PlanIn{ch, nblocks, nch, delt, nsamp, GPSBB_CHAIN_CARRIER}, plan_opts(seed_where, 0, false, 0, NSETS));
+    if (rc != GPSBB_OK)
+        return rc;
+    memset(out, 0, GPSBB_TEST_CHAIN_PLAN_NQ * sizeof out[0]);
+    out[0] = cp.laps;
+    out[1] = cp.pieces.size();
+    out[2] = fnv1a(img.h_cd);
+    out[3] = fnv1a(img.h_start0);
+    for (size_t k = 0; k < cp.pieces.size() && k < GPSBB_TEST_CHAIN_PLAN_PIECES; k++) {
+        const ChainOnlyPiece &pc = cp.pieces[k];
+        const unsigned long long v[4] = {(unsigned long long)pc.b0, (unsigned long long)pc.nb, pc.cont0_mask,
+                                         cp.laps ? fnv1a(pc.chunk0, sizeof pc.chunk0) : 0ull};
+        memcpy(out + 4 + 4 * k, v, sizeof v);
+    }
+    return GPSBB_OK;
 }
 
 extern "C" int gpsbb_test_table_digest(gpsbb_batch_t *b, unsigned long long out[3])

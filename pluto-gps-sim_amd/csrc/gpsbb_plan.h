@@ -1,10 +1,11 @@
 /*
  * gpsbb_plan.h — how a batch is planned: everything batch set-up decides from the descriptors, the handle's options and a stream's
- * carry, as one pure host function (plan_batch) and the plain structs it fills; and, ahead of it for a ring's push, on which side
- * the push chains its carrier (plan_push_side).  No HIP call, neither the handle nor the batch: gpsbb.hip stages what the plan says
- * (batch_setup) and launches from it; gpsbb_test_plan and gpsbb_test_push_side run them without a GPU.
- * Included by gpsbb.hip behind the descriptor checks and kernel plans it calls (chan_ok, ev_plan, lap_eligible, lap_bound, row_bound,
- * CarrDrift) and the constants it reads (NSETS, CHAIN_*); not a translation unit of its own.
+ * carry, as one pure host function (plan_batch) and the plain structs it fills; ahead of it for a ring's push, on which side
+ * the push chains its carrier (plan_push_side); and what gpsbb_chain_carrier decides, the chain alone (plan_chain_only).  No HIP call,
+ * neither the handle nor the batch: gpsbb.hip stages what the plan says (batch_setup) and launches from it; gpsbb_test_plan,
+ * gpsbb_test_push_side and gpsbb_test_chain_plan run them without a GPU.
+ * Included by gpsbb.hip behind the descriptor checks and kernel plans it calls (chan_ok, ev_plan, lap_eligible, lap_bound, lap_unit,
+ * row_bound, CarrDrift, channel_threads) and the constants it reads (NSETS, CHAIN_*); not a translation unit of its own.
  */
 #ifndef GPSBB_PLAN_H
 #define GPSBB_PLAN_H
@@ -68,6 +69,9 @@ struct StreamLink {
 /* ---- plan_batch and its steps ------------------------------------------------------------------------ */
 
 constexpr size_t HOST_SEED_MAX_CHANNELS = 64; /* blocks x channels up to which the host seeds */
+/* gpsbb_chain_carrier cuts its blocks into sub-batches that fit its scratch */
+constexpr int CHAIN_ONLY_BLOCKS = 16384;  /* blocks per sub-batch: 168 MB of ChainAux at 16 channels */
+constexpr double CHAIN_ONLY_LAPS = 6.0e6; /* laps per sub-batch of the lap-parallel chain (40 bytes of scratch each) */
 
 struct PlanIn {
     const gpsbb_chan_t *ch;
@@ -86,6 +90,8 @@ struct PlanOpts {
     size_t host_seed_max = HOST_SEED_MAX_CHANNELS;
     long state_log2 = 0, indep_min_tiles = 0, seg_rows = 0, walk_lanes = 0;
     long nsets[2] = {3, 4}; /* table sets without / with the device-side chain */
+    int chain_only_blocks = CHAIN_ONLY_BLOCKS; /* plan_chain_only's limits: a knob only makes sub-batches smaller (the scratch is */
+    double chain_only_laps = CHAIN_ONLY_LAPS;  /* sized by the constants) */
 };
 
 static PlanOpts plan_opts(int seed_where, int synth_kernel, bool skip_seed, int chain_where, int max_sets)
@@ -107,6 +113,8 @@ static PlanOpts plan_opts(int seed_where, int synth_kernel, bool skip_seed, int 
      * (M1 geometry, per-sample kernel: two sets 6.6e10, three 7.7e10 samples/s), the chained ones longer still */
     o.nsets[0] = GPSBB_KNOB_LONG("GPSBB_NSETS", 3);
     o.nsets[1] = GPSBB_KNOB_LONG("GPSBB_NSETS", 4);
+    o.chain_only_blocks = (int)std::min(std::max(GPSBB_KNOB_LONG("GPSBB_CHAIN_ONLY_BLOCKS", CHAIN_ONLY_BLOCKS), 1L), (long)CHAIN_ONLY_BLOCKS);
+    o.chain_only_laps = (double)std::min(std::max(GPSBB_KNOB_LONG("GPSBB_CHAIN_ONLY_LAPS", CHAIN_ONLY_LAPS), 1L), (long)CHAIN_ONLY_LAPS);
     return o;
 }
 
@@ -406,41 +414,52 @@ static void plan_fixed_point(PlanImages &img, const PlanIn &in, const StreamLink
     }
 }
 
+/* The part of the descriptor contract the carrier chain depends on.  Not chan_ok: the node driver chains descriptors whose code
+ * fields it has not filled. */
+static bool chain_only_chan_ok(const gpsbb_chan_t &d, double delt)
+{
+    return d.prn == 0 || (d.prn > 0 && d.prn <= 32 && std::isfinite(d.f_carr) && std::isfinite(d.carr_phase) &&
+                          !std::signbit(d.carr_phase) && d.carr_phase <= 1.0 && std::fabs(d.f_carr * delt) <= 0.125);
+}
+
 /* The carrier chain is resolved exactly on the device, in parallel over the blocks (k_walk pass A,
  * k_chain_prefix, k_walk pass B, k_chain_fix).  All the host contributes is a rough start phase per block:
  * the descriptor's phase carried forward by nsamp*step in plain double arithmetic (good to ~1e-7 cycles
- * after a few hundred blocks; pass A takes it from there). */
-static void plan_chain_desc(BatchPlan &pl, PlanImages &img, const PlanIn &in, const StreamLink &lk)
+ * after a few hundred blocks; pass A takes it from there).
+ * The channels [i0, i1) of images the caller has sized; cont0: their bits of the plan's cont0_mask.
+ * ALONE: plan_chain_only's instance (a thread per channel over tens of thousands of blocks: nothing of the general case may cost
+ * it anything) — whole blocks, no model, nothing carried in, and the descriptors checked on the way (a batch's are checked by
+ * plan_begin): false at the first one chain_only_chan_ok refuses. */
+template <bool ALONE>
+static bool plan_chain_desc(const BatchPlan &pl, PlanImages &img, const PlanIn &in, const StreamLink &lk, int i0, int i1, uint32_t &cont0)
 {
-    const int nblocks = in.nblocks, nch = in.nch, nsamp = in.nsamp;
-    const size_t nvbc = (size_t)nblocks * nch * (size_t)pl.nseg;
-    img.h_cd.resize(nvbc);
-    img.h_start0.resize(nvbc);
-    for (int i = 0; i < nch; i++) {
-        double x = lk.d_carry && lk.carry_phase ? lk.carry_phase[i] : 0.0;
-        int prev_prn = lk.d_carry && lk.carry_prn ? lk.carry_prn[i] : 0;
+    const int nblocks = in.nblocks, nch = in.nch, nsamp = in.nsamp, nseg = ALONE ? 1 : pl.nseg, full = pl.seg_tiles * TILE;
+    const bool model = !ALONE && pl.chain_model, indep = !ALONE && pl.chain_indep, carry = !ALONE && lk.d_carry;
+    const double delt = in.delt;
+    ChainDesc *const h_cd = img.h_cd.data(); /* (locals: the stores below may alias anything read through a reference) */
+    double *const h_start0 = img.h_start0.data();
+    for (int i = i0; i < i1; i++) {
+        double x = carry && lk.carry_phase ? lk.carry_phase[i] : 0.0;
+        int prev_prn = carry && lk.carry_prn ? lk.carry_prn[i] : 0;
         for (int blk = 0; blk < nblocks; blk++) {
             const gpsbb_chan_t &c = in.ch[(size_t)blk * nch + i];
-            const volatile double sk = c.f_carr * in.delt;
-            const CarrDrift drift(pl.chain_model && c.prn > 0 ? (double)sk : 0.0);
+            if (ALONE && !chain_only_chan_ok(c, delt))
+                return false;
+            const volatile double sk = c.f_carr * delt;
+            const CarrDrift drift(model && c.prn > 0 ? (double)sk : 0.0);
             if (c.prn > 0) {
-                if (c.prn != prev_prn || pl.chain_indep)
+                if (c.prn != prev_prn || indep)
                     x = c.carr_phase;
                 else if (blk == 0)
-                    pl.cont0_mask |= 1u << i;
+                    cont0 |= 1u << i;
             }
-            for (int sgi = 0; sgi < pl.nseg; sgi++) {
-                const size_t kv = ((size_t)blk * pl.nseg + sgi) * nch + i;
-                ChainDesc &cd = img.h_cd[kv];
-                cd.f_carr = c.f_carr;
-                cd.carr_phase = c.carr_phase; /* read for a block's first segment only (one that starts a chain) */
-                cd.prn = c.prn;
-                cd.start = (pl.chain_indep && sgi == 0) ? 1 : 0;
-                img.h_start0[kv] = c.prn > 0 ? x : 0.0;
+            for (int sgi = 0; sgi < nseg; sgi++) {
+                const size_t kv = ((size_t)blk * nseg + sgi) * nch + i;
+                h_cd[kv] = ChainDesc{c.f_carr, c.carr_phase /* read for a segment that starts a chain only */, c.prn, indep && sgi == 0 ? 1 : 0};
+                h_start0[kv] = c.prn > 0 ? x : 0.0;
                 if (c.prn > 0) {
-                    const int left = nsamp - sgi * pl.seg_tiles * TILE, full = pl.seg_tiles * TILE;
-                    const int ns = pl.nseg == 1 ? nsamp : (left < full ? left : full);
-                    if (pl.chain_model && x < 1.0) {
+                    const int left = nsamp - sgi * full, ns = nseg == 1 ? nsamp : (left < full ? left : full);
+                    if (model && x < 1.0) {
                         x = drift.advance(x, ns, sk);
                     } else {
                         x = x + (double)ns * sk;
@@ -450,9 +469,10 @@ static void plan_chain_desc(BatchPlan &pl, PlanImages &img, const PlanIn &in, co
             }
             prev_prn = c.prn > 0 ? c.prn : 0;
         }
-        if (lk.d_carry && lk.carry_phase)
+        if (carry && lk.carry_phase)
             lk.carry_phase[i] = x;
     }
+    return true;
 }
 
 /* The descriptors as the device gets them, and what the carrier of the batch's first block continues: the lap-parallel pre-pass's
@@ -474,8 +494,11 @@ static void plan_chain(BatchPlan &pl, PlanImages &img, const PlanIn &in, const S
                 if (ch[i].prn > 0 && ch[i].prn == lk.carry_prn[i])
                     pl.cont0_mask |= 1u << i;
     }
-    if (pl.chain_dev && !pl.laps)
-        plan_chain_desc(pl, img, in, lk);
+    if (pl.chain_dev && !pl.laps) {
+        img.h_cd.resize(nbc * (size_t)pl.nseg);
+        img.h_start0.resize(nbc * (size_t)pl.nseg);
+        plan_chain_desc<false>(pl, img, in, lk, 0, in.nch, pl.cont0_mask);
+    }
     if ((in.flags & GPSBB_CHAIN_CARRIER) && !fixed && in.nblocks > 1 && !pl.chain_dev) {
         /* blocks consecutive in time: resolve the carrier phase at the start of every block here, exactly
          * (same jump-ahead as the device, one host thread per channel), so that the device's chains are all
@@ -604,6 +627,86 @@ static int plan_batch(BatchPlan &pl, PlanImages &img, const PlanIn &in, const Pl
     if (rc == GPSBB_OK)
         plan_finish(pl, img, in, o, lk);
     return rc;
+}
+
+/* ---- plan_chain_only: the carrier chain alone (gpsbb_chain_carrier) ------------------------------------ */
+
+/* One sub-batch of the call: nb blocks from block b0 on. */
+struct ChainOnlyPiece {
+    int b0 = 0, nb = 0;
+    uint32_t cont0_mask = 0; /* which channels of its first block go on from the block before it */
+    uint32_t chunk0[2][GPSBB_MAX_CHAN + 1] = {}; /* the lap-parallel pre-pass: room for its laps (lap_bound, carriers only) */
+};
+
+struct ChainOnlyPlan {
+    bool laps = false; /* every piece by the lap-parallel pre-pass; else by the row walks */
+    std::vector<ChainOnlyPiece> pieces;
+};
+
+/* How many of the blocks from b0 on make the next lap-parallel piece: as many as fit the scratch, by the laps they hold (at least
+ * one).  Lanes by the laps per lane a piece of nb + 1 blocks would get: lap_unit grows with the batch, so a block counted with the
+ * smaller unit of a smaller batch is over-counted, never under, and the scratch stays within max_laps. */
+static int chain_only_lap_blocks(const ChainDesc *cd, int b0, const PlanIn &in, const PlanOpts &o)
+{
+    double laps = 0.0;
+    int nb = 0;
+    while (b0 + nb < in.nblocks && nb < o.chain_only_blocks) {
+        double l = 0.0;
+        const double unit = (double)lap_unit(NCO_CARR, (size_t)(nb + 1) * in.nch);
+        for (int i = 0; i < in.nch; i++) {
+            const ChainDesc &d = cd[(size_t)(b0 + nb) * in.nch + i];
+            if (d.prn > 0)
+                l += std::floor((std::floor((double)in.nsamp * std::fabs(d.f_carr * in.delt)) + 1.0) / unit) + 3.0;
+        }
+        if (nb > 0 && laps + l > o.chain_only_laps)
+            break;
+        laps += l;
+        nb++;
+    }
+    return nb;
+}
+
+/* What gpsbb_chain_carrier decides before its first HIP call: the chain descriptors and rough start phases of all its blocks (img.h_cd,
+ * h_start0: nseg = 1, no model, nothing carried in; a thread per channel, the blocks in order), which pre-pass walks them, and the
+ * sub-batches that fit the scratch.  Lap-parallel wherever no carrier step is below 2^-50: a fraction of a millisecond per
+ * sub-batch whatever its blocks are — the row walks take as long as their longest chain, twice (a feeder that chains every few
+ * slots of a stream, the node driver's incremental run, could not live with 8 ms per call).
+ * GPSBB_E_BADARG before anything is written; GPSBB_E_BADCHAN leaves cp alone (the images are the threads' scratch by then: the
+ * descriptors are checked where they are read, once). */
+static int plan_chain_only(ChainOnlyPlan &cp, PlanImages &img, const PlanIn &in, const PlanOpts &o)
+{
+    if (!in.ch || in.nblocks < 1 || in.nch < 1 || in.nch > GPSBB_MAX_CHAN || in.nsamp < 1 || !(in.delt > 0.0) || !std::isfinite(in.delt))
+        return GPSBB_E_BADARG;
+    const int nblocks = in.nblocks, nch = in.nch;
+    const size_t nbc = (size_t)nblocks * nch;
+    img.h_cd.resize(nbc);
+    img.h_start0.resize(nbc);
+    std::atomic<bool> bad(false);
+    channel_threads(nch, nch, [&](int i0, int i1) {
+        uint32_t cont0 = 0; /* (nothing is carried in: no channel of block 0 continues) */
+        if (!plan_chain_desc<true>(BatchPlan(), img, in, StreamLink(), i0, i1, cont0))
+            bad = true;
+    });
+    if (bad)
+        return GPSBB_E_BADCHAN;
+    cp.laps = o.seed_where != 1 && !o.no_laps;
+    for (size_t k = 0; k < nbc && cp.laps; k++)
+        cp.laps = img.h_cd[k].prn <= 0 || lap_carr_step_ok(img.h_cd[k].f_carr, in.delt);
+    cp.pieces.clear();
+    for (int b0 = 0; b0 < nblocks; b0 += cp.pieces.back().nb) {
+        ChainOnlyPiece pc;
+        pc.b0 = b0;
+        pc.nb = cp.laps ? chain_only_lap_blocks(img.h_cd.data(), b0, in, o) : std::min(nblocks - b0, o.chain_only_blocks);
+        for (int i = 0; i < nch && b0 > 0; i++) {
+            const int prn = img.h_cd[(size_t)b0 * nch + i].prn;
+            if (prn > 0 && prn == img.h_cd[(size_t)(b0 - 1) * nch + i].prn)
+                pc.cont0_mask |= 1u << i;
+        }
+        if (cp.laps)
+            lap_bound(in.ch + (size_t)b0 * nch, pc.nb, nch, in.delt, in.nsamp, false, pc.chunk0, true);
+        cp.pieces.push_back(pc);
+    }
+    return GPSBB_OK;
 }
 
 #endif

@@ -52,6 +52,14 @@ int gpsbb_test_plan(const struct gpsbb_chan *ch, int nblocks, int nch, double de
  * Returns GPSBB_OK or the error the push would return from there. */
 int gpsbb_test_push_side(const struct gpsbb_chan *ch, int nblocks, int nch, double delt, int nsamp, unsigned flags, const int opt[5],
                          int out[2]);
+/* plan_chain_only (gpsbb_plan.h) on the arguments of a gpsbb_chain_carrier call and a handle's GPSBB_OPT_SEED_WHERE: what the call
+ * would decide before its first HIP call.  out: laps (1 the lap-parallel pre-pass, 0 the row walks), the number of sub-batches,
+ * the 64-bit FNV-1a of h_cd and of h_start0, then for each of the first GPSBB_TEST_CHAIN_PLAN_PIECES sub-batches (the count is the
+ * true one) b0, nb, cont0_mask and the FNV-1a of its chunk0 (0: the row walks).  Returns GPSBB_OK or the error the call would. */
+#define GPSBB_TEST_CHAIN_PLAN_PIECES 64
+#define GPSBB_TEST_CHAIN_PLAN_NQ (4 + 4 * GPSBB_TEST_CHAIN_PLAN_PIECES)
+int gpsbb_test_chain_plan(const struct gpsbb_chan *ch, int nblocks, int nch, double delt, int nsamp, int seed_where,
+                          unsigned long long out[GPSBB_TEST_CHAIN_PLAN_NQ]);
 
 /* The error budgets of the model kernels, measured (gpsbb_modelerr.hip.h): the realised |model - truth| of everything
  * k_synth_ev / k_synth_pd test, over every tile of the batch's last run, per channel index.  Needs a GPU. */

@@ -1,6 +1,9 @@
 // plan_batch (csrc/gpsbb_plan.h) under the host sanitizers, on a machine without a GPU: the matrix of tests/test_batch_plan.py, as
 // `python tests/batch_plan_cases.py FILE` writes it, through gpsbb_test_plan; prints what the test compares, one line per set-up —
-// and, for every set-up with GPSBB_CHAIN_CARRIER and the IEEE carrier, what plan_push_side makes of it (gpsbb_test_push_side).
+// and, for every set-up with GPSBB_CHAIN_CARRIER and the IEEE carrier, what plan_push_side makes of it (gpsbb_test_push_side) and, on
+// a line of its own ("chain ..."), what plan_chain_only makes of gpsbb_chain_carrier over the same blocks (gpsbb_test_chain_plan);
+// `python tests/chain_plan_cases.py FILE [lowered]` writes that plan's own matrix, many-block records among them, in the same
+// format (lowered: the cases to run with GPSBB_CHAIN_ONLY_BLOCKS=16 GPSBB_CHAIN_ONLY_LAPS=2000 in the environment).
 //   hipcc --offload-arch=gfx950 -std=c++17 -ffp-contract=off -DGPSBB_EXPERIMENTS -Xarch_host -fsanitize=address,undefined \
 //         -Ipluto-gps-sim_amd/csrc -Iinclude tools/plan_asan.cpp pluto-gps-sim_amd/csrc/gpsbb_node.cpp -o plan_asan
 //   ./plan_asan FILE
@@ -39,6 +42,14 @@ int main(int argc, char **argv)
             printf(" side %d %d %d", rs, side[0], side[1]);
         }
         printf("\n");
+        if ((r.flags & GPSBB_CHAIN_CARRIER) && !(r.flags & GPSBB_FIXED_CARRIER)) { // gpsbb_chain_carrier on the same blocks: its plan, a line of its own
+            unsigned long long co[GPSBB_TEST_CHAIN_PLAN_NQ];
+            const int rc = gpsbb_test_chain_plan(r.nch > 0 ? ch.data() : nullptr, r.nblocks, r.nch, r.delt, r.nsamp, r.opt[0], co);
+            printf("chain %d", rc);
+            for (unsigned long long i = 0; rc == GPSBB_OK && i < 4 + 4 * std::min<unsigned long long>(co[1], GPSBB_TEST_CHAIN_PLAN_PIECES); i++)
+                printf(" %llx", co[i]);
+            printf("\n");
+        }
         n++;
     }
     fclose(f);

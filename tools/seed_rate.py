@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What the seed of a time shard costs: gpsbb_chain_carrier (device) over the first B blocks of bench.py's stream, next to
 gpsbb_chain_carrier_host (16 host threads) over the same blocks; both give the exact carr_phase at block B.
-   python tools/seed_rate.py [--blocks 56000] [--host]"""
+   python tools/seed_rate.py [--blocks 56000] [--host] [--small CALLS]"""
 import argparse
 import os
 import sys
@@ -15,6 +15,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--blocks", type=int, default=56000)
     ap.add_argument("--host", action="store_true", help="also time the host chain (seconds at this size)")
+    ap.add_argument("--small", type=int, default=0, metavar="CALLS", help="also time that many calls on 8 blocks x 16 channels")
     a = ap.parse_args()
     import torch  # noqa: F401
     from __graft_entry__ import load_package
@@ -39,6 +40,15 @@ def main():
                 want = pkg.chain_carrier_host(ch[:b0 + 1], delt, nsamp)[b0]
                 line += "   host chain %.3f s   equal %s" % (time.perf_counter() - t0, want.tobytes() == seed.tobytes())
             print(line, flush=True)
+        if a.small:
+            # the node driver's incremental feed: the same call on 8 blocks x 16 channels, where the host part is what it costs
+            dts = []
+            for _ in range(a.small):
+                t0 = time.perf_counter()
+                s.chain_carrier(ch[:8], delt, nsamp)
+                dts.append(time.perf_counter() - t0)
+            dts.sort()
+            print("blocks      8  device chain, %d calls: median %.1f us  min %.1f us" % (a.small, 1e6 * dts[len(dts) // 2], 1e6 * dts[0]), flush=True)
         print("chain fallbacks", s.info(pkg.INFO_CHAIN_FALLBACKS))
 
 
