@@ -2945,128 +2945,131 @@ extern "C" long gpsbb_despread_segments(long nsamp, int seg_tiles)
     return (nsamp + len - 1) / len;
 }
 
+/* the kernel of a despreading call: K<view, noise, g, interf> for every view, with and without noise, for every state granule
+ * (BatchDev::st_log2), without and with the set's J in the view (gpsbb_batch_despread_impaired) */
+#define GPSBB_DS_G(K, V, N, J) {K<V, N, 0, J>, K<V, N, 1, J>, K<V, N, 2, J>}
+#define GPSBB_DS_V(K, V, J) {GPSBB_DS_G(K, V, false, J), GPSBB_DS_G(K, V, true, J)}
+#define GPSBB_DS_KERNEL(FN, NAME, K)                                                                                                    \
+    static FN NAME(int view, bool noise, int g, bool interf)                                                                            \
+    {                                                                                                                                   \
+        static const FN k[2][3][2][EV_STATE_LOG2_MAX + 1] = {{GPSBB_DS_V(K, DS_SC16, false), GPSBB_DS_V(K, PACK_SC8, false), GPSBB_DS_V(K, PACK_SC1, false)}, \
+                                                             {GPSBB_DS_V(K, DS_SC16, true), GPSBB_DS_V(K, PACK_SC8, true), GPSBB_DS_V(K, PACK_SC1, true)}};    \
+        return k[interf ? 1 : 0][view][noise ? 1 : 0][g];                                                                               \
+    }
 typedef void (*DsKernelFn)(BatchDev, DsArgs);
-static DsKernelFn ds_kernel(int view, bool noise, int g)
-{
-#define GPSBB_DS_ROW(V, N) {k_despread<V, N, 0>, k_despread<V, N, 1>, k_despread<V, N, 2>}
-    static const DsKernelFn k[3][2][EV_STATE_LOG2_MAX + 1] = {{GPSBB_DS_ROW(DS_SC16, false), GPSBB_DS_ROW(DS_SC16, true)},
-                                                               {GPSBB_DS_ROW(PACK_SC8, false), GPSBB_DS_ROW(PACK_SC8, true)},
-                                                               {GPSBB_DS_ROW(PACK_SC1, false), GPSBB_DS_ROW(PACK_SC1, true)}};
-#undef GPSBB_DS_ROW
-    return k[view][noise ? 1 : 0][g];
-}
-/* ... with the set's J in the view (gpsbb_batch_despread_impaired) */
-static DsKernelFn ds_kernel_interf(int view, bool noise, int g)
-{
-#define GPSBB_DS_ROW(V, N) {k_despread<V, N, 0, true>, k_despread<V, N, 1, true>, k_despread<V, N, 2, true>}
-    static const DsKernelFn k[3][2][EV_STATE_LOG2_MAX + 1] = {{GPSBB_DS_ROW(DS_SC16, false), GPSBB_DS_ROW(DS_SC16, true)},
-                                                               {GPSBB_DS_ROW(PACK_SC8, false), GPSBB_DS_ROW(PACK_SC8, true)},
-                                                               {GPSBB_DS_ROW(PACK_SC1, false), GPSBB_DS_ROW(PACK_SC1, true)}};
-#undef GPSBB_DS_ROW
-    return k[view][noise ? 1 : 0][g];
-}
-
-/* ... at lags (gpsbb_batch_despread_lags) */
 typedef void (*DslKernelFn)(BatchDev, DslArgs);
-static DslKernelFn dsl_kernel(int view, bool noise, int g, bool interf)
+GPSBB_DS_KERNEL(DsKernelFn, ds_kernel, k_despread)
+GPSBB_DS_KERNEL(DslKernelFn, dsl_kernel, k_despread_lags) /* ... at lags (gpsbb_batch_despread_lags) */
+#undef GPSBB_DS_KERNEL
+#undef GPSBB_DS_V
+#undef GPSBB_DS_G
+
+/* what a view's impairments need of a call (gpsbb_batch_despread*, gpsbb_device_acquire), after noise_ready, which makes the table */
+static void ds_fill_impair(DsArgs &d, const gpsbb *h, const ImpairCall &ic)
 {
-#define GPSBB_DSL_ROW(V, N, J) {k_despread_lags<V, N, 0, J>, k_despread_lags<V, N, 1, J>, k_despread_lags<V, N, 2, J>}
-#define GPSBB_DSL_SET(J)                                                                                               \
-    {{GPSBB_DSL_ROW(DS_SC16, false, J), GPSBB_DSL_ROW(DS_SC16, true, J)},                                               \
-     {GPSBB_DSL_ROW(PACK_SC8, false, J), GPSBB_DSL_ROW(PACK_SC8, true, J)},                                             \
-     {GPSBB_DSL_ROW(PACK_SC1, false, J), GPSBB_DSL_ROW(PACK_SC1, true, J)}}
-    static const DslKernelFn k[2][3][2][EV_STATE_LOG2_MAX + 1] = {GPSBB_DSL_SET(false), GPSBB_DSL_SET(true)};
-#undef GPSBB_DSL_SET
-#undef GPSBB_DSL_ROW
-    return k[interf ? 1 : 0][view][noise ? 1 : 0][g];
+    d.nz = ic.a.nz;
+    d.ntab = h->d_noise_tab;
+    d.it = ic.a.it;
 }
 
-/* the checks, scratch, chunking, launch and copy-back of every despreading call.  lags == nullptr: the prompt sums by k_despread,
- * out [nblocks][nch][nseg]; otherwise k_despread_lags at lags[0 .. nlags), out [nblocks][nch][nseg][nlags] */
-static int batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, const gpsbb_noise_t *nz, const gpsbb_interf_set_t *set,
-                          int seg_tiles, const int *lags, int nlags, gpsbb_corr_t *out)
+/* the argument checks of every despreading call, in the order the tests pin, and what they settle of its arguments: the lags, the
+ * source, the segments, the view's shift.  *fmt: the view's kernel number; *ic: the impairments, for ds_fill_impair */
+static int ds_make_args(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, const gpsbb_noise_t *nz, const gpsbb_interf_set_t *set,
+                        int seg_tiles, const int *lags, int nlags, const gpsbb_corr_t *out, DslArgs *al, int *fmt, ImpairCall *ic)
 {
     if (!b)
         return GPSBB_E_BADARG;
-    gpsbb *h = b->h;
     const BatchPlan &pl = b->plan;
-    int shift8 = 0;
-    ImpairCall ic;
-    if (!impair_make(nz, set, (uint64_t)pl.nblocks * (uint64_t)pl.nsamp, &ic))
+    memset(al, 0, sizeof *al);
+    if (!impair_make(nz, set, (uint64_t)pl.nblocks * (uint64_t)pl.nsamp, ic))
         return GPSBB_E_BADARG;
     /* (nothing is packed here, so SC1 takes any nsamp: the format is looked up for a length it accepts) */
-    const int fmt = (view & ~(GPSBB_OUT_FORMAT_MASK | GPSBB_OUT_SHIFT_MASK)) ? -1 : out_format(view, 4, &shift8);
-    if (!out || seg_tiles < 1 || fmt < 0 || ((uintptr_t)d_iq & 3))
+    *fmt = (view & ~(GPSBB_OUT_FORMAT_MASK | GPSBB_OUT_SHIFT_MASK)) ? -1 : out_format(view, 4, &al->d.shift8);
+    if (!out || seg_tiles < 1 || *fmt < 0 || ((uintptr_t)d_iq & 3))
         return GPSBB_E_BADARG;
-    DslArgs al;
-    memset(&al, 0, sizeof al);
     for (int l = 0; lags && l < nlags; l++) {
-        al.lags[l] = lags[l];
-        al.halo_lo |= lags[l] < 0;
-        al.halo_hi |= lags[l] > 0;
+        al->lags[l] = lags[l];
+        al->halo_lo |= lags[l] < 0;
+        al->halo_hi |= lags[l] > 0;
     }
-    al.nlags = nlags;
+    al->nlags = nlags;
     if (!b->ran)
         return GPSBB_E_STATE;
     /* the two limits of this call: the accumulator's batches, and runs of the per-sample kernel, which leave rows and no
      * tile states */
     if ((pl.flags & GPSBB_FIXED_CARRIER) || !pl.ev)
         return GPSBB_E_BADARG;
-    const int16_t *src = d_iq ? d_iq : b->last_iq;
-    if (!src)
+    DsArgs &a = al->d;
+    a.iq = reinterpret_cast<const uint32_t *>(d_iq ? d_iq : b->last_iq);
+    if (!a.iq)
         return GPSBB_E_STATE; /* the last run rendered into the caller's buffer: it has to be named */
+    a.seg_tiles = seg_tiles;
+    a.nseg = (int)gpsbb_despread_segments(pl.nsamp, seg_tiles);
+    a.danger = (uint32_t)GPSBB_KNOB_LONG("GPSBB_DS_DANGER", 2u * PD_BAND); /* (larger: more samples take the exact path; a test aid) */
+    return GPSBB_OK;
+}
+
+/* pure: the tiles a wavefront takes at a time and the workgroups of a block, for a device of cus compute units.  A chunk never
+ * spans more segments than it must, and small batches hand their tiles out one at a time */
+static void ds_geometry(int nblocks, int ntiles, int seg_tiles, long cus, int &chunk, int &wgs_per_block)
+{
+    chunk = seg_tiles < DS_CHUNK ? seg_tiles : DS_CHUNK;
+    while (chunk > 1 && (long)nblocks * (((long)ntiles + chunk - 1) / chunk) < cus * 8 * DS_WAVES)
+        chunk--;
+    const long chunks = ((long)ntiles + chunk - 1) / chunk, max_useful = (chunks + DS_WAVES - 1) / DS_WAVES;
+    const long want = (cus * 16 + nblocks - 1) / nblocks;
+    wgs_per_block = (int)(want < 1 ? 1 : (want > max_useful ? max_useful : want));
+}
+
+/* every despreading call: the checks, then scratch, geometry, launch and copy-back.  lags == nullptr: the prompt sums by k_despread,
+ * out [nblocks][nch][nseg]; otherwise k_despread_lags at lags[0 .. nlags), out [nblocks][nch][nseg][nlags] */
+static int batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, const gpsbb_noise_t *nz, const gpsbb_interf_set_t *set,
+                          int seg_tiles, const int *lags, int nlags, gpsbb_corr_t *out)
+{
+    DslArgs al;
+    ImpairCall ic;
+    int fmt = -1, rc = ds_make_args(b, d_iq, view, nz, set, seg_tiles, lags, nlags, out, &al, &fmt, &ic);
+    if (rc != GPSBB_OK)
+        return rc;
+    gpsbb *h = b->h;
+    const BatchPlan &pl = b->plan;
+    DsArgs &a = al.d;
     HIPCHK(h, hipSetDevice(h->device));
-    const int rc = gpsbb_sync(h);
+    rc = gpsbb_sync(h);
     if (rc != GPSBB_OK)
         return rc;
     if (nz)
         HIPCHK(h, noise_ready(h));
-    const long nseg = gpsbb_despread_segments(pl.nsamp, seg_tiles);
-    const size_t nsum = (size_t)pl.nblocks * pl.nch * (size_t)nseg * (size_t)(lags ? nlags : 1) * 2;
+    ds_fill_impair(a, h, ic);
+    /* ---- scratch, zeroed: the sums, behind them the count of exact-path samples; the blocks' tile counters ---- */
+    const size_t nsum = (size_t)pl.nblocks * pl.nch * (size_t)a.nseg * (size_t)(lags ? nlags : 1) * 2;
     HIPCHK(h, (hipError_t)b->d_ds.reserve(nsum + 1));
     HIPCHK(h, (hipError_t)b->d_ds_ctr.reserve((size_t)pl.nblocks));
     hipStream_t cs = h->s_compute;
     HIPCHK(h, hipMemsetAsync(b->d_ds.p, 0, (nsum + 1) * sizeof(unsigned long long), cs));
     HIPCHK(h, hipMemsetAsync(b->d_ds_ctr.p, 0, (size_t)pl.nblocks * sizeof(int32_t), cs));
-    const BatchDev p = batch_dev(b, b->sets[b->last_set]);
-    DsArgs &a = al.d;
-    a.iq = reinterpret_cast<const uint32_t *>(src);
     a.out = b->d_ds.p;
     a.n_exact = b->d_ds.p + nsum;
     a.ctr = b->d_ds_ctr.p;
-    a.seg_tiles = seg_tiles;
-    a.nseg = (int)nseg;
-    /* a chunk never spans more segments than it must, and small batches hand their tiles out one at a time */
-    const long cus = h->sm_count > 0 ? h->sm_count : 256;
-    int chunk = seg_tiles < DS_CHUNK ? seg_tiles : DS_CHUNK;
-    while (chunk > 1 && (long)pl.nblocks * (((long)pl.ntiles + chunk - 1) / chunk) < cus * 8 * DS_WAVES)
-        chunk--;
-    a.chunk = chunk;
-    const long chunks = ((long)pl.ntiles + chunk - 1) / chunk;
-    const long max_useful = (chunks + DS_WAVES - 1) / DS_WAVES;
-    long want = (cus * 16 + pl.nblocks - 1) / pl.nblocks;
-    want = want < 1 ? 1 : (want > max_useful ? max_useful : want);
-    a.wgs_per_block = (int)want;
-    a.shift8 = shift8;
-    a.danger = (uint32_t)GPSBB_KNOB_LONG("GPSBB_DS_DANGER", 2u * PD_BAND); /* (larger: more samples take the exact path; a test aid) */
-    a.nz = ic.a.nz;
-    a.ntab = h->d_noise_tab;
-    a.it = ic.a.it;
+    /* ---- launch ---- */
+    ds_geometry(pl.nblocks, pl.ntiles, seg_tiles, h->sm_count > 0 ? h->sm_count : 256, a.chunk, a.wgs_per_block);
+    const BatchDev p = batch_dev(b, b->sets[b->last_set]);
 #ifdef GPSBB_EXPERIMENTS
     for (auto &e : b->ds_ev)
         if (!e)
             HIPCHK(h, hipEventCreate(&e));
     HIPCHK(h, hipEventRecord(b->ds_ev[0], cs));
 #endif
-    const dim3 grid((unsigned)(want * pl.nblocks));
+    const dim3 grid((unsigned)((long)a.wgs_per_block * pl.nblocks));
     if (lags)
         hipLaunchKernelGGL(dsl_kernel(fmt, nz != nullptr, p.st_log2, set != nullptr), grid, dim3(DS_WG), 0, cs, p, al);
     else
-        hipLaunchKernelGGL(set ? ds_kernel_interf(fmt, nz != nullptr, p.st_log2) : ds_kernel(fmt, nz != nullptr, p.st_log2), grid, dim3(DS_WG), 0, cs, p, a);
+        hipLaunchKernelGGL(ds_kernel(fmt, nz != nullptr, p.st_log2, set != nullptr), grid, dim3(DS_WG), 0, cs, p, a);
     HIPCHK(h, hipGetLastError());
 #ifdef GPSBB_EXPERIMENTS
     HIPCHK(h, hipEventRecord(b->ds_ev[1], cs));
 #endif
+    /* ---- copy back ---- */
     HIPCHK(h, hipMemcpyAsync(out, b->d_ds.p, nsum * sizeof(unsigned long long), hipMemcpyDeviceToHost, cs));
     HIPCHK(h, hipMemcpyAsync(&b->ds_last_exact, b->d_ds.p + nsum, sizeof(unsigned long long), hipMemcpyDeviceToHost, cs));
     HIPCHK(h, hipStreamSynchronize(cs));
@@ -3166,9 +3169,7 @@ extern "C" int gpsbb_device_acquire(gpsbb_t *h, const int16_t *d_iq, long nsamp,
         HIPCHK(h, hipMemsetAsync(h->d_acq_grid.p, 0, grid_words * 8, cs));
     a.d.iq = reinterpret_cast<const uint32_t *>(d_iq);
     a.d.shift8 = shift8;
-    a.d.nz = ic.a.nz;
-    a.d.ntab = h->d_noise_tab;
-    a.d.it = ic.a.it;
+    ds_fill_impair(a.d, h, ic);
     a.tabs = h->d_tabs;
     a.chips = reinterpret_cast<const int8_t *>(h->d_acq_chips.p);
     a.grid = grid ? h->d_acq_grid.p : nullptr;
@@ -4543,16 +4544,15 @@ extern "C" int gpsbb_test_table_digest(gpsbb_batch_t *b, unsigned long long out[
         return rc;
     const BatchDev p = batch_dev(b, b->sets[b->last_set]);
     auto mix = [](unsigned long long z) { z ^= z >> 31; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 29; return z; };
-    const size_t nst = (size_t)pl.nstates;
-    const size_t nx = (size_t)pl.nblocks * 2 * pl.nch * nst, nn = (size_t)pl.nblocks * pl.nch * nst, ne = (size_t)pl.nblocks * pl.nch;
+    const int nst = pl.nstates;
+    const size_t nx = (size_t)pl.nblocks * 2 * pl.nch * (size_t)nst, nn = (size_t)pl.nblocks * pl.nch * (size_t)nst, ne = (size_t)pl.nblocks * pl.nch;
     /* The states keyed by the tile t they start: every tile's, but for a batch that k_synth_ev renders — whose tables hold one state
      * per granule behind the lap-parallel pre-pass (BatchDev::st_log2) and one per tile behind the row walks — those of the tiles that
      * start a granule of the size the lap-parallel pre-pass would use: the two pre-passes' tables digest alike where they agree, and
      * every other batch's are compared tile by tile.  The granule is per kind: a carrier row's is ev_carr_log2 of the code's, in the
      * tables and in the key alike */
     const int dg = pl.ev_dense || (pl.flags & GPSBB_FIXED_CARRIER) ? 0 : (int)GPSBB_KNOB_LONG("GPSBB_EV_STATE_LOG2", GPSBB_EV_STATE_LOG2);
-    const int tstep = 1 << (dg > pl.st_log2 ? dg : pl.st_log2);
-    const int gc = ev_carr_log2(pl.st_log2), tstep_carr = 1 << ev_carr_log2(dg > pl.st_log2 ? dg : pl.st_log2);
+    const int kg = dg > pl.st_log2 ? dg : pl.st_log2; /* the key's granule (the code's) */
     std::vector<unsigned long long> hx(nx);
     std::vector<uint32_t> hn(nn);
     std::vector<gpsbb_chan_state_t> he(ne);
@@ -4568,14 +4568,15 @@ extern "C" int gpsbb_test_table_digest(gpsbb_batch_t *b, unsigned long long out[
             continue;
         const size_t blk = k / (size_t)pl.nch, i = k % (size_t)pl.nch;
         for (int kind = 0; kind < 2; kind++)
-            for (int t = 0; t < pl.ntiles; t += kind == NCO_CARR ? tstep_carr : tstep) {
-                const size_t at = (blk * 2 * pl.nch + 2 * i + kind) * (size_t)pl.ntiles + t;
-                out[0] += mix(hx[(blk * 2 * pl.nch + 2 * i + kind) * nst + (t >> (kind == NCO_CARR ? gc : pl.st_log2))] +
+            for (int t = 0; t < pl.ntiles; t += 1 << ev_kind_log2(kg, kind)) {
+                const size_t at = ev_tile_x_row(blk, pl.nch, (int)i, kind, pl.ntiles) + t;
+                out[0] += mix(hx[ev_tile_x_row(blk, pl.nch, (int)i, kind, nst) + ev_state_at(pl.st_log2, kind, t).entry] +
                               0x9E3779B97F4A7C15ull * (at + 1));
             }
-        for (int t = 0; t < pl.ntiles; t += tstep) {
-            const size_t at = k * (size_t)pl.ntiles + t;
-            out[1] += mix((unsigned long long)(hn[k * nst + (t >> pl.st_log2)] & 3u) + 0x9E3779B97F4A7C15ull * (at + 1));
+        for (int t = 0; t < pl.ntiles; t += 1 << kg) {
+            const size_t at = ev_tile_nav_row(blk, pl.nch, (int)i, pl.ntiles) + t;
+            out[1] += mix((unsigned long long)(hn[ev_tile_nav_row(blk, pl.nch, (int)i, nst) + ev_state_at(pl.st_log2, NCO_CODE, t).entry] & 3u) +
+                          0x9E3779B97F4A7C15ull * (at + 1));
         }
         unsigned long long w[5];
         memcpy(w, &he[k], sizeof w);

@@ -155,19 +155,12 @@ __device__ __forceinline__ uint32_t ds_view(uint32_t v, unsigned long long pos, 
     return ds_pair(vi, vq);
 }
 
-/* SG: the batch's state granule (BatchDev::st_log2) */
-template <int VIEW, bool NOISE, int SG, bool INTERF = false>
-__global__ __launch_bounds__(DS_WG) void k_despread(BatchDev p, DsArgs a)
+/* ---- what k_despread (below) and k_despread_lags (gpsbb_despread_lags.hip.h) do alike around their own sums.  Which state serves
+ * a tile, and where its row lies, is ev_state_at's and ev_tile_x_row's to say (gpsbb_events.hip.h). ---- */
+/* stage, by the whole workgroup of the block with descriptors cb: the carrier table as replica pairs, the block's chips, the noise's knots */
+template <bool NOISE>
+__device__ __forceinline__ void ds_stage(const BatchDev &p, const DsArgs &a, const gpsbb_chan_t *__restrict__ cb, int tid, DsLds &L, int2 *ntab)
 {
-    __shared__ DsLds L;
-    __shared__ int2 ntab[NOISE ? NOISE_KNOTS - 1 : 1];
-    const int tid = (int)threadIdx.x;
-    const int b = (int)(blockIdx.x / (unsigned)a.wgs_per_block);
-    if (b >= p.nblocks)
-        return;
-    const gpsbb_chan_t *__restrict__ cb = p.ch + (size_t)b * p.nch;
-    const EvConst *__restrict__ kb = p.evc + (size_t)b * p.nch;
-    /* ---- stage: the carrier table as replica pairs, the block's chips, the noise's knots ---- */
     for (int k = tid; k < 512; k += DS_WG) {
         const int c = p.tabs[k], s = p.tabs[512 + k];
         L.rep[0][k] = make_uint2(ds_pair(c, s), ds_pair(-s, c));
@@ -180,19 +173,57 @@ __global__ __launch_bounds__(DS_WG) void k_despread(BatchDev p, DsArgs a)
     if (NOISE)
         for (int k = tid; k < NOISE_KNOTS - 1; k += DS_WG)
             ntab[k] = a.ntab[k];
+}
+/* bit i: channel i of the block has a PRN */
+__device__ __forceinline__ uint32_t ds_active(const gpsbb_chan_t *__restrict__ cb, int nch, int lane)
+{
+    return (uint32_t)__ballot(lane < nch && cb[lane < nch ? lane : 0].prn > 0);
+}
+/* the wavefront's next chunk of tiles from block b's counter */
+__device__ __forceinline__ int ds_claim(const DsArgs &a, int b, int lane)
+{
+    int base = 0;
+    if (lane == 0)
+        base = atomicAdd(&a.ctr[b], a.chunk);
+    return __builtin_amdgcn_readfirstlane(base);
+}
+/* the exact replica (out of line) of the sample n after the code's state and ny after the carrier's: one granule for both, or two */
+template <int SG>
+__device__ __forceinline__ uint32_t ds_exact(double xt, double yt, double S, double sc, uint32_t down, uint32_t nav, int n, int ny, const uint32_t *chips)
+{
+    return ev_kind_log2(SG, NCO_CARR) == SG ? ds_exact_sample(xt, yt, S, sc, down, nav, n, chips) : ds_exact_sample_2g(xt, yt, S, sc, down, nav, n, ny, chips);
+}
+/* the samples this wavefront sent down the exact path, added to the call's count (the tests' view of the fallback) */
+__device__ __forceinline__ void ds_count_exact(const DsArgs &a, int lane, unsigned long long n_exact)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        n_exact += (unsigned long long)__shfl_xor((long long)n_exact, off);
+    if (lane == 0 && n_exact)
+        atomicAdd(a.n_exact, n_exact);
+}
+
+/* SG: the batch's state granule (BatchDev::st_log2) */
+template <int VIEW, bool NOISE, int SG, bool INTERF = false>
+__global__ __launch_bounds__(DS_WG) void k_despread(BatchDev p, DsArgs a)
+{
+    __shared__ DsLds L;
+    __shared__ int2 ntab[NOISE ? NOISE_KNOTS - 1 : 1];
+    const int tid = (int)threadIdx.x;
+    const int b = (int)(blockIdx.x / (unsigned)a.wgs_per_block);
+    if (b >= p.nblocks)
+        return;
+    const gpsbb_chan_t *__restrict__ cb = p.ch + (size_t)b * p.nch;
+    const EvConst *__restrict__ kb = p.evc + (size_t)b * p.nch;
+    ds_stage<NOISE>(p, a, cb, tid, L, ntab);
     __syncthreads();
 
     /* ---- from here on every wavefront works alone ---- */
     const int lane = tid & 63;
-    uint32_t act_mask;
-    {
-        const bool act = lane < p.nch && cb[lane < p.nch ? lane : 0].prn > 0;
-        act_mask = (uint32_t)__ballot(act);
-    }
-    const int ntw = p.ntiles;
-    const int nst = SG ? p.nstates : ntw;
-    const double *__restrict__ txb = p.tile_x + (size_t)b * nst * 2 * p.nch;
-    const uint32_t *__restrict__ tnb = p.tile_nav + (size_t)b * p.nch * nst;
+    const uint32_t act_mask = ds_active(cb, p.nch, lane);
+    const int ntw = p.ntiles, nst = SG ? p.nstates : ntw;
+    const double *__restrict__ txb = p.tile_x + ev_tile_x_row((size_t)b, p.nch, 0, NCO_CODE, nst);
+    const uint32_t *__restrict__ tnb = p.tile_nav + ev_tile_nav_row((size_t)b, p.nch, 0, nst);
     const uint32_t *__restrict__ iqb = a.iq + (size_t)b * p.nsamp;
     const double guard = 0x1p+20 + (double)PD_BAND * 0x1p-32;
     long long run_i = 0, run_q = 0; /* lane i: channel i's sums over the tiles of segment run_seg this wavefront has taken */
@@ -209,10 +240,7 @@ __global__ __launch_bounds__(DS_WG) void k_despread(BatchDev p, DsArgs a)
         run_i = run_q = 0;
     };
     for (;;) {
-        int base = 0;
-        if (lane == 0)
-            base = atomicAdd(&a.ctr[b], a.chunk);
-        base = __builtin_amdgcn_readfirstlane(base);
+        const int base = ds_claim(a, b, lane);
         if (base >= ntw)
             break;
         const int stop = base + a.chunk < ntw ? base + a.chunk : ntw;
@@ -233,16 +261,15 @@ __global__ __launch_bounds__(DS_WG) void k_despread(BatchDev p, DsArgs a)
                 u[j] = j * 64 < left ? ds_view<VIEW, NOISE, INTERF>(u[j], (unsigned long long)b * (unsigned long long)p.nsamp +
                                                                               (unsigned long long)(wt * TILE + j * 64 + lane), a, ntab, L.rep[0])
                                      : 0u; /* a sample that does not exist adds nothing */
-            constexpr int GC = ev_carr_log2(SG); /* the carrier's granule; SG is the code's */
-            const int g = wt >> SG, gy = wt >> GC;
-            const int ns = (wt & ((1 << SG) - 1)) * TILE + lane, nsy = GC == SG ? ns : (wt & ((1 << GC) - 1)) * TILE + lane;
+            const EvStateAt cx = ev_state_at(SG, NCO_CODE, wt), cy = ev_state_at(SG, NCO_CARR, wt); /* SG is the code's granule */
+            const int g = cx.entry, gy = cy.entry, ns = cx.since * TILE + lane, nsy = cy.since * TILE + lane;
             const double n0 = (double)ns, n0y = (double)nsy; /* samples since the state's */
             for (uint32_t mk = act_mask; mk; mk &= mk - 1) {
                 const int i = __builtin_ctz(mk);
                 const double S = scalar_load(&kb[i].S), sc = scalar_load(&kb[i].sc);
                 const uint32_t down = scalar_load(&kb[i].down) != 0 ? 1u : 0u;
-                const double xt = txb[(size_t)(2 * i) * nst + g], yt = txb[(size_t)(2 * i + 1) * nst + gy];
-                const uint32_t nav = tnb[(size_t)i * nst + g];
+                const double xt = txb[ev_tile_x_row(0, p.nch, i, NCO_CODE, nst) + g], yt = txb[ev_tile_x_row(0, p.nch, i, NCO_CARR, nst) + gy];
+                const uint32_t nav = tnb[ev_tile_nav_row(0, p.nch, i, nst) + g];
                 const double yg = (down ? 512.0 - yt : yt) + guard, xg = xt + guard;
                 const uint32_t flip = down ? 511u : 0u;
                 const uint32_t *chips = L.chips[i];
@@ -269,8 +296,7 @@ __global__ __launch_bounds__(DS_WG) void k_despread(BatchDev p, DsArgs a)
                             uw = q == j ? u[q] : uw;
                         bool bj;
                         const uint32_t rm = ds_model_sample(n0 + (double)(j * 64), n0y + (double)(j * 64), S, sc, yg, xg, flip, nav, chips, a.danger, bj);
-                        const uint32_t re = GC == SG ? ds_exact_sample(xt, yt, S, sc, down, nav, ns + j * 64, chips)
-                                                     : ds_exact_sample_2g(xt, yt, S, sc, down, nav, ns + j * 64, nsy + j * 64, chips);
+                        const uint32_t re = ds_exact<SG>(xt, yt, S, sc, down, nav, ns + j * 64, nsy + j * 64, chips);
                         const uint2 tm = (&L.rep[0][0])[rm], te = (&L.rep[0][0])[re];
                         const ds_s16x2 uj = __builtin_bit_cast(ds_s16x2, uw);
                         pi += __builtin_amdgcn_sdot2(uj, __builtin_bit_cast(ds_s16x2, te.x), 0, false) -
@@ -295,11 +321,7 @@ __global__ __launch_bounds__(DS_WG) void k_despread(BatchDev p, DsArgs a)
         }
     }
     flush();
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        n_exact += (unsigned long long)__shfl_xor((long long)n_exact, off);
-    if (lane == 0 && n_exact)
-        atomicAdd(a.n_exact, n_exact);
+    ds_count_exact(a, lane, n_exact);
 }
 
 } /* namespace gpsbb_impl */

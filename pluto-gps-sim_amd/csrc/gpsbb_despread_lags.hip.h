@@ -65,18 +65,7 @@ __global__ __launch_bounds__(DS_WG) void k_despread_lags(BatchDev p, DslArgs al)
     const gpsbb_chan_t *__restrict__ cb = p.ch + (size_t)b * p.nch;
     const EvConst *__restrict__ kb = p.evc + (size_t)b * p.nch;
     /* ---- stage: k_despread's image, and the lags ---- */
-    for (int k = tid; k < 512; k += DS_WG) {
-        const int c = p.tabs[k], s = p.tabs[512 + k];
-        L.rep[0][k] = make_uint2(ds_pair(c, s), ds_pair(-s, c));
-        L.rep[1][k] = make_uint2(ds_pair(-c, -s), ds_pair(s, -c));
-    }
-    for (int k = tid; k < p.nch * 32; k += DS_WG) {
-        const int prn = cb[k >> 5].prn;
-        L.chips[k >> 5][k & 31] = p.ca_bits[(prn > 0 ? prn : 0) * 32 + (k & 31)];
-    }
-    if (NOISE)
-        for (int k = tid; k < NOISE_KNOTS - 1; k += DS_WG)
-            ntab[k] = a.ntab[k];
+    ds_stage<NOISE>(p, a, cb, tid, L, ntab);
     if (tid < DSL_MAX_LAGS)
         lagv[tid] = tid < al.nlags ? al.lags[tid] : 0;
     __syncthreads();
@@ -86,16 +75,11 @@ __global__ __launch_bounds__(DS_WG) void k_despread_lags(BatchDev p, DslArgs al)
     uint32_t *__restrict__ vw = strip[tid >> 6];
     int(*__restrict__ rd)[DSL_RED_ROW] = red[tid >> 6];
     const int rv = lane & 15, rq = lane >> 4; /* the value and the quarter of its row this lane sums; the channels it keeps */
-    uint32_t act_mask;
-    {
-        const bool act = lane < p.nch && cb[lane < p.nch ? lane : 0].prn > 0;
-        act_mask = (uint32_t)__ballot(act);
-    }
+    const uint32_t act_mask = ds_active(cb, p.nch, lane);
     const int nlags = al.nlags;
-    const int ntw = p.ntiles;
-    const int nst = SG ? p.nstates : ntw;
-    const double *__restrict__ txb = p.tile_x + (size_t)b * nst * 2 * p.nch;
-    const uint32_t *__restrict__ tnb = p.tile_nav + (size_t)b * p.nch * nst;
+    const int ntw = p.ntiles, nst = SG ? p.nstates : ntw;
+    const double *__restrict__ txb = p.tile_x + ev_tile_x_row((size_t)b, p.nch, 0, NCO_CODE, nst);
+    const uint32_t *__restrict__ tnb = p.tile_nav + ev_tile_nav_row((size_t)b, p.nch, 0, nst);
     const uint32_t *__restrict__ iqb = a.iq + (size_t)b * p.nsamp;
     const double guard = 0x1p+20 + (double)PD_BAND * 0x1p-32;
     /* lane (v, q), set r: value v (lag v >> 1, component v & 1) of channel 4 r + q over the tiles of segment run_seg this
@@ -114,10 +98,7 @@ __global__ __launch_bounds__(DS_WG) void k_despread_lags(BatchDev p, DslArgs al)
         }
     };
     for (;;) {
-        int base = 0;
-        if (lane == 0)
-            base = atomicAdd(&a.ctr[b], a.chunk);
-        base = __builtin_amdgcn_readfirstlane(base);
+        const int base = ds_claim(a, b, lane);
         if (base >= ntw)
             break;
         const int stop = base + a.chunk < ntw ? base + a.chunk : ntw;
@@ -144,16 +125,15 @@ __global__ __launch_bounds__(DS_WG) void k_despread_lags(BatchDev p, DslArgs al)
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); /* the strip is written before any lane reads it */
             __builtin_amdgcn_wave_barrier();
             const int left = p.nsamp - wt * TILE - lane; /* samples j*64 < left exist */
-            constexpr int GC = ev_carr_log2(SG); /* the carrier's granule; SG is the code's */
-            const int g = wt >> SG, gy = wt >> GC;
-            const int ns = (wt & ((1 << SG) - 1)) * TILE + lane, nsy = GC == SG ? ns : (wt & ((1 << GC) - 1)) * TILE + lane;
+            const EvStateAt cx = ev_state_at(SG, NCO_CODE, wt), cy = ev_state_at(SG, NCO_CARR, wt); /* SG is the code's granule */
+            const int g = cx.entry, gy = cy.entry, ns = cx.since * TILE + lane, nsy = cy.since * TILE + lane;
             const double n0 = (double)ns, n0y = (double)nsy; /* samples since the state's */
             for (uint32_t mk = act_mask; mk; mk &= mk - 1) {
                 const int i = __builtin_ctz(mk);
                 const double S = scalar_load(&kb[i].S), sc = scalar_load(&kb[i].sc);
                 const uint32_t down = scalar_load(&kb[i].down) != 0 ? 1u : 0u;
-                const double xt = txb[(size_t)(2 * i) * nst + g], yt = txb[(size_t)(2 * i + 1) * nst + gy];
-                const uint32_t nav = tnb[(size_t)i * nst + g];
+                const double xt = txb[ev_tile_x_row(0, p.nch, i, NCO_CODE, nst) + g], yt = txb[ev_tile_x_row(0, p.nch, i, NCO_CARR, nst) + gy];
+                const uint32_t nav = tnb[ev_tile_nav_row(0, p.nch, i, nst) + g];
                 const double yg = (down ? 512.0 - yt : yt) + guard, xg = xt + guard;
                 const uint32_t flip = down ? 511u : 0u;
                 const uint32_t *chips = L.chips[i];
@@ -175,8 +155,7 @@ __global__ __launch_bounds__(DS_WG) void k_despread_lags(BatchDev p, DslArgs al)
                     for (int j = 0; j < SPT; j++) { /* (one call site, the entry put back by selects: t[] stays in registers) */
                         if (!((bad >> j) & 1u))
                             continue;
-                        const uint32_t re = GC == SG ? ds_exact_sample(xt, yt, S, sc, down, nav, ns + j * 64, chips)
-                                                     : ds_exact_sample_2g(xt, yt, S, sc, down, nav, ns + j * 64, nsy + j * 64, chips);
+                        const uint32_t re = ds_exact<SG>(xt, yt, S, sc, down, nav, ns + j * 64, nsy + j * 64, chips);
                         const uint2 te = (&L.rep[0][0])[re];
 #pragma unroll
                         for (int q = 0; q < SPT; q++)
@@ -227,11 +206,7 @@ __global__ __launch_bounds__(DS_WG) void k_despread_lags(BatchDev p, DslArgs al)
         }
     }
     flush();
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        n_exact += (unsigned long long)__shfl_xor((long long)n_exact, off);
-    if (lane == 0 && n_exact)
-        atomicAdd(a.n_exact, n_exact);
+    ds_count_exact(a, lane, n_exact);
 }
 
 } /* namespace gpsbb_impl */

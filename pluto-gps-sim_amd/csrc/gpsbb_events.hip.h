@@ -128,6 +128,27 @@ constexpr int ev_carr_log2(int g)
         gc--;
     return gc;
 }
+/* THE RULE for "the state of kind K that serves tile t", for every reader and writer of tile_x / tile_nav, on host and device: with
+ * the code's granule g (BatchDev::st_log2), the kind's own granule log2, the entry of the kind's row that holds the state, the
+ * tiles since that entry's first (the state lies since * TILE samples before the tile's first), and the entries a row of the kind
+ * uses.  tile_nav goes by the code's.  With a constant g everything here folds to constants and one shift or mask. */
+constexpr int ev_kind_log2(int g, int kind) { return kind == NCO_CARR ? ev_carr_log2(g) : g; }
+struct EvStateAt {
+    int log2, entry, since;
+};
+constexpr EvStateAt ev_state_at(int g, int kind, int t)
+{
+    const int gk = ev_kind_log2(g, kind);
+    return EvStateAt{gk, t >> gk, t & ((1 << gk) - 1)};
+}
+constexpr int ev_states_used(int g, int kind, int ntiles)
+{
+    const int gk = ev_kind_log2(g, kind);
+    return (ntiles + (1 << gk) - 1) >> gk;
+}
+/* ... and where the rows start: nst is the rows' stride, BatchDev::nstates (ntiles where g == 0: one state per tile) */
+constexpr size_t ev_tile_x_row(size_t b, int nch, int i, int kind, int nst) { return (b * 2 * (size_t)nch + (size_t)(2 * i + kind)) * (size_t)nst; }
+constexpr size_t ev_tile_nav_row(size_t b, int nch, int i, int nst) { return (b * (size_t)nch + (size_t)i) * (size_t)nst; }
 #ifdef GPSBB_EV_MODEL_ERR_OWN
 static_assert(ev_carr_granule_fits(EV_STATE_LOG2_MAX), "the carrier model of the largest state granule must stay inside the error budget");
 static_assert(EV_STATE_LOG2_MAX == 2, "ev_second names the one granule whose carrier's differs (ev_exact_run_2g<1>)");
@@ -321,7 +342,8 @@ __device__ __noinline__ uint32_t ev_exact_run(LDS &L, int wave, int lane, int i,
 }
 /* ... behind a carrier granule that is not the code's (ev_carr_log2(SG) != SG): each NCO from the state of its kind's granule of
  * tile wt.  tile_x: the block's first state (chain c's row at [c * nst]); wt_nb: wt << 2 | nb; off: the run's first sample in the
- * tile.  Where the two states lie is worked out here, behind the call: its caller has no registers for it. */
+ * tile.  Where the two states lie is worked out here, behind the call: its caller has no registers for it.  (ev_state_at's rule,
+ * written out: this function and synth_ev_body carry the headline and keep the code they were measured with.) */
 template <int SG, class LDS>
 __device__ __noinline__ uint32_t ev_exact_run_2g(LDS &L, int wave, int lane, int i, const EvConst *kbi, const double *tile_x, int nst,
                                                  uint32_t wt_nb, int off)
@@ -491,7 +513,7 @@ __device__ __forceinline__ EvExactAt ev_exact_at(const EvTile &T, int i)
     return a;
 }
 /* (where the carrier's granule is not the code's — T.sg is a constant of the kernel — ev_exact_run_2g finds both states itself) */
-__device__ __forceinline__ bool ev_exact_2g(const EvTile &T) { return ev_carr_log2(T.sg) != T.sg; }
+__device__ __forceinline__ bool ev_exact_2g(const EvTile &T) { return ev_carr_log2(T.sg) != T.sg; } /* (k_synth_ev's: left as it was measured) */
 
 /*
  * Second half: signs, the contribution at sample 0 (into acc0) and its changes (into D).  db / db_next: the
@@ -840,6 +862,8 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
     const bool chain_lane = lane < nch2;
     const bool mirror = chain_lane && (lane & 1) && kb[lane >> 1].down != 0;
     /* this lane's chain (state-contiguous) in the state arrays: one exact state per GRANULE of 2^sg tiles (BatchDev::st_log2) */
+    /* (ev_state_at's rule is written out by hand in this body — t >> sg, t & ((1 << sg) - 1), and gc for the odd lanes: the kernel is
+     * short of registers and keeps the code it was measured with) */
     constexpr int sg = SG; /* == p.st_log2 (the host launches the instance of its batch's granule): the code's */
     constexpr int gc = ev_carr_log2(SG); /* the carrier's (odd chain lanes) */
     const int nst = SG ? p.nstates : ntw;

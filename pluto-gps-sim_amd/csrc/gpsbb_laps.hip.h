@@ -459,12 +459,12 @@ __device__ __forceinline__ void lap_enter_block(const BatchDev &p, const LapDev 
 /* SG (here and in lap_emit_row, lap_run, lap_walk): the batch's state granule BatchDev::st_log2 as a constant (pass 2: what
  * costs registers as a variable shift), or -1: read it from p (the repair).  It is the CODE's granule; a carrier chain leaves a
  * state per 2^ev_carr_log2(SG) tiles (gpsbb_events.hip.h), into the same row with the same stride p.nstates: lap_tsl is the log2 of
- * the samples per state of a kind, lap_nstates the states a row of the kind holds. */
+ * the samples per state of a kind (ev_kind_log2), lap_nstates the states a row of the kind holds: ev_states_used
+ * (gpsbb_events.hip.h: the rule every reader goes by) written out, because through it k_lap_repair's device code comes out different. */
 template <int KIND, int SG>
 __device__ __forceinline__ uint32_t lap_tsl(const BatchDev &p)
 {
-    const int g = SG >= 0 ? SG : p.st_log2;
-    return (uint32_t)__builtin_ctz(TILE) + (uint32_t)(KIND == NCO_CARR ? ev_carr_log2(g) : g);
+    return (uint32_t)__builtin_ctz(TILE) + (uint32_t)ev_kind_log2(SG >= 0 ? SG : p.st_log2, KIND);
 }
 template <int KIND, int SG>
 __device__ __forceinline__ int lap_nstates(const BatchDev &p)

@@ -234,10 +234,12 @@ __global__ __launch_bounds__(256) void k_model_err_ev(BatchDev p, double *mx, un
     if (p.ch[b * p.nch + i].prn <= 0)
         return;
     const EvConst kb = p.evc[b * p.nch + i];
-    /* the tile's granules (BatchDev::st_log2 is the code's, ev_carr_log2 of it the carrier's) and its place in each */
-    const int sg = p.st_log2, gc = ev_carr_log2(sg), nst = p.nstates, r = wt & ((1 << sg) - 1), ry_t = wt & ((1 << gc) - 1);
-    const double *txb = p.tile_x + b * (size_t)nst * 2 * p.nch;
-    const double ts_x_g = txb[(size_t)(2 * i) * nst + (wt >> sg)], ts_y = txb[(size_t)(2 * i + 1) * nst + (wt >> gc)];
+    /* the states that serve the tile, and its place in the code's granule and in the carrier's (ev_state_at) */
+    const int sg = p.st_log2, nst = p.nstates;
+    const EvStateAt cx = ev_state_at(sg, NCO_CODE, wt), cy = ev_state_at(sg, NCO_CARR, wt);
+    const int r = cx.since, ry_t = cy.since;
+    const double ts_x_g = p.tile_x[ev_tile_x_row(b, p.nch, i, NCO_CODE, nst) + cx.entry];
+    const double ts_y = p.tile_x[ev_tile_x_row(b, p.nch, i, NCO_CARR, nst) + cy.entry];
     const bool down = kb.down != 0;
     /* exactly what synth_ev_body puts into EvLds::tstate (IEEE carrier) */
     const bool fixed = p.kph0 != nullptr; /* k_synth_ev_fixed: the carrier lanes carry no bias, a falling phase is mirrored bit by bit */

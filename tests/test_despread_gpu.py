@@ -171,16 +171,22 @@ def test_states_that_graze_an_integer_at_a_sample(pkg, synth, oracle, default_op
     synth.hazards(reset=True)
 
 
-@pytest.mark.parametrize("where", ["0", "1"])
-def test_the_exact_path_forced_often(pkg, where):
+@pytest.mark.parametrize("where,state_log2", [pytest.param("0", None, id="0"), pytest.param("1", None, id="1"),
+                                              pytest.param("0", "2", id="0-g2")])
+def test_the_exact_path_forced_often(pkg, where, state_log2):
     """The experiments build with the danger threshold raised from 40 to 2^22 units of 2^-32: about one sample in five hundred
     of every channel is recomputed by ds_exact_sample, in nearly every tile; same sums.  Once per table layout: a state per two
-    tiles behind the lap pre-pass (0), a state per tile behind the row walks (1)."""
+    tiles behind the lap pre-pass (0), a state per tile behind the row walks (1) — and with the knob at 2 (0-g2) a state per four
+    tiles for code and carrier alike: the equal-granule exact path at a place in the granule that is not its first tile."""
     env = dict(os.environ, GPSBB_PY_LIB="exp", GPSBB_DS_DANGER=str(1 << 22))
+    if state_log2 is not None:
+        env["GPSBB_EV_STATE_LOG2"] = state_log2
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "despread_check.py"), "--where", where, "--views"], env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "bit-exact" in r.stdout
+    if state_log2 is not None:   # the knob took: the breakpoint kernel's batches have one state per 2^state_log2 tiles, both kinds
+        assert "ev: state granule log2 %s, the carrier's %s" % (state_log2, state_log2) in r.stdout, r.stdout[-2000:]
     n = [int(l.split(":")[1]) for l in r.stdout.splitlines() if l.startswith("exact-path samples")][0]
     # the last despread of each of the four batches looked at all its channel-samples: two tests of 2^22 / 2^32 each
     assert n > 10000, r.stdout[-2000:]

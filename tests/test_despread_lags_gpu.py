@@ -182,16 +182,23 @@ def test_chunks_of_four_tiles_on_a_large_batch(pkg, synth, default_options):
         b.close()
 
 
-@pytest.mark.parametrize("where", ["0", "1"])
-def test_the_exact_path_forced_often(pkg, where):
+@pytest.mark.parametrize("where,state_log2", [pytest.param("0", None, id="0"), pytest.param("1", None, id="1"),
+                                              pytest.param("0", "2", id="0-g2")])
+def test_the_exact_path_forced_often(pkg, where, state_log2):
     """The experiments build with the danger threshold raised from 40 to 2^22 units of 2^-32 (tests/test_despread_gpu.py's way, in
     a child process): about one channel-sample in five hundred takes ds_exact_sample's replica before the lags' sums are formed;
-    the same numpy result at every lag, and the count says the path ran."""
+    the same numpy result at every lag, and the count says the path ran.  0-g2: the knob at 2, one state per four tiles for code
+    and carrier alike — the equal-granule exact path at a place in the granule that is not its first tile."""
     env = dict(os.environ, GPSBB_PY_LIB="exp", GPSBB_DS_DANGER=str(1 << 22))
+    if state_log2 is not None:
+        env["GPSBB_EV_STATE_LOG2"] = state_log2
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "despread_lags_check.py"), "--where", where], env=env,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "bit-exact" in r.stdout
+    if state_log2 is not None:   # the knob took: the breakpoint kernel's batches have one state per 2^state_log2 tiles, both kinds
+        for name in ("ev", "ev_odd"):
+            assert "%s: state granule log2 %s, the carrier's %s" % (name, state_log2, state_log2) in r.stdout, r.stdout[-2000:]
     n = [int(l.split(":")[1]) for l in r.stdout.splitlines() if l.startswith("exact-path samples")][0]
     assert n > 100, r.stdout[-2000:]
 

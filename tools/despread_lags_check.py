@@ -110,6 +110,8 @@ def main():
                     L.gpsbb_test_despread_exact.argtypes = [C.c_void_p]
                     L.gpsbb_test_despread_exact.restype = C.c_ulonglong
                     exact += L.gpsbb_test_despread_exact(b._b)
+                    print("%s: state granule log2 %d, the carrier's %d" % (name, L.gpsbb_test_state_log2(b._b),
+                                                                          L.gpsbb_test_state_log2_carr(b._b)))
             b.close()
             if bad:
                 print("%s (seed where %d):\n%s" % (name, where, "\n".join(bad)))
