@@ -24,10 +24,38 @@
 extern "C" {
 #endif
 
+/*
+ * Input that is not valid.  On a valid file the front end is the reference, bit for bit; it departs from the reference on
+ * invalid input only, where the reference indexes out of bounds (date2gps with a month of 0, as a trailing blank line
+ * gives), never returns (satpos with an eccentricity of 1 or more) or hands out descriptors that are not finite.
+ *
+ * GPSFE_E_NAVFILE.  An ephemeris record is taken only if it is complete and valid:
+ *   - all eight lines are there, none longer than the reader's line buffer (99 characters), and every numeric field of
+ *     them is finite (a blank or cut-off field reads 0, as in the reference);
+ *   - month 1..12, day 1..31, hour 0..23, minute 0..59, seconds in [0, 61), year 1980 or later, PRN 1..32;
+ *   - every value is one its field of the navigation message can hold (IS-GPS-200: the field's bits times its scale factor):
+ *     0 <= ecc < 0.5 (32 bits of 2^-33), 0 < sqrt(A) < 8192 (32 bits of 2^-19), 0 <= toe < 604800, |af0| <= 2^-10,
+ *     |af1| <= 2^-28, |af2| <= 2^-48, |tgd| <= 2^-24, |crs|, |crc| <= 1024, |cuc|, |cus|, |cic|, |cis| <= 2^-14,
+ *     |delta n| <= 2^-28 pi, |omega dot| <= 2^-20 pi, |idot| <= 2^-30 pi, the four angles within one turn (2 pi),
+ *     IODE 0..255, IODC 0..1023, codes on L2 0..3, health 0..63, week 0..65535.
+ * Reading stops at the first record that fails; that record is not used, the sets read so far are.  A file with more
+ * sets than the table holds (13) gives its first 13.  A file that cannot be opened, that is of the other RINEX version, or
+ * that yields no valid record is GPSFE_E_NAVFILE.
+ * Header: ionosphere or UTC terms that are not finite, or that page 18 cannot hold (alpha 8 bits of 2^-30, 2^-27, 2^-24,
+ * 2^-24; beta 8 bits of 2^11, 2^14, 2^16, 2^16; A0 32 bits of 2^-30; A1 24 bits of 2^-50), leave the ionosphere model at
+ * its default, as a header without these lines does.
+ *
+ * GPSFE_E_MOTION.  The motion file ends at the first line that is not four numbers, finite and at most 1e9 m in size, or
+ * that is longer than the reader's line buffer; the points read so far are used.  A file that cannot be opened or that yields
+ * no point is GPSFE_E_MOTION.
+ *
+ * The Newton iteration of the orbit is bounded (a valid record never reaches the bound), and the antenna-pattern index is
+ * kept within its table.  tests/test_frontend_malformed.py, tests/rinex_mutants.py, tools/fe_asan.c.
+ */
 #define GPSFE_OK 0
 #define GPSFE_E_BADARG (-1)
-#define GPSFE_E_NAVFILE (-2)   /* cannot open / not a RINEX-2 GPS nav file / no ephemeris          */
-#define GPSFE_E_MOTION (-3)    /* cannot open / empty user-motion file                              */
+#define GPSFE_E_NAVFILE (-2)   /* cannot open / not a RINEX GPS nav file of the version asked for / no valid record */
+#define GPSFE_E_MOTION (-3)    /* cannot open / no valid point in the user-motion file                */
 #define GPSFE_E_TIME (-4)      /* start time outside the ephemeris window (c:2555-2564)             */
 #define GPSFE_E_NOEPH (-5)     /* no ephemeris set within an hour of the start time (c:2593-2596)   */
 #define GPSFE_E_NOMEM (-6)
@@ -114,6 +142,9 @@ int gpsfe_set_threads(gpsfe_t *fe, int nthreads);
 int gpsfe_time(const gpsfe_t *fe, int *week, double *sec);
 int gpsfe_channel_info(const gpsfe_t *fe, int i, int *prn, double *az_deg, double *el_deg, double *range_m,
                        double *iono_m);
+/* the ephemeris sets the navigation file gave: returns their number and writes the valid satellites of the first `cap`
+ * of them to nvalid[] */
+int gpsfe_eph_sets(const gpsfe_t *fe, int *nvalid, int cap);
 
 #ifdef __cplusplus
 }

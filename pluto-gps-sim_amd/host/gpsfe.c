@@ -24,6 +24,10 @@
 #define N_SAT 32       /* MAX_SAT h:18 */
 #define N_EPH_SETS 13  /* EPHEM_ARRAY_SIZE h:78 */
 #define N_MOTION 3000  /* USER_MOTION_SIZE h:24-26 */
+/* sat_state's Newton loop: 4 iterations is the most that any satellite of tests/golden's three navigation files takes, at any
+ * block of the four hours after their first epoch, all 32 satellites and 16 channels (measured with a counter in the loop);
+ * the bound is eight times that */
+#define NEWTON_MAX 32
 #define K_PI 3.1415926535898
 #define K_GM 3.986005e14
 #define K_OMEGA_E 7.2921151467e-5
@@ -255,7 +259,10 @@ static void sat_state(const eph_t *e, gtime_t g, double *pos, double *vel, doubl
     /* Kepler's equation by Newton iteration to 1e-14 (c:478-487) */
     const double mk = e->m0 + e->n * tk;
     double ek = mk, ek_old = ek + 1.0, one_m_ecos = 0;
-    while (fabs(ek - ek_old) > 1.0E-14) {
+    /* NEWTON_MAX: the reference's loop has no bound and never ends where ek steps between two neighbouring doubles more
+     * than 1e-14 apart (|ek| above 64: a mean motion far from a GPS orbit's).  A valid record takes at most 4 iterations
+     * (see NEWTON_MAX), so no valid result passes through the bound. */
+    for (int it = 0; it < NEWTON_MAX && fabs(ek - ek_old) > 1.0E-14; it++) {
         ek_old = ek;
         one_m_ecos = 1.0 - e->ecc * cos(ek_old);
         ek = ek + (mk - ek_old + e->ecc * sin(ek_old)) / one_m_ecos;
@@ -740,7 +747,9 @@ static void seed_code_phase(chan_t *c, const range_t *rho1, double dt)
 static double channel_gain(const gpsfe_t *fe, const range_t *rho)
 {
     const double path_loss = 20200000.0 / rho->d;
-    const int ibs = (int)((90.0 - rho->azel[1] * K_R2D) / 5.0); /* elevation -> boresight bin */
+    const double bs = (90.0 - rho->azel[1] * K_R2D) / 5.0; /* elevation -> boresight bin */
+    /* a finite elevation gives 0..36; one that is not (the reference indexes with it as it is) takes bin 0 */
+    const int ibs = (bs >= 0.0 && bs < 37.0) ? (int)bs : (bs >= 37.0 ? 36 : 0);
     return (double)(path_loss * fe->ant_pat[ibs]);
 }
 
@@ -784,6 +793,67 @@ static int label_is(const char *line, size_t len, const char *label)
     return len >= 60 + l && strncmp(line + 60, label, l) == 0;
 }
 
+/* The next line of the file, as gzgets(fp, line, size) gives it, 0 at the end of the file; but a line that does not fit
+ * is read to its end, so that its tail is not taken for the next line, and *cut says that it was. */
+static int nav_line(gzFile fp, char *line, int size, int *cut)
+{
+    int n = 0, c;
+    *cut = 0;
+    while ((c = gzgetc(fp)) != -1) {
+        if (n < size - 1)
+            line[n++] = (char)c;
+        else
+            *cut = 1;
+        if (c == '\n')
+            break;
+    }
+    line[n] = 0;
+    return n > 0;
+}
+
+/* ---- what the reader takes (include/gpsfe.h, GPSFE_E_NAVFILE).  The reference takes every record and every header term
+ * as it reads it; a damaged file then indexes out of bounds (date2gps with month 0), spins (satpos with an eccentricity of
+ * 99) or hands out descriptors that are not finite.  Here a value is taken only if it is finite and within what its field of
+ * the navigation message can hold (IS-GPS-200 tables 20-I, 20-III, 20-X: the field's bits times its scale factor), which
+ * every value of a real broadcast is.  NaN fails every comparison below. ---- */
+static int within(double v, double lim) { return fabs(v) <= lim; }
+static int from_to(double v, double lo, double hi) { return v >= lo && v <= hi; }
+
+static int epoch_ok(const caltime_t *t)
+{
+    return t->y >= 1980 && t->m >= 1 && t->m <= 12 && t->d >= 1 && t->d <= 31 && t->hh >= 0 && t->hh <= 23 && t->mm >= 0 &&
+           t->mm <= 59 && t->sec >= 0.0 && t->sec < 61.0;
+}
+
+static int eph_ok(const eph_t *e)
+{
+    return within(e->af0, 0x1p-10) && within(e->af1, 0x1p-28) && within(e->af2, 0x1p-48) && within(e->tgd, 0x1p-24) &&
+           within(e->crs, 1024.0) && within(e->crc, 1024.0) && within(e->cuc, 0x1p-14) && within(e->cus, 0x1p-14) &&
+           within(e->cic, 0x1p-14) && within(e->cis, 0x1p-14) && within(e->deltan, 0x1p-28 * K_PI) &&
+           within(e->omgdot, 0x1p-20 * K_PI) && within(e->idot, 0x1p-30 * K_PI) &&
+           /* the four angles: 32 bits of 2^-31 semicircles is one turn; files hold them in [-pi, pi] */
+           within(e->m0, 2.0 * K_PI) && within(e->omg0, 2.0 * K_PI) && within(e->inc0, 2.0 * K_PI) && within(e->aop, 2.0 * K_PI) &&
+           e->ecc >= 0.0 && e->ecc < 0.5 &&          /* 32 bits of 2^-33 */
+           e->sqrta > 0.0 && e->sqrta < 8192.0 &&    /* 32 bits of 2^-19 */
+           e->toe.sec >= 0.0 && e->toe.sec < K_WEEK; /* 16 bits of 16 s */
+}
+
+/* the four 19-character fields of an orbit line (three on the record's first line): finite, also where the reader uses none */
+static int fields_finite(const char *line, size_t len, int first_col)
+{
+    for (int col = first_col; col < 79; col += 19)
+        if (!isfinite(field(line, len, col, 19)))
+            return 0;
+    return 1;
+}
+
+static int iono_ok(const iono_t *io)
+{
+    return within(io->alpha[0], 0x1p-23) && within(io->alpha[1], 0x1p-20) && within(io->alpha[2], 0x1p-17) &&
+           within(io->alpha[3], 0x1p-17) && within(io->beta[0], 0x1p18) && within(io->beta[1], 0x1p21) &&
+           within(io->beta[2], 0x1p23) && within(io->beta[3], 0x1p23) && within(io->A0, 2.0) && within(io->A1, 0x1p-27);
+}
+
 /* RINEX-2 (readRinex2 c:874-1233) and RINEX-3 (readRinex3 c:1241-1610) GPS navigation files: same
  * content, the v3 columns are shifted by one and the header carries the iono/UTC terms under other labels */
 static int read_rinex(gpsfe_t *fe, const char *path, int v3)
@@ -792,14 +862,14 @@ static int read_rinex(gpsfe_t *fe, const char *path, int v3)
     if (!fp)
         return -1;
     char line[100];
-    int flags = 0;
+    int flags = 0, cut;
     iono_t *io = &fe->iono;
     for (int s = 0; s <= N_EPH_SETS; s++)
         for (int sv = 0; sv < N_SAT; sv++)
             fe->eph[s][sv].valid = 0;
 
     /* header: labels start at column 60 (c:899-1000 / c:1266-1362) */
-    while (gzgets(fp, line, sizeof line)) {
+    while (nav_line(fp, line, sizeof line, &cut)) {
         const size_t len = strlen(line);
         if (label_is(line, len, "COMMENT"))
             continue;
@@ -850,15 +920,25 @@ static int read_rinex(gpsfe_t *fe, const char *path, int v3)
         }
     }
     io->valid = (flags == 0xF);
+    if (!iono_ok(io)) { /* page 18 is not sent and the Klobuchar terms are not used: nothing reads them from here on */
+        io->valid = 0;
+        memset(io->alpha, 0, sizeof io->alpha);
+        memset(io->beta, 0, sizeof io->beta);
+        io->A0 = io->A1 = 0.0;
+    }
 
-    /* records: 8 lines per satellite; a new set starts when TOC jumps by more than an hour (c:1046-1054) */
+    /* records: 8 lines per satellite; a new set starts when TOC jumps by more than an hour (c:1046-1054).  A record is read
+     * into `rec` and taken only when it is complete and eph_ok: reading stops at the first one that is not, the sets read so
+     * far are used, and the return value counts the sets that hold a record. */
     const int o = v3 ? 1 : 0; /* column shift of the four 19-character fields */
     gtime_t g_set = {-1, 0.0};
-    int ieph = 0;
-    while (gzgets(fp, line, sizeof line)) {
+    int ieph = 0, nsets = 0;
+    while (nav_line(fp, line, sizeof line, &cut)) {
         size_t len = strlen(line);
         int sv;
         caltime_t t;
+        eph_t rec, *e = &rec;
+        memset(&rec, 0, sizeof rec);
         if (v3) {
             if (line[0] != 'G') /* other constellations (c:1380-1382) */
                 continue;
@@ -878,28 +958,25 @@ static int read_rinex(gpsfe_t *fe, const char *path, int v3)
             t.mm = field_int(line, len, 15, 2);
             t.sec = field(line, len, 18, 2); /* two characters of the seconds field (c:1036-1038) */
         }
+        if (cut || !epoch_ok(&t) || sv < 0 || sv >= N_SAT)
+            break; /* (the reference indexes out of bounds with such a month or satellite) */
+        int ok = fields_finite(line, len, 22 + o);
         const gtime_t g = cal_to_gps(&t);
-        if (g_set.week == -1)
-            g_set = g;
-        if (gps_diff(g, g_set) > K_HOUR) {
-            g_set = g;
-            if (++ieph >= N_EPH_SETS)
-                break;
-        }
-        if (sv < 0 || sv >= N_SAT)
-            break; /* malformed record: the reference would index out of bounds here */
-        eph_t *e = &fe->eph[ieph][sv];
         e->t = t;
         e->toc = g;
         e->af0 = field(line, len, 22 + o, 19);
         e->af1 = field(line, len, 41 + o, 19);
         e->af2 = field(line, len, 60 + o, 19);
 #define NEXT_LINE()                                  \
-    if (!gzgets(fp, line, sizeof line))              \
+    if (!nav_line(fp, line, sizeof line, &cut))      \
         break;                                       \
-    len = strlen(line)
+    len = strlen(line);                              \
+    ok = ok && !cut && fields_finite(line, len, 3 + o)
+/* a field the reference casts to int: within lo..hi before the cast */
+#define INT_FIELD(col, lo, hi) (v = field(line, len, (col) + o, 19), ok = ok && from_to(v, lo, hi), ok ? (int)v : 0)
+        double v;
         NEXT_LINE(); /* orbit 1 */
-        e->iode = (int)field(line, len, 3 + o, 19);
+        e->iode = INT_FIELD(3, 0.0, 255.0);
         e->crs = field(line, len, 22 + o, 19);
         e->deltan = field(line, len, 41 + o, 19);
         e->m0 = field(line, len, 60 + o, 19);
@@ -920,26 +997,36 @@ static int read_rinex(gpsfe_t *fe, const char *path, int v3)
         e->omgdot = field(line, len, 60 + o, 19);
         NEXT_LINE(); /* orbit 5 */
         e->idot = field(line, len, 3 + o, 19);
-        e->codeL2 = (int)field(line, len, 22 + o, 19);
-        e->toe.week = (int)field(line, len, 41 + o, 19);
+        e->codeL2 = INT_FIELD(22, 0.0, 3.0);
+        e->toe.week = INT_FIELD(41, 0.0, 65535.0);
         NEXT_LINE(); /* orbit 6 */
-        e->svhlth = (int)field(line, len, 22 + o, 19);
+        e->svhlth = INT_FIELD(22, 0.0, 63.0);
         if (e->svhlth > 0 && e->svhlth < 32)
             e->svhlth += 32;
         e->tgd = field(line, len, 41 + o, 19);
-        e->iodc = (int)field(line, len, 60 + o, 19);
+        e->iodc = INT_FIELD(60, 0.0, 1023.0);
         NEXT_LINE(); /* orbit 7: not used */
+#undef INT_FIELD
 #undef NEXT_LINE
+        if (!ok || !eph_ok(e))
+            break;
+        if (g_set.week == -1)
+            g_set = g;
+        if (gps_diff(g, g_set) > K_HOUR) {
+            g_set = g;
+            if (++ieph >= N_EPH_SETS)
+                break; /* the file holds more sets than the table: the first N_EPH_SETS are used */
+        }
         e->valid = 1;
         e->A = e->sqrta * e->sqrta;
         e->n = sqrt(K_GM / (e->A * e->A * e->A)) + e->deltan;
         e->sq1e2 = sqrt(1.0 - e->ecc * e->ecc);
         e->omgkdot = e->omgdot - K_OMEGA_E;
+        fe->eph[ieph][sv] = rec;
+        nsets = ieph + 1;
     }
     gzclose(fp);
-    if (g_set.week >= 0)
-        ieph += 1;
-    return ieph;
+    return nsets;
 }
 
 /* user motion "t,x,y,z" per line (readUserMotion c:1794-1818) */
@@ -954,7 +1041,12 @@ static int read_motion(gpsfe_t *fe, const char *path)
         double t, x, y, z;
         if (!fgets(line, sizeof line, fp))
             break;
-        if (EOF == sscanf(line, "%lf,%lf,%lf,%lf", &t, &x, &y, &z))
+        /* The file ends at the first line that is not four finite numbers, or that does not fit the buffer (its tail would
+         * be read as the next line).  The reference stops at a blank line only and stores what a short line left unset.
+         * 1e9 m: far beyond every orbit, and keeps the geodesy's sums of squares finite. */
+        const size_t len = strlen(line);
+        if ((len == sizeof line - 1 && line[len - 1] != '\n') || 4 != sscanf(line, "%lf,%lf,%lf,%lf", &t, &x, &y, &z) ||
+            !isfinite(t) || !within(x, 1.0e9) || !within(y, 1.0e9) || !within(z, 1.0e9))
             break;
         fe->xyz[n][0] = x;
         fe->xyz[n][1] = y;
@@ -973,8 +1065,8 @@ const char *gpsfe_strerror(int err)
     switch (err) {
     case GPSFE_OK: return "ok";
     case GPSFE_E_BADARG: return "bad argument";
-    case GPSFE_E_NAVFILE: return "cannot read the RINEX-2 navigation file";
-    case GPSFE_E_MOTION: return "cannot read the user-motion file";
+    case GPSFE_E_NAVFILE: return "cannot read the RINEX navigation file, or no valid ephemeris record in it";
+    case GPSFE_E_MOTION: return "cannot read the user-motion file, or no valid point in it";
     case GPSFE_E_TIME: return "start time outside the ephemeris window";
     case GPSFE_E_NOEPH: return "no current set of ephemerides";
     case GPSFE_E_NOMEM: return "out of memory";
@@ -1513,6 +1605,18 @@ int gpsfe_time(const gpsfe_t *fe, int *week, double *sec)
     if (sec)
         *sec = fe->grx.sec;
     return GPSFE_OK;
+}
+
+int gpsfe_eph_sets(const gpsfe_t *fe, int *nvalid, int cap)
+{
+    if (!fe || cap < 0 || (cap > 0 && !nvalid))
+        return GPSFE_E_BADARG;
+    for (int s = 0; s < fe->neph && s < cap; s++) {
+        nvalid[s] = 0;
+        for (int sv = 0; sv < N_SAT; sv++)
+            nvalid[s] += fe->eph[s][sv].valid != 0;
+    }
+    return fe->neph;
 }
 
 int gpsfe_channel_info(const gpsfe_t *fe, int i, int *prn, double *az_deg, double *el_deg, double *range_m,
