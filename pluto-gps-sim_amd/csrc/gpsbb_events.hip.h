@@ -195,7 +195,12 @@ struct EvLdsT {
                                                     (synth_ev_body).  The kernel has no register to keep its lane's step in, and
                                                     out of global memory the read put a vector-memory wait at the top of every tile */
     uint16_t chip2[GPSBB_MAX_CHAN][CHIP_LEN];    /* low byte: 0 where codeCA of chip c mod 1023 is +1, 0xff where -1;
-                                                    high byte: the same for chip c+1 */
+                                                    high byte: a flag, 0x0f where chip c+1 (chip 1023 is chip 0) has the SAME
+                                                    sign as chip c, 0 where it differs: whether two neighbours are equal is a
+                                                    property of the PRN, worked out once per workgroup by the staging loop and
+                                                    not per lane, channel and run.  0x0f is what turns the high word of any
+                                                    position into EV_SAT_HI when ORed into it (ev_second).  Only ev_second
+                                                    reads the high byte */
 };
 typedef EvLdsT<EV_AMP_STRIDE, EV_CHIP_LEN> EvLds;                   /* k_synth_ev_dense */
 typedef EvLdsT<EV_AMP_STRIDE_LONG, EV_CHIP_LEN_SHORT> EvLdsLean;    /* k_synth_ev, k_synth_ev_fixed */
@@ -405,6 +410,10 @@ __device__ __forceinline__ EvK ev_load_k(const LDS &L, const EvConst *kb, int i)
  * lane that comes within the model error of one recomputes exactly anyway), so this code only knows rising
  * phases.  The code phase is not reduced modulo 1023: the chip table simply continues past 1023.
  */
+/* 16 bits that are nobody's integer: ev_second's SDWA instructions pick the two bytes of a chip table entry out of the register
+ * the load wrote.  Held as uint16_t, the second channel of a pair — its entry is loaded ahead of the first channel's rare branch
+ * and used behind it — paid a v_and 0xffff for the widening to a 32-bit operand; a half-precision value travels as it is. */
+typedef _Float16 __attribute__((may_alias)) ev_raw16;
 template <int KC>
 struct EvHalf {
     uint32_t hk[KC]; /* the k-th index change as the HIGH WORD of its position in guard format (clamped to 15.5): the low byte
@@ -414,7 +423,7 @@ struct EvHalf {
     unsigned long long um; /* lanes that cannot rule out a disagreement between the model and the reference (wave mask:
                               the comparisons land in scalar registers and are combined there) */
     uint32_t A[KC + 1];
-    uint32_t ch2;
+    ev_raw16 ch2; /* the chip table's entry of the first sample's chip (EvLdsT::chip2), as loaded */
 };
 
 /* FIXED: the fixed-point carrier (GPSBB_FIXED_CARRIER).  Its table index (phase mod 2^25) / 2^16 and its step are multiples of
@@ -465,7 +474,7 @@ __device__ __forceinline__ EvHalf<KC> ev_first(const LDS &L, int i, const EvK &K
      * exponent bits a constant that the channel's base already has taken off — no masking instruction */
     uint32_t chip_at;
     asm("v_lshl_add_u32 %0, %1, 1, %2" : "=v"(chip_at) : "v"(__double2hiint(x0)), "s"(K.chip_base));
-    h.ch2 = lds_read_at<uint16_t>(chip_at);
+    h.ch2 = lds_read_at<ev_raw16>(chip_at);
     /* lanes that cannot rule out a disagreement between the model and the reference: one comparison for everything tested */
     h.um = __builtin_amdgcn_uicmp(m, K.danger, 37 /* ule */);
     return h;
@@ -518,23 +527,44 @@ __device__ __forceinline__ bool ev_exact_2g(const EvTile &T) { return ev_carr_lo
 /*
  * Second half: signs, the contribution at sample 0 (into acc0) and its changes (into D).  db / db_next: the
  * data bit in force at the tile start / after the next code roll-over as masks (0 = +1, -1 = -1; wave-uniform);
- * DF: they differ, so lanes past the roll-over (chip index >= 1023) take the other one.
+ * DF: they differ, so lanes past the roll-over (chip index >= 1023) take the other one.  m0_out: the sign mask of sample 0, which
+ * the caller still has to take off acc0 (ev_channels: once per pair).
  */
 template <int KC, bool DF, bool FIXED, class LDS>
 __device__ __forceinline__ void ev_second(LDS &L, uint32_t &drow, int wave, int lane, int i, EvHalf<KC> &h, uint32_t db, uint32_t db_next,
                                           unsigned long long live_mask, const EvConst *kb, const EvTile &T,
-                                          double off, uint32_t &acc0, unsigned long long *n_exact, const EvFixed &fx)
+                                          double off, uint32_t &acc0, uint32_t &m0_out, unsigned long long *n_exact, const EvFixed &fx)
 {
-    const uint32_t ma = (uint32_t)(int32_t)(int8_t)(h.ch2 & 0xffu), mb = (uint32_t)(int32_t)(int8_t)(h.ch2 >> 8);
-    uint32_t m0, m1;
+    uint32_t m0, m1, hc;
     if (DF) {
+        /* the chip behind the change from the table's flag; the two chips may stand under different data bits (c0 == 1022), so
+         * whether anything changes at the boundary is looked at here, lane by lane */
+        const uint32_t ch2 = __builtin_bit_cast(uint16_t, h.ch2);
+        const uint32_t ma = (uint32_t)(int32_t)(int8_t)(ch2 & 0xffu); /* the sign of the first sample's chip (EvLdsT::chip2) */
+        const uint32_t mb = ma ^ ((ch2 >> 8) ? 0u : 0xffffffffu);
         m0 = ma ^ (h.c0 >= 1023 ? db_next : db);
         m1 = mb ^ (h.c0 >= 1022 ? db_next : db);
+        hc = m0 == m1 ? EV_SAT_HI : h.hc; /* equal neighbours: nothing changes at the chip boundary */
     } else {
-        m0 = ma ^ db;
-        m1 = mb ^ db;
+        /* One data bit for both chips: nothing changes at the boundary exactly where the table's flag says the neighbours are
+         * equal.  h.hc is EV_GUARD_HI + row with row <= 15 and the flag is 0x0f, so ONE or turns it into EV_SAT_HI there and
+         * leaves it alone elsewhere (in plain C++ the compiler shifts the byte down first, and masks the register for the second
+         * channel of a pair: SDWA reads the byte where it is, as ev_d_add's add does).
+         * m1 is then simply the other sign.  That is wrong where the neighbours are equal, and harmless: with hc == EV_SAT_HI
+         * every h.hk[k] < hc holds unless hk[k] is EV_SAT_HI itself, whose difference goes to the discard row — so mk is m0
+         * wherever it matters — and the chip change's own difference, the only user of Ax and of m1 as a sign, goes to row 15
+         * as well. */
+        /* (m0 = sign ^ db, and the or, both off the 16-bit register as it was loaded, EvHalf::ch2: one SDWA instruction each) */
+        asm("v_xor_b32_sdwa %0, sext(%1), %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:DWORD"
+            : "=v"(m0)
+            : "v"(h.ch2), "s"(db));
+        /* (written out: left to itself the compiler never forms m1 — it makes a 0 / -1 mask of every comparison below and xors
+         * it into m0, one more instruction per index change) */
+        asm("v_not_b32 %0, %1" : "=v"(m1) : "v"(m0));
+        asm("v_or_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1"
+            : "=v"(hc)
+            : "v"(h.hc), "v"(h.ch2));
     }
-    uint32_t hc = m0 == m1 ? EV_SAT_HI : h.hc; /* equal neighbours: nothing changes at the chip boundary */
 
     /* ---- rare: this lane cannot rule out that the model and the reference disagree (a channel that is always recomputed
      * exactly has a threshold every low word is below: EvConst::danger_le).  The branch is on the comparison as it comes
@@ -565,9 +595,10 @@ __device__ __forceinline__ void ev_second(LDS &L, uint32_t &drow, int wave, int 
 
     /* ---- the contribution at sample 0 and its changes ---- */
     {
-        /* += signed_by(A[0], m0) as (A ^ m) + (acc - m): two instructions (the compiler's own choice is xor, sub, add) */
-        const uint32_t c = acc0 - m0;
+        /* += signed_by(A[0], m0) = (A ^ m) - m: the xor and the add here in one instruction, the - m handed to the caller */
+        const uint32_t c = acc0;
         asm("v_xad_u32 %0, %1, %2, %3" : "=v"(acc0) : "v"(h.A[0]), "v"(m0), "v"(c));
+        m0_out = m0;
     }
     uint32_t Ax = h.A[KC];
 #pragma unroll
@@ -630,10 +661,12 @@ __device__ __forceinline__ void ev_dense(LDS &L, int wave, int lane, int i, cons
 }
 
 /* the channels of `mask` (bit i = channel i), all with KC breakpoints; two at a time, so that one channel's
- * arithmetic covers the other's LDS latency */
+ * arithmetic covers the other's LDS latency.  msum: the sum of the channels' sample-0 sign masks, which acc0 is still short of
+ * (ev_second): a pair's two go in with ONE v_add3_u32 where each channel took its own off acc0 before, and the tile takes the
+ * sum off once (synth_ev_body) — one instruction less per pair for one more register across the channel loops */
 template <int KC, bool DF, bool FIXED, class LDS>
 __device__ __forceinline__ void ev_channels(LDS &L, uint32_t &drow, int wave, int lane, uint32_t mask, const EvConst *kb, const EvTile &T,
-                                            double off, unsigned long long live_mask, uint32_t &acc0, unsigned long long *n_exact,
+                                            double off, unsigned long long live_mask, uint32_t &acc0, uint32_t &msum, unsigned long long *n_exact,
                                             const EvFixed &fx)
 {
 #define GPSBB_EV_STATES(i)                                                                                             \
@@ -643,10 +676,10 @@ __device__ __forceinline__ void ev_channels(LDS &L, uint32_t &drow, int wave, in
 #define GPSBB_EV_IN(i)                                                                                                 \
     const EvK K##i = ev_load_k(L, kb, GPSBB_EV_KIDX(i));                                                               \
     GPSBB_EV_STATES(i)
-#define GPSBB_EV_OUT(i, h)                                                                                             \
+#define GPSBB_EV_OUT(i, h, m)                                                                                          \
     {                                                                                                                  \
         const uint32_t db_ = 0u - ((T.dbits >> i) & 1u), dn_ = 0u - ((T.dnext >> i) & 1u);                             \
-        ev_second<KC, DF, FIXED>(L, drow, wave, lane, i, h, db_, dn_, live_mask, kb, T, off, acc0, n_exact, fx);       \
+        ev_second<KC, DF, FIXED>(L, drow, wave, lane, i, h, db_, dn_, live_mask, kb, T, off, acc0, m, n_exact, fx);    \
     }
     while (mask & (mask - 1)) { /* at least two channels left */
         const int i0 = __builtin_ctz(mask);
@@ -657,14 +690,18 @@ __device__ __forceinline__ void ev_channels(LDS &L, uint32_t &drow, int wave, in
         GPSBB_EV_IN(i1)
         EvHalf<KC> h0 = ev_first<KC, FIXED>(L, i0, Ki0, xti0, yti0, tki0, tci0, off);
         EvHalf<KC> h1 = ev_first<KC, FIXED>(L, i1, Ki1, xti1, yti1, tki1, tci1, off);
-        GPSBB_EV_OUT(i0, h0)
-        GPSBB_EV_OUT(i1, h1)
+        uint32_t ma, mb;
+        GPSBB_EV_OUT(i0, h0, ma)
+        GPSBB_EV_OUT(i1, h1, mb)
+        asm("v_add3_u32 %0, %1, %2, %3" : "=v"(msum) : "v"(msum), "v"(ma), "v"(mb));
     }
     if (mask) {
         const int i0 = __builtin_ctz(mask);
         GPSBB_EV_IN(i0)
         EvHalf<KC> h0 = ev_first<KC, FIXED>(L, i0, Ki0, xti0, yti0, tki0, tci0, off);
-        GPSBB_EV_OUT(i0, h0)
+        uint32_t ma;
+        GPSBB_EV_OUT(i0, h0, ma)
+        msum += ma;
     }
 #undef GPSBB_EV_IN
 #undef GPSBB_EV_OUT
@@ -821,7 +858,7 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
             if (prn > 0) {
                 const uint32_t b0 = (w0 >> (ca & 31)) & 1u;
                 const uint32_t b1 = (w1 >> (cb1 & 31)) & 1u;
-                v = (b0 ? 0x00u : 0xffu) | (b1 ? 0x0000u : 0xff00u);
+                v = (b0 ? 0x00u : 0xffu) | (b0 == b1 ? 0x0f00u : 0x0000u); /* the sign of chip c; chip c+1 has the same (EvLdsT::chip2) */
             }
             if (c < LDS::CHIPS)
                 L.chip2[i][c] = (uint16_t)v;
@@ -1003,20 +1040,21 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
         const int nvalid = p.nsamp - n0 < SPT ? p.nsamp - n0 : SPT;
         const bool lane_live = nvalid > 0;
         const unsigned long long live_mask = __builtin_amdgcn_ballot_w64(lane_live);
+        uint32_t msum = 0u;      /* the sample-0 sign masks still to come off acc0 (ev_channels) */
         uint32_t acc0 = 0x8000u; /* the I sum travels biased by 2^15: never negative, so the low half never borrows from the Q sum */
-        ev_channels<1, false, FIXED>(L, drow, wave, lane, mk[0] & ~dflip, kb, T, off, live_mask, acc0, n_exact, fx);
-        ev_channels<2, false, FIXED>(L, drow, wave, lane, mk[1] & ~dflip, kb, T, off, live_mask, acc0, n_exact, fx);
+        ev_channels<1, false, FIXED>(L, drow, wave, lane, mk[0] & ~dflip, kb, T, off, live_mask, acc0, msum, n_exact, fx);
+        ev_channels<2, false, FIXED>(L, drow, wave, lane, mk[1] & ~dflip, kb, T, off, live_mask, acc0, msum, n_exact, fx);
         if (__builtin_expect((mk[2] | mk[3] | dflip) != 0u, 0)) {
-            ev_channels<3, false, FIXED>(L, drow, wave, lane, mk[2] & ~dflip, kb, T, off, live_mask, acc0, n_exact, fx);
-            ev_channels<4, false, FIXED>(L, drow, wave, lane, mk[3] & ~dflip, kb, T, off, live_mask, acc0, n_exact, fx);
-            ev_channels<1, true, FIXED>(L, drow, wave, lane, mk[0] & dflip, kb, T, off, live_mask, acc0, n_exact, fx);
-            ev_channels<2, true, FIXED>(L, drow, wave, lane, mk[1] & dflip, kb, T, off, live_mask, acc0, n_exact, fx);
-            ev_channels<3, true, FIXED>(L, drow, wave, lane, mk[2] & dflip, kb, T, off, live_mask, acc0, n_exact, fx);
-            ev_channels<4, true, FIXED>(L, drow, wave, lane, mk[3] & dflip, kb, T, off, live_mask, acc0, n_exact, fx);
+            ev_channels<3, false, FIXED>(L, drow, wave, lane, mk[2] & ~dflip, kb, T, off, live_mask, acc0, msum, n_exact, fx);
+            ev_channels<4, false, FIXED>(L, drow, wave, lane, mk[3] & ~dflip, kb, T, off, live_mask, acc0, msum, n_exact, fx);
+            ev_channels<1, true, FIXED>(L, drow, wave, lane, mk[0] & dflip, kb, T, off, live_mask, acc0, msum, n_exact, fx);
+            ev_channels<2, true, FIXED>(L, drow, wave, lane, mk[1] & dflip, kb, T, off, live_mask, acc0, msum, n_exact, fx);
+            ev_channels<3, true, FIXED>(L, drow, wave, lane, mk[2] & dflip, kb, T, off, live_mask, acc0, msum, n_exact, fx);
+            ev_channels<4, true, FIXED>(L, drow, wave, lane, mk[3] & dflip, kb, T, off, live_mask, acc0, msum, n_exact, fx);
         }
         /* ---- prefix sum over the run, back to int16 pairs (c:2754-2755) ---- */
         uint32_t o[SPT];
-        uint32_t P = acc0;
+        uint32_t P = acc0 - msum;
         uint32_t accd[DENSE ? SPT : 1];
         if (DENSE) {
 #pragma unroll

@@ -3,6 +3,8 @@
 of carrier breakpoints a run can hold (KC), against a count by hand of the same algorithm's vector operations — what a hand-written
 loop could save at most.  Reads the ISA dump `make -C pluto-gps-sim_amd/csrc asm` leaves in /tmp.
 
+    python tools/ev_loop_budget.py [ISA dump, default the one in /tmp] [kernel, default k_synth_ev<1>: "k_synth_evILi1E"]
+
 The count by hand, per channel and run (gpsbb_events.hip.h):
   ev_first   carrier model fma, fract, time-to-next-change fma (3); clamp of every change KC, the changes after the first KC - 1;
              code model fma, fract, fma, clamp (4); the danger test: KC + 3 low words -> ceil((KC + 2) / 2) min3 / min, 1 compare;
@@ -12,9 +14,10 @@ The count by hand, per channel and run (gpsbb_events.hip.h):
              address, amplitude in force before the chip change; the chip change 4 (shift, xor, sub, address)
 """
 import re
+import sys
 
-s = open('/tmp/gpsbb-hip-amdgcn-amd-amdhsa-gfx950.s').read()
-m = re.search(r'^(_ZN10gpsbb_impl\d+k_synth_evENS[^\n]*):(.*?)\.Lfunc_end\d+:', s, re.S | re.M)
+s = open(sys.argv[1] if len(sys.argv) > 1 else '/tmp/gpsbb-hip-amdgcn-amd-amdhsa-gfx950.s').read()
+m = re.search(r'^(_ZN10gpsbb_impl\d+%s[^\n]*):(.*?)\.Lfunc_end\d+:' % (sys.argv[2] if len(sys.argv) > 2 else 'k_synth_evILi1E'), s, re.S | re.M)
 body = m.group(2)
 parts = re.split(r'\n(\.LBB\d+_\d+):([^\n]*)', body)
 blocks = []  # (label, comment, text)
@@ -38,7 +41,7 @@ print("KC   compiler: VALU per pair (loop head + two ev_second tails)   DS   SAL
 for kc in (1, 2, 3, 4):
     # the pair loop of ev_channels<KC, false, false>: the block that holds the two ev_first (a loop header at depth 2) is followed by
     # the two blocks named after ev_second<KC, false, false> exits
-    idx = [i for i, b in enumerate(blocks) if re.search(r'ev_secondILi%dELb0ELb0E' % kc, b[1])]
+    idx = [i for i, b in enumerate(blocks) if re.search(r'ev_secondILi%dELb0ELb[01]E' % kc, b[1])]
     if len(idx) < 2:
         continue
     i0 = idx[0] - 1
