@@ -377,6 +377,8 @@ def exp_lib():
         L.gpsbb_test_despread_ms.restype = C.c_float
         if hasattr(L, "gpsbb_test_plan"):  # (an older build loaded for an A/B: tools/ab_lib.sh)
             L.gpsbb_test_plan.argtypes = [vp, i, i, d, i, u, vp, i, vp, vp, vp, vp, vp]
+        if hasattr(L, "gpsbb_test_launch_plan"):  # (an older build loaded for an A/B: tools/ab_lib.sh)
+            L.gpsbb_test_launch_plan.argtypes = [vp, i, i, d, i, u, vp, i, vp, vp, vp, vp, i, i, i, vp]
         if hasattr(L, "gpsbb_test_push_side"):  # (an older build loaded for an A/B: tools/ab_lib.sh)
             L.gpsbb_test_push_side.argtypes = [vp, i, i, d, i, u, vp, vp]
         if hasattr(L, "gpsbb_test_chain_plan"):  # (an older build loaded for an A/B: tools/ab_lib.sh)
@@ -412,6 +414,44 @@ def plan(ch, delt, nsamp, flags=0, seed_where=0, synth_kernel=0, chain_where=0, 
                                    ptr(carry_prn, np.int32), ptr(carry_phase, np.float64), ptr(fixed_prev_prn, np.int32),
                                    ptr(fixed_prev_phase, np.uint32), out.ctypes.data)
     return rc, ({f: int(v) for f, v in zip(PLAN_FIELDS, out)} if rc == 0 else None)
+
+
+LAUNCH_FIELDS = ("prepass", "lap_wide", "lap_merged", "lap_fixed", "chain", "pass_a", "pass_b", "fix_wg", "carr_lanes", "walk_lanes",
+                 "chain_order", "seed_ev", "seed_lanes", "ctr_reset", "info_prepass", "variant", "digest_fused", "granule", "ev_chunk",
+                 "pd_danger", "helpers", "grid_x", "grid_y", "wg", "lds", "digest_gx", "digest_gy", "last_kernel", "last_chain_dev")
+LAUNCH_KERNELS = 16
+PREPASS_SKIP, PREPASS_HOST, PREPASS_LAPS, PREPASS_WALKS, PREPASS_SEED = range(5)
+# kernel ids of a launch plan: family + 256 * instance (csrc/gpsbb_plan.h: LaunchKernel)
+(LK_LAP_PLAN, LK_LAP_PASS1, LK_LAP_SCAN, LK_LAP_PASS2, LK_LAP_REPAIR, LK_LAP_FIXED_TILES, LK_WALK, LK_CHAIN_PREFIX, LK_CHAIN_FIX,
+ LK_CHAIN_FIX_PAR, LK_TILES, LK_SEED, LK_BLOCK_DIGEST) = range(1, 14)
+LK_SYNTH0 = 100  # + VARIANT_*
+
+
+def launch_plan(ch, delt, nsamp, flags=0, cus=256, want_digest=0, skip=0, seed_where=0, synth_kernel=0, chain_where=0, skip_seed=0,
+                max_sets=6, carry_prn=None, carry_phase=None, fixed_prev_prn=None, fixed_prev_phase=None):
+    """gpsbb_test_launch_plan (csrc/gpsbb_testhooks.h): what one run of the batch plan() describes would launch on a device of `cus`
+    CUs, without a handle or a GPU.  Returns (rc, values): values = LAUNCH_FIELDS -> the LaunchPlan scalar, and "kernels": the run's
+    kernels in order, each [id, grid x, grid y, workgroup, LDS bytes].  The other arguments: as plan()."""
+    ch = _as_chan(ch)
+    nb, nch = ch.shape
+    opt = np.array([seed_where, synth_kernel, skip_seed, chain_where, max_sets], np.int32)
+    out = np.zeros(len(LAUNCH_FIELDS) + 1 + 5 * LAUNCH_KERNELS, np.int64)
+
+    def ptr(a, dtype):
+        if a is None:
+            return None
+        assert a.dtype == dtype and a.flags.c_contiguous and a.size >= nch
+        return a.ctypes.data
+
+    rc = exp_lib().gpsbb_test_launch_plan(ch.ctypes.data, nb, nch, delt, nsamp, flags, opt.ctypes.data, int(carry_prn is not None),
+                                          ptr(carry_prn, np.int32), ptr(carry_phase, np.float64), ptr(fixed_prev_prn, np.int32),
+                                          ptr(fixed_prev_phase, np.uint32), cus, int(want_digest), int(skip), out.ctypes.data)
+    if rc != 0:
+        return rc, None
+    nf = len(LAUNCH_FIELDS)
+    v = {f: int(x) for f, x in zip(LAUNCH_FIELDS, out)}
+    v["kernels"] = [[int(x) for x in out[nf + 1 + 5 * k:nf + 6 + 5 * k]] for k in range(int(out[nf]))]
+    return rc, v
 
 
 PUSH_CHAIN_NONE, PUSH_CHAIN_HOST, PUSH_CHAIN_DEVICE = 0, 1, 2

@@ -1102,8 +1102,11 @@ static hipError_t zero_now(gpsbb *h, void *ptr, size_t bytes)
     return e != hipSuccess ? e : hipStreamSynchronize(h->s_seed);
 }
 
-typedef void (*EvKernelFn)(BatchDev, int16_t *);
-static EvKernelFn ev_kernel(int g, bool digest);
+struct SynthKernel {
+    void (*fn)(BatchDev, int16_t *);
+    int lds; /* dynamic LDS bytes */
+};
+static const SynthKernel &synth_kernel(int variant, bool digest, int g);
 
 extern "C" int gpsbb_create(gpsbb_t **out, int device)
 {
@@ -1170,27 +1173,14 @@ extern "C" int gpsbb_create(gpsbb_t **out, int device)
     if ((e = zero_now(h, h->d_status, 4)) != hipSuccess) return fail(e);
     if ((e = zero_now(h, h->d_hz, 64)) != hipSuccess) return fail(e);
     if ((e = zero_now(h, h->d_clip, 8)) != hipSuccess) return fail(e);
-    /* k_synth carves ~76 KB of dynamic LDS per workgroup: above the 64 KB default limit */
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_synth), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)sizeof(SynthLds))) != hipSuccess) return fail(e);
-    for (int g = 0; g <= EV_STATE_LOG2_MAX; g++) {
-        if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(ev_kernel(g, false)), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)sizeof(EvLdsLean) + EV_PICK_LDS)) != hipSuccess) return fail(e);
-        if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(ev_kernel(g, true)), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)sizeof(EvLdsLean) + EV_PICK_LDS)) != hipSuccess) return fail(e);
-    }
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_synth_ev_dense), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)sizeof(EvLds) + EV_PICK_LDS)) != hipSuccess) return fail(e);
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_synth_ev_fixed), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)sizeof(EvLdsLean) + EV_PICK_LDS)) != hipSuccess) return fail(e);
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_synth_pd<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)sizeof(PdLds<true>) + EV_PICK_LDS)) != hipSuccess) return fail(e);
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_synth_pd<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)sizeof(PdLds<false>) + EV_PICK_LDS)) != hipSuccess) return fail(e);
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_synth_pd<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)sizeof(PdLds<true>) + EV_PICK_LDS)) != hipSuccess) return fail(e);
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_synth_pd<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)sizeof(PdLds<false>) + EV_PICK_LDS)) != hipSuccess) return fail(e);
+    /* the synthesis kernels carve 76 - 156 KB of dynamic LDS per workgroup: above the 64 KB default limit */
+    for (int v = GPSBB_VARIANT_SYNTH; v <= GPSBB_VARIANT_EV_FIXED; v++)
+        for (int dg = 0; dg < 2; dg++)
+            for (int g = 0; g <= EV_STATE_LOG2_MAX; g++) {
+                const SynthKernel &k = synth_kernel(v, dg != 0, g);
+                if (k.fn && (e = hipFuncSetAttribute(reinterpret_cast<const void *>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                     k.lds)) != hipSuccess) return fail(e);
+            }
     *out = h;
     return GPSBB_OK;
 }
@@ -1208,12 +1198,28 @@ static LapKernelFn lap_pass2_kernel(int kind, bool wide, int g)
     return k[wide ? 1 : 0][kind < 0 ? 2 : kind][g];
 }
 
-/* the instance of k_synth_ev / k_synth_ev_digest for a state granule of 2^g tiles */
-static EvKernelFn ev_kernel(int g, bool digest)
+/* The synthesis kernels by GPSBB_VARIANT_*, without / with the blocks' digests fused, for a state granule of 2^g tiles (k_synth_ev
+ * alone has instances beyond g = 0); fn null: no such instance. */
+static const SynthKernel &synth_kernel(int variant, bool digest, int g)
 {
-    static const EvKernelFn k[2][EV_STATE_LOG2_MAX + 1] = {{k_synth_ev<0>, k_synth_ev<1>, k_synth_ev<2>},
-                                                            {k_synth_ev_digest<0>, k_synth_ev_digest<1>, k_synth_ev_digest<2>}};
-    return k[digest ? 1 : 0][g];
+#define GPSBB_SK(v, k) {k, synth_lds(v)}
+#define GPSBB_SK1(v, k) {GPSBB_SK(v, k), {}, {}}
+    static const SynthKernel k[GPSBB_VARIANT_EV_FIXED + 1][2][EV_STATE_LOG2_MAX + 1] = {
+        {},
+        {GPSBB_SK1(GPSBB_VARIANT_SYNTH, k_synth), {}},
+        {{GPSBB_SK(GPSBB_VARIANT_EV, k_synth_ev<0>), GPSBB_SK(GPSBB_VARIANT_EV, k_synth_ev<1>), GPSBB_SK(GPSBB_VARIANT_EV, k_synth_ev<2>)},
+         {GPSBB_SK(GPSBB_VARIANT_EV, k_synth_ev_digest<0>), GPSBB_SK(GPSBB_VARIANT_EV, k_synth_ev_digest<1>),
+          GPSBB_SK(GPSBB_VARIANT_EV, k_synth_ev_digest<2>)}},
+        {GPSBB_SK1(GPSBB_VARIANT_EV_DENSE, k_synth_ev_dense), {}},
+        {GPSBB_SK1(GPSBB_VARIANT_PD_WIDE, k_synth_pd<true>), GPSBB_SK1(GPSBB_VARIANT_PD_WIDE, (k_synth_pd<true, true>))},
+        {GPSBB_SK1(GPSBB_VARIANT_PD_NARROW, k_synth_pd<false>), GPSBB_SK1(GPSBB_VARIANT_PD_NARROW, (k_synth_pd<false, true>))},
+        {GPSBB_SK1(GPSBB_VARIANT_EV_FIXED, k_synth_ev_fixed), {}},
+    };
+#undef GPSBB_SK1
+#undef GPSBB_SK
+    static_assert(GPSBB_VARIANT_SYNTH == 1 && GPSBB_VARIANT_EV == 2 && GPSBB_VARIANT_EV_DENSE == 3 && GPSBB_VARIANT_PD_WIDE == 4 &&
+                      GPSBB_VARIANT_PD_NARROW == 5 && GPSBB_VARIANT_EV_FIXED == 6 && EV_STATE_LOG2_MAX == 2, "synth_kernel's table");
+    return k[variant][digest ? 1 : 0][g];
 }
 
 /* upload `bytes` from pageable `src` through the batch's pinned arena (grown at the start of a set-up) */
@@ -1734,7 +1740,13 @@ static int host_seed_run(gpsbb_batch *b, const TableSet &ts, hipStream_t stream)
     return GPSBB_OK;
 }
 
-static BatchDev batch_dev(const gpsbb_batch *b, const TableSet &ts)
+/* The launch plan of the batch's next run (skip: the measurement hook takes effect on it), or of any run as far as batch_dev reads it. */
+static LaunchPlan batch_launch_plan(const gpsbb_batch *b, bool skip = false)
+{
+    return plan_launch(b->plan, LaunchIn{cu_count(b->h->sm_count), b->want_digest, b->link.d_carry != nullptr, skip}, launch_opts());
+}
+
+static BatchDev batch_dev(const gpsbb_batch *b, const TableSet &ts, const LaunchPlan &lp)
 {
     const BatchPlan &pl = b->plan;
     const size_t set = (size_t)(&ts - b->sets);
@@ -1763,18 +1775,10 @@ static BatchDev batch_dev(const gpsbb_batch *b, const TableSet &ts)
     p.hazards = b->h->d_hz;
     p.digest = b->want_digest ? b->d_dig.p : nullptr;
     p.seed_order = b->d_seed_order.p;
-    p.seed_lanes = (int)b->img.h_seed_order.size();
+    p.seed_lanes = lp.seed_lanes;
     p.ev = pl.ev ? 1 : 0;
-    int ev_chunk = pl.ev_all_dense ? (int)GPSBB_KNOB_LONG("GPSBB_PD_CHUNK", PD_CHUNK) : (int)GPSBB_KNOB_LONG("GPSBB_EV_CHUNK", EV_CHUNK);
-    /* a batch too small to give every CU a workgroup's worth of chunks (the drop-in call's one block: 293 tiles) hands its tiles out
-     * in smaller chunks, down to one at a time: twice the workgroups, half the tiles each (0.116 -> 0.110 ms for the reference's
-     * block rendered into a registered buffer) */
-    const long cus = b->h->sm_count > 0 ? b->h->sm_count : 256;
-    while (ev_chunk > 1 && GPSBB_KNOB_LONG("GPSBB_SMALL_CHUNKS", 1) != 0 &&
-           (long)pl.nblocks * (((long)pl.ntiles + ev_chunk - 1) / ev_chunk) < cus * EV_WAVES)
-        ev_chunk--;
-    p.ev_chunk = ev_chunk < 1 ? 1 : ev_chunk;
-    p.pd_danger = (uint32_t)GPSBB_KNOB_LONG("GPSBB_PD_DANGER", 2u * PD_BAND); /* (larger: more lanes take the exact path; a test aid) */
+    p.ev_chunk = lp.ev_chunk;
+    p.pd_danger = lp.pd_danger;
     p.tile_x = ts.tile_x.p;
     p.tile_nav = ts.tile_nav.p;
     p.evc = b->d_evc.p;
@@ -1910,156 +1914,77 @@ static int launch_events(gpsbb_batch *b, hipEvent_t **ev)
     return GPSBB_OK;
 }
 
-/* The pre-pass of one run into table set `set`, on stream ss.  *ctr_reset: it zeroes the set's tile counters itself. */
-static int prepass_launch(gpsbb_batch *b, int set, const BatchDev &p, hipStream_t ss, bool *ctr_reset)
+/* The pre-pass of one run into table set `set`, on stream ss, as the launch plan says. */
+static int prepass_launch(gpsbb_batch *b, int set, const BatchDev &p, const LaunchPlan &lp, hipStream_t ss)
 {
     const BatchPlan &pl = b->plan;
     gpsbb *h = b->h;
     const TableSet &ts = b->sets[set];
-    const int lanes = (int)b->img.h_seed_order.size();
     const CarryEvents ce = {b->link.d_carry ? b->link.ev_prefix : nullptr, b->link.d_carry ? b->link.ev_fix : nullptr};
-    const int fix_wg = pl.chain_fix_seq ? 0 : pl.fix_wg;
-    *ctr_reset = false;
-    if (h->opt_skip_seed && b->run_count >= (unsigned)pl.nsets) {
-        /* measurement hook: time the synthesis kernel alone on tables already built */
-    } else if (pl.host_seed) {
+    if (lp.chain) {
+        /* the carrier chain by the row walks: over the seed order (rows for the model kernels), or over the chain order */
+        BatchDev pw = p;
+        if (lp.chain_order) {
+            pw.seed_order = b->d_chain_order.p;
+            pw.seed_lanes = lp.walk_lanes;
+        }
+        HIPCHK(h, walk_chain_launch(ss, pw, lp.carr_lanes, lp.pass_a, lp.pass_b, lp.fix_wg, ce));
+    }
+    switch (lp.prepass) {
+    case PREPASS_SKIP:
+        break;
+    case PREPASS_HOST: {
         /* the previous user of the pinned images (this batch's last run) has been copied out: its upload was
          * followed by the synthesis kernel, which that set's synth_done_ref covers */
         const TableSet &prev = b->sets[(set + pl.nsets - 1) % pl.nsets];
         if (prev.synth_pending)
             HIPCHK(h, hipEventSynchronize(prev.synth_done_ref));
-        const int rc = host_seed_run(b, ts, ss);
-        if (rc != GPSBB_OK)
-            return rc;
-    } else if (pl.ev && pl.laps) {
-        /* the lap-parallel pre-pass (gpsbb_laps.hip.h): plan, reference walks, scan, true walks, repair — the code chains
-         * first (nothing of theirs waits for another push), then the carriers: a stream's push starts from the exact phase the
-         * push before it left on the device, so its plan follows that push's repair kernel */
+        return host_seed_run(b, ts, ss);
+    }
+    case PREPASS_LAPS: {
+        /* plan, reference walks, scan, true walks, repair — the code chains first (nothing of theirs waits for another push), then
+         * the carriers: a stream's push starts from the exact phase the push before it left on the device, so its plan follows
+         * that push's repair kernel */
         const LapDev L = lap_dev(b, ts);
-        /* a batch that continues nothing (no stream carry: the drop-in call's block, resident batches): both kinds in one grid
-         * per step, five launches instead of ten — the chain of small launches IS the latency of a small batch's pre-pass (one
-         * block of the reference's geometry: 98 -> 50 us), and a big batch's two plan kernels (16 wavefronts each, 0.1 - 0.2 ms)
-         * run side by side.  A stream's pushes keep the kinds apart: their code chains wait for nobody, their carriers for the
-         * push before (GPSBB_LAP_MERGE=1, experiments build: merged there too). */
-        /* pass 2 writes the tile states in 32- / 16-byte pieces where the geometry has them (several tiles per lap: a code period is
-         * 1023 chips / (1.023e6 * delt) samples) — k_lap_pass2<., true>; at the reference's 2.6 MS/s a period is 2.5 tiles and the
-         * plain loop is the faster one */
-        const bool wide = GPSBB_KNOB_LONG("GPSBB_LAP_WIDE", pl.delt <= 1.0 / 8.0e6 ? 1 : 0) != 0;
-        const bool merged = !p.kph0 && (!ce.fix || GPSBB_KNOB_LONG("GPSBB_LAP_MERGE", 0) == 1) &&
-                            GPSBB_KNOB_LONG("GPSBB_LAP_MERGE", 0) != 2;
-        if (merged) {
+        if (!lp.lap_merged)
+            lap_chain_launch(ss, p, L, pl.nch, NCO_CODE, lap_pass2_kernel(NCO_CODE, lp.lap_wide, lp.granule));
+        if (lp.lap_fixed) {
+            /* no chain to walk: the plan kernel leaves the end states, the tile states are a closed form */
+            hipLaunchKernelGGL(k_lap_plan<NCO_CARR>, dim3(pl.nch), dim3(64), 0, ss, p, L);
+            hipLaunchKernelGGL(k_lap_fixed_tiles, dim3(pl.nblocks * pl.nch), dim3(256), 0, ss, p);
+        } else {
+            const int kind = lp.lap_merged ? -1 : NCO_CARR;
             HIPCHK(h, ce.wait_both(ss));
-            lap_chain_launch(ss, p, L, pl.nch, -1, lap_pass2_kernel(-1, wide, p.st_log2));
+            lap_chain_launch(ss, p, L, pl.nch, kind, lap_pass2_kernel(kind, lp.lap_wide, lp.granule));
             HIPCHK(h, ce.record_both(ss));
-        } else {
-            lap_chain_launch(ss, p, L, pl.nch, NCO_CODE, lap_pass2_kernel(NCO_CODE, wide, p.st_log2));
-            if (p.kph0) {
-                /* fixed-point carrier: no chain to walk; the plan kernel leaves the end states, the tile states are a closed form */
-                hipLaunchKernelGGL(k_lap_plan<NCO_CARR>, dim3(pl.nch), dim3(64), 0, ss, p, L);
-                hipLaunchKernelGGL(k_lap_fixed_tiles, dim3(pl.nblocks * pl.nch), dim3(256), 0, ss, p);
-            } else {
-                HIPCHK(h, ce.wait_both(ss));
-                lap_chain_launch(ss, p, L, pl.nch, NCO_CARR, lap_pass2_kernel(NCO_CARR, wide, p.st_log2));
-                HIPCHK(h, ce.record_both(ss));
-            }
         }
-        *ctr_reset = true; /* k_lap_plan zeroes the set's tile counters */
-    } else if (pl.ev) {
-        if (GPSBB_KNOB_SET("GPSBB_EV_KSEED")) { /* experiment: the one-kernel pre-pass */
-            hipLaunchKernelGGL(k_seed<true>, dim3((lanes + GPSBB_SEED_WG - 1) / GPSBB_SEED_WG), dim3(GPSBB_SEED_WG), 0, ss, p);
-        } else {
-            if (pl.chain_dev)
-                HIPCHK(h, walk_chain_launch(ss, p, pl.carr_lanes, !pl.chain_model, 2, fix_wg, ce));
-            else
-                hipLaunchKernelGGL(k_walk<0>, dim3((lanes + GPSBB_WALK_WG - 1) / GPSBB_WALK_WG), dim3(GPSBB_WALK_WG), 0, ss, p);
-            hipLaunchKernelGGL(k_tiles, dim3((1 + pl.nseg) * pl.nblocks * pl.nch), dim3(GPSBB_TILES_WG), 0, ss, p);
-            *ctr_reset = true; /* k_tiles zeroes the set's tile counters */
-        }
-    } else {
-        if (pl.chain_starts) {
-            /* the carrier chained on the device for the per-sample kernel: pass A, prefix, pass B without rows and the
-             * fix-up put the exact start phase of every block into its descriptor; k_seed then sees independent blocks */
-            BatchDev pc = p;
-            pc.seed_order = b->d_chain_order.p;
-            pc.seed_lanes = pl.chain_lanes;
-            HIPCHK(h, walk_chain_launch(ss, pc, pl.chain_lanes, true, 3, fix_wg, ce));
-        }
-        hipLaunchKernelGGL(k_seed<false>, dim3((lanes + GPSBB_SEED_WG - 1) / GPSBB_SEED_WG), dim3(GPSBB_SEED_WG), 0, ss, p);
+        break;
+    }
+    case PREPASS_WALKS:
+        if (!lp.chain)
+            hipLaunchKernelGGL(k_walk<0>, dim3((lp.seed_lanes + GPSBB_WALK_WG - 1) / GPSBB_WALK_WG), dim3(GPSBB_WALK_WG), 0, ss, p);
+        hipLaunchKernelGGL(k_tiles, dim3((1 + pl.nseg) * pl.nblocks * pl.nch), dim3(GPSBB_TILES_WG), 0, ss, p);
+        break;
+    case PREPASS_SEED: {
+        const dim3 grid((lp.seed_lanes + GPSBB_SEED_WG - 1) / GPSBB_SEED_WG);
+        if (lp.seed_ev)
+            hipLaunchKernelGGL(k_seed<true>, grid, dim3(GPSBB_SEED_WG), 0, ss, p);
+        else
+            hipLaunchKernelGGL(k_seed<false>, grid, dim3(GPSBB_SEED_WG), 0, ss, p);
+        break;
+    }
     }
     return GPSBB_OK;
 }
 
 /* The synthesis kernel of one run on stream sc, and the blocks' digests behind it where no variant leaves them itself. */
-static int synth_launch(gpsbb_batch *b, const BatchDev &p, hipStream_t sc, int16_t *d_iq)
+static int synth_launch(gpsbb_batch *b, const BatchDev &p, const LaunchPlan &lp, hipStream_t sc, int16_t *d_iq)
 {
-    const BatchPlan &pl = b->plan;
-    gpsbb *h = b->h;
-    bool digest_fused = false;
-    h->last_chain_dev = pl.chain_dev && !pl.chain_indep ? 1 : 0;
-    if (pl.ev) {
-        /* One workgroup of EV_WG lanes fits a CU (its LDS image takes ~140 - 156 KB).  Grid = the blocks' primaries, then the
-         * helpers (ev_pick_block: a helper joins one of the blocks that still have tiles to hand out, chosen when it starts):
-         * as many as can be useful when there are few blocks (never more workgroups per block than there are chunks of tiles
-         * per wavefront), else enough to keep every CU busy through the end of the launch — the last round of blocks and then
-         * what is left of it take the CUs twice over. */
-        const long wg_slots = (long)(h->sm_count > 0 ? h->sm_count : 256);
-        const long chunks = ((long)pl.ntiles + p.ev_chunk - 1) / p.ev_chunk;
-        const long max_useful = (chunks + EV_WAVES - 1) / EV_WAVES;
-        const long oversub = GPSBB_KNOB_LONG("GPSBB_EV_HELPERS", 2);
-        long helpers = (long)pl.nblocks * (max_useful - 1);
-        if (helpers > wg_slots * oversub)
-            helpers = wg_slots * oversub;
-        if (helpers < 0)
-            helpers = 0;
-        const dim3 grid((unsigned)(pl.nblocks + helpers));
-        if (pl.ev_all_dense && b->want_digest) {
-            if (pl.nch <= PD_WIDE_CHAN)
-                hipLaunchKernelGGL((k_synth_pd<true, true>), grid, dim3(EV_WG), sizeof(PdLds<true>) + EV_PICK_LDS, sc, p, d_iq);
-            else
-                hipLaunchKernelGGL((k_synth_pd<false, true>), grid, dim3(EV_WG), sizeof(PdLds<false>) + EV_PICK_LDS, sc, p, d_iq);
-            digest_fused = true;
-        } else if (pl.ev_all_dense && pl.nch <= PD_WIDE_CHAN)
-            hipLaunchKernelGGL(k_synth_pd<true>, grid, dim3(EV_WG), sizeof(PdLds<true>) + EV_PICK_LDS, sc, p, d_iq);
-        else if (pl.ev_all_dense)
-            hipLaunchKernelGGL(k_synth_pd<false>, grid, dim3(EV_WG), sizeof(PdLds<false>) + EV_PICK_LDS, sc, p, d_iq);
-        else if (pl.ev_dense)
-            hipLaunchKernelGGL(k_synth_ev_dense, grid, dim3(EV_WG), sizeof(EvLds) + EV_PICK_LDS, sc, p, d_iq);
-        else if (p.kph0)
-            hipLaunchKernelGGL(k_synth_ev_fixed, grid, dim3(EV_WG), sizeof(EvLdsLean) + EV_PICK_LDS, sc, p, d_iq);
-        else if (b->want_digest) {
-            hipLaunchKernelGGL(ev_kernel(p.st_log2, true), grid, dim3(EV_WG),
-                               sizeof(EvLdsLean) + EV_PICK_LDS, sc, p, d_iq);
-            digest_fused = true;
-        } else
-            hipLaunchKernelGGL(ev_kernel(p.st_log2, false), grid, dim3(EV_WG),
-                               sizeof(EvLdsLean) + EV_PICK_LDS, sc, p, d_iq);
-        h->last_kernel = 2;
-        /* (the same order as the launches above; a digest-fused instantiation is the same variant) */
-        h->last_variant = pl.ev_all_dense ? (pl.nch <= PD_WIDE_CHAN ? GPSBB_VARIANT_PD_WIDE : GPSBB_VARIANT_PD_NARROW)
-                          : (pl.ev_dense ? GPSBB_VARIANT_EV_DENSE : (p.kph0 ? GPSBB_VARIANT_EV_FIXED : GPSBB_VARIANT_EV));
-    } else {
-        h->last_kernel = 1;
-        h->last_variant = GPSBB_VARIANT_SYNTH;
-        /* Workgroups per block: enough of them to oversubscribe the chip ~3x (tiles are handed out
-         * dynamically in chunks, so the tail is short), never more than there are chunks; the per-block
-         * LDS tables (amplitude LUT, chips, nav words) are then built few times per block. */
-        const long wg_slots = (long)(h->sm_count > 0 ? h->sm_count : 256) * 2;
-        const long chunks = ((long)pl.ntiles + TILE_CHUNK - 1) / TILE_CHUNK;
-        const long max_useful = (chunks + WAVES_PER_WG - 1) / WAVES_PER_WG;
-        const long oversub = GPSBB_KNOB_LONG("GPSBB_OVERSUB", 12);
-        long want = (wg_slots * oversub + pl.nblocks - 1) / pl.nblocks;
-        want = want < 1 ? 1 : (want > max_useful ? max_useful : want);
-        const int gx = (int)want;
-        hipLaunchKernelGGL(k_synth, dim3(gx, pl.nblocks), dim3(TILE_THREADS), sizeof(SynthLds), sc, p, d_iq);
-    }
-    if (b->want_digest && !digest_fused) {
-        /* a synthesis kernel without a digesting variant: the blocks read back behind it, on its stream */
-        long chunks = (2048 + pl.nblocks - 1) / pl.nblocks;
-        const long max_chunks = ((long)pl.nsamp + 1023) / 1024;
-        chunks = chunks > max_chunks ? max_chunks : (chunks < 1 ? 1 : chunks);
-        hipLaunchKernelGGL(k_block_digest, dim3((unsigned)chunks, (unsigned)pl.nblocks), dim3(256), 0, sc, (const uint32_t *)d_iq, pl.nsamp, b->d_dig.p);
-    }
-    HIPCHK(h, hipGetLastError());
+    const SynthKernel &k = synth_kernel(lp.variant, lp.digest_fused, lp.granule);
+    hipLaunchKernelGGL(k.fn, dim3(lp.grid_x, lp.grid_y), dim3(lp.wg), k.lds, sc, p, d_iq);
+    if (lp.digest_gx)
+        hipLaunchKernelGGL(k_block_digest, dim3(lp.digest_gx, lp.digest_gy), dim3(256), 0, sc, (const uint32_t *)d_iq, b->plan.nsamp, b->d_dig.p);
+    HIPCHK(b->h, hipGetLastError());
     return GPSBB_OK;
 }
 
@@ -2073,7 +1998,8 @@ static int batch_launch(gpsbb_batch *b, int16_t *d_iq)
     b->fix.epoch++; /* a number no earlier launch of this batch handed to k_chain_fix_par */
     if (b->want_digest)
         HIPCHK(h, (hipError_t)b->d_dig.reserve((size_t)pl.nblocks));
-    const BatchDev p = batch_dev(b, ts);
+    const LaunchPlan lp = batch_launch_plan(b, h->opt_skip_seed && b->run_count >= (unsigned)pl.nsets);
+    const BatchDev p = batch_dev(b, ts, lp);
     const bool timed = !b->one_stream;
     hipEvent_t *ev = nullptr;
     int rc = launch_events(b, &ev);
@@ -2093,14 +2019,16 @@ static int batch_launch(gpsbb_batch *b, int16_t *d_iq)
         HIPCHK(h, hipStreamWaitEvent(ss, ts.synth_done_ref, 0));
     if (timed)
         HIPCHK(h, hipEventRecord(ev[0], ss));
-    bool ctr_reset_by_prepass = false;
-    rc = prepass_launch(b, set, p, ss, &ctr_reset_by_prepass);
+    rc = prepass_launch(b, set, p, lp, ss);
     if (rc != GPSBB_OK)
         return rc;
     HIPCHK(h, hipGetLastError());
     if (timed)
         HIPCHK(h, hipEventRecord(ev[1], ss));
-    h->last_prepass = pl.host_seed ? 2 : (pl.ev && pl.laps ? 3 : 1);
+    h->last_prepass = lp.info_prepass;
+    h->last_kernel = lp.last_kernel;
+    h->last_variant = lp.variant;
+    h->last_chain_dev = lp.last_chain_dev;
     PUSH_MARK("l_pre");
 
     /* off by default: +2 % on a stream of pushes, but overlapping kernels make the per-launch time (the roofline figure)
@@ -2117,13 +2045,13 @@ static int batch_launch(gpsbb_batch *b, int16_t *d_iq)
     b->last_cs = sc;
     if (sc != ss)
         HIPCHK(h, hipStreamWaitEvent(sc, ev[1], 0));
-    if (!ctr_reset_by_prepass)
+    if (!lp.ctr_reset)
         HIPCHK(h, hipMemsetAsync(p.tile_ctr, 0, ((size_t)pl.nblocks + 1) * sizeof(int32_t), sc));
     if (timed)
         HIPCHK(h, hipEventRecord(ev[2], sc));
     if (b->want_digest)
         HIPCHK(h, hipMemsetAsync(b->d_dig.p, 0, (size_t)pl.nblocks * sizeof(unsigned long long), sc));
-    rc = synth_launch(b, p, sc, d_iq);
+    rc = synth_launch(b, p, lp, sc, d_iq);
     if (rc != GPSBB_OK)
         return rc;
     if (timed)
@@ -2312,7 +2240,7 @@ extern "C" int gpsbb_fill_ceiling(gpsbb_t *h, void *d_dst, size_t bytes, int ite
     HIPCHK(h, hipEventCreate(&e0));
     HIPCHK(h, hipEventCreate(&e1));
     const size_t n16 = bytes / 16;
-    const int grid = h->sm_count > 0 ? h->sm_count * 8 : 2048;
+    const int grid = (int)cu_count(h->sm_count) * 8;
     hipLaunchKernelGGL(k_fill_ceiling, dim3(grid), dim3(256), 0, h->s_compute, (uint4 *)d_dst, n16, 1u);
     HIPCHK(h, hipEventRecord(e0, h->s_compute));
     for (int i = 0; i < iters; i++)
@@ -3052,8 +2980,8 @@ static int batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, 
     a.n_exact = b->d_ds.p + nsum;
     a.ctr = b->d_ds_ctr.p;
     /* ---- launch ---- */
-    ds_geometry(pl.nblocks, pl.ntiles, seg_tiles, h->sm_count > 0 ? h->sm_count : 256, a.chunk, a.wgs_per_block);
-    const BatchDev p = batch_dev(b, b->sets[b->last_set]);
+    ds_geometry(pl.nblocks, pl.ntiles, seg_tiles, cu_count(h->sm_count), a.chunk, a.wgs_per_block);
+    const BatchDev p = batch_dev(b, b->sets[b->last_set], batch_launch_plan(b));
 #ifdef GPSBB_EXPERIMENTS
     for (auto &e : b->ds_ev)
         if (!e)
@@ -4405,7 +4333,7 @@ extern "C" int gpsbb_test_model_err(gpsbb_batch_t *b, double *maxima, unsigned l
     const int rc = gpsbb_sync(h);
     if (rc != GPSBB_OK)
         return rc;
-    const BatchDev p = batch_dev(b, b->sets[b->last_set]);
+    const BatchDev p = batch_dev(b, b->sets[b->last_set], batch_launch_plan(b));
     double *d_mx = nullptr;
     unsigned long long *d_cnt = nullptr;
     const size_t mx_bytes = sizeof(double) * GPSBB_MAX_CHAN * ME_NQ, cnt_bytes = sizeof(unsigned long long) * GPSBB_MAX_CHAN * MEC_NQ;
@@ -4494,6 +4422,42 @@ extern "C" int gpsbb_test_plan(const gpsbb_chan_t *ch, int nblocks, int nch, dou
     return GPSBB_OK;
 }
 
+/* plan_launch behind plan_batch: the launch plan's fields in LaunchPlan's order, the number of kernels, then the kernels in order */
+extern "C" int gpsbb_test_launch_plan(const gpsbb_chan_t *ch, int nblocks, int nch, double delt, int nsamp, unsigned flags, const int opt[5],
+                                      int carry, const int *carry_prn, double *carry_phase, const int *fixed_prev_prn,
+                                      const uint32_t *fixed_prev_phase, int cus, int want_digest, int skip,
+                                      long long out[GPSBB_TEST_LAUNCH_NQ])
+{
+    if (!opt || !out)
+        return GPSBB_E_BADARG;
+    static ChainCarryDev none;
+    StreamLink lk;
+    lk.d_carry = carry ? &none : nullptr;
+    lk.carry_prn = carry_prn;
+    lk.carry_phase = carry_phase;
+    lk.fixed_prev_prn = fixed_prev_prn;
+    lk.fixed_prev_phase = fixed_prev_phase;
+    BatchPlan pl;
+    PlanImages img;
+    const int rc = plan_batch(pl, img, PlanIn{ch, nblocks, nch, delt, nsamp, flags}, plan_opts(opt[0], opt[1], opt[2] != 0, opt[3], opt[4]), lk);
+    if (rc != GPSBB_OK)
+        return rc;
+    const LaunchPlan lp = plan_launch(pl, LaunchIn{cu_count(cus), want_digest != 0, carry != 0, skip != 0}, launch_opts());
+    const std::vector<LaunchRec> ks = launch_list(pl, lp);
+    const long long v[GPSBB_TEST_LAUNCH_NF + 1] = {
+        lp.prepass, lp.lap_wide, lp.lap_merged, lp.lap_fixed, lp.chain, lp.pass_a, lp.pass_b, lp.fix_wg, lp.carr_lanes, lp.walk_lanes,
+        lp.chain_order, lp.seed_ev, lp.seed_lanes, lp.ctr_reset, lp.info_prepass, lp.variant, lp.digest_fused, lp.granule, lp.ev_chunk,
+        lp.pd_danger, lp.helpers, lp.grid_x, lp.grid_y, lp.wg, lp.lds, lp.digest_gx, lp.digest_gy, lp.last_kernel, lp.last_chain_dev,
+        (long long)ks.size()};
+    memset(out, 0, GPSBB_TEST_LAUNCH_NQ * sizeof out[0]);
+    memcpy(out, v, sizeof v);
+    for (size_t k = 0; k < ks.size() && k < GPSBB_TEST_LAUNCH_KERNELS; k++) {
+        const long long r[5] = {ks[k].id, ks[k].gx, ks[k].gy, ks[k].wg, ks[k].lds};
+        memcpy(out + GPSBB_TEST_LAUNCH_NF + 1 + 5 * k, r, sizeof r);
+    }
+    return GPSBB_OK;
+}
+
 /* plan_push_side on its own: the side (PUSH_CHAIN_*), and whether the decision took the plan's first step */
 extern "C" int gpsbb_test_push_side(const gpsbb_chan_t *ch, int nblocks, int nch, double delt, int nsamp, unsigned flags, const int opt[5],
                                     int out[2])
@@ -4542,7 +4506,7 @@ extern "C" int gpsbb_test_table_digest(gpsbb_batch_t *b, unsigned long long out[
     const int rc = gpsbb_sync(h);
     if (rc != GPSBB_OK)
         return rc;
-    const BatchDev p = batch_dev(b, b->sets[b->last_set]);
+    const BatchDev p = batch_dev(b, b->sets[b->last_set], batch_launch_plan(b));
     auto mix = [](unsigned long long z) { z ^= z >> 31; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 29; return z; };
     const int nst = pl.nstates;
     const size_t nx = (size_t)pl.nblocks * 2 * pl.nch * (size_t)nst, nn = (size_t)pl.nblocks * pl.nch * (size_t)nst, ne = (size_t)pl.nblocks * pl.nch;

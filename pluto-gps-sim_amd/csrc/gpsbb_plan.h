@@ -1,11 +1,14 @@
 /*
  * gpsbb_plan.h — how a batch is planned: everything batch set-up decides from the descriptors, the handle's options and a stream's
  * carry, as one pure host function (plan_batch) and the plain structs it fills; ahead of it for a ring's push, on which side
- * the push chains its carrier (plan_push_side); and what gpsbb_chain_carrier decides, the chain alone (plan_chain_only).  No HIP call,
- * neither the handle nor the batch: gpsbb.hip stages what the plan says (batch_setup) and launches from it; gpsbb_test_plan,
- * gpsbb_test_push_side and gpsbb_test_chain_plan run them without a GPU.
+ * the push chains its carrier (plan_push_side); what gpsbb_chain_carrier decides, the chain alone (plan_chain_only); and what one run
+ * of a planned batch launches (plan_launch: which pre-pass in which form, which synthesis kernel over which grid with how much LDS,
+ * what the handle reports afterwards).  No HIP call, neither the handle nor the batch: gpsbb.hip stages what the plan says
+ * (batch_setup) and launches from it (batch_launch); gpsbb_test_plan, gpsbb_test_push_side, gpsbb_test_chain_plan and
+ * gpsbb_test_launch_plan run them without a GPU.
  * Included by gpsbb.hip behind the descriptor checks and kernel plans it calls (chan_ok, ev_plan, lap_eligible, lap_bound, lap_unit,
- * row_bound, CarrDrift, channel_threads) and the constants it reads (NSETS, CHAIN_*); not a translation unit of its own.
+ * row_bound, CarrDrift, channel_threads) and the constants it reads (NSETS, CHAIN_*, the kernels' workgroup sizes and LDS images); not
+ * a translation unit of its own.
  */
 #ifndef GPSBB_PLAN_H
 #define GPSBB_PLAN_H
@@ -35,6 +38,7 @@ struct BatchPlan {
     /* sizes and lanes */
     int nsets = 2;               /* table sets in use: run k works on set k % nsets */
     uint64_t total_rows = 0;
+    int seed_lanes = 0;          /* lanes of the seed plan (h_seed_order): what k_seed / k_walk are launched over */
     int carr_lanes = 0;          /* lanes of the seed plan that walk carrier chains (they come first) */
     int chain_lanes = 0;         /* chain_starts: lanes of the chain order */
     uint32_t cont0_mask = 0;     /* a stream's push: which channels of its first block go on from the push before */
@@ -556,6 +560,7 @@ static void plan_seed_order(BatchPlan &pl, PlanImages &img, const PlanOpts &o)
 {
     std::vector<int32_t> &order = img.h_seed_order;
     order.clear();
+    pl.seed_lanes = 0;
     if (pl.laps) {
         pl.carr_lanes = 0;
         return;
@@ -588,6 +593,7 @@ static void plan_seed_order(BatchPlan &pl, PlanImages &img, const PlanOpts &o)
         waves_of(order, carr.data() + n8 + n16, n32, 32, (int32_t)nbc);
         waves_of(order, carr.data() + n8 + n16 + n32, nbc - n8 - n16 - n32, 64, (int32_t)nbc);
     }
+    pl.seed_lanes = (int)order.size();
     PUSH_MARK("order");
     if (pl.chain_starts) {
         /* the chain's two walks take the carrier chains alone, in lockstep: by direction, then by |f_carr| (nseg = 1
@@ -707,6 +713,263 @@ static int plan_chain_only(ChainOnlyPlan &cp, PlanImages &img, const PlanIn &in,
         cp.pieces.push_back(pc);
     }
     return GPSBB_OK;
+}
+
+/* ---- plan_launch: what one run of a batch launches ------------------------------------------------------ */
+
+/* The CUs a launch is sized for: the device's, or an MI355X's where the handle could not ask. */
+static inline long cu_count(int sm_count) { return sm_count > 0 ? sm_count : 256; }
+
+/* What a run knows besides the batch's plan. */
+struct LaunchIn {
+    long cus = 256;           /* cu_count() */
+    bool want_digest = false; /* this run also leaves every block's digest */
+    bool carry = false;       /* the batch continues a stream's push (StreamLink::d_carry) */
+    bool skip = false;        /* measurement hook (GPSBB_OPT_SKIP_SEED): this run renders from the tables an earlier run left */
+};
+
+/* The measurement knobs the launch path consults (experiments build: from the environment), read once. */
+struct LaunchOpts {
+    int ev_chunk = EV_CHUNK, pd_chunk = PD_CHUNK; /* tiles a wavefront of the model kernels takes at a time */
+    bool small_chunks = true;                     /* ... fewer for a batch too small to fill the CUs */
+    uint32_t pd_danger = 2u * PD_BAND;            /* (larger: more lanes take the exact path; a test aid) */
+    bool lap_wide_set = false, lap_wide = false;  /* k_lap_pass2's wide stores: as asked, else by the sample rate */
+    long lap_merge = 0;                           /* 1: both kinds of chain in one grid also for a stream's push; 2: never */
+    bool ev_kseed = false;                        /* experiment: the one-kernel pre-pass of the model kernels */
+    long ev_helpers = 2, oversub = 12;            /* helper workgroups per CU (model kernels), workgroups per slot (k_synth) */
+};
+
+static LaunchOpts launch_opts()
+{
+    LaunchOpts o;
+    o.ev_chunk = (int)GPSBB_KNOB_LONG("GPSBB_EV_CHUNK", EV_CHUNK);
+    o.pd_chunk = (int)GPSBB_KNOB_LONG("GPSBB_PD_CHUNK", PD_CHUNK);
+    o.small_chunks = GPSBB_KNOB_LONG("GPSBB_SMALL_CHUNKS", 1) != 0;
+    o.pd_danger = (uint32_t)GPSBB_KNOB_LONG("GPSBB_PD_DANGER", 2u * PD_BAND);
+    o.lap_wide_set = GPSBB_KNOB_SET("GPSBB_LAP_WIDE");
+    o.lap_wide = GPSBB_KNOB_LONG("GPSBB_LAP_WIDE", 0) != 0;
+    o.lap_merge = GPSBB_KNOB_LONG("GPSBB_LAP_MERGE", 0);
+    o.ev_kseed = GPSBB_KNOB_SET("GPSBB_EV_KSEED");
+    o.ev_helpers = GPSBB_KNOB_LONG("GPSBB_EV_HELPERS", 2);
+    o.oversub = GPSBB_KNOB_LONG("GPSBB_OVERSUB", 12);
+    return o;
+}
+
+enum PrepassKind {
+    PREPASS_SKIP,  /* none: the tables are there */
+    PREPASS_HOST,  /* host threads build the tables and upload them */
+    PREPASS_LAPS,  /* lap-parallel (gpsbb_laps.hip.h) */
+    PREPASS_WALKS, /* the row walks for the model kernels: k_walk<0>, or the chain's walks, then k_tiles */
+    PREPASS_SEED   /* k_seed: behind a start-phase chain (the per-sample kernel, chain_starts), or alone */
+};
+
+/* Dynamic LDS of a synthesis kernel, by GPSBB_VARIANT_*: one workgroup of the model kernels fits a CU (140 - 156 KB) */
+static constexpr int synth_lds(int variant)
+{
+    return variant == GPSBB_VARIANT_SYNTH      ? (int)sizeof(SynthLds)
+           : variant == GPSBB_VARIANT_EV_DENSE ? (int)sizeof(EvLds) + EV_PICK_LDS
+           : variant == GPSBB_VARIANT_PD_WIDE  ? (int)sizeof(PdLds<true>) + EV_PICK_LDS
+           : variant == GPSBB_VARIANT_PD_NARROW ? (int)sizeof(PdLds<false>) + EV_PICK_LDS
+                                                : (int)sizeof(EvLdsLean) + EV_PICK_LDS;
+}
+
+/* Everything one run decides: which pre-pass in which form, which synthesis kernel over which grid, what the handle reports
+ * afterwards.  plan_launch fills it without a HIP call; prepass_launch and synth_launch only read it. */
+struct LaunchPlan {
+    PrepassKind prepass = PREPASS_SKIP;
+    /* PREPASS_LAPS */
+    bool lap_wide = false;   /* pass 2 writes the tile states in 32- / 16-byte pieces (k_lap_pass2<., true>) */
+    bool lap_merged = false; /* both kinds of chain in one grid per step: five launches instead of ten */
+    bool lap_fixed = false;  /* the accumulator's carrier: no chain to walk, k_lap_plan<NCO_CARR> and k_lap_fixed_tiles */
+    /* PREPASS_WALKS, PREPASS_SEED: walk_chain_launch's arguments */
+    bool chain = false;       /* the carrier chain's walks run */
+    bool pass_a = false;      /* ... with pass A and the prefix (else from the host's drift model) */
+    int pass_b = 0;           /* k_walk<2> leaves rows, k_walk<3> the blocks' start phases only */
+    int fix_wg = 0;           /* k_chain_fix_par's workgroup; 0: k_chain_fix, the blocks in order */
+    int carr_lanes = 0;       /* pass A's lanes */
+    int walk_lanes = 0;       /* pass B's lanes */
+    bool chain_order = false; /* the walks take the chain order (BatchPlan::chain_lanes), not the seed order */
+    bool seed_ev = false;     /* PREPASS_SEED: k_seed<true> */
+    int seed_lanes = 0;       /* BatchDev::seed_lanes: lanes of k_seed and k_walk<0> */
+    bool ctr_reset = false;   /* the pre-pass zeroes the set's tile counters (k_lap_plan, k_tiles); else a memset does */
+    int info_prepass = 1;     /* GPSBB_INFO_PREPASS */
+    /* synthesis */
+    int variant = 0;           /* GPSBB_VARIANT_*: GPSBB_INFO_LAST_VARIANT */
+    bool digest_fused = false; /* the kernel leaves the blocks' digests itself */
+    int granule = 0;           /* log2 of the tiles per exact state (BatchPlan::st_log2): k_synth_ev's instance */
+    int ev_chunk = 1;
+    uint32_t pd_danger = 0;
+    long helpers = 0;          /* model kernels: workgroups beyond one per block */
+    unsigned grid_x = 0, grid_y = 1;
+    int wg = 0, lds = 0;
+    unsigned digest_gx = 0, digest_gy = 0; /* k_block_digest behind the kernel; 0: none */
+    int last_kernel = 0, last_chain_dev = 0; /* GPSBB_INFO_LAST_KERNEL, _CHAIN_ON_DEVICE */
+};
+
+static LaunchPlan plan_launch(const BatchPlan &pl, const LaunchIn &in, const LaunchOpts &o)
+{
+    LaunchPlan lp;
+    const bool fixed = (pl.flags & GPSBB_FIXED_CARRIER) != 0;
+    lp.seed_lanes = pl.seed_lanes;
+    lp.info_prepass = pl.host_seed ? 2 : (pl.ev && pl.laps ? 3 : 1);
+    if (in.skip) {
+        lp.prepass = PREPASS_SKIP;
+    } else if (pl.host_seed) {
+        lp.prepass = PREPASS_HOST;
+    } else if (pl.ev && pl.laps) {
+        /* A batch that continues nothing (no stream carry: the drop-in call's block, resident batches): both kinds in one grid per
+         * step — the chain of small launches IS the latency of a small batch's pre-pass (one block of the reference's geometry:
+         * 98 -> 50 us), and a big batch's two plan kernels (16 wavefronts each, 0.1 - 0.2 ms) run side by side.  A stream's pushes
+         * keep the kinds apart: their code chains wait for nobody, their carriers for the push before.
+         * Wide stores where the geometry has several tiles per lap (a code period is 1023 chips / (1.023e6 * delt) samples); at the
+         * reference's 2.6 MS/s a period is 2.5 tiles and the plain loop is the faster one. */
+        lp.prepass = PREPASS_LAPS;
+        lp.lap_wide = o.lap_wide_set ? o.lap_wide : pl.delt <= 1.0 / 8.0e6;
+        lp.lap_merged = !fixed && (!in.carry || o.lap_merge == 1) && o.lap_merge != 2;
+        lp.lap_fixed = fixed;
+        lp.ctr_reset = true;
+    } else if (pl.ev && !o.ev_kseed) {
+        lp.prepass = PREPASS_WALKS;
+        lp.ctr_reset = true;
+        if (pl.chain_dev) { /* (else k_walk<0> over the seed order) */
+            lp.chain = true;
+            lp.pass_a = !pl.chain_model;
+            lp.pass_b = 2;
+            lp.carr_lanes = pl.carr_lanes;
+            lp.walk_lanes = pl.seed_lanes;
+        }
+    } else {
+        lp.prepass = PREPASS_SEED;
+        lp.seed_ev = pl.ev;
+        if (!pl.ev && pl.chain_starts) {
+            /* the carrier chained on the device for the per-sample kernel: pass A, prefix, pass B without rows and the fix-up put
+             * the exact start phase of every block into its descriptor; k_seed then sees independent blocks */
+            lp.chain = lp.chain_order = lp.pass_a = true;
+            lp.pass_b = 3;
+            lp.carr_lanes = lp.walk_lanes = pl.chain_lanes;
+        }
+    }
+    if (lp.chain) /* k_chain_fix_par in workgroups of fix_wg lanes, or (0) k_chain_fix, the blocks in order */
+        lp.fix_wg = pl.chain_fix_seq ? 0 : pl.fix_wg;
+
+    lp.last_chain_dev = pl.chain_dev && !pl.chain_indep ? 1 : 0;
+    lp.granule = pl.st_log2;
+    lp.pd_danger = o.pd_danger;
+    /* a batch too small to give every CU a workgroup's worth of chunks (the drop-in call's one block: 293 tiles) hands its tiles out
+     * in smaller chunks, down to one at a time: twice the workgroups, half the tiles each (0.116 -> 0.110 ms for the reference's
+     * block rendered into a registered buffer) */
+    int ev_chunk = pl.ev_all_dense ? o.pd_chunk : o.ev_chunk;
+    while (ev_chunk > 1 && o.small_chunks && (long)pl.nblocks * (((long)pl.ntiles + ev_chunk - 1) / ev_chunk) < in.cus * EV_WAVES)
+        ev_chunk--;
+    lp.ev_chunk = ev_chunk < 1 ? 1 : ev_chunk;
+    if (pl.ev) {
+        /* Grid = the blocks' primaries, then the helpers (ev_pick_block: a helper joins one of the blocks that still have tiles to
+         * hand out, chosen when it starts): as many as can be useful when there are few blocks (never more workgroups per block than
+         * there are chunks of tiles per wavefront), else enough to keep every CU busy through the end of the launch — the last round
+         * of blocks and then what is left of it take the CUs twice over. */
+        lp.variant = pl.ev_all_dense ? (pl.nch <= PD_WIDE_CHAN ? GPSBB_VARIANT_PD_WIDE : GPSBB_VARIANT_PD_NARROW)
+                                     : (pl.ev_dense ? GPSBB_VARIANT_EV_DENSE : (fixed ? GPSBB_VARIANT_EV_FIXED : GPSBB_VARIANT_EV));
+        lp.last_kernel = 2;
+        lp.digest_fused = in.want_digest && (pl.ev_all_dense || lp.variant == GPSBB_VARIANT_EV);
+        const long chunks = ((long)pl.ntiles + lp.ev_chunk - 1) / lp.ev_chunk;
+        const long max_useful = (chunks + EV_WAVES - 1) / EV_WAVES;
+        lp.helpers = std::max(0L, std::min((long)pl.nblocks * (max_useful - 1), in.cus * o.ev_helpers));
+        lp.grid_x = (unsigned)(pl.nblocks + lp.helpers);
+        lp.wg = EV_WG;
+    } else {
+        /* Workgroups per block: enough of them to oversubscribe the chip ~3x (tiles are handed out dynamically in chunks, so the
+         * tail is short), never more than there are chunks; the per-block LDS tables (amplitude LUT, chips, nav words) are then
+         * built few times per block. */
+        lp.variant = GPSBB_VARIANT_SYNTH;
+        lp.last_kernel = 1;
+        const long chunks = ((long)pl.ntiles + TILE_CHUNK - 1) / TILE_CHUNK;
+        const long max_useful = (chunks + WAVES_PER_WG - 1) / WAVES_PER_WG;
+        const long want = (in.cus * 2 * o.oversub + pl.nblocks - 1) / pl.nblocks;
+        lp.grid_x = (unsigned)(int)(want < 1 ? 1 : (want > max_useful ? max_useful : want));
+        lp.grid_y = (unsigned)pl.nblocks;
+        lp.wg = TILE_THREADS;
+    }
+    lp.lds = synth_lds(lp.variant);
+    if (in.want_digest && !lp.digest_fused) {
+        /* a synthesis kernel without a digesting variant: the blocks read back behind it, on its stream */
+        const long max_chunks = ((long)pl.nsamp + 1023) / 1024;
+        const long chunks = (2048 + pl.nblocks - 1) / pl.nblocks;
+        lp.digest_gx = (unsigned)(chunks > max_chunks ? max_chunks : (chunks < 1 ? 1 : chunks));
+        lp.digest_gy = (unsigned)pl.nblocks;
+    }
+    return lp;
+}
+
+/* The kernels of a run by name, for whoever asks what a plan launches (gpsbb_test_launch_plan): a family, and from bit 8 up the
+ * instance — the lap kernels' kind (NCO_CODE, NCO_CARR, 2: both in one grid; k_lap_pass2 also wide << 2 and the granule << 3), k_walk's
+ * pass, k_chain_fix_par's workgroup, k_seed<true> 1, the synthesis kernels' granule and digest << 2. */
+enum LaunchKernel {
+    LK_LAP_PLAN = 1, LK_LAP_PASS1, LK_LAP_SCAN, LK_LAP_PASS2, LK_LAP_REPAIR, LK_LAP_FIXED_TILES, LK_WALK, LK_CHAIN_PREFIX, LK_CHAIN_FIX,
+    LK_CHAIN_FIX_PAR, LK_TILES, LK_SEED, LK_BLOCK_DIGEST,
+    LK_SYNTH0 = 100 /* + GPSBB_VARIANT_* */
+};
+struct LaunchRec {
+    int id;
+    unsigned gx, gy;
+    int wg, lds;
+};
+
+/* What prepass_launch and synth_launch (with lap_chain_launch and walk_chain_launch) put on their streams for this plan, in order. */
+[[maybe_unused]] static std::vector<LaunchRec> launch_list(const BatchPlan &pl, const LaunchPlan &lp)
+{
+    std::vector<LaunchRec> v;
+    auto add = [&v](int family, int inst, unsigned gx, unsigned gy, int wg, int lds) { v.push_back(LaunchRec{family | inst << 8, gx, gy, wg, lds}); };
+    const unsigned nch = (unsigned)pl.nch, nbc = (unsigned)pl.nblocks * nch;
+    auto laps = [&](int kind) {
+        unsigned chunks = 0;
+        for (int k = 0; k < 2; k++)
+            if (kind == k || kind == 2)
+                chunks += pl.lap_chunk0[k][nch] - pl.lap_chunk0[k][0];
+        const unsigned per_chan = kind == 2 ? 2 * nch : nch;
+        add(LK_LAP_PLAN, kind, per_chan, 1, 64, 0);
+        add(LK_LAP_PASS1, kind, chunks, 1, LAP_WG, 0);
+        add(LK_LAP_SCAN, kind, per_chan, 1, 64, 0);
+        add(LK_LAP_PASS2, kind | (lp.lap_wide ? 4 : 0) | lp.granule << 3, chunks, 1, LAP_WG, 0);
+        add(LK_LAP_REPAIR, kind, per_chan, 1, 64, 0);
+    };
+    if (lp.chain) {
+        if (lp.pass_a) {
+            add(LK_WALK, 1, (unsigned)(lp.carr_lanes + GPSBB_WALK_WG - 1) / GPSBB_WALK_WG, 1, GPSBB_WALK_WG, 0);
+            add(LK_CHAIN_PREFIX, 0, nch, 1, PREFIX_WG, 0);
+        }
+        add(LK_WALK, lp.pass_b, (unsigned)(lp.walk_lanes + GPSBB_WALK_WG - 1) / GPSBB_WALK_WG, 1, GPSBB_WALK_WG, 0);
+        if (lp.fix_wg == 0)
+            add(LK_CHAIN_FIX, 0, 1, 1, 64, 0);
+        else
+            add(LK_CHAIN_FIX_PAR, lp.fix_wg, nch, (unsigned)pl.fix_chunks, lp.fix_wg, 0);
+    }
+    switch (lp.prepass) {
+    case PREPASS_SKIP:
+    case PREPASS_HOST:
+        break;
+    case PREPASS_LAPS:
+        if (!lp.lap_merged)
+            laps(NCO_CODE);
+        if (lp.lap_fixed) {
+            add(LK_LAP_PLAN, NCO_CARR, nch, 1, 64, 0);
+            add(LK_LAP_FIXED_TILES, 0, nbc, 1, 256, 0);
+        } else {
+            laps(lp.lap_merged ? 2 : NCO_CARR);
+        }
+        break;
+    case PREPASS_WALKS:
+        if (!lp.chain)
+            add(LK_WALK, 0, (unsigned)(lp.seed_lanes + GPSBB_WALK_WG - 1) / GPSBB_WALK_WG, 1, GPSBB_WALK_WG, 0);
+        add(LK_TILES, 0, (1 + (unsigned)pl.nseg) * nbc, 1, GPSBB_TILES_WG, 0);
+        break;
+    case PREPASS_SEED:
+        add(LK_SEED, lp.seed_ev ? 1 : 0, (unsigned)(lp.seed_lanes + GPSBB_SEED_WG - 1) / GPSBB_SEED_WG, 1, GPSBB_SEED_WG, 0);
+        break;
+    }
+    add(LK_SYNTH0 + lp.variant, lp.granule | (lp.digest_fused ? 4 : 0), lp.grid_x, lp.grid_y, lp.wg, lp.lds);
+    if (lp.digest_gx)
+        add(LK_BLOCK_DIGEST, 0, lp.digest_gx, lp.digest_gy, 256, 0);
+    return v;
 }
 
 #endif

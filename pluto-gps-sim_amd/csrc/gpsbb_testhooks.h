@@ -46,6 +46,19 @@ struct gpsbb_chan;
 int gpsbb_test_plan(const struct gpsbb_chan *ch, int nblocks, int nch, double delt, int nsamp, unsigned flags, const int opt[5],
                     int carry, const int *carry_prn, double *carry_phase, const int *fixed_prev_prn,
                     const uint32_t *fixed_prev_phase, unsigned long long out[GPSBB_TEST_PLAN_NQ]);
+/* plan_launch (gpsbb_plan.h) behind plan_batch on the same arguments: what one run of that batch would launch on a device of `cus`
+ * CUs (0: unknown), with or without the blocks' digests, skip: as a run GPSBB_OPT_SKIP_SEED leaves without its pre-pass.  out: the
+ * GPSBB_TEST_LAUNCH_NF fields of LaunchPlan in its order (prepass kind, lap_wide, lap_merged, lap_fixed, chain, pass_a, pass_b, fix_wg,
+ * carr_lanes, walk_lanes, chain_order, seed_ev, seed_lanes, ctr_reset, info_prepass, variant, digest_fused, granule, ev_chunk,
+ * pd_danger, helpers, grid_x, grid_y, wg, lds, digest_gx, digest_gy, last_kernel, last_chain_dev), the number of kernels, then per
+ * kernel in launch order (at most GPSBB_TEST_LAUNCH_KERNELS) its id (LaunchKernel: family + 256 * instance), grid x, grid y,
+ * workgroup, dynamic LDS bytes.  Returns GPSBB_OK or the error batch set-up would return. */
+#define GPSBB_TEST_LAUNCH_NF 29
+#define GPSBB_TEST_LAUNCH_KERNELS 16
+#define GPSBB_TEST_LAUNCH_NQ (GPSBB_TEST_LAUNCH_NF + 1 + 5 * GPSBB_TEST_LAUNCH_KERNELS)
+int gpsbb_test_launch_plan(const struct gpsbb_chan *ch, int nblocks, int nch, double delt, int nsamp, unsigned flags, const int opt[5],
+                           int carry, const int *carry_prn, double *carry_phase, const int *fixed_prev_prn,
+                           const uint32_t *fixed_prev_phase, int cus, int want_digest, int skip, long long out[GPSBB_TEST_LAUNCH_NQ]);
 /* plan_push_side (gpsbb_plan.h) on the descriptors of one push of a ring with these flags: on which side gpsbb_stream_push would
  * chain the IEEE carrier.  opt: as above.  out[0]: 0 not at all (no GPSBB_CHAIN_CARRIER, or the accumulator), 1 on host threads,
  * 2 on the device; out[1]: the decision ran plan_begin (its result is handed on to set-up where the side is the device).
