@@ -196,6 +196,32 @@ class AcqCfg(C.Structure):
 assert ACQ_ROW_DTYPE.itemsize == 32 and C.sizeof(AcqCfg) == 288
 
 
+# blind tracking (include/gpsbb.h gpsbb_device_track): a carrier and a code loop per channel, epoch by epoch
+TRK_LEN, TRK_MAX_CH = 1023 << 32, 32
+TRK_STATE_DTYPE = np.dtype([("prn", "<i4"), ("epoch", "<i4"), ("n0", "<i8"), ("carr_phase", "<u4"), ("_pad", "<u4"), ("carr_int", "<i8"),
+                            ("carr_step", "<i8"), ("code_phase", "<u8"), ("code_int", "<i8"), ("code_adj", "<i8"), ("prev_i", "<i8"),
+                            ("prev_q", "<i8")])
+TRK_EPOCH_DTYPE = np.dtype([("n0", "<i8"), ("N", "<i4"), ("q", "<i4"), ("e_i", "<i8"), ("e_q", "<i8"), ("p_i", "<i8"), ("p_q", "<i8"),
+                            ("l_i", "<i8"), ("l_q", "<i8"), ("carr_step", "<i8"), ("code_phase", "<u8"), ("carr_phase", "<u4"),
+                            ("e_c", "<i4"), ("e_d", "<i4"), ("mode", "<i4")])
+
+
+class TrkCfg(C.Structure):
+    """gpsbb_trk_cfg_t: code_nom (2^-32 chips per sample), aid_div, spacing (2^-32 chips), nfll, kf, kp1, kp2, kd1, kd2, max_epochs"""
+    _fields_ = [("code_nom", C.c_uint64), ("aid_div", C.c_int64), ("spacing", C.c_uint32), ("nfll", C.c_int32), ("kf", C.c_int32),
+                ("kp1", C.c_int32), ("kp2", C.c_int32), ("kd1", C.c_int32), ("kd2", C.c_int32), ("max_epochs", C.c_int32)]
+
+    def copy(self, **fields):
+        """the same configuration with some fields replaced"""
+        c = TrkCfg.from_buffer_copy(self)
+        for k, v in fields.items():
+            setattr(c, k, v)
+        return c
+
+
+assert TRK_STATE_DTYPE.itemsize == 80 and TRK_EPOCH_DTYPE.itemsize == 96 and C.sizeof(TrkCfg) == 48
+
+
 ERRORS = {0: "GPSBB_OK", -1: "GPSBB_E_BADARG", -2: "GPSBB_E_BADCHAN", -3: "GPSBB_E_HIP", -4: "GPSBB_E_NOMEM",
           -5: "GPSBB_E_INTERNAL", -6: "GPSBB_E_NODEVICE", -7: "GPSBB_E_STATE"}
 
@@ -215,6 +241,7 @@ API_SYMBOLS = [
     "gpsbb_batch_despread_impaired", "gpsbb_batch_despread_lags",
     "gpsbb_device_level", "gpsbb_level_clips", "gpsbb_level_choose", "gpsbb_level_rms", "gpsbb_stream_pop_level",
     "gpsbb_device_acquire", "gpsbb_acq_min_shift", "gpsbb_acq_make", "gpsbb_acq_best",
+    "gpsbb_device_track", "gpsbb_trk_make", "gpsbb_trk_seed", "gpsbb_trk_bitsync", "gpsbb_trk_bits",
 ]
 # ... and include/gpsbb_node.h
 NODE_API_SYMBOLS = ["gpsbb_node_create", "gpsbb_node_run", "gpsbb_node_run_digest", "gpsbb_node_slot_digests", "gpsbb_node_destroy", "gpsbb_node_plan", "gpsbb_node_begin", "gpsbb_node_feed", "gpsbb_node_end",
@@ -344,6 +371,12 @@ def lib():
             L.gpsbb_acq_min_shift.argtypes = [u, i, i]
             L.gpsbb_acq_make.argtypes = [vp, d, d, d, i, d, i, i, u]
             L.gpsbb_acq_best.argtypes = [vp, vp, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_uint64), C.POINTER(d)]
+        if hasattr(L, "gpsbb_device_track"):  # the tracking calls, as a group (an older build loaded for an A/B: tools/ab_lib.sh)
+            L.gpsbb_device_track.argtypes = [vp, vp, C.c_long, u, vp, vp, vp, vp, i, vp, vp]
+            L.gpsbb_trk_make.argtypes = [vp, d, d, d, d, i, i]
+            L.gpsbb_trk_seed.argtypes = [vp, vp, i, i, i]
+            L.gpsbb_trk_bitsync.argtypes = [vp, i, i, C.POINTER(i), vp]
+            L.gpsbb_trk_bits.argtypes = [vp, i, i, vp, i]
         _lib = L
     return _lib
 
@@ -628,6 +661,25 @@ class Synth:
         _chk(lib().gpsbb_device_acquire(self._h, C.c_void_p(int(d_ptr)), int(nsamp), view, _ref(nz), _ref(js), C.byref(cfg),
                                         rows.ctypes.data, None if grid is None else grid.ctypes.data), "gpsbb_device_acquire")
         return (rows, grid) if want_grid else rows
+
+    def device_track(self, d_ptr, nsamp, cfg, states, view=OUT_SC16, noise=None, interf=None):
+        """gpsbb_device_track: the channels of `states` (TRK_STATE_DTYPE [nch], left as they are) followed through nsamp int16 I/Q
+        pairs in device memory -> (the states after, TRK_STATE_DTYPE [nch]; per channel its records, a list of TRK_EPOCH_DTYPE
+        arrays).  track_host is the same in numpy"""
+        nz, js = _as_noise(noise), _as_interf(interf)
+        st = np.array(states, TRK_STATE_DTYPE).reshape(-1)
+        nch = st.size
+        # (no more records than epochs can fit the buffer: every epoch after a channel's first has more than LEN / cs - 1 samples.
+        # The call lays the records out as [nch][max_epochs], so it is handed the smaller number: the same records)
+        cs_max = int(cfg.code_nom) + int(cfg.code_nom) // 8
+        fit = 2 + max(int(nsamp), 0) // max(1, TRK_LEN // max(cs_max, 1) - 1)
+        if 1 <= int(cfg.max_epochs) and fit < int(cfg.max_epochs):
+            cfg = cfg.copy(max_epochs=fit)
+        room = np.zeros((nch, max(int(cfg.max_epochs), 1)), TRK_EPOCH_DTYPE)
+        counts = np.zeros(max(nch, 1), np.int32)
+        _chk(lib().gpsbb_device_track(self._h, C.c_void_p(int(d_ptr)), int(nsamp), view, _ref(nz), _ref(js), C.byref(cfg), st.ctypes.data, nch,
+                                      room.ctypes.data, counts.ctypes.data), "gpsbb_device_track")
+        return st, [room[c, :int(counts[c])].copy() for c in range(nch)]
 
     def device_noise(self, d_src, nblocks, nsamp, noise, d_dst=None):
         """gpsbb_device_noise: nblocks blocks of int16 IQ in device memory at d_src, with noise, into d_dst (default: in place)"""
@@ -1492,6 +1544,140 @@ def acquire_host(u, cfg, blas=None):
             tot = (int(hi32[p, k]) << 32) + int(lo32[p, k])
             rows["sum_lo"][p, k], rows["sum_hi"][p, k] = tot & 0xFFFFFFFFFFFFFFFF, tot >> 64
     return rows, grid
+
+
+def trk_make(delt, fll_gain=0.0, pll_bw_hz=0.0, dll_gain=0.0, nfll=0, max_epochs=0):
+    """gpsbb_trk_make: a TrkCfg from physical units; an argument <= 0 takes its default (0.15, 15 Hz, 0.1, 100 epochs, 1000 records)"""
+    cfg = TrkCfg()
+    _chk(lib().gpsbb_trk_make(C.byref(cfg), float(delt), float(fll_gain), float(pll_bw_hz), float(dll_gain), int(nfll), int(max_epochs)),
+         "gpsbb_trk_make")
+    return cfg
+
+
+def trk_seed(acq_cfg, prn, bin, lag):
+    """gpsbb_trk_seed: a channel's first state (TRK_STATE_DTYPE, one element) from an acquisition hit"""
+    st = np.zeros(1, TRK_STATE_DTYPE)
+    _chk(lib().gpsbb_trk_seed(st.ctypes.data, C.byref(acq_cfg), int(prn), int(bin), int(lag)), "gpsbb_trk_seed")
+    return st[0]
+
+
+def trk_bitsync(epochs, skip):
+    """gpsbb_trk_bitsync -> (offset, hist int32 [20]): the sign changes of p_i after record `skip`, by record index mod 20"""
+    e = np.ascontiguousarray(epochs, TRK_EPOCH_DTYPE).reshape(-1)
+    off, hist = C.c_int(), np.zeros(20, np.int32)
+    _chk(lib().gpsbb_trk_bitsync(e.ctypes.data, e.size, int(skip), C.byref(off), hist.ctypes.data), "gpsbb_trk_bitsync")
+    return off.value, hist
+
+
+def trk_bits(epochs, first, max_bits=None):
+    """gpsbb_trk_bits -> int8 [nbits]: the signs of the sums of p_i over whole groups of 20 records from record `first`"""
+    e = np.ascontiguousarray(epochs, TRK_EPOCH_DTYPE).reshape(-1)
+    cap = e.size // 20 + 1 if max_bits is None else int(max_bits)
+    bits = np.zeros(max(cap, 1), np.int8)
+    n = lib().gpsbb_trk_bits(e.ctypes.data, e.size, int(first), bits.ctypes.data, cap)
+    _chk(n if n < 0 else 0, "gpsbb_trk_bits")
+    return bits[:n].copy()
+
+
+def _tdiv(a, b):
+    """C's / on integers: truncates toward zero"""
+    q = abs(a) // abs(b)
+    return q if (a < 0) == (b < 0) else -q
+
+
+def _trk_m(x):
+    """m(x): the bit length of x for x >= 0, of ~x otherwise"""
+    return (x if x >= 0 else ~x).bit_length()
+
+
+def _clamp(x, lo, hi):
+    return lo if x < lo else (hi if x > hi else x)
+
+
+def trk_plan_host(cfg, st):
+    """steps 1 and 2 of an epoch in Python integers: st a dict of a state's fields -> (cs, N)"""
+    nom = int(cfg.code_nom)
+    aid = _tdiv(st["carr_step"], int(cfg.aid_div)) if int(cfg.aid_div) else 0
+    cs = _clamp(nom + aid + st["code_adj"], nom - nom // 8, nom + nom // 8)
+    return cs, -((st["code_phase"] - TRK_LEN) // cs)
+
+
+def trk_close_host(cfg, st, cs, N, sums):
+    """steps 4 to 8 in Python integers: the six sums (E.i, E.q, P.i, P.q, L.i, L.q) of the epoch correlated at st (a dict of a
+    state's fields, advanced in place) with cs and N -> the record, a dict of TRK_EPOCH_DTYPE's fields"""
+    cmax = (1 << 47) - 1
+    q = max(0, max(_trk_m(v) for v in sums) - 20)
+    Ei, Eq, Pi, Pq, Li, Lq = (v >> q for v in sums)
+    E2, L2 = Ei * Ei + Eq * Eq, Li * Li + Lq * Lq
+    e_d = _tdiv((E2 - L2) << 14, E2 + L2 + 1)
+    mode = 0 if st["epoch"] < int(cfg.nfll) else 1
+    used = st["carr_step"]
+    if mode == 0:
+        e_c = 0
+        if st["epoch"] > 0:
+            cross, dot = st["prev_i"] * Pq - st["prev_q"] * Pi, st["prev_i"] * Pi + st["prev_q"] * Pq
+            e_c = _tdiv(((1 if dot >= 0 else -1) * cross) << 14, abs(dot) + abs(cross) + 1)
+        st["carr_int"] = _clamp(st["carr_int"] + int(cfg.kf) * e_c, -cmax, cmax)
+        st["carr_step"] = st["carr_int"]
+    else:
+        e_c = _tdiv(((1 if Pi >= 0 else -1) * Pq) << 14, abs(Pi) + abs(Pq) + 1)
+        st["carr_int"] = _clamp(st["carr_int"] + int(cfg.kp2) * e_c, -cmax, cmax)
+        st["carr_step"] = _clamp(st["carr_int"] + int(cfg.kp1) * e_c, -cmax, cmax)
+    st["code_int"] = _clamp(st["code_int"] + int(cfg.kd2) * e_d, -(1 << 56), 1 << 56)
+    st["code_adj"] = (st["code_int"] + int(cfg.kd1) * e_d) >> 8
+    rec = dict(n0=st["n0"], N=N, q=q, e_i=sums[0], e_q=sums[1], p_i=sums[2], p_q=sums[3], l_i=sums[4], l_q=sums[5], carr_step=used,
+               code_phase=st["code_phase"], carr_phase=st["carr_phase"], e_c=e_c, e_d=e_d, mode=mode)
+    s32 = (used >> 16) & 0xFFFFFFFF
+    st["carr_phase"] = (st["carr_phase"] + s32 * N) & 0xFFFFFFFF
+    st["code_phase"] = st["code_phase"] + cs * N - TRK_LEN
+    st["n0"] += N
+    st["epoch"] += 1
+    st["prev_i"], st["prev_q"] = Pi, Pq
+    return rec
+
+
+def track_host(u, cfg, states):
+    """gpsbb_device_track in numpy: u int64 [nsamp, 2] (view_host's output of the buffer), states TRK_STATE_DTYPE [nch] (left as
+    they are) -> (the states after; per channel its records, a list of TRK_EPOCH_DTYPE arrays).  An epoch's samples are taken at
+    once (step 3 vectorised: every product and partial sum an integer below 2^45); steps 1-2 and 4-8 are Python integers."""
+    u = np.asarray(u, np.int64)
+    if u.ndim != 2 or u.shape[1] != 2:
+        raise ValueError("u [nsamp, 2] wanted, got %r" % (u.shape,))
+    nsamp = u.shape[0]
+    sin512, cos512 = sincos_tables()
+    cosv, sinv = cos512.astype(np.int64), sin512.astype(np.int64)
+    out_st = np.array(states, TRK_STATE_DTYPE).reshape(-1)
+    recs = []
+    sp = int(cfg.spacing)
+    for c in range(out_st.size):
+        st = {k: int(out_st[c][k]) for k in TRK_STATE_DTYPE.names}
+        x = 2 * codegen(st["prn"]).astype(np.int64) - 1
+        mine = []
+        while len(mine) < int(cfg.max_epochs):
+            cs, N = trk_plan_host(cfg, st)
+            if st["n0"] + N > nsamp:
+                break
+            j = np.arange(N, dtype=np.uint64)
+            s32 = (st["carr_step"] >> 16) & 0xFFFFFFFF
+            idx = (((np.uint64(st["carr_phase"]) + np.uint64(s32) * j) & np.uint64(0xFFFFFFFF)) >> np.uint64(23)).astype(np.int64)
+            w = u[st["n0"]:st["n0"] + N]
+            cc, ss = cosv[idx], sinv[idx]
+            yi, yq = w[:, 0] * cc + w[:, 1] * ss, w[:, 1] * cc - w[:, 0] * ss
+            phi = np.uint64(st["code_phase"]) + np.uint64(cs) * j   # < LEN
+            sums = []
+            for o in (sp, 0, -sp):
+                chip = ((phi + np.uint64(o + TRK_LEN)) % np.uint64(TRK_LEN)) >> np.uint64(32)
+                xs = x[chip.astype(np.int64)]
+                sums += [int((xs * yi).sum()), int((xs * yq).sum())]
+            mine.append(trk_close_host(cfg, st, cs, N, sums))
+        for k in TRK_STATE_DTYPE.names:
+            out_st[c][k] = st[k]
+        r = np.zeros(len(mine), TRK_EPOCH_DTYPE)
+        for i, m in enumerate(mine):
+            for k, v in m.items():
+                r[i][k] = v
+        recs.append(r)
+    return out_st, recs
 
 
 def block_digest_host(iq):

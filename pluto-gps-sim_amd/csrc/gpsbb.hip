@@ -33,6 +33,7 @@
 #include "gpsbb_despread.hip.h"
 #include "gpsbb_despread_lags.hip.h"
 #include "gpsbb_acq.hip.h"
+#include "gpsbb_track.hip.h"
 #include "gpsbb_walk.hip.h"
 #include "gpsbb_laps.hip.h"
 #include "gpsbb_nco.h"
@@ -563,11 +564,13 @@ struct gpsbb {
     } d_digest;
 #ifdef GPSBB_EXPERIMENTS
     hipEvent_t acq_ev[2] = {}; /* around the last gpsbb_device_acquire's kernels, gpsbb_test_acquire_ms */
+    hipEvent_t trk_ev[2] = {}; /* around the last gpsbb_device_track's kernel, gpsbb_test_track_ms */
 #endif
     DigestBuf d_acq_chips, d_acq_rows; /* gpsbb_device_acquire's scratch, kept between calls (in 8-byte words): the expanded chips; the
                                           tiles' partials with the rows behind them */
     DigestBuf d_acq_grid;              /* ... and the grid where wanted (up to 512 MiB, for tests and plots): freed when the call
                                           that asked for it has copied it out, here only while that call runs or after it failed */
+    DigestBuf d_trk;                   /* gpsbb_device_track's scratch, null until the first call: the states, the counts, the records */
 };
 
 /* every stream the handle has created, in no particular order */
@@ -1055,8 +1058,11 @@ extern "C" void gpsbb_destroy(gpsbb_t *h)
     for (hipEvent_t e : h->acq_ev)
         if (e)
             (void)hipEventDestroy(e);
+    for (hipEvent_t e : h->trk_ev)
+        if (e)
+            (void)hipEventDestroy(e);
 #endif
-    for (gpsbb::DigestBuf *b : {&h->d_acq_chips, &h->d_acq_rows, &h->d_acq_grid})
+    for (gpsbb::DigestBuf *b : {&h->d_acq_chips, &h->d_acq_rows, &h->d_acq_grid, &h->d_trk})
         if (b->p)
             (void)hipFree(b->p);
     delete h->pool;
@@ -3133,6 +3139,108 @@ extern "C" int gpsbb_device_acquire(gpsbb_t *h, const int16_t *d_iq, long nsamp,
     return GPSBB_OK;
 }
 
+/* ---- blind tracking (include/gpsbb.h gpsbb_device_track; gpsbb_track.h, gpsbb_track.hip.h) ---- */
+
+static_assert(sizeof(gpsbb_trk_cfg_t) == 48 && sizeof(gpsbb_trk_state_t) == 80 && sizeof(gpsbb_trk_epoch_t) == 96,
+              "gpsbb_trk_cfg_t / gpsbb_trk_state_t / gpsbb_trk_epoch_t layout");
+
+extern "C" int gpsbb_trk_make(gpsbb_trk_cfg_t *cfg, double delt, double fll_gain, double pll_bw_hz, double dll_gain, int nfll, int max_epochs)
+{
+    return trk_make(cfg, delt, fll_gain, pll_bw_hz, dll_gain, nfll, max_epochs);
+}
+
+extern "C" int gpsbb_trk_seed(gpsbb_trk_state_t *state, const gpsbb_acq_cfg_t *acq_cfg, int prn, int bin, int lag)
+{
+    return trk_seed(state, acq_cfg, prn, bin, lag);
+}
+
+extern "C" int gpsbb_trk_bitsync(const gpsbb_trk_epoch_t *epochs, int n, int skip, int *offset, int32_t hist[20])
+{
+    return trk_bitsync(epochs, n, skip, offset, hist);
+}
+
+extern "C" int gpsbb_trk_bits(const gpsbb_trk_epoch_t *epochs, int n, int first, int8_t *bits, int max)
+{
+    return trk_bits(epochs, n, first, bits, max);
+}
+
+typedef void (*TrkKernelFn)(TrkArgs);
+static TrkKernelFn trk_kernel(int fmt, bool noise, bool interf)
+{
+#define GPSBB_TK_ROW(V) {{k_track<V, false, false>, k_track<V, false, true>}, {k_track<V, true, false>, k_track<V, true, true>}}
+    static const TrkKernelFn k[3][2][2] = {GPSBB_TK_ROW(DS_SC16), GPSBB_TK_ROW(PACK_SC8), GPSBB_TK_ROW(PACK_SC1)};
+#undef GPSBB_TK_ROW
+    return k[fmt][noise ? 1 : 0][interf ? 1 : 0];
+}
+
+extern "C" int gpsbb_device_track(gpsbb_t *h, const int16_t *d_iq, long nsamp, unsigned view, const gpsbb_noise_t *nz,
+                                  const gpsbb_interf_set_t *set, const gpsbb_trk_cfg_t *cfg, gpsbb_trk_state_t *states, int nch,
+                                  gpsbb_trk_epoch_t *epochs, int32_t *counts)
+{
+    int shift8 = 0;
+    const int fmt = acq_view_format(view, &shift8);
+    ImpairCall ic;
+    if (!h || !d_iq || !cfg || !states || !epochs || !counts || ((uintptr_t)d_iq & 3) || nsamp < 1 || nch < 1 || nch > TRK_MAX_CH || fmt < 0 ||
+        !trk_cfg_ok(cfg) || !impair_make(nz, set, (uint64_t)nsamp, &ic))
+        return GPSBB_E_BADARG;
+    for (int c = 0; c < nch; c++)
+        if (!trk_state_ok(&states[c], nsamp))
+            return GPSBB_E_BADARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int rc = gpsbb_sync(h); /* as gpsbb_device_acquire: whatever the handle was rendering into d_iq is there */
+    if (rc != GPSBB_OK)
+        return rc;
+    if (nz)
+        HIPCHK(h, noise_ready(h));
+    /* ---- scratch, in 8-byte words: the states, the counts, the records ---- */
+    const size_t st_words = (size_t)nch * sizeof(gpsbb_trk_state_t) / 8, cnt_words = ((size_t)nch + 1) / 2;
+    const size_t rec_words = (size_t)nch * (size_t)cfg->max_epochs * (sizeof(gpsbb_trk_epoch_t) / 8);
+    HIPCHK(h, (hipError_t)h->d_trk.reserve(st_words + cnt_words + rec_words));
+    hipStream_t cs = h->s_compute;
+    TrkArgs a;
+    memset(&a, 0, sizeof a);
+    a.d.iq = reinterpret_cast<const uint32_t *>(d_iq);
+    a.d.shift8 = shift8;
+    ds_fill_impair(a.d, h, ic);
+    a.tabs = h->d_tabs;
+    a.ca_bits = h->d_ca;
+    a.cfg = *cfg;
+    a.states = reinterpret_cast<gpsbb_trk_state_t *>(h->d_trk.p);
+    a.counts = reinterpret_cast<int32_t *>(h->d_trk.p + st_words);
+    a.epochs = reinterpret_cast<gpsbb_trk_epoch_t *>(h->d_trk.p + st_words + cnt_words);
+    a.nsamp = nsamp;
+    HIPCHK(h, hipMemcpyAsync(a.states, states, (size_t)nch * sizeof(gpsbb_trk_state_t), hipMemcpyHostToDevice, cs));
+    HIPCHK(h, hipMemsetAsync(a.counts, 0, cnt_words * 8, cs));
+#ifdef GPSBB_EXPERIMENTS
+    for (auto &e : h->trk_ev)
+        if (!e)
+            HIPCHK(h, hipEventCreate(&e));
+    HIPCHK(h, hipEventRecord(h->trk_ev[0], cs));
+#endif
+    hipLaunchKernelGGL(trk_kernel(fmt, nz != nullptr, set != nullptr), dim3((unsigned)nch), dim3(TK_WG), 0, cs, a);
+    HIPCHK(h, hipGetLastError());
+#ifdef GPSBB_EXPERIMENTS
+    HIPCHK(h, hipEventRecord(h->trk_ev[1], cs));
+#endif
+    /* ---- copy back: the counts first, then each channel's records as far as they go, and the states ---- */
+    int32_t n_out[TRK_MAX_CH];
+    gpsbb_trk_state_t st_out[TRK_MAX_CH];
+    HIPCHK(h, hipMemcpyAsync(n_out, a.counts, (size_t)nch * sizeof(int32_t), hipMemcpyDeviceToHost, cs));
+    HIPCHK(h, hipMemcpyAsync(st_out, a.states, (size_t)nch * sizeof(gpsbb_trk_state_t), hipMemcpyDeviceToHost, cs));
+    HIPCHK(h, hipStreamSynchronize(cs));
+    for (int c = 0; c < nch; c++) {
+        if (n_out[c] < 0 || n_out[c] > cfg->max_epochs)
+            return GPSBB_E_INTERNAL;
+        if (n_out[c])
+            HIPCHK(h, hipMemcpyAsync(epochs + (size_t)c * (size_t)cfg->max_epochs, a.epochs + (size_t)c * (size_t)cfg->max_epochs,
+                                     (size_t)n_out[c] * sizeof(gpsbb_trk_epoch_t), hipMemcpyDeviceToHost, cs));
+    }
+    HIPCHK(h, hipStreamSynchronize(cs));
+    memcpy(states, st_out, (size_t)nch * sizeof(gpsbb_trk_state_t));
+    memcpy(counts, n_out, (size_t)nch * sizeof(int32_t));
+    return GPSBB_OK;
+}
+
 extern "C" double gpsbb_cn0_estimate(const gpsbb_corr_t *p, long n, long stride, double seg_seconds)
 {
     if (!p || n < 2 || stride < 1 || !(seg_seconds > 0.0) || !std::isfinite(seg_seconds))
@@ -4599,6 +4707,14 @@ extern "C" float gpsbb_test_acquire_ms(gpsbb *h)
 {
     float ms = -1.0f;
     if (!h || !h->acq_ev[0] || !h->acq_ev[1] || hipEventElapsedTime(&ms, h->acq_ev[0], h->acq_ev[1]) != hipSuccess)
+        return -1.0f;
+    return ms;
+}
+
+extern "C" float gpsbb_test_track_ms(gpsbb *h)
+{
+    float ms = -1.0f;
+    if (!h || !h->trk_ev[0] || !h->trk_ev[1] || hipEventElapsedTime(&ms, h->trk_ev[0], h->trk_ev[1]) != hipSuccess)
         return -1.0f;
     return ms;
 }

@@ -86,6 +86,8 @@ unsigned long long gpsbb_test_despread_exact(struct gpsbb_batch *b);
 float gpsbb_test_despread_ms(struct gpsbb_batch *b);
 /* milliseconds the three kernels of the handle's last gpsbb_device_acquire took (k_acq_chips, k_acq, k_acq_fold), by HIP events */
 float gpsbb_test_acquire_ms(struct gpsbb *h);
+/* ... and the kernel of its last gpsbb_device_track (k_track) */
+float gpsbb_test_track_ms(struct gpsbb *h);
 /* the state granule of the batch's tile tables as log2 of its tiles: the code rows' (BatchDev::st_log2) and the carrier rows'
  * (ev_carr_log2 of it, gpsbb_events.hip.h) */
 int gpsbb_test_state_log2(struct gpsbb_batch *b);
