@@ -222,6 +222,30 @@ class TrkCfg(C.Structure):
 assert TRK_STATE_DTYPE.itemsize == 80 and TRK_EPOCH_DTYPE.itemsize == 96 and C.sizeof(TrkCfg) == 48
 
 
+# the front-end filter (include/gpsbb.h gpsbb_device_fir): a real FIR on I and on Q, one output per `decim` inputs
+FIR_MAX_TAPS, FIR_MAX_DECIM, FIR_MAX_SHIFT, FIR_MAX_SUM = 129, 16, 16, 65535
+FIR_TILE = 256   # the outputs one of k_fir's workgroups takes (csrc/gpsbb_fir.hip.h; gpsbb_test_fir_tile says the same)
+
+
+class Fir(C.Structure):
+    """gpsbb_fir_t: ntaps, decim, shift, h[0..ntaps-1] with the sum of |h| at most 65535"""
+    _fields_ = [("ntaps", C.c_int32), ("decim", C.c_int32), ("shift", C.c_int32), ("_pad", C.c_int32), ("h", C.c_int16 * FIR_MAX_TAPS),
+                ("_pad2", C.c_int16)]
+
+    def __init__(self, h=(), decim=1, shift=0):
+        super().__init__()
+        self.ntaps, self.decim, self.shift = len(h), decim, shift
+        for k, v in enumerate(h):
+            self.h[k] = v
+
+    def taps(self):
+        """h[0..ntaps-1] as int64"""
+        return np.array(self.h[:max(int(self.ntaps), 0)], np.int64)
+
+
+assert C.sizeof(Fir) == 276
+
+
 ERRORS = {0: "GPSBB_OK", -1: "GPSBB_E_BADARG", -2: "GPSBB_E_BADCHAN", -3: "GPSBB_E_HIP", -4: "GPSBB_E_NOMEM",
           -5: "GPSBB_E_INTERNAL", -6: "GPSBB_E_NODEVICE", -7: "GPSBB_E_STATE"}
 
@@ -242,6 +266,7 @@ API_SYMBOLS = [
     "gpsbb_device_level", "gpsbb_level_clips", "gpsbb_level_choose", "gpsbb_level_rms", "gpsbb_stream_pop_level",
     "gpsbb_device_acquire", "gpsbb_acq_min_shift", "gpsbb_acq_make", "gpsbb_acq_best",
     "gpsbb_device_track", "gpsbb_trk_make", "gpsbb_trk_seed", "gpsbb_trk_bitsync", "gpsbb_trk_bits",
+    "gpsbb_device_fir", "gpsbb_fir_make",
 ]
 # ... and include/gpsbb_node.h
 NODE_API_SYMBOLS = ["gpsbb_node_create", "gpsbb_node_run", "gpsbb_node_run_digest", "gpsbb_node_slot_digests", "gpsbb_node_destroy", "gpsbb_node_plan", "gpsbb_node_begin", "gpsbb_node_feed", "gpsbb_node_end",
@@ -377,6 +402,9 @@ def lib():
             L.gpsbb_trk_seed.argtypes = [vp, vp, i, i, i]
             L.gpsbb_trk_bitsync.argtypes = [vp, i, i, C.POINTER(i), vp]
             L.gpsbb_trk_bits.argtypes = [vp, i, i, vp, i]
+        if hasattr(L, "gpsbb_device_fir"):  # the filter's calls, as a group (an older build loaded for an A/B: tools/ab_lib.sh)
+            L.gpsbb_device_fir.argtypes = [vp, vp, C.c_long, vp, vp, vp, vp, vp, vp, vp]
+            L.gpsbb_fir_make.argtypes = [vp, i, i, d, d]
         _lib = L
     return _lib
 
@@ -416,6 +444,10 @@ def exp_lib():
             L.gpsbb_test_push_side.argtypes = [vp, i, i, d, i, u, vp, vp]
         if hasattr(L, "gpsbb_test_chain_plan"):  # (an older build loaded for an A/B: tools/ab_lib.sh)
             L.gpsbb_test_chain_plan.argtypes = [vp, i, i, d, i, i, vp]
+        if hasattr(L, "gpsbb_test_fir_ms"):  # (an older build loaded for an A/B: tools/ab_lib.sh)
+            L.gpsbb_test_fir_ms.argtypes = [vp]
+            L.gpsbb_test_fir_ms.restype = C.c_float
+            L.gpsbb_test_fir_tile.argtypes = []
         _exp_lib = L
     return _exp_lib
 
@@ -680,6 +712,20 @@ class Synth:
         _chk(lib().gpsbb_device_track(self._h, C.c_void_p(int(d_ptr)), int(nsamp), view, _ref(nz), _ref(js), C.byref(cfg), st.ctypes.data, nch,
                                       room.ctypes.data, counts.ctypes.data), "gpsbb_device_track")
         return st, [room[c, :int(counts[c])].copy() for c in range(nch)]
+
+    def device_fir(self, d_ptr, nsamp, fir, d_out, hist=None, noise=None, interf=None):
+        """gpsbb_device_fir: nsamp int16 I/Q pairs in device memory at d_ptr, filtered and decimated into nsamp / fir.decim pairs at
+        d_out -> (the history to hand to the next call, int16 [ntaps - 1, 2]; the components the clamp changed).  hist: the
+        history a call before returned, or None (zeros).  fir_host over view_host's output is the same in numpy"""
+        nz, js = _as_noise(noise), _as_interf(interf)
+        nh = max(int(fir.ntaps) - 1, 0)
+        hin = None if hist is None else np.ascontiguousarray(hist, np.int16).reshape(nh, 2)
+        hout = np.zeros((nh, 2), np.int16)
+        clipped = C.c_uint64(0)
+        _chk(lib().gpsbb_device_fir(self._h, C.c_void_p(int(d_ptr)), int(nsamp), _ref(nz), _ref(js), C.byref(fir),
+                                    None if hin is None else hin.ctypes.data, hout.ctypes.data, C.c_void_p(int(d_out)), C.byref(clipped)),
+             "gpsbb_device_fir")
+        return hout, int(clipped.value)
 
     def device_noise(self, d_src, nblocks, nsamp, noise, d_dst=None):
         """gpsbb_device_noise: nblocks blocks of int16 IQ in device memory at d_src, with noise, into d_dst (default: in place)"""
@@ -1678,6 +1724,38 @@ def track_host(u, cfg, states):
                 r[i][k] = v
         recs.append(r)
     return out_st, recs
+
+
+# ---- the front-end filter (include/gpsbb.h, gpsbb_device_fir): the numpy restatement the GPU's output is checked against ----
+
+def fir_make(ntaps, decim, cutoff=0.0, atten_db=0.0):
+    """gpsbb_fir_make: a Kaiser-windowed sinc for decimation by decim -> Fir (cutoff: a fraction of the output's Nyquist rate,
+    default 0.8; atten_db: default 60)"""
+    f = Fir()
+    _chk(lib().gpsbb_fir_make(C.byref(f), int(ntaps), int(decim), float(cutoff), float(atten_db)), "gpsbb_fir_make")
+    return f
+
+
+def fir_host(w, fir, hist=None):
+    """gpsbb_device_fir in numpy on view samples w [nsamp, 2] (view_host's output: already impaired) -> (y int16 [nsamp / D, 2],
+    the history to hand on int16 [T - 1, 2], the components the clamp changed).  hist: [T - 1, 2] or None (zeros)"""
+    T, D, shift = int(fir.ntaps), int(fir.decim), int(fir.shift)
+    h = fir.taps()
+    w = np.asarray(w, np.int64)
+    if not (1 <= T <= FIR_MAX_TAPS and 1 <= D <= FIR_MAX_DECIM and 0 <= shift <= FIR_MAX_SHIFT and int(np.abs(h).sum()) <= FIR_MAX_SUM):
+        raise ValueError("a filter gpsbb_device_fir refuses")
+    if w.ndim != 2 or w.shape[1] != 2 or w.shape[0] < 1 or w.shape[0] % D:
+        raise ValueError("w of shape (nsamp, 2) with nsamp a multiple of %d wanted, got %r" % (D, w.shape))
+    hin = np.zeros((T - 1, 2), np.int64) if hist is None else np.asarray(hist, np.int64).reshape(T - 1, 2)
+    x = np.concatenate([hin, w])              # x[T - 1 + n] = w[n]
+    M = w.shape[0] // D
+    acc = np.zeros((M, 2), np.int64)
+    first = T - 1 + D - 1                     # output m, tap k: x[first + m * D - k]
+    for k in range(T):
+        acc += int(h[k]) * x[first - k: first - k + (M - 1) * D + 1: D]
+    y = (acc + (1 << (shift - 1))) >> shift if shift else acc
+    out = np.clip(y, -32768, 32767)
+    return out.astype(np.int16), x[x.shape[0] - (T - 1):].astype(np.int16), int(np.count_nonzero(out != y))
 
 
 def block_digest_host(iq):

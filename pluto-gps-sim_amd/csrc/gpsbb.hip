@@ -34,6 +34,7 @@
 #include "gpsbb_despread_lags.hip.h"
 #include "gpsbb_acq.hip.h"
 #include "gpsbb_track.hip.h"
+#include "gpsbb_fir.hip.h"
 #include "gpsbb_walk.hip.h"
 #include "gpsbb_laps.hip.h"
 #include "gpsbb_nco.h"
@@ -565,12 +566,14 @@ struct gpsbb {
 #ifdef GPSBB_EXPERIMENTS
     hipEvent_t acq_ev[2] = {}; /* around the last gpsbb_device_acquire's kernels, gpsbb_test_acquire_ms */
     hipEvent_t trk_ev[2] = {}; /* around the last gpsbb_device_track's kernel, gpsbb_test_track_ms */
+    hipEvent_t fir_ev[2] = {}; /* around the last gpsbb_device_fir's kernel, gpsbb_test_fir_ms */
 #endif
     DigestBuf d_acq_chips, d_acq_rows; /* gpsbb_device_acquire's scratch, kept between calls (in 8-byte words): the expanded chips; the
                                           tiles' partials with the rows behind them */
     DigestBuf d_acq_grid;              /* ... and the grid where wanted (up to 512 MiB, for tests and plots): freed when the call
                                           that asked for it has copied it out, here only while that call runs or after it failed */
     DigestBuf d_trk;                   /* gpsbb_device_track's scratch, null until the first call: the states, the counts, the records */
+    DigestBuf d_fir;                   /* gpsbb_device_fir's scratch, null until the first call: the clip count, the two histories */
 };
 
 /* every stream the handle has created, in no particular order */
@@ -1061,8 +1064,11 @@ extern "C" void gpsbb_destroy(gpsbb_t *h)
     for (hipEvent_t e : h->trk_ev)
         if (e)
             (void)hipEventDestroy(e);
+    for (hipEvent_t e : h->fir_ev)
+        if (e)
+            (void)hipEventDestroy(e);
 #endif
-    for (gpsbb::DigestBuf *b : {&h->d_acq_chips, &h->d_acq_rows, &h->d_acq_grid, &h->d_trk})
+    for (gpsbb::DigestBuf *b : {&h->d_acq_chips, &h->d_acq_rows, &h->d_acq_grid, &h->d_trk, &h->d_fir})
         if (b->p)
             (void)hipFree(b->p);
     delete h->pool;
@@ -3241,6 +3247,95 @@ extern "C" int gpsbb_device_track(gpsbb_t *h, const int16_t *d_iq, long nsamp, u
     return GPSBB_OK;
 }
 
+/* ---- the front-end filter (include/gpsbb.h gpsbb_device_fir; gpsbb_fir.h, gpsbb_fir.hip.h) ---- */
+
+static_assert(sizeof(gpsbb_fir_t) == 276, "gpsbb_fir_t layout");
+
+extern "C" int gpsbb_fir_make(gpsbb_fir_t *f, int ntaps, int decim, double cutoff, double atten_db)
+{
+    return fir_make(f, ntaps, decim, cutoff, atten_db);
+}
+
+typedef void (*FirKernelFn)(FirArgs);
+static FirKernelFn fir_kernel(bool noise, bool interf)
+{
+    static const FirKernelFn k[2][2] = {{k_fir<false, false>, k_fir<false, true>}, {k_fir<true, false>, k_fir<true, true>}};
+    return k[noise ? 1 : 0][interf ? 1 : 0];
+}
+
+extern "C" int gpsbb_device_fir(gpsbb_t *h, const int16_t *d_iq, long nsamp, const gpsbb_noise_t *nz, const gpsbb_interf_set_t *set,
+                                const gpsbb_fir_t *fir, const int16_t *hist_in, int16_t *hist_out, int16_t *d_out, uint64_t *clipped)
+{
+    ImpairCall ic;
+    if (!h || !d_iq || !fir || !d_out || (((uintptr_t)d_iq | (uintptr_t)d_out) & 3) || nsamp < 1 || !fir_ok(fir) || nsamp % fir->decim ||
+        !impair_make(nz, set, (uint64_t)nsamp, &ic))
+        return GPSBB_E_BADARG;
+    const int T = fir->ntaps, D = fir->decim, Te = T + (T & 1);
+    const long nout = nsamp / D, tiles = (nout + FIR_TILE - 1) / FIR_TILE;
+    const uintptr_t in0 = (uintptr_t)d_iq, in1 = in0 + 4 * (uintptr_t)nsamp, out0 = (uintptr_t)d_out, out1 = out0 + 4 * (uintptr_t)nout;
+    if ((out0 < in1 && in0 < out1) || tiles > 0x7fffffffL)
+        return GPSBB_E_BADARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int rc = gpsbb_sync(h); /* as gpsbb_device_track: whatever the handle was rendering into d_iq is there */
+    if (rc != GPSBB_OK)
+        return rc;
+    if (nz)
+        HIPCHK(h, noise_ready(h));
+    /* ---- scratch, in 8-byte words: the clip count, then room for the longest history twice ---- */
+    constexpr size_t hist_words = (GPSBB_FIR_MAX_TAPS - 1) / 2;
+    HIPCHK(h, (hipError_t)h->d_fir.reserve(1 + 2 * hist_words));
+    hipStream_t cs = h->s_compute;
+    FirArgs a;
+    memset(&a, 0, sizeof a);
+    a.d.iq = reinterpret_cast<const uint32_t *>(d_iq);
+    ds_fill_impair(a.d, h, ic);
+    a.tabs = h->d_tabs;
+    a.clipped = h->d_fir.p;
+    uint32_t *d_hist_in = reinterpret_cast<uint32_t *>(h->d_fir.p + 1), *d_hist_out = reinterpret_cast<uint32_t *>(h->d_fir.p + 1 + hist_words);
+    a.hist_in = d_hist_in;
+    a.hist_out = d_hist_out;
+    a.out = reinterpret_cast<uint32_t *>(d_out);
+    a.nsamp = nsamp;
+    a.nout = nout;
+    a.T = T;
+    a.Te = Te;
+    a.D = D;
+    a.shift = fir->shift;
+    a.PL = fir_plane(Te, D);
+    a.npairs = Te / 2;
+    a.rcp = ((1u << FIR_RCP_BITS) + (uint32_t)D - 1u) / (uint32_t)D;
+    for (int j = 0; j < a.npairs; j++) {
+        const int k = 2 * j, c = Te - 2 - k;
+        a.hp[j] = ((uint32_t)(uint16_t)(k + 1 < T ? fir->h[k + 1] : 0)) | ((uint32_t)(uint16_t)fir->h[k] << 16);
+        a.off[j] = (uint32_t)((c % D) * a.PL + c / D);
+    }
+    HIPCHK(h, hipMemsetAsync(h->d_fir.p, 0, (1 + 2 * hist_words) * 8, cs));
+    if (hist_in && T > 1)
+        HIPCHK(h, hipMemcpyAsync(d_hist_in, hist_in, (size_t)(T - 1) * 4, hipMemcpyHostToDevice, cs));
+#ifdef GPSBB_EXPERIMENTS
+    for (auto &e : h->fir_ev)
+        if (!e)
+            HIPCHK(h, hipEventCreate(&e));
+    HIPCHK(h, hipEventRecord(h->fir_ev[0], cs));
+#endif
+    hipLaunchKernelGGL(fir_kernel(nz != nullptr, set != nullptr), dim3((unsigned)tiles), dim3(FIR_WG), fir_lds_bytes(Te, D), cs, a);
+    HIPCHK(h, hipGetLastError());
+#ifdef GPSBB_EXPERIMENTS
+    HIPCHK(h, hipEventRecord(h->fir_ev[1], cs));
+#endif
+    uint32_t tail[GPSBB_FIR_MAX_TAPS];
+    unsigned long long clips = 0;
+    HIPCHK(h, hipMemcpyAsync(&clips, a.clipped, sizeof clips, hipMemcpyDeviceToHost, cs));
+    if (T > 1)
+        HIPCHK(h, hipMemcpyAsync(tail, d_hist_out, (size_t)(T - 1) * 4, hipMemcpyDeviceToHost, cs));
+    HIPCHK(h, hipStreamSynchronize(cs));
+    if (hist_out && T > 1)
+        memcpy(hist_out, tail, (size_t)(T - 1) * 4);
+    if (clipped)
+        *clipped = clips;
+    return GPSBB_OK;
+}
+
 extern "C" double gpsbb_cn0_estimate(const gpsbb_corr_t *p, long n, long stride, double seg_seconds)
 {
     if (!p || n < 2 || stride < 1 || !(seg_seconds > 0.0) || !std::isfinite(seg_seconds))
@@ -4718,6 +4813,16 @@ extern "C" float gpsbb_test_track_ms(gpsbb *h)
         return -1.0f;
     return ms;
 }
+
+extern "C" float gpsbb_test_fir_ms(gpsbb *h)
+{
+    float ms = -1.0f;
+    if (!h || !h->fir_ev[0] || !h->fir_ev[1] || hipEventElapsedTime(&ms, h->fir_ev[0], h->fir_ev[1]) != hipSuccess)
+        return -1.0f;
+    return ms;
+}
+
+extern "C" int gpsbb_test_fir_tile(void) { return FIR_TILE; }
 
 #ifdef GPSBB_WG_TRACE
 /* The workgroup trace of the measurement build (gpsbb_kernels.hip.h: wg_trace_leave; make trace; tools/corun_diag.py).

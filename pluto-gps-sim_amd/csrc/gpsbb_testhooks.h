@@ -88,6 +88,9 @@ float gpsbb_test_despread_ms(struct gpsbb_batch *b);
 float gpsbb_test_acquire_ms(struct gpsbb *h);
 /* ... and the kernel of its last gpsbb_device_track (k_track) */
 float gpsbb_test_track_ms(struct gpsbb *h);
+/* ... and of its last gpsbb_device_fir (k_fir); the outputs one of k_fir's workgroups takes (FIR_TILE) */
+float gpsbb_test_fir_ms(struct gpsbb *h);
+int gpsbb_test_fir_tile(void);
 /* the state granule of the batch's tile tables as log2 of its tiles: the code rows' (BatchDev::st_log2) and the carrier rows'
  * (ev_carr_log2 of it, gpsbb_events.hip.h) */
 int gpsbb_test_state_log2(struct gpsbb_batch *b);

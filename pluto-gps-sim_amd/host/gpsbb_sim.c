@@ -3,7 +3,8 @@
  * reference's own program structure (front end -> fill -> TX hand-off) and the fill done on an MI355X.
  *
  *   gpsbb-sim -e nav.14n [-l lat,lon,h | -c x,y,z | -u motion.csv] [-t Y/M/D,h:m:s] [-T] [-i] [-3]
- *             [-s fs_hz] [-d seconds] [-n samples_per_block] [-N channels] [-g gpu] [-F] [-b 1|8|16] [-q shift] -o out.bin
+ *             [-s fs_hz] [-d seconds] [-n samples_per_block] [-N channels] [-g gpu] [-F] [-b 1|8|16] [-q shift]
+ *             [-D decim[,ntaps[,cutoff[,atten_db]]]] -o out.bin
  *
  * Options mirror the reference's (plutogpssim.c:1991-2012, 2296-2390) where they concern the signal; the
  * Pluto-specific ones (-A -B -U -N host) have no meaning here.  -n defaults to 300000, the reference's
@@ -46,6 +47,13 @@
  * within clip_ppm parts per million are taken (gpsbb_level_choose; 100 is the usual budget).  The run then goes on exactly as if
  * those shifts had been given: the bytes are those of the explicit options, on every path.  The choice is made once, from the
  * first second: a power change later in the run shows up in the clip counters, not in the scale.
+ * -D decim[,ntaps[,cutoff[,atten_db]]] puts a front-end filter before the sample format (include/gpsbb.h gpsbb_device_fir): the front
+ * end and the render run at -s times decim (-n counts samples of the file: a block is rendered decim times as long), a Kaiser-windowed
+ * sinc of ntaps taps (default 8 * decim + 1; gpsbb_fir_make: cutoff as a fraction of the file's Nyquist rate, default 0.8, and 60 dB)
+ * band-limits it, every decim-th output is kept, and the file is written at -s in the -b format.  -W and -J apply at the rendered
+ * rate, in the filter's view of its input.  A path of its own from public calls: a device-only ring with chained pushes, per popped
+ * slot gpsbb_device_fir with the history carried from slot to slot, then gpsbb_device_pack and the write.  Not together with -A
+ * (which measures the level before the filter), -P, -k, -S, -R or -G.
  */
 #include <math.h>
 #include <stdio.h>
@@ -296,6 +304,9 @@ static void usage(void)
                     "                 [-A clip_ppm]   choose the -W/-j shift and -q from the level of the first second (up to 10 blocks),\n"
                     "                                 once: a later power change shows in the clip counters, not in the scale;\n"
                     "                                 not together with -q, -j or a shift inside -W cn0,shift\n"
+                    "                 [-D decim[,ntaps[,cutoff[,atten_db]]]]   render at -s times decim (1..16), band-limit with a Kaiser-windowed\n"
+                    "                                 sinc (default 8 * decim + 1 taps, cutoff 0.8 of the file's Nyquist rate, 60 dB) and write\n"
+                    "                                 every decim-th sample at -s; -W and -J act at the rendered rate; not with -A -P -k -S -R -G\n"
                     "                 -o out.bin\n");
 }
 
@@ -324,6 +335,7 @@ int main(int argc, char **argv)
     const char *out_path = NULL;
     int bits = 16, shift = 5, shift_given = 0;
     const char *agc_arg = NULL;
+    const char *decim_arg = NULL;
     const char *noise_arg = NULL;
     unsigned long long noise_seed = 1;
     const char *interf_arg[GPSBB_INTERF_MAX + 1];
@@ -332,7 +344,7 @@ int main(int argc, char **argv)
     const char *echo_arg[GPSFE_MAX_ECHOES + 1];
     int nechoarg = 0;
 
-    while ((opt = getopt(argc, argv, "e:u:c:l:s:Tt:in:N:d:o:g:3FG:P:S:k:Q:ICRb:q:W:w:J:j:A:M:")) != -1) {
+    while ((opt = getopt(argc, argv, "e:u:c:l:s:Tt:in:N:d:o:g:3FG:P:S:k:Q:ICRb:q:W:w:J:j:A:M:D:")) != -1) {
         switch (opt) {
         case 'e': cfg.navfile = optarg; break;
         case 'u': cfg.motion_file = optarg; break;
@@ -386,6 +398,7 @@ int main(int argc, char **argv)
         case 'b': bits = atoi(optarg); break;
         case 'q': shift = atoi(optarg); shift_given = 1; break;
         case 'A': agc_arg = optarg; break;
+        case 'D': decim_arg = optarg; break;
         case 'W': noise_arg = optarg; break;
         case 'w': noise_seed = strtoull(optarg, NULL, 0); break;
         case 'J':
@@ -418,9 +431,48 @@ int main(int argc, char **argv)
     }
     if (nsamp == 0)
         nsamp = fs_hz / 10;
+    /* -D: the filter, checked before anything is opened; from here on fs_hz and nsamp are the render's, nsamp_out the file's */
+    const long nsamp_out = nsamp;
+    int decim = 0;
+    gpsbb_fir_t fir;
+    memset(&fir, 0, sizeof fir);
+    if (decim_arg) {
+        double v[4] = {0.0, 0.0, 0.0, 0.0};
+        int n = 0, ok = 1;
+        for (const char *arg = decim_arg; ok;) {
+            char *end = NULL;
+            ok = n < 4;
+            if (!ok)
+                break;
+            v[n] = strtod(arg, &end);
+            ok = end != arg && isfinite(v[n]) && (*end == 0 || *end == ',');
+            n++;
+            if (!ok || *end == 0)
+                break;
+            arg = end + 1;
+        }
+        ok = ok && v[0] >= 1.0 && v[0] <= 16.0 && v[0] == (double)(int)v[0] && (n < 2 || (v[1] >= 1.0 && v[1] <= 1e6 && v[1] == (double)(int)v[1]));
+        decim = ok ? (int)v[0] : 0;
+        if (!ok || gpsbb_fir_make(&fir, n >= 2 ? (int)v[1] : 8 * decim + 1, decim, v[2], v[3]) != GPSBB_OK) {
+            fprintf(stderr, "ERROR: -D wants decim[,ntaps[,cutoff[,atten_db]]]: decim 1..16, ntaps 1..%d, a cutoff in (0, 1], at most 180 dB\n",
+                    GPSBB_FIR_MAX_TAPS);
+            return 1;
+        }
+        int refused = 0;
+        if (agc_arg) refused += fprintf(stderr, "ERROR: -D not together with -A: -A measures the level before the filter\n") > 0;
+        if (paced.period_ns) refused += fprintf(stderr, "ERROR: -D not together with -P: the filter's path is not paced\n") > 0;
+        if (paced.nkeep) refused += fprintf(stderr, "ERROR: -D not together with -k: the filter's path writes every block\n") > 0;
+        if (nshards > 0) refused += fprintf(stderr, "ERROR: -D not together with -G: the node driver has no filter stage\n") > 0;
+        if (stats_path || no_register)
+            refused += fprintf(stderr, "ERROR: -D not together with -S or -R: they belong to the block-by-block hand-off, which has no filter stage\n") > 0;
+        if (refused)
+            return 1;
+        fs_hz *= decim;
+        nsamp *= decim;
+    }
     /* the output format, the same bits on every path (fill, stream, node) */
     unsigned oflags = bits == 8 ? GPSBB_OUT_SC8(shift) : (bits == 1 ? GPSBB_OUT_SC1 : GPSBB_OUT_SC16);
-    const long obytes = gpsbb_out_bytes(oflags, nsamp);
+    const long obytes = gpsbb_out_bytes(oflags, nsamp_out);
     if (obytes < 0) {
         fprintf(stderr, "ERROR: -b %d needs a block of a multiple of 4 samples (-n)\n", bits);
         return 1;
@@ -597,6 +649,75 @@ int main(int argc, char **argv)
     if (!fout) {
         fprintf(stderr, "ERROR: cannot open %s\n", out_path);
         return 1;
+    }
+    if (decim) {
+        /* -D: render at the input rate into a device-only ring, filter each popped slot on the device with the history carried,
+         * pack what is left and write it.  The decimated slot needs device memory and the ABI hands out none by itself: it is
+         * the output buffer of a resident batch of the slot's shape at the file's rate, run once and then only written to. */
+        const int bps = nblocks < 4 ? (int)(nblocks > 0 ? nblocks : 1) : 4, depth = 3;
+        gpsbb_stream_t *st = NULL;
+        gpsbb_batch_t *room = NULL;
+        gpsfe_t *fe2 = NULL;
+        gpsbb_chan_t *slot = malloc((size_t)bps * nchan * sizeof *slot);
+        unsigned char *host = malloc((size_t)bps * (size_t)obytes);
+        int16_t hist[2 * GPSBB_FIR_MAX_TAPS];
+        memset(hist, 0, sizeof hist);
+        int16_t *d_out = NULL;
+        rc = slot && host ? GPSBB_OK : GPSBB_E_NOMEM;
+        if (rc == GPSBB_OK && (gpsfe_open(&cfg, &fe2) != GPSFE_OK || gpsfe_set_echoes(fe2, echo, necho) != GPSFE_OK))
+            rc = GPSBB_E_STATE;
+        if (rc == GPSBB_OK) {
+            gpsfe_generate(fe2, bps, slot);
+            rc = gpsbb_batch_create(bb, slot, bps, nchan, delt * decim, (int)nsamp_out, GPSBB_CHAIN_CARRIER, &room);
+        }
+        if (rc == GPSBB_OK) rc = gpsbb_batch_run(room, NULL);
+        if (rc == GPSBB_OK) rc = gpsbb_sync(bb);
+        if (rc == GPSBB_OK && !(d_out = gpsbb_batch_device_iq(room))) rc = GPSBB_E_STATE;
+        if (rc == GPSBB_OK)
+            rc = gpsbb_stream_create(bb, nchan, delt, (int)nsamp, bps, depth, GPSBB_CHAIN_CARRIER | GPSBB_STREAM_DEVICE_ONLY, &st);
+        long pushed = 0, written = 0;
+        uint64_t pos = 0, clipped = 0;
+        while (rc == GPSBB_OK && written < nblocks) {
+            while (rc == GPSBB_OK && pushed < nblocks && gpsbb_stream_pending(st) < depth) {
+                gpsfe_generate(fe, bps, slot); /* a short last slot is padded with blocks that are generated but not written */
+                rc = gpsbb_stream_push(st, slot);
+                pushed += bps;
+            }
+            const int16_t *d_iq = NULL;
+            if (rc == GPSBB_OK)
+                rc = gpsbb_stream_pop(st, &d_iq, NULL);
+            if (rc == GPSBB_OK) {
+                uint64_t c = 0;
+                nz.sample0 = jset.sample0 = pos;
+                rc = gpsbb_device_fir(bb, d_iq, (long)bps * nsamp, noise, interf, &fir, hist, hist, d_out, &c);
+                pos += (uint64_t)bps * (uint64_t)nsamp;
+                clipped += c;
+            }
+            if (rc == GPSBB_OK)
+                rc = gpsbb_device_pack(bb, d_out, bps, (int)nsamp_out, oflags, host);
+            if (rc == GPSBB_OK) {
+                const long n = nblocks - written < bps ? nblocks - written : bps;
+                if (fwrite(host, (size_t)obytes, (size_t)n, fout) != (size_t)n)
+                    rc = GPSBB_E_STATE;
+                written += n;
+            }
+        }
+        if (rc != GPSBB_OK)
+            fprintf(stderr, "ERROR: -D: %s\n", gpsbb_strerror(rc));
+        fprintf(stderr, "filter: %d taps, decimation %d, shift %d; components clipped: %llu\n", fir.ntaps, fir.decim, fir.shift,
+                (unsigned long long)clipped);
+        if (st) gpsbb_stream_destroy(st);
+        if (room) gpsbb_batch_destroy(room);
+        report_clipped(bb, bits, 0);
+        free(slot);
+        free(host);
+        if (fout != stdout)
+            fclose(fout);
+        gpsbb_destroy(bb);
+        if (fe2) gpsfe_close(fe2);
+        gpsfe_close(fe);
+        fprintf(stderr, "%ld blocks of %ld samples written\n", written, nsamp_out);
+        return rc == GPSBB_OK ? 0 : 1;
     }
     if (fast) {
         /* offline generation: slots of up to 16 blocks through the ring, three in flight */
