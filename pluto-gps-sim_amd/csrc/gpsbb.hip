@@ -495,112 +495,7 @@ constexpr unsigned STREAM_SEED_STREAMS = 2; /* pre-passes of a stream's pushes i
                                                queue to itself: a pre-pass that shares a queue with the synthesis, or with a stream that holds a
                                                wait for one, runs after it and not beside it */
 
-struct gpsbb {
-    int device = 0;
-    /* The streams (DESIGN 4.1).  gpsbb_create makes the first three: with the process's null stream they are what the steady state
-     * of a chained ring or of a re-run batch keeps busy, one hardware queue each at HIP's default of four.  The others exist once
-     * something has asked for them. */
-    hipStream_t s_seed = nullptr;    /* pre-pass: the descriptor and plan uploads of a set-up, then the NCO pre-pass (k_lap_*, k_seed, ...) */
-    hipStream_t s_more[SEED_STREAMS_MAX - 1] = {}; /* ... [0] the second one: every other batch, every other push of a stream, every other
-                                                      run of a batch with three table sets (batch_prepass_stream); [1..] experiments only */
-    unsigned batches_created = 0;
-    hipStream_t s_compute = nullptr; /* synthesis kernel, and what merely follows it in order: a device-only ring's end states and digests */
-    hipStream_t s_compute2 = nullptr; /* (experiments, GPSBB_TWO_COMPUTE_STREAMS: the synthesis of every other launch; created on first use) */
-    unsigned compute_turn = 0;
-    hipStream_t s_copy = nullptr;    /* host-bound output of a ring: gather, pack and noise kernels into pinned memory; created by the first
-                                        push that has any.  A device-only ring never touches it */
-    hipStream_t s_digest = nullptr;  /* gpsbb_slot_digest, created on first use: a stream nothing else waits on (the copy stream holds a
-                                        wait for every push in flight: a digest queued there ran when the whole ring had drained) */
-    std::vector<uint32_t> h_ca;      /* host copy of the C/A chips (seeding of small batches on the host)  */
-    unsigned long long host_dwrd_oob = 0, host_itable_512 = 0; /* hazards counted by host-side seeding      */
-    WorkPool *pool = nullptr;        /* host threads for seeding small batches (created on first use)      */
-    int32_t *d_tabs = nullptr;
-    uint32_t *d_ca = nullptr;
-    uint32_t *d_status = nullptr;
-    unsigned long long *d_hz = nullptr;
-    unsigned long long *d_clip = nullptr; /* GPSBB_INFO_SC8_CLIPPED: the packing kernels add their saturated components here */
-    unsigned char *d_pack = nullptr;      /* device scratch of a packed fill / gpsbb_device_pack, kept between calls */
-    int2 *d_noise_tab = nullptr;          /* the noise's knots (K[i], K[i + 1] - K[i]) and ... */
-    unsigned long long *d_nclip = nullptr; /* ... GPSBB_INFO_NOISE_CLIPPED: both on the first call with noise */
-    size_t pack_cap = 0;
-    LevelOut *d_level = nullptr;          /* gpsbb_device_level's result on the device, kept between calls */
-    size_t level_cap = 0;                 /* ... in blocks */
-    int last_hip = 0;
-    gpsbb_batch *scratch = nullptr;
-    unsigned char *h_bounce = nullptr; /* pinned: a fill whose iq_out lies partly in a registered range is copied through here */
-    size_t bounce_cap = 0;
-    unsigned char *h_fill = nullptr; /* pinned: what the drop-in call brings back besides the IQ — the end states and the status word
-                                        (fill_block_finish) */
-    struct HostReg { char *host; char *dev; size_t bytes; };
-    std::vector<HostReg> host_regs;         /* gpsbb_host_register: host ranges the device writes straight into */
-    struct ChainOnly *chain_only = nullptr; /* device scratch of gpsbb_chain_carrier, kept between calls */
-    int sm_count = 0;
-    /* per-handle options (gpsbb_set_option) */
-    int opt_seed_where = 0;   /* 0 by size (on the device: lap-parallel where eligible), 1 always the row walks (k_seed / k_walk), 2 always
-                                 host threads, 3 always on the device, lap-parallel where eligible */
-    int opt_synth_kernel = 0; /* 0 automatic, 1 always the per-sample kernel */
-    int opt_skip_seed = 0;    /* measurement: re-use the tables of the first two runs of a batch */
-    int opt_chain_where = 0;  /* GPSBB_CHAIN_CARRIER: 0 automatic (on the device wherever the pre-pass runs there), 1 host threads,
-                                 2 as 0 with the fix-up walking the blocks in order (k_chain_fix instead of k_chain_fix_par) */
-    int last_kernel = 0;      /* synthesis kernel of the last launch: 1 per-sample, 2 breakpoint */
-    int last_variant = 0;     /* ... and which one exactly: GPSBB_VARIANT_* */
-    int last_chain_dev = 0;   /* the last launch resolved GPSBB_CHAIN_CARRIER on the device */
-    int last_prepass = 0;     /* pre-pass of the last launch: 1 row walks on the device, 2 host threads, 3 lap-parallel on the device */
-    struct DigestBuf { /* gpsbb_device_digest's scratch, kept between calls */
-        unsigned long long *p = nullptr;
-        size_t cap = 0;
-        int reserve(size_t n)
-        {
-            if (n <= cap)
-                return hipSuccess;
-            if (p)
-                (void)hipFree(p);
-            p = nullptr;
-            cap = 0;
-            const hipError_t e = hipMalloc((void **)&p, n * sizeof(unsigned long long));
-            if (e == hipSuccess)
-                cap = n;
-            return e;
-        }
-    } d_digest;
-#ifdef GPSBB_EXPERIMENTS
-    hipEvent_t acq_ev[2] = {}; /* around the last gpsbb_device_acquire's kernels, gpsbb_test_acquire_ms */
-    hipEvent_t trk_ev[2] = {}; /* around the last gpsbb_device_track's kernel, gpsbb_test_track_ms */
-    hipEvent_t fir_ev[2] = {}; /* around the last gpsbb_device_fir's kernel, gpsbb_test_fir_ms */
-#endif
-    DigestBuf d_acq_chips, d_acq_rows; /* gpsbb_device_acquire's scratch, kept between calls (in 8-byte words): the expanded chips; the
-                                          tiles' partials with the rows behind them */
-    DigestBuf d_acq_grid;              /* ... and the grid where wanted (up to 512 MiB, for tests and plots): freed when the call
-                                          that asked for it has copied it out, here only while that call runs or after it failed */
-    DigestBuf d_trk;                   /* gpsbb_device_track's scratch, null until the first call: the states, the counts, the records */
-    DigestBuf d_fir;                   /* gpsbb_device_fir's scratch, null until the first call: the clip count, the two histories */
-};
-
-/* every stream the handle has created, in no particular order */
-template <class F>
-static void for_each_stream(const gpsbb *h, F f)
-{
-    for (hipStream_t st : {h->s_seed, h->s_compute, h->s_compute2, h->s_copy, h->s_digest})
-        if (st)
-            f(st);
-    for (hipStream_t st : h->s_more)
-        if (st)
-            f(st);
-}
-
-/* Wait for everything the handle has enqueued, whichever stream holds it: before memory any of it may touch is freed,
- * unregistered or read by the host (gpsbb_sync, the destroy calls, gpsbb_host_unregister).  An idle stream costs a call. */
-static hipError_t drain_streams(const gpsbb *h)
-{
-    hipError_t first = hipSuccess;
-    for_each_stream(h, [&](hipStream_t st) {
-        const hipError_t e = hipStreamSynchronize(st);
-        if (first == hipSuccess)
-            first = e;
-    });
-    return first;
-}
-
+/* device memory that is kept between calls and only ever grows */
 template <class T>
 struct DevBuf {
     T *p = nullptr;
@@ -639,6 +534,135 @@ template <class... B>
 static void release_all(B &...b)
 {
     (b.release(), ...);
+}
+
+/* Two events around the kernels of a call's last run, for the experiments build's gpsbb_test_*_ms hooks: without
+ * GPSBB_EXPERIMENTS start and stop do nothing, and no event is ever made. */
+struct KernelTimer {
+    hipEvent_t ev[2] = {};
+    hipError_t start(hipStream_t stream)
+    {
+#ifdef GPSBB_EXPERIMENTS
+        for (hipEvent_t &e : ev)
+            if (!e) {
+                const hipError_t rc = hipEventCreate(&e);
+                if (rc != hipSuccess)
+                    return rc;
+            }
+        return hipEventRecord(ev[0], stream);
+#else
+        return hipSuccess;
+#endif
+    }
+    hipError_t stop(hipStream_t stream)
+    {
+#ifdef GPSBB_EXPERIMENTS
+        return hipEventRecord(ev[1], stream);
+#else
+        return hipSuccess;
+#endif
+    }
+    /* milliseconds between the two, once both have happened; -1: nothing was timed yet */
+    float ms() const
+    {
+        float t = -1.0f;
+        return ev[0] && ev[1] && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess ? t : -1.0f;
+    }
+    void release()
+    {
+        for (hipEvent_t &e : ev) {
+            if (e)
+                (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+    }
+};
+
+struct gpsbb {
+    int device = 0;
+    /* The streams (DESIGN 4.1).  gpsbb_create makes the first three: with the process's null stream they are what the steady state
+     * of a chained ring or of a re-run batch keeps busy, one hardware queue each at HIP's default of four.  The others exist once
+     * something has asked for them. */
+    hipStream_t s_seed = nullptr;    /* pre-pass: the descriptor and plan uploads of a set-up, then the NCO pre-pass (k_lap_*, k_seed, ...) */
+    hipStream_t s_more[SEED_STREAMS_MAX - 1] = {}; /* ... [0] the second one: every other batch, every other push of a stream, every other
+                                                      run of a batch with three table sets (batch_prepass_stream); [1..] experiments only */
+    unsigned batches_created = 0;
+    hipStream_t s_compute = nullptr; /* synthesis kernel, and what merely follows it in order: a device-only ring's end states and digests */
+    hipStream_t s_compute2 = nullptr; /* (experiments, GPSBB_TWO_COMPUTE_STREAMS: the synthesis of every other launch; created on first use) */
+    unsigned compute_turn = 0;
+    hipStream_t s_copy = nullptr;    /* host-bound output of a ring: gather, pack and noise kernels into pinned memory; created by the first
+                                        push that has any.  A device-only ring never touches it */
+    hipStream_t s_digest = nullptr;  /* gpsbb_slot_digest, created on first use: a stream nothing else waits on (the copy stream holds a
+                                        wait for every push in flight: a digest queued there ran when the whole ring had drained) */
+    std::vector<uint32_t> h_ca;      /* host copy of the C/A chips (seeding of small batches on the host)  */
+    unsigned long long host_dwrd_oob = 0, host_itable_512 = 0; /* hazards counted by host-side seeding      */
+    WorkPool *pool = nullptr;        /* host threads for seeding small batches (created on first use)      */
+    int32_t *d_tabs = nullptr;
+    uint32_t *d_ca = nullptr;
+    uint32_t *d_status = nullptr;
+    unsigned long long *d_hz = nullptr;
+    unsigned long long *d_clip = nullptr; /* GPSBB_INFO_SC8_CLIPPED: the packing kernels add their saturated components here */
+    int2 *d_noise_tab = nullptr;          /* the noise's knots (K[i], K[i + 1] - K[i]) and ... */
+    unsigned long long *d_nclip = nullptr; /* ... GPSBB_INFO_NOISE_CLIPPED: both on the first call with noise */
+    int last_hip = 0;
+    gpsbb_batch *scratch = nullptr;
+    unsigned char *h_bounce = nullptr; /* pinned: a fill whose iq_out lies partly in a registered range is copied through here */
+    size_t bounce_cap = 0;
+    unsigned char *h_fill = nullptr; /* pinned: what the drop-in call brings back besides the IQ — the end states and the status word
+                                        (fill_block_finish) */
+    struct HostReg { char *host; char *dev; size_t bytes; };
+    std::vector<HostReg> host_regs;         /* gpsbb_host_register: host ranges the device writes straight into */
+    struct ChainOnly *chain_only = nullptr; /* device scratch of gpsbb_chain_carrier, kept between calls */
+    int sm_count = 0;
+    /* per-handle options (gpsbb_set_option) */
+    int opt_seed_where = 0;   /* 0 by size (on the device: lap-parallel where eligible), 1 always the row walks (k_seed / k_walk), 2 always
+                                 host threads, 3 always on the device, lap-parallel where eligible */
+    int opt_synth_kernel = 0; /* 0 automatic, 1 always the per-sample kernel */
+    int opt_skip_seed = 0;    /* measurement: re-use the tables of the first two runs of a batch */
+    int opt_chain_where = 0;  /* GPSBB_CHAIN_CARRIER: 0 automatic (on the device wherever the pre-pass runs there), 1 host threads,
+                                 2 as 0 with the fix-up walking the blocks in order (k_chain_fix instead of k_chain_fix_par) */
+    int last_kernel = 0;      /* synthesis kernel of the last launch: 1 per-sample, 2 breakpoint */
+    int last_variant = 0;     /* ... and which one exactly: GPSBB_VARIANT_* */
+    int last_chain_dev = 0;   /* the last launch resolved GPSBB_CHAIN_CARRIER on the device */
+    int last_prepass = 0;     /* pre-pass of the last launch: 1 row walks on the device, 2 host threads, 3 lap-parallel on the device */
+    /* The scratch of the calls that read device IQ, null until the first call that needs it and kept between calls.  One that is
+     * outgrown comes back a quarter larger than asked (DevBuf::reserve): more memory held, the same results. */
+    DevBuf<unsigned char> d_pack;          /* a packed fill's / gpsbb_device_pack's bytes */
+    DevBuf<LevelOut> d_level;              /* gpsbb_device_level's result, per block */
+    DevBuf<unsigned long long> d_digest;   /* gpsbb_device_digest's and gpsbb_slot_digest's sums, per block */
+    DevBuf<unsigned long long> d_acq_chips, d_acq_rows; /* gpsbb_device_acquire's (in 8-byte words): the expanded chips; the tiles'
+                                                           partials with the rows behind them */
+    DevBuf<unsigned long long> d_acq_grid; /* ... and the grid where wanted (up to 512 MiB, for tests and plots): released when the call
+                                              that asked for it has copied it out, here only while that call runs or after it failed:
+                                              but for that, a first allocation every time, of exactly what was asked */
+    DevBuf<unsigned long long> d_trk;      /* gpsbb_device_track's: the states, the counts, the records */
+    DevBuf<unsigned long long> d_fir;      /* gpsbb_device_fir's: the clip count, the two histories */
+    KernelTimer acq_tm, trk_tm, fir_tm;    /* around the kernels of the last gpsbb_device_acquire, _track, _fir (gpsbb_test_*_ms) */
+};
+
+/* every stream the handle has created, in no particular order */
+template <class F>
+static void for_each_stream(const gpsbb *h, F f)
+{
+    for (hipStream_t st : {h->s_seed, h->s_compute, h->s_compute2, h->s_copy, h->s_digest})
+        if (st)
+            f(st);
+    for (hipStream_t st : h->s_more)
+        if (st)
+            f(st);
+}
+
+/* Wait for everything the handle has enqueued, whichever stream holds it: before memory any of it may touch is freed,
+ * unregistered or read by the host (gpsbb_sync, the destroy calls, gpsbb_host_unregister).  An idle stream costs a call. */
+static hipError_t drain_streams(const gpsbb *h)
+{
+    hipError_t first = hipSuccess;
+    for_each_stream(h, [&](hipStream_t st) {
+        const hipError_t e = hipStreamSynchronize(st);
+        if (first == hipSuccess)
+            first = e;
+    });
+    return first;
 }
 
 /* The lap-parallel pre-pass's device scratch (gpsbb_laps.hip.h: what LapDev points at): one per table set of a batch, one for
@@ -882,7 +906,7 @@ struct gpsbb_batch {
     DevBuf<unsigned long long> d_ds;
     DevBuf<int32_t> d_ds_ctr;
     unsigned long long ds_last_exact = 0;
-    hipEvent_t ds_ev[2] = {}; /* (experiments build: around the last k_despread, gpsbb_test_despread_ms) */
+    KernelTimer ds_tm; /* around the last k_despread (gpsbb_test_despread_ms) */
 };
 
 #define HIPCHK(h, call)                                                                            \
@@ -1047,30 +1071,12 @@ extern "C" void gpsbb_destroy(gpsbb_t *h)
         (void)hipFree(h->d_hz);
     if (h->d_clip)
         (void)hipFree(h->d_clip);
-    if (h->d_pack)
-        (void)hipFree(h->d_pack);
     if (h->d_noise_tab)
         (void)hipFree(h->d_noise_tab);
     if (h->d_nclip)
         (void)hipFree(h->d_nclip);
-    if (h->d_digest.p)
-        (void)hipFree(h->d_digest.p);
-    if (h->d_level)
-        (void)hipFree(h->d_level);
-#ifdef GPSBB_EXPERIMENTS
-    for (hipEvent_t e : h->acq_ev)
-        if (e)
-            (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->trk_ev)
-        if (e)
-            (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->fir_ev)
-        if (e)
-            (void)hipEventDestroy(e);
-#endif
-    for (gpsbb::DigestBuf *b : {&h->d_acq_chips, &h->d_acq_rows, &h->d_acq_grid, &h->d_trk, &h->d_fir})
-        if (b->p)
-            (void)hipFree(b->p);
+    release_all(h->d_pack, h->d_level, h->d_digest, h->d_acq_chips, h->d_acq_rows, h->d_acq_grid, h->d_trk, h->d_fir);
+    release_all(h->acq_tm, h->trk_tm, h->fir_tm);
     delete h->pool;
     h->pool = nullptr;
     for_each_stream(h, [](hipStream_t st) { (void)hipStreamDestroy(st); });
@@ -1468,10 +1474,7 @@ extern "C" void gpsbb_batch_destroy(gpsbb_batch_t *b)
         (void)hipHostFree(b->hs_tile_x);
     if (b->hs_tile_nav)
         (void)hipHostFree(b->hs_tile_nav);
-    release_all(b->d_iq, b->d_dig, b->d_ds, b->d_ds_ctr);
-    for (auto &e : b->ds_ev)
-        if (e)
-            (void)hipEventDestroy(e);
+    release_all(b->d_iq, b->d_dig, b->d_ds, b->d_ds_ctr, b->ds_tm);
     for (auto &t : b->evs)
         for (auto &e : t.e)
             if (e)
@@ -2140,29 +2143,36 @@ extern "C" int gpsbb_device_read(gpsbb_t *h, void *host_dst, const void *device_
     return GPSBB_OK;
 }
 
+/* How every call that reads device IQ begins, once its arguments have passed: the device; then the work of every launch the
+ * caller may be reading the output of is on this handle's streams, so wait for it (what follows goes on the synthesis stream,
+ * ordered behind everything the handle rendered); then, for a call with noise, the knot table.  Returns a GPSBB_* code. */
+static int iq_call_begin(gpsbb *h, bool noise);
+
+/* both digest calls: k_block_digest over nblocks blocks at d_iq on `stream`, about wgs workgroups in all, and the sums copied out */
+static int digest_blocks(gpsbb *h, hipStream_t stream, long wgs, const int16_t *d_iq, long nblocks, int nsamp, uint64_t *digest_out)
+{
+    HIPCHK(h, (hipError_t)h->d_digest.reserve((size_t)nblocks));
+    HIPCHK(h, hipMemsetAsync(h->d_digest.p, 0, (size_t)nblocks * sizeof(unsigned long long), stream));
+    /* enough workgroups per block to fill the chip however few blocks there are, never pieces below 4 KB */
+    long chunks = (wgs + nblocks - 1) / nblocks;
+    const long max_chunks = ((long)nsamp + 1023) / 1024;
+    chunks = chunks > max_chunks ? max_chunks : (chunks < 1 ? 1 : chunks);
+    hipLaunchKernelGGL(k_block_digest, dim3((unsigned)chunks, (unsigned)nblocks), dim3(256), 0, stream, (const uint32_t *)d_iq, nsamp, h->d_digest.p);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(digest_out, h->d_digest.p, (size_t)nblocks * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIPCHK(h, hipStreamSynchronize(stream));
+    return GPSBB_OK;
+}
+
 extern "C" int gpsbb_device_digest(gpsbb_t *h, const int16_t *d_iq, long nblocks, int nsamp, uint64_t *digest_out)
 {
     if (!h || !d_iq || !digest_out || nblocks < 1 || nblocks > 65535 || nsamp < 1)
         return GPSBB_E_BADARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    /* the work of every launch the caller may be reading the output of is on this handle's streams: wait for it, then digest on
-     * the synthesis stream (ordered behind everything the handle rendered) */
-    const int rc = gpsbb_sync(h);
-    if (rc != GPSBB_OK)
-        return rc;
-    HIPCHK(h, (hipError_t)h->d_digest.reserve((size_t)nblocks));
-    HIPCHK(h, hipMemsetAsync(h->d_digest.p, 0, (size_t)nblocks * sizeof(unsigned long long), h->s_compute));
-    /* enough workgroups per block to fill the chip however few blocks there are, never pieces below 4 KB */
-    long chunks = (2048 + nblocks - 1) / nblocks;
-    const long max_chunks = ((long)nsamp + 1023) / 1024;
-    chunks = chunks > max_chunks ? max_chunks : (chunks < 1 ? 1 : chunks);
-    hipLaunchKernelGGL(k_block_digest, dim3((unsigned)chunks, (unsigned)nblocks), dim3(256), 0, h->s_compute, (const uint32_t *)d_iq, nsamp, h->d_digest.p);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(digest_out, h->d_digest.p, (size_t)nblocks * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->s_compute));
-    HIPCHK(h, hipStreamSynchronize(h->s_compute));
-    return GPSBB_OK;
+    const int rc = iq_call_begin(h, false);
+    return rc != GPSBB_OK ? rc : digest_blocks(h, h->s_compute, 2048, d_iq, nblocks, nsamp, digest_out);
 }
 
+/* (no wait for the handle: a ring's slot is digested while the pushes behind it run) */
 extern "C" int gpsbb_slot_digest(gpsbb_t *h, const int16_t *d_iq, long nblocks, int nsamp, uint64_t *digest_out)
 {
     if (!h || !d_iq || !digest_out || nblocks < 1 || nblocks > 65535 || nsamp < 1)
@@ -2170,17 +2180,7 @@ extern "C" int gpsbb_slot_digest(gpsbb_t *h, const int16_t *d_iq, long nblocks, 
     HIPCHK(h, hipSetDevice(h->device));
     if (!h->s_digest)
         HIPCHK(h, hipStreamCreateWithFlags(&h->s_digest, hipStreamNonBlocking));
-    hipStream_t cs = h->s_digest;
-    HIPCHK(h, (hipError_t)h->d_digest.reserve((size_t)nblocks));
-    HIPCHK(h, hipMemsetAsync(h->d_digest.p, 0, (size_t)nblocks * sizeof(unsigned long long), cs));
-    long chunks = (GPSBB_KNOB_LONG("GPSBB_SLOT_DIGEST_WGS", 2048) + nblocks - 1) / nblocks;
-    const long max_chunks = ((long)nsamp + 1023) / 1024;
-    chunks = chunks > max_chunks ? max_chunks : (chunks < 1 ? 1 : chunks);
-    hipLaunchKernelGGL(k_block_digest, dim3((unsigned)chunks, (unsigned)nblocks), dim3(256), 0, cs, (const uint32_t *)d_iq, nsamp, h->d_digest.p);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(digest_out, h->d_digest.p, (size_t)nblocks * sizeof(unsigned long long), hipMemcpyDeviceToHost, cs));
-    HIPCHK(h, hipStreamSynchronize(cs));
-    return GPSBB_OK;
+    return digest_blocks(h, h->s_digest, GPSBB_KNOB_LONG("GPSBB_SLOT_DIGEST_WGS", 2048), d_iq, nblocks, nsamp, digest_out);
 }
 
 extern "C" int gpsbb_get_hazards(gpsbb_t *h, gpsbb_hazards_t *out, int reset)
@@ -2311,28 +2311,13 @@ extern "C" long gpsbb_out_bytes(unsigned flags, long nsamp)
 struct ImpairCall;
 static hipError_t out_launch(gpsbb *h, int fmt, int shift8, const ImpairCall *ic, const int16_t *src, void *dst, size_t n, hipStream_t stream);
 
-static hipError_t pack_reserve(gpsbb *h, size_t bytes)
-{
-    if (bytes <= h->pack_cap)
-        return hipSuccess;
-    if (h->d_pack)
-        (void)hipFree(h->d_pack);
-    h->d_pack = nullptr;
-    h->pack_cap = 0;
-    const hipError_t e = hipMalloc((void **)&h->d_pack, bytes);
-    if (e == hipSuccess)
-        h->pack_cap = bytes;
-    return e;
-}
-
 extern "C" int gpsbb_device_pack(gpsbb_t *h, const int16_t *d_iq, long nblocks, int nsamp, unsigned flags, void *host_dst)
 {
     int shift;
     const int fmt = out_format(flags, nsamp, &shift);
     if (!h || !d_iq || !host_dst || nblocks < 1 || nsamp < 1 || fmt < 0 || (flags & 0xffu))
         return GPSBB_E_BADARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    const int rc = gpsbb_sync(h); /* as gpsbb_device_digest: whatever the handle was rendering into d_iq is there */
+    const int rc = iq_call_begin(h, false);
     if (rc != GPSBB_OK)
         return rc;
     const size_t bytes = (size_t)nblocks * out_block_bytes(fmt, (size_t)nsamp);
@@ -2340,9 +2325,9 @@ extern "C" int gpsbb_device_pack(gpsbb_t *h, const int16_t *d_iq, long nblocks, 
         HIPCHK(h, hipMemcpy(host_dst, d_iq, bytes, hipMemcpyDeviceToHost));
         return GPSBB_OK;
     }
-    HIPCHK(h, pack_reserve(h, bytes));
-    HIPCHK(h, out_launch(h, fmt, shift, nullptr, d_iq, h->d_pack, (size_t)nblocks * (size_t)nsamp * 2, h->s_compute));
-    HIPCHK(h, hipMemcpyAsync(host_dst, h->d_pack, bytes, hipMemcpyDeviceToHost, h->s_compute));
+    HIPCHK(h, (hipError_t)h->d_pack.reserve(bytes));
+    HIPCHK(h, out_launch(h, fmt, shift, nullptr, d_iq, h->d_pack.p, (size_t)nblocks * (size_t)nsamp * 2, h->s_compute));
+    HIPCHK(h, hipMemcpyAsync(host_dst, h->d_pack.p, bytes, hipMemcpyDeviceToHost, h->s_compute));
     HIPCHK(h, hipStreamSynchronize(h->s_compute));
     return GPSBB_OK;
 }
@@ -2457,6 +2442,17 @@ static hipError_t noise_ready(gpsbb *h)
         h->d_noise_tab = nullptr;
     }
     return e;
+}
+
+static int iq_call_begin(gpsbb *h, bool noise)
+{
+    HIPCHK(h, hipSetDevice(h->device));
+    const int rc = gpsbb_sync(h);
+    if (rc != GPSBB_OK)
+        return rc;
+    if (noise)
+        HIPCHK(h, noise_ready(h));
+    return GPSBB_OK;
 }
 
 extern "C" int gpsbb_device_noise(gpsbb_t *h, const int16_t *d_src, int16_t *d_dst, long nblocks, int nsamp, const gpsbb_noise_t *nz)
@@ -2697,11 +2693,9 @@ extern "C" int gpsbb_device_impair(gpsbb_t *h, const int16_t *d_src, int16_t *d_
     if (!h || !d_src || !d_dst || (!nz && !set) || nblocks < 1 || nsamp < 1 || (((uintptr_t)d_src | (uintptr_t)d_dst) & 1) ||
         !impair_make(nz, set, (uint64_t)nblocks * (uint64_t)nsamp, &c))
         return GPSBB_E_BADARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    const int rc = gpsbb_sync(h); /* as gpsbb_device_pack: whatever the handle was rendering into d_src is there */
+    const int rc = iq_call_begin(h, true); /* (noise or none: k_impair_iq is handed the table and the clip counter either way) */
     if (rc != GPSBB_OK)
         return rc;
-    HIPCHK(h, noise_ready(h));
     HIPCHK(h, out_launch(h, NOISE_SC16, 0, &c, d_src, d_dst, (size_t)nblocks * (size_t)nsamp * 2, h->s_compute));
     HIPCHK(h, hipStreamSynchronize(h->s_compute));
     return GPSBB_OK;
@@ -2731,6 +2725,12 @@ static bool level_fits(const ImpairArgs &a, bool noise, int nsamp)
     return bb * (unsigned __int128)nsamp < ((unsigned __int128)1 << 64);
 }
 
+/* How a call picks its kernel among K<noise, interf>, or for the calls that read a view K<view, noise, interf>: the table
+ * [noise][interf] or [fmt][noise][interf] of every instance, indexed by what the call was given */
+#define GPSBB_NI_KERNELS(K) {{K<false, false>, K<false, true>}, {K<true, false>, K<true, true>}}
+#define GPSBB_VNI_ROW(K, V) {{K<V, false, false>, K<V, false, true>}, {K<V, true, false>, K<V, true, true>}}
+#define GPSBB_VNI_KERNELS(K) {GPSBB_VNI_ROW(K, DS_SC16), GPSBB_VNI_ROW(K, PACK_SC8), GPSBB_VNI_ROW(K, PACK_SC1)}
+
 /* Enqueue k_level over nblocks blocks at src into d_out (zeroed on the stream first).  The grid: the flattened (block, chunk) list,
  * at most one workgroup per CU, as k_impair_iq's. */
 static hipError_t level_launch(gpsbb *h, const ImpairArgs &a, bool noise, const int16_t *src, long nblocks, int nsamp, LevelOut *d_out,
@@ -2743,14 +2743,9 @@ static hipError_t level_launch(gpsbb *h, const ImpairArgs &a, bool noise, const 
     const long long items = (long long)nblocks * cpb;
     const int gwg = (int)std::min<long long>(256, items);
     const bool interf = a.it.n > 0;
-#define GPSBB_LEVEL_GO(N, I) \
-    hipLaunchKernelGGL((k_level<N, I>), dim3(gwg), dim3(256), 0, stream, src, nblocks, nsamp, cpb, a, h->d_noise_tab, h->d_tabs, d_out)
-    if (noise) {
-        if (interf) GPSBB_LEVEL_GO(true, true); else GPSBB_LEVEL_GO(true, false);
-    } else {
-        if (interf) GPSBB_LEVEL_GO(false, true); else GPSBB_LEVEL_GO(false, false);
-    }
-#undef GPSBB_LEVEL_GO
+    typedef void (*LevelKernelFn)(const int16_t *, long, int, int, ImpairArgs, const int2 *, const int32_t *, LevelOut *);
+    static const LevelKernelFn k[2][2] = GPSBB_NI_KERNELS(k_level);
+    hipLaunchKernelGGL(k[noise][interf], dim3(gwg), dim3(256), 0, stream, src, nblocks, nsamp, cpb, a, h->d_noise_tab, h->d_tabs, d_out);
     return hipGetLastError();
 }
 
@@ -2761,22 +2756,12 @@ extern "C" int gpsbb_device_level(gpsbb_t *h, const int16_t *d_iq, long nblocks,
     if (!h || !d_iq || !out || nblocks < 1 || nsamp < 1 || ((uintptr_t)d_iq & 3) ||
         !impair_make(nz, set, (uint64_t)nblocks * (uint64_t)nsamp, &c) || !level_fits(c.a, c.noise, nsamp))
         return GPSBB_E_BADARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    const int rc = gpsbb_sync(h); /* as gpsbb_device_impair: whatever the handle was rendering into d_iq is there */
+    const int rc = iq_call_begin(h, c.noise);
     if (rc != GPSBB_OK)
         return rc;
-    if (c.noise)
-        HIPCHK(h, noise_ready(h));
-    if ((size_t)nblocks > h->level_cap) {
-        if (h->d_level)
-            (void)hipFree(h->d_level);
-        h->d_level = nullptr;
-        h->level_cap = 0;
-        HIPCHK(h, hipMalloc((void **)&h->d_level, (size_t)nblocks * sizeof(LevelOut)));
-        h->level_cap = (size_t)nblocks;
-    }
-    HIPCHK(h, level_launch(h, c.a, c.noise, d_iq, nblocks, nsamp, h->d_level, h->s_compute));
-    HIPCHK(h, hipMemcpyAsync(out, h->d_level, (size_t)nblocks * sizeof(LevelOut), hipMemcpyDeviceToHost, h->s_compute));
+    HIPCHK(h, (hipError_t)h->d_level.reserve((size_t)nblocks));
+    HIPCHK(h, level_launch(h, c.a, c.noise, d_iq, nblocks, nsamp, h->d_level.p, h->s_compute));
+    HIPCHK(h, hipMemcpyAsync(out, h->d_level.p, (size_t)nblocks * sizeof(LevelOut), hipMemcpyDeviceToHost, h->s_compute));
     HIPCHK(h, hipStreamSynchronize(h->s_compute));
     return GPSBB_OK;
 }
@@ -2904,16 +2889,22 @@ GPSBB_DS_KERNEL(DslKernelFn, dsl_kernel, k_despread_lags) /* ... at lags (gpsbb_
 #undef GPSBB_DS_V
 #undef GPSBB_DS_G
 
-/* what a view's impairments need of a call (gpsbb_batch_despread*, gpsbb_device_acquire), after noise_ready, which makes the table */
-static void ds_fill_impair(DsArgs &d, const gpsbb *h, const ImpairCall &ic)
+/* The view of a call that reads device IQ (gpsbb_batch_despread*, gpsbb_device_acquire, _track, _fir): the samples, PACK_SC8's
+ * shift and the call's impairments, everything else zero.  After iq_call_begin, which makes the table. */
+static DsArgs iq_view(const gpsbb *h, const void *d_iq, int shift8, const ImpairCall &ic)
 {
+    DsArgs d;
+    memset(&d, 0, sizeof d);
+    d.iq = static_cast<const uint32_t *>(d_iq);
+    d.shift8 = shift8;
     d.nz = ic.a.nz;
     d.ntab = h->d_noise_tab;
     d.it = ic.a.it;
+    return d;
 }
 
 /* the argument checks of every despreading call, in the order the tests pin, and what they settle of its arguments: the lags, the
- * source, the segments, the view's shift.  *fmt: the view's kernel number; *ic: the impairments, for ds_fill_impair */
+ * source and the view's shift (al->d.iq, al->d.shift8).  *fmt: the view's kernel number; *ic: the impairments, for iq_view */
 static int ds_make_args(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, const gpsbb_noise_t *nz, const gpsbb_interf_set_t *set,
                         int seg_tiles, const int *lags, int nlags, const gpsbb_corr_t *out, DslArgs *al, int *fmt, ImpairCall *ic)
 {
@@ -2939,14 +2930,8 @@ static int ds_make_args(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, co
      * tile states */
     if ((pl.flags & GPSBB_FIXED_CARRIER) || !pl.ev)
         return GPSBB_E_BADARG;
-    DsArgs &a = al->d;
-    a.iq = reinterpret_cast<const uint32_t *>(d_iq ? d_iq : b->last_iq);
-    if (!a.iq)
-        return GPSBB_E_STATE; /* the last run rendered into the caller's buffer: it has to be named */
-    a.seg_tiles = seg_tiles;
-    a.nseg = (int)gpsbb_despread_segments(pl.nsamp, seg_tiles);
-    a.danger = (uint32_t)GPSBB_KNOB_LONG("GPSBB_DS_DANGER", 2u * PD_BAND); /* (larger: more samples take the exact path; a test aid) */
-    return GPSBB_OK;
+    al->d.iq = reinterpret_cast<const uint32_t *>(d_iq ? d_iq : b->last_iq);
+    return al->d.iq ? GPSBB_OK : GPSBB_E_STATE; /* the last run rendered into the caller's buffer: it has to be named */
 }
 
 /* pure: the tiles a wavefront takes at a time and the workgroups of a block, for a device of cus compute units.  A chunk never
@@ -2974,13 +2959,13 @@ static int batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, 
     gpsbb *h = b->h;
     const BatchPlan &pl = b->plan;
     DsArgs &a = al.d;
-    HIPCHK(h, hipSetDevice(h->device));
-    rc = gpsbb_sync(h);
+    rc = iq_call_begin(h, ic.noise);
     if (rc != GPSBB_OK)
         return rc;
-    if (nz)
-        HIPCHK(h, noise_ready(h));
-    ds_fill_impair(a, h, ic);
+    a = iq_view(h, a.iq, a.shift8, ic);
+    a.seg_tiles = seg_tiles;
+    a.nseg = (int)gpsbb_despread_segments(pl.nsamp, seg_tiles);
+    a.danger = (uint32_t)GPSBB_KNOB_LONG("GPSBB_DS_DANGER", 2u * PD_BAND); /* (larger: more samples take the exact path; a test aid) */
     /* ---- scratch, zeroed: the sums, behind them the count of exact-path samples; the blocks' tile counters ---- */
     const size_t nsum = (size_t)pl.nblocks * pl.nch * (size_t)a.nseg * (size_t)(lags ? nlags : 1) * 2;
     HIPCHK(h, (hipError_t)b->d_ds.reserve(nsum + 1));
@@ -2994,21 +2979,14 @@ static int batch_despread(gpsbb_batch_t *b, const int16_t *d_iq, unsigned view, 
     /* ---- launch ---- */
     ds_geometry(pl.nblocks, pl.ntiles, seg_tiles, cu_count(h->sm_count), a.chunk, a.wgs_per_block);
     const BatchDev p = batch_dev(b, b->sets[b->last_set], batch_launch_plan(b));
-#ifdef GPSBB_EXPERIMENTS
-    for (auto &e : b->ds_ev)
-        if (!e)
-            HIPCHK(h, hipEventCreate(&e));
-    HIPCHK(h, hipEventRecord(b->ds_ev[0], cs));
-#endif
+    HIPCHK(h, b->ds_tm.start(cs));
     const dim3 grid((unsigned)((long)a.wgs_per_block * pl.nblocks));
     if (lags)
-        hipLaunchKernelGGL(dsl_kernel(fmt, nz != nullptr, p.st_log2, set != nullptr), grid, dim3(DS_WG), 0, cs, p, al);
+        hipLaunchKernelGGL(dsl_kernel(fmt, ic.noise, p.st_log2, ic.set), grid, dim3(DS_WG), 0, cs, p, al);
     else
-        hipLaunchKernelGGL(ds_kernel(fmt, nz != nullptr, p.st_log2, set != nullptr), grid, dim3(DS_WG), 0, cs, p, a);
+        hipLaunchKernelGGL(ds_kernel(fmt, ic.noise, p.st_log2, ic.set), grid, dim3(DS_WG), 0, cs, p, a);
     HIPCHK(h, hipGetLastError());
-#ifdef GPSBB_EXPERIMENTS
-    HIPCHK(h, hipEventRecord(b->ds_ev[1], cs));
-#endif
+    HIPCHK(h, b->ds_tm.stop(cs));
     /* ---- copy back ---- */
     HIPCHK(h, hipMemcpyAsync(out, b->d_ds.p, nsum * sizeof(unsigned long long), hipMemcpyDeviceToHost, cs));
     HIPCHK(h, hipMemcpyAsync(&b->ds_last_exact, b->d_ds.p + nsum, sizeof(unsigned long long), hipMemcpyDeviceToHost, cs));
@@ -3060,10 +3038,8 @@ extern "C" int gpsbb_acq_best(const gpsbb_acq_row_t *rows, const gpsbb_acq_cfg_t
 typedef void (*AcqKernelFn)(AcqArgs);
 static AcqKernelFn acq_kernel(int fmt, bool noise, bool interf)
 {
-#define GPSBB_AQ_ROW(V) {{k_acq<V, false, false>, k_acq<V, false, true>}, {k_acq<V, true, false>, k_acq<V, true, true>}}
-    static const AcqKernelFn k[3][2][2] = {GPSBB_AQ_ROW(DS_SC16), GPSBB_AQ_ROW(PACK_SC8), GPSBB_AQ_ROW(PACK_SC1)};
-#undef GPSBB_AQ_ROW
-    return k[fmt][noise ? 1 : 0][interf ? 1 : 0];
+    static const AcqKernelFn k[3][2][2] = GPSBB_VNI_KERNELS(k_acq);
+    return k[fmt][noise][interf];
 }
 
 extern "C" int gpsbb_device_acquire(gpsbb_t *h, const int16_t *d_iq, long nsamp, unsigned view, const gpsbb_noise_t *nz,
@@ -3076,12 +3052,9 @@ extern "C" int gpsbb_device_acquire(gpsbb_t *h, const int16_t *d_iq, long nsamp,
         !impair_make(nz, set, (uint64_t)nsamp, &ic))
         return GPSBB_E_BADARG;
     static_assert(DS_SC16 == 0 && PACK_SC8 == 1 && PACK_SC1 == 2, "acq_view_format's numbers are the kernels'");
-    HIPCHK(h, hipSetDevice(h->device));
-    const int rc = gpsbb_sync(h); /* as gpsbb_device_level: whatever the handle was rendering into d_iq is there */
+    const int rc = iq_call_begin(h, ic.noise);
     if (rc != GPSBB_OK)
         return rc;
-    if (nz)
-        HIPCHK(h, noise_ready(h));
     AcqArgs a;
     memset(&a, 0, sizeof a);
     a.nbins = cfg->nbins;
@@ -3107,41 +3080,28 @@ extern "C" int gpsbb_device_acquire(gpsbb_t *h, const int16_t *d_iq, long nsamp,
     HIPCHK(h, hipMemsetAsync(h->d_acq_rows.p, 0, row_words * 8, cs));
     if (grid)
         HIPCHK(h, hipMemsetAsync(h->d_acq_grid.p, 0, grid_words * 8, cs));
-    a.d.iq = reinterpret_cast<const uint32_t *>(d_iq);
-    a.d.shift8 = shift8;
-    ds_fill_impair(a.d, h, ic);
+    a.d = iq_view(h, d_iq, shift8, ic);
     a.tabs = h->d_tabs;
     a.chips = reinterpret_cast<const int8_t *>(h->d_acq_chips.p);
     a.grid = grid ? h->d_acq_grid.p : nullptr;
     a.part = d_part;
     const long long nchip = (long long)a.nnc * a.npad;
-#ifdef GPSBB_EXPERIMENTS
-    for (auto &e : h->acq_ev)
-        if (!e)
-            HIPCHK(h, hipEventCreate(&e));
-    HIPCHK(h, hipEventRecord(h->acq_ev[0], cs));
-#endif
+    HIPCHK(h, h->acq_tm.start(cs));
     hipLaunchKernelGGL(k_acq_chips, dim3((unsigned)((nchip + 255) / 256)), dim3(256), 0, cs, h->d_ca, reinterpret_cast<int8_t *>(h->d_acq_chips.p),
                        cfg->prn_mask, (unsigned long long)cfg->code_step, a.ncoh, a.npad, a.nnc);
     HIPCHK(h, hipGetLastError());
     /* x: runs of four delay tiles (at most 256), y: the bins (at most 64) */
-    hipLaunchKernelGGL(acq_kernel(fmt, nz != nullptr, set != nullptr), dim3((unsigned)((a.ntiles + AQ_WAVES - 1) / AQ_WAVES), (unsigned)a.nbins),
+    hipLaunchKernelGGL(acq_kernel(fmt, ic.noise, ic.set), dim3((unsigned)((a.ntiles + AQ_WAVES - 1) / AQ_WAVES), (unsigned)a.nbins),
                        dim3(AQ_WG), 0, cs, a);
     HIPCHK(h, hipGetLastError());
     hipLaunchKernelGGL(k_acq_fold, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, cs, d_part, d_rows, (int)nrows, a.ntiles);
     HIPCHK(h, hipGetLastError());
-#ifdef GPSBB_EXPERIMENTS
-    HIPCHK(h, hipEventRecord(h->acq_ev[1], cs));
-#endif
+    HIPCHK(h, h->acq_tm.stop(cs));
     HIPCHK(h, hipMemcpyAsync(rows, d_rows, nrows * sizeof(gpsbb_acq_row_t), hipMemcpyDeviceToHost, cs));
     if (grid)
         HIPCHK(h, hipMemcpyAsync(grid, h->d_acq_grid.p, grid_words * 8, hipMemcpyDeviceToHost, cs));
     HIPCHK(h, hipStreamSynchronize(cs));
-    if (grid) { /* the grid is not kept: it can be half a gigabyte, and the next call may not want one */
-        (void)hipFree(h->d_acq_grid.p);
-        h->d_acq_grid.p = nullptr;
-        h->d_acq_grid.cap = 0;
-    }
+    h->d_acq_grid.release(); /* the grid is not kept: it can be half a gigabyte, and the next call may not want one */
     return GPSBB_OK;
 }
 
@@ -3173,10 +3133,8 @@ extern "C" int gpsbb_trk_bits(const gpsbb_trk_epoch_t *epochs, int n, int first,
 typedef void (*TrkKernelFn)(TrkArgs);
 static TrkKernelFn trk_kernel(int fmt, bool noise, bool interf)
 {
-#define GPSBB_TK_ROW(V) {{k_track<V, false, false>, k_track<V, false, true>}, {k_track<V, true, false>, k_track<V, true, true>}}
-    static const TrkKernelFn k[3][2][2] = {GPSBB_TK_ROW(DS_SC16), GPSBB_TK_ROW(PACK_SC8), GPSBB_TK_ROW(PACK_SC1)};
-#undef GPSBB_TK_ROW
-    return k[fmt][noise ? 1 : 0][interf ? 1 : 0];
+    static const TrkKernelFn k[3][2][2] = GPSBB_VNI_KERNELS(k_track);
+    return k[fmt][noise][interf];
 }
 
 extern "C" int gpsbb_device_track(gpsbb_t *h, const int16_t *d_iq, long nsamp, unsigned view, const gpsbb_noise_t *nz,
@@ -3192,12 +3150,9 @@ extern "C" int gpsbb_device_track(gpsbb_t *h, const int16_t *d_iq, long nsamp, u
     for (int c = 0; c < nch; c++)
         if (!trk_state_ok(&states[c], nsamp))
             return GPSBB_E_BADARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    const int rc = gpsbb_sync(h); /* as gpsbb_device_acquire: whatever the handle was rendering into d_iq is there */
+    const int rc = iq_call_begin(h, ic.noise);
     if (rc != GPSBB_OK)
         return rc;
-    if (nz)
-        HIPCHK(h, noise_ready(h));
     /* ---- scratch, in 8-byte words: the states, the counts, the records ---- */
     const size_t st_words = (size_t)nch * sizeof(gpsbb_trk_state_t) / 8, cnt_words = ((size_t)nch + 1) / 2;
     const size_t rec_words = (size_t)nch * (size_t)cfg->max_epochs * (sizeof(gpsbb_trk_epoch_t) / 8);
@@ -3205,9 +3160,7 @@ extern "C" int gpsbb_device_track(gpsbb_t *h, const int16_t *d_iq, long nsamp, u
     hipStream_t cs = h->s_compute;
     TrkArgs a;
     memset(&a, 0, sizeof a);
-    a.d.iq = reinterpret_cast<const uint32_t *>(d_iq);
-    a.d.shift8 = shift8;
-    ds_fill_impair(a.d, h, ic);
+    a.d = iq_view(h, d_iq, shift8, ic);
     a.tabs = h->d_tabs;
     a.ca_bits = h->d_ca;
     a.cfg = *cfg;
@@ -3217,17 +3170,10 @@ extern "C" int gpsbb_device_track(gpsbb_t *h, const int16_t *d_iq, long nsamp, u
     a.nsamp = nsamp;
     HIPCHK(h, hipMemcpyAsync(a.states, states, (size_t)nch * sizeof(gpsbb_trk_state_t), hipMemcpyHostToDevice, cs));
     HIPCHK(h, hipMemsetAsync(a.counts, 0, cnt_words * 8, cs));
-#ifdef GPSBB_EXPERIMENTS
-    for (auto &e : h->trk_ev)
-        if (!e)
-            HIPCHK(h, hipEventCreate(&e));
-    HIPCHK(h, hipEventRecord(h->trk_ev[0], cs));
-#endif
-    hipLaunchKernelGGL(trk_kernel(fmt, nz != nullptr, set != nullptr), dim3((unsigned)nch), dim3(TK_WG), 0, cs, a);
+    HIPCHK(h, h->trk_tm.start(cs));
+    hipLaunchKernelGGL(trk_kernel(fmt, ic.noise, ic.set), dim3((unsigned)nch), dim3(TK_WG), 0, cs, a);
     HIPCHK(h, hipGetLastError());
-#ifdef GPSBB_EXPERIMENTS
-    HIPCHK(h, hipEventRecord(h->trk_ev[1], cs));
-#endif
+    HIPCHK(h, h->trk_tm.stop(cs));
     /* ---- copy back: the counts first, then each channel's records as far as they go, and the states ---- */
     int32_t n_out[TRK_MAX_CH];
     gpsbb_trk_state_t st_out[TRK_MAX_CH];
@@ -3259,8 +3205,8 @@ extern "C" int gpsbb_fir_make(gpsbb_fir_t *f, int ntaps, int decim, double cutof
 typedef void (*FirKernelFn)(FirArgs);
 static FirKernelFn fir_kernel(bool noise, bool interf)
 {
-    static const FirKernelFn k[2][2] = {{k_fir<false, false>, k_fir<false, true>}, {k_fir<true, false>, k_fir<true, true>}};
-    return k[noise ? 1 : 0][interf ? 1 : 0];
+    static const FirKernelFn k[2][2] = GPSBB_NI_KERNELS(k_fir);
+    return k[noise][interf];
 }
 
 extern "C" int gpsbb_device_fir(gpsbb_t *h, const int16_t *d_iq, long nsamp, const gpsbb_noise_t *nz, const gpsbb_interf_set_t *set,
@@ -3275,20 +3221,16 @@ extern "C" int gpsbb_device_fir(gpsbb_t *h, const int16_t *d_iq, long nsamp, con
     const uintptr_t in0 = (uintptr_t)d_iq, in1 = in0 + 4 * (uintptr_t)nsamp, out0 = (uintptr_t)d_out, out1 = out0 + 4 * (uintptr_t)nout;
     if ((out0 < in1 && in0 < out1) || tiles > 0x7fffffffL)
         return GPSBB_E_BADARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    const int rc = gpsbb_sync(h); /* as gpsbb_device_track: whatever the handle was rendering into d_iq is there */
+    const int rc = iq_call_begin(h, ic.noise);
     if (rc != GPSBB_OK)
         return rc;
-    if (nz)
-        HIPCHK(h, noise_ready(h));
     /* ---- scratch, in 8-byte words: the clip count, then room for the longest history twice ---- */
     constexpr size_t hist_words = (GPSBB_FIR_MAX_TAPS - 1) / 2;
     HIPCHK(h, (hipError_t)h->d_fir.reserve(1 + 2 * hist_words));
     hipStream_t cs = h->s_compute;
     FirArgs a;
     memset(&a, 0, sizeof a);
-    a.d.iq = reinterpret_cast<const uint32_t *>(d_iq);
-    ds_fill_impair(a.d, h, ic);
+    a.d = iq_view(h, d_iq, 0, ic);
     a.tabs = h->d_tabs;
     a.clipped = h->d_fir.p;
     uint32_t *d_hist_in = reinterpret_cast<uint32_t *>(h->d_fir.p + 1), *d_hist_out = reinterpret_cast<uint32_t *>(h->d_fir.p + 1 + hist_words);
@@ -3312,17 +3254,10 @@ extern "C" int gpsbb_device_fir(gpsbb_t *h, const int16_t *d_iq, long nsamp, con
     HIPCHK(h, hipMemsetAsync(h->d_fir.p, 0, (1 + 2 * hist_words) * 8, cs));
     if (hist_in && T > 1)
         HIPCHK(h, hipMemcpyAsync(d_hist_in, hist_in, (size_t)(T - 1) * 4, hipMemcpyHostToDevice, cs));
-#ifdef GPSBB_EXPERIMENTS
-    for (auto &e : h->fir_ev)
-        if (!e)
-            HIPCHK(h, hipEventCreate(&e));
-    HIPCHK(h, hipEventRecord(h->fir_ev[0], cs));
-#endif
-    hipLaunchKernelGGL(fir_kernel(nz != nullptr, set != nullptr), dim3((unsigned)tiles), dim3(FIR_WG), fir_lds_bytes(Te, D), cs, a);
+    HIPCHK(h, h->fir_tm.start(cs));
+    hipLaunchKernelGGL(fir_kernel(ic.noise, ic.set), dim3((unsigned)tiles), dim3(FIR_WG), fir_lds_bytes(Te, D), cs, a);
     HIPCHK(h, hipGetLastError());
-#ifdef GPSBB_EXPERIMENTS
-    HIPCHK(h, hipEventRecord(h->fir_ev[1], cs));
-#endif
+    HIPCHK(h, h->fir_tm.stop(cs));
     uint32_t tail[GPSBB_FIR_MAX_TAPS];
     unsigned long long clips = 0;
     HIPCHK(h, hipMemcpyAsync(&clips, a.clipped, sizeof clips, hipMemcpyDeviceToHost, cs));
@@ -3506,9 +3441,9 @@ static int fill_block_impl(gpsbb_t *h, const gpsbb_chan_t *ch, int nch, double d
     if (fmt || ic) {
         void *dst = direct;
         if (!dst) {
-            HIPCHK(h, pack_reserve(h, out_bytes));
-            dst = h->d_pack;
-            src = h->d_pack;
+            HIPCHK(h, (hipError_t)h->d_pack.reserve(out_bytes));
+            dst = h->d_pack.p;
+            src = h->d_pack.p;
         }
         HIPCHK(h, out_launch(h, fmt, shift, ic, b->last_iq, dst, (size_t)nsamp * 2, b->last_cs));
     }
@@ -4790,37 +4725,10 @@ extern "C" long long gpsbb_test_read_pattern(gpsbb_t *h, const void *d_src, size
 }
 
 extern "C" unsigned long long gpsbb_test_despread_exact(gpsbb_batch *b) { return b ? b->ds_last_exact : 0ull; }
-extern "C" float gpsbb_test_despread_ms(gpsbb_batch *b)
-{
-    float ms = -1.0f;
-    if (!b || !b->ds_ev[0] || !b->ds_ev[1] || hipEventElapsedTime(&ms, b->ds_ev[0], b->ds_ev[1]) != hipSuccess)
-        return -1.0f;
-    return ms;
-}
-
-extern "C" float gpsbb_test_acquire_ms(gpsbb *h)
-{
-    float ms = -1.0f;
-    if (!h || !h->acq_ev[0] || !h->acq_ev[1] || hipEventElapsedTime(&ms, h->acq_ev[0], h->acq_ev[1]) != hipSuccess)
-        return -1.0f;
-    return ms;
-}
-
-extern "C" float gpsbb_test_track_ms(gpsbb *h)
-{
-    float ms = -1.0f;
-    if (!h || !h->trk_ev[0] || !h->trk_ev[1] || hipEventElapsedTime(&ms, h->trk_ev[0], h->trk_ev[1]) != hipSuccess)
-        return -1.0f;
-    return ms;
-}
-
-extern "C" float gpsbb_test_fir_ms(gpsbb *h)
-{
-    float ms = -1.0f;
-    if (!h || !h->fir_ev[0] || !h->fir_ev[1] || hipEventElapsedTime(&ms, h->fir_ev[0], h->fir_ev[1]) != hipSuccess)
-        return -1.0f;
-    return ms;
-}
+extern "C" float gpsbb_test_despread_ms(gpsbb_batch *b) { return b ? b->ds_tm.ms() : -1.0f; }
+extern "C" float gpsbb_test_acquire_ms(gpsbb *h) { return h ? h->acq_tm.ms() : -1.0f; }
+extern "C" float gpsbb_test_track_ms(gpsbb *h) { return h ? h->trk_tm.ms() : -1.0f; }
+extern "C" float gpsbb_test_fir_ms(gpsbb *h) { return h ? h->fir_tm.ms() : -1.0f; }
 
 extern "C" int gpsbb_test_fir_tile(void) { return FIR_TILE; }
 
