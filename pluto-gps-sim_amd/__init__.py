@@ -20,10 +20,10 @@ import subprocess
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# The product is libgpsbb.so: it reads no environment variable and exports include/gpsbb.h, nothing else.  The experiments
-# build of the same sources (libgpsbb_exp.so: measurement knobs from the environment, gpsbb_test_* hooks) is what the
-# tuning scripts under tools/ use when they say so (GPSBB_PY_LIB=exp, read HERE, in the Python veneer) and what
-# exp_lib() hands to the NCO unit tests.
+# The product is libgpsbb.so: it reads no environment variable and exports include/gpsbb.h and one counter of what it holds
+# (gpsbb_test_live), nothing else.  The experiments build of the same sources (libgpsbb_exp.so: measurement knobs from the
+# environment, gpsbb_test_* hooks) is what the tuning scripts under tools/ use when they say so (GPSBB_PY_LIB=exp, read HERE, in
+# the Python veneer) and what exp_lib() hands to the NCO unit tests.
 _which = os.environ.get("GPSBB_PY_LIB")  # "exp", the tag of a variant a tuning script built (libgpsbb_<tag>.so), or the PATH of a library
 # (the deliberately wrong builds of the tests live in the tests' temporary directories, never beside the product)
 LIB_PATH = _which if _which and os.sep in _which else os.path.join(HERE, "libgpsbb_%s.so" % _which if _which else "libgpsbb.so")
@@ -405,6 +405,9 @@ def lib():
         if hasattr(L, "gpsbb_device_fir"):  # the filter's calls, as a group (an older build loaded for an A/B: tools/ab_lib.sh)
             L.gpsbb_device_fir.argtypes = [vp, vp, C.c_long, vp, vp, vp, vp, vp, vp, vp]
             L.gpsbb_fir_make.argtypes = [vp, i, i, d, d]
+        if hasattr(L, "gpsbb_test_live"):  # (an older build loaded for an A/B: tools/ab_lib.sh)
+            L.gpsbb_test_live.argtypes = [vp]
+            L.gpsbb_test_live.restype = None
         _lib = L
     return _lib
 

@@ -495,6 +495,11 @@ constexpr unsigned STREAM_SEED_STREAMS = 2; /* pre-passes of a stream's pushes i
                                                queue to itself: a pre-pass that shares a queue with the synthesis, or with a stream that holds a
                                                wait for one, runs after it and not beside it */
 
+/* How many of each kind of resource this process holds right now (gpsbb_test_live): counted where an owner's allocation succeeds
+ * and where it releases.  A launch never allocates, so none of this is on a hot path. */
+static std::atomic<long long> g_live_dev{0}, g_live_pinned{0}, g_live_events{0};
+static void live_add(std::atomic<long long> &n, long long d) { n.fetch_add(d, std::memory_order_relaxed); }
+
 /* device memory that is kept between calls and only ever grows */
 template <class T>
 struct DevBuf {
@@ -507,48 +512,109 @@ struct DevBuf {
         if (n <= cap)
             return hipSuccess;
         n += room;
-        if (p) {
-            (void)hipFree(p); /* synchronises the device: grow with head-room so that a ring whose slots see
-                                 slightly different row counts stops re-allocating after a few pushes */
-            n += n / 4;
-        }
-        p = nullptr;
-        cap = 0;
+        if (p)
+            n += n / 4; /* the free synchronises the device: grow with head-room so that a ring whose slots see
+                           slightly different row counts stops re-allocating after a few pushes */
+        release();
         hipError_t e = hipMalloc((void **)&p, n * sizeof(T));
-        if (e != hipSuccess)
+        if (e != hipSuccess) {
+            p = nullptr;
             return e;
+        }
         cap = n;
+        live_add(g_live_dev, 1);
         return hipSuccess;
     }
     void release()
     {
-        if (p)
+        if (p) {
             (void)hipFree(p);
+            live_add(g_live_dev, -1);
+        }
         p = nullptr;
         cap = 0;
     }
 };
 
-/* release() of every buffer named (DevBuf, or a struct of them) */
+/* pinned host memory, likewise: what is outgrown comes back as n + room elements, and each site says how much room it wants */
+template <class T>
+struct PinnedBuf {
+    T *p = nullptr;
+    size_t cap = 0; /* elements */
+    int reserve(size_t n, size_t room = 0)
+    {
+        if (n <= cap)
+            return hipSuccess;
+        release();
+        hipError_t e = hipHostMalloc((void **)&p, (n + room) * sizeof(T), hipHostMallocDefault);
+        if (e != hipSuccess) {
+            p = nullptr;
+            return e;
+        }
+        cap = n + room;
+        live_add(g_live_pinned, 1);
+        return hipSuccess;
+    }
+    void release()
+    {
+        if (p) {
+            (void)hipHostFree(p);
+            live_add(g_live_pinned, -1);
+        }
+        p = nullptr;
+        cap = 0;
+    }
+};
+
+/* an event, made once: hipEventDefault for the ones whose times are read, hipEventDisableTiming for the ones that only order */
+struct Event {
+    hipEvent_t e = nullptr;
+    hipError_t make(unsigned flags)
+    {
+        if (e)
+            return hipSuccess;
+        const hipError_t rc = hipEventCreateWithFlags(&e, flags);
+        if (rc != hipSuccess)
+            e = nullptr;
+        else
+            live_add(g_live_events, 1);
+        return rc;
+    }
+    void release()
+    {
+        if (e) {
+            (void)hipEventDestroy(e);
+            live_add(g_live_events, -1);
+        }
+        e = nullptr;
+    }
+    operator hipEvent_t() const { return e; }
+};
+
+/* release() of every owner named (DevBuf, PinnedBuf, Event, or a struct of them) */
 template <class... B>
 static void release_all(B &...b)
 {
     (b.release(), ...);
 }
 
+/* ... of a call's own temporaries, on every way out of it: const AtExit done{[&] { release_all(a, b); }}; */
+template <class F>
+struct AtExit { F f; ~AtExit() { f(); } };
+template <class F> AtExit(F) -> AtExit<F>;
+
 /* Two events around the kernels of a call's last run, for the experiments build's gpsbb_test_*_ms hooks: without
  * GPSBB_EXPERIMENTS start and stop do nothing, and no event is ever made. */
 struct KernelTimer {
-    hipEvent_t ev[2] = {};
+    Event ev[2];
     hipError_t start(hipStream_t stream)
     {
 #ifdef GPSBB_EXPERIMENTS
-        for (hipEvent_t &e : ev)
-            if (!e) {
-                const hipError_t rc = hipEventCreate(&e);
-                if (rc != hipSuccess)
-                    return rc;
-            }
+        for (Event &e : ev) {
+            const hipError_t rc = e.make(hipEventDefault);
+            if (rc != hipSuccess)
+                return rc;
+        }
         return hipEventRecord(ev[0], stream);
 #else
         return hipSuccess;
@@ -568,14 +634,7 @@ struct KernelTimer {
         float t = -1.0f;
         return ev[0] && ev[1] && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess ? t : -1.0f;
     }
-    void release()
-    {
-        for (hipEvent_t &e : ev) {
-            if (e)
-                (void)hipEventDestroy(e);
-            e = nullptr;
-        }
-    }
+    void release() { release_all(ev[0], ev[1]); }
 };
 
 struct gpsbb {
@@ -597,19 +656,18 @@ struct gpsbb {
     std::vector<uint32_t> h_ca;      /* host copy of the C/A chips (seeding of small batches on the host)  */
     unsigned long long host_dwrd_oob = 0, host_itable_512 = 0; /* hazards counted by host-side seeding      */
     WorkPool *pool = nullptr;        /* host threads for seeding small batches (created on first use)      */
-    int32_t *d_tabs = nullptr;
-    uint32_t *d_ca = nullptr;
-    uint32_t *d_status = nullptr;
-    unsigned long long *d_hz = nullptr;
-    unsigned long long *d_clip = nullptr; /* GPSBB_INFO_SC8_CLIPPED: the packing kernels add their saturated components here */
-    int2 *d_noise_tab = nullptr;          /* the noise's knots (K[i], K[i + 1] - K[i]) and ... */
-    unsigned long long *d_nclip = nullptr; /* ... GPSBB_INFO_NOISE_CLIPPED: both on the first call with noise */
+    DevBuf<int32_t> d_tabs;
+    DevBuf<uint32_t> d_ca;
+    DevBuf<uint32_t> d_status;
+    DevBuf<unsigned long long> d_hz;
+    DevBuf<unsigned long long> d_clip;  /* GPSBB_INFO_SC8_CLIPPED: the packing kernels add their saturated components here */
+    DevBuf<int2> d_noise_tab;           /* the noise's knots (K[i], K[i + 1] - K[i]) and ... */
+    DevBuf<unsigned long long> d_nclip; /* ... GPSBB_INFO_NOISE_CLIPPED: both on the first call with noise, both or neither */
     int last_hip = 0;
     gpsbb_batch *scratch = nullptr;
-    unsigned char *h_bounce = nullptr; /* pinned: a fill whose iq_out lies partly in a registered range is copied through here */
-    size_t bounce_cap = 0;
-    unsigned char *h_fill = nullptr; /* pinned: what the drop-in call brings back besides the IQ — the end states and the status word
-                                        (fill_block_finish) */
+    PinnedBuf<unsigned char> h_bounce; /* a fill whose iq_out lies partly in a registered range is copied through here */
+    PinnedBuf<unsigned char> h_fill;   /* what the drop-in call brings back besides the IQ — the end states and the status word
+                                          (fill_block_finish) */
     struct HostReg { char *host; char *dev; size_t bytes; };
     std::vector<HostReg> host_regs;         /* gpsbb_host_register: host ranges the device writes straight into */
     struct ChainOnly *chain_only = nullptr; /* device scratch of gpsbb_chain_carrier, kept between calls */
@@ -873,9 +931,9 @@ struct gpsbb_batch {
     DevBuf<unsigned long long> d_dig;
     /* pinned staging arena of the uploads of one set-up: hipMemcpyAsync from pageable memory is not asynchronous
      * (it waits for the stream's earlier work — the previous push's pre-pass — before it returns) */
-    char *stage = nullptr;
-    size_t stage_cap = 0, stage_used = 0;
-    hipEvent_t upload_done = nullptr; /* descriptors and plans of the last set-up are on the device */
+    PinnedBuf<char> stage;
+    size_t stage_used = 0;
+    Event upload_done; /* descriptors and plans of the last set-up are on the device */
     hipStream_t upload_stream = nullptr; /* ... the stream that carried them */
 
     /* per-launch state */
@@ -885,7 +943,10 @@ struct gpsbb_batch {
     hipEvent_t last_done = nullptr;
     unsigned run_count = 0;
     int last_set = 0;
-    struct Ev4 { hipEvent_t e[4]; }; /* seed start/end (seed stream), synth start/end (compute stream) */
+    struct Ev4 { /* seed start/end (seed stream), synth start/end (compute stream) */
+        Event e[4];
+        void release() { release_all(e[0], e[1], e[2], e[3]); }
+    };
     std::vector<Ev4> evs; /* one set per run since the last timing reset */
     size_t ev_used = 0;
     bool ran = false;
@@ -893,13 +954,11 @@ struct gpsbb_batch {
     int16_t *last_ext_iq = nullptr; /* the caller's device buffer of the last run, if it used one */
 
     /* seeding on the host (small batches): pinned images of the row pool, tile index and end states, or (ev) of the tile states */
-    SynRow *hs_rows = nullptr;
-    int32_t *hs_tile_row = nullptr;
-    gpsbb_chan_state_t *hs_end = nullptr;
-    size_t hs_rows_cap = 0, hs_tr_cap = 0, hs_end_cap = 0;
-    double *hs_tile_x = nullptr;
-    uint32_t *hs_tile_nav = nullptr;
-    size_t hs_tx_cap = 0, hs_tn_cap = 0;
+    PinnedBuf<SynRow> hs_rows;
+    PinnedBuf<int32_t> hs_tile_row;
+    PinnedBuf<gpsbb_chan_state_t> hs_end;
+    PinnedBuf<double> hs_tile_x;
+    PinnedBuf<uint32_t> hs_tile_nav;
 
     /* gpsbb_batch_despread's scratch, kept between calls: the sums (and behind them the count of samples that took the exact
      * path), the tile counters */
@@ -983,7 +1042,7 @@ extern "C" int gpsbb_get_info(gpsbb_t *h, int what, uint64_t *out)
     case GPSBB_INFO_TILES_RENDERED: {
         HIPCHK(h, hipSetDevice(h->device));
         unsigned long long v = 0;
-        HIPCHK(h, hipMemcpy(&v, h->d_hz + (what == GPSBB_INFO_EXACT_RUNS ? 2 : (what == GPSBB_INFO_CHAIN_FALLBACKS ? 4 : (what == GPSBB_INFO_CHAIN_TIES ? 5 : (what == GPSBB_INFO_TILES_RENDERED ? 7 : 6)))), 8,
+        HIPCHK(h, hipMemcpy(&v, h->d_hz.p + (what == GPSBB_INFO_EXACT_RUNS ? 2 : (what == GPSBB_INFO_CHAIN_FALLBACKS ? 4 : (what == GPSBB_INFO_CHAIN_TIES ? 5 : (what == GPSBB_INFO_TILES_RENDERED ? 7 : 6)))), 8,
                             hipMemcpyDeviceToHost));
         *out = v;
         return GPSBB_OK;
@@ -991,15 +1050,15 @@ extern "C" int gpsbb_get_info(gpsbb_t *h, int what, uint64_t *out)
     case GPSBB_INFO_SC8_CLIPPED: {
         HIPCHK(h, hipSetDevice(h->device));
         unsigned long long v = 0;
-        HIPCHK(h, hipMemcpy(&v, h->d_clip, 8, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(&v, h->d_clip.p, 8, hipMemcpyDeviceToHost));
         *out = v;
         return GPSBB_OK;
     }
     case GPSBB_INFO_NOISE_CLIPPED: {
         unsigned long long v = 0;
-        if (h->d_nclip) {
+        if (h->d_nclip.p) {
             HIPCHK(h, hipSetDevice(h->device));
-            HIPCHK(h, hipMemcpy(&v, h->d_nclip, 8, hipMemcpyDeviceToHost));
+            HIPCHK(h, hipMemcpy(&v, h->d_nclip.p, 8, hipMemcpyDeviceToHost));
         }
         *out = v;
         return GPSBB_OK;
@@ -1052,29 +1111,13 @@ extern "C" void gpsbb_destroy(gpsbb_t *h)
     (void)hipSetDevice(h->device);
     if (h->scratch)
         gpsbb_batch_destroy(h->scratch);
-    if (h->h_fill)
-        (void)hipHostFree(h->h_fill);
-    if (h->h_bounce)
-        (void)hipHostFree(h->h_bounce);
+    release_all(h->h_fill, h->h_bounce);
     for (const gpsbb::HostReg &r : h->host_regs)
         (void)hipHostUnregister(r.host);
     h->host_regs.clear();
     chain_only_free(h);
     (void)drain_streams(h);
-    if (h->d_tabs)
-        (void)hipFree(h->d_tabs);
-    if (h->d_ca)
-        (void)hipFree(h->d_ca);
-    if (h->d_status)
-        (void)hipFree(h->d_status);
-    if (h->d_hz)
-        (void)hipFree(h->d_hz);
-    if (h->d_clip)
-        (void)hipFree(h->d_clip);
-    if (h->d_noise_tab)
-        (void)hipFree(h->d_noise_tab);
-    if (h->d_nclip)
-        (void)hipFree(h->d_nclip);
+    release_all(h->d_tabs, h->d_ca, h->d_status, h->d_hz, h->d_clip, h->d_noise_tab, h->d_nclip);
     release_all(h->d_pack, h->d_level, h->d_digest, h->d_acq_chips, h->d_acq_rows, h->d_acq_grid, h->d_trk, h->d_fir);
     release_all(h->acq_tm, h->trk_tm, h->fir_tm);
     delete h->pool;
@@ -1179,18 +1222,18 @@ extern "C" int gpsbb_create(gpsbb_t **out, int device)
         }
     }
     if ((e = create_seed_stream(&h->s_more[0])) != hipSuccess) return fail(e);
-    if ((e = hipMalloc((void **)&h->d_tabs, sizeof tabs)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc((void **)&h->d_ca, ca.size() * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc((void **)&h->d_status, 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc((void **)&h->d_hz, 64)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc((void **)&h->d_clip, 8)) != hipSuccess) return fail(e);
-    if ((e = hipMemcpy(h->d_tabs, tabs, sizeof tabs, hipMemcpyHostToDevice)) != hipSuccess) return fail(e);
-    if ((e = hipMemcpy(h->d_ca, ca.data(), ca.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail(e);
+    if ((e = (hipError_t)h->d_tabs.reserve(sizeof tabs / sizeof tabs[0])) != hipSuccess) return fail(e);
+    if ((e = (hipError_t)h->d_ca.reserve(ca.size())) != hipSuccess) return fail(e);
+    if ((e = (hipError_t)h->d_status.reserve(1)) != hipSuccess) return fail(e);
+    if ((e = (hipError_t)h->d_hz.reserve(8)) != hipSuccess) return fail(e);
+    if ((e = (hipError_t)h->d_clip.reserve(1)) != hipSuccess) return fail(e);
+    if ((e = hipMemcpy(h->d_tabs.p, tabs, sizeof tabs, hipMemcpyHostToDevice)) != hipSuccess) return fail(e);
+    if ((e = hipMemcpy(h->d_ca.p, ca.data(), ca.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail(e);
     if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return fail(e); /* (the tables are there before any non-blocking stream runs) */
     h->h_ca = ca;
-    if ((e = zero_now(h, h->d_status, 4)) != hipSuccess) return fail(e);
-    if ((e = zero_now(h, h->d_hz, 64)) != hipSuccess) return fail(e);
-    if ((e = zero_now(h, h->d_clip, 8)) != hipSuccess) return fail(e);
+    if ((e = zero_now(h, h->d_status.p, 4)) != hipSuccess) return fail(e);
+    if ((e = zero_now(h, h->d_hz.p, h->d_hz.cap * sizeof *h->d_hz.p)) != hipSuccess) return fail(e);
+    if ((e = zero_now(h, h->d_clip.p, 8)) != hipSuccess) return fail(e);
     /* the synthesis kernels carve 76 - 156 KB of dynamic LDS per workgroup: above the 64 KB default limit */
     for (int v = GPSBB_VARIANT_SYNTH; v <= GPSBB_VARIANT_EV_FIXED; v++)
         for (int dg = 0; dg < 2; dg++)
@@ -1244,11 +1287,11 @@ static const SynthKernel &synth_kernel(int variant, bool digest, int g)
 static hipError_t stage_upload(gpsbb_batch *b, void *dst, const void *src, size_t bytes, hipStream_t stream)
 {
     const size_t at = (b->stage_used + 63) & ~(size_t)63;
-    if (at + bytes > b->stage_cap) /* cannot happen: the arena was sized for this set-up */
+    if (at + bytes > b->stage.cap) /* cannot happen: the arena was sized for this set-up */
         return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream);
-    memcpy(b->stage + at, src, bytes);
+    memcpy(b->stage.p + at, src, bytes);
     b->stage_used = at + bytes;
-    return hipMemcpyAsync(dst, b->stage + at, bytes, hipMemcpyHostToDevice, stream);
+    return hipMemcpyAsync(dst, b->stage.p + at, bytes, hipMemcpyHostToDevice, stream);
 }
 
 /* ---- batch set-up: plan, then stage ---------------------------------------------------------------- */
@@ -1262,14 +1305,7 @@ static int stage_arena(gpsbb_batch *b, size_t nbc)
     if (b->upload_done) /* the previous set-up's copies out of the arena are long done; make sure */
         HIPCHK(h, hipEventSynchronize(b->upload_done));
     PUSH_MARK("arena");
-    if (need > b->stage_cap) {
-        if (b->stage)
-            (void)hipHostFree(b->stage);
-        b->stage = nullptr;
-        b->stage_cap = 0;
-        HIPCHK(h, hipHostMalloc((void **)&b->stage, need + need / 4, hipHostMallocDefault));
-        b->stage_cap = need + need / 4;
-    }
+    HIPCHK(h, (hipError_t)b->stage.reserve(need, need / 4));
     b->stage_used = 0;
     return GPSBB_OK;
 }
@@ -1339,8 +1375,7 @@ static int stage_plan(gpsbb_batch *b, hipStream_t upload_stream)
             HIPCHK(h, stage_upload(b, b->d_chain_order.p, img.h_chain_order.data(), img.h_chain_order.size() * 4, upload_stream));
         }
     }
-    if (!b->upload_done)
-        HIPCHK(h, hipEventCreateWithFlags(&b->upload_done, hipEventDisableTiming));
+    HIPCHK(h, b->upload_done.make(hipEventDisableTiming));
     HIPCHK(h, hipEventRecord(b->upload_done, upload_stream));
     b->upload_stream = upload_stream;
     return GPSBB_OK;
@@ -1456,29 +1491,14 @@ extern "C" void gpsbb_batch_destroy(gpsbb_batch_t *b)
         return;
     (void)hipSetDevice(b->h->device);
     (void)drain_streams(b->h); /* its tables, its output and its events: pre-pass, synthesis and copy streams may all hold work on them */
-    release_all(b->d_ch, b->d_row_off);
-    if (b->upload_done)
-        (void)hipEventDestroy(b->upload_done);
+    release_all(b->d_ch, b->d_row_off, b->upload_done);
     for (TableSet &ts : b->sets)
         ts.release();
     release_all(b->d_tile_ctr, b->d_seed_order, b->d_kph0, b->d_kstep, b->d_cd, b->d_start0, b->fix, b->d_chain_order, b->d_evc);
-    if (b->hs_rows)
-        (void)hipHostFree(b->hs_rows);
-    if (b->hs_tile_row)
-        (void)hipHostFree(b->hs_tile_row);
-    if (b->hs_end)
-        (void)hipHostFree(b->hs_end);
-    if (b->stage)
-        (void)hipHostFree(b->stage);
-    if (b->hs_tile_x)
-        (void)hipHostFree(b->hs_tile_x);
-    if (b->hs_tile_nav)
-        (void)hipHostFree(b->hs_tile_nav);
+    release_all(b->hs_rows, b->hs_tile_row, b->hs_end, b->stage, b->hs_tile_x, b->hs_tile_nav);
     release_all(b->d_iq, b->d_dig, b->d_ds, b->d_ds_ctr, b->ds_tm);
-    for (auto &t : b->evs)
-        for (auto &e : t.e)
-            if (e)
-                (void)hipEventDestroy(e);
+    for (gpsbb_batch::Ev4 &t : b->evs)
+        t.release();
     delete b;
 }
 
@@ -1599,7 +1619,7 @@ bool host_seed_chain(const gpsbb_batch *b, int kind, size_t k, unsigned long lon
     const BatchPlan &pl = b->plan;
     const PlanImages &img = b->img;
     const gpsbb_chan_t &c = img.h_ch[k];
-    gpsbb_chan_state_t &e = b->hs_end[k];
+    gpsbb_chan_state_t &e = b->hs_end.p[k];
     const size_t nbc = (size_t)pl.nblocks * pl.nch;
     const bool fixed = (pl.flags & GPSBB_FIXED_CARRIER) != 0;
     if (c.prn <= 0) {
@@ -1617,7 +1637,7 @@ bool host_seed_chain(const gpsbb_batch *b, int kind, size_t k, unsigned long lon
         e.carr_phase = (double)(uint32_t)(img.h_kph0[k] + (uint32_t)pl.nsamp * (uint32_t)img.h_kstep[k]);
         if (pl.ev) {
             /* k_synth_pd: the table index at every tile start, in closed form (what k_tiles writes on the device) */
-            double *tx = b->hs_tile_x + (blk * (2 * (size_t)pl.nch) + 2 * i + 1) * (size_t)pl.ntiles;
+            double *tx = b->hs_tile_x.p + (blk * (2 * (size_t)pl.nch) + 2 * i + 1) * (size_t)pl.ntiles;
             for (int t = 0; t < pl.ntiles; t++)
                 tx[t] = fixed_tile_index(img.h_kph0[k], img.h_kstep[k], t);
         }
@@ -1626,7 +1646,7 @@ bool host_seed_chain(const gpsbb_batch *b, int kind, size_t k, unsigned long lon
     if (pl.ev) {
         /* breakpoint kernel: tile-start states instead of rows (what k_seed<true> writes) */
         uint32_t nav = kind == 0 ? nav_pack(c.icode, c.ibit, c.iword) : 0u;
-        TileSink sink = make_tile_sink(b->hs_tile_x, b->hs_tile_nav, pl.nch, pl.ntiles, (int)blk, (int)i, kind,
+        TileSink sink = make_tile_sink(b->hs_tile_x.p, b->hs_tile_nav.p, pl.nch, pl.ntiles, (int)blk, (int)i, kind,
                                        kind == 0 ? c.dwrd : nullptr, nav, nullptr);
         if (kind == 0) {
             const double s = mul_rn(c.f_code, pl.delt);
@@ -1651,7 +1671,7 @@ bool host_seed_chain(const gpsbb_batch *b, int kind, size_t k, unsigned long lon
     }
     const size_t chain = (size_t)kind * nbc + k;
     HostRowSink sink;
-    sink.rows = b->hs_rows + img.row_off[chain];
+    sink.rows = b->hs_rows.p + img.row_off[chain];
     sink.cap = (uint32_t)(img.row_off[chain + 1] - img.row_off[chain] - 1);
     sink.cnt = 0;
     sink.overflow = false;
@@ -1660,7 +1680,7 @@ bool host_seed_chain(const gpsbb_batch *b, int kind, size_t k, unsigned long lon
     sink.dwrd = kind == 0 ? c.dwrd : nullptr;
     uint32_t nav = kind == 0 ? nav_pack(c.icode, c.ibit, c.iword) : 0u;
     sink.dbit = kind == 0 && nav_bit(c.dwrd, nav) < 0 ? 0x80000000u : 0u;
-    sink.tr = b->hs_tile_row + (blk * ((size_t)pl.ntiles + 1)) * (2 * (size_t)pl.nch) + 2 * i + (size_t)kind;
+    sink.tr = b->hs_tile_row.p + (blk * ((size_t)pl.ntiles + 1)) * (2 * (size_t)pl.nch) + 2 * i + (size_t)kind;
     sink.tstride = 2 * (size_t)pl.nch;
     sink.tile_t = 0;
     sink.ntiles = pl.ntiles;
@@ -1687,21 +1707,6 @@ bool host_seed_chain(const gpsbb_batch *b, int kind, size_t k, unsigned long lon
     return !sink.overflow;
 }
 
-int host_pinned_reserve(void **p, size_t *cap, size_t bytes)
-{
-    if (bytes <= *cap)
-        return hipSuccess;
-    if (*p)
-        (void)hipHostFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    bytes += bytes / 4;
-    hipError_t e = hipHostMalloc(p, bytes, hipHostMallocDefault);
-    if (e == hipSuccess)
-        *cap = bytes;
-    return e;
-}
-
 } /* namespace */
 
 /* Build the tables of one run on host threads and queue their upload on the seeding stream. */
@@ -1713,13 +1718,13 @@ static int host_seed_run(gpsbb_batch *b, const TableSet &ts, hipStream_t stream)
     const size_t tr_n = 2 * nbc * ((size_t)pl.ntiles + 1);
     const size_t tx_n = 2 * nbc * (size_t)pl.ntiles, tn_n = nbc * (size_t)pl.ntiles;
     if (pl.ev) {
-        HIPCHK(h, (hipError_t)host_pinned_reserve((void **)&b->hs_tile_x, &b->hs_tx_cap, tx_n * sizeof(double)));
-        HIPCHK(h, (hipError_t)host_pinned_reserve((void **)&b->hs_tile_nav, &b->hs_tn_cap, tn_n * sizeof(uint32_t)));
+        HIPCHK(h, (hipError_t)b->hs_tile_x.reserve(tx_n, tx_n / 4));
+        HIPCHK(h, (hipError_t)b->hs_tile_nav.reserve(tn_n, tn_n / 4));
     } else {
-        HIPCHK(h, (hipError_t)host_pinned_reserve((void **)&b->hs_rows, &b->hs_rows_cap, (pl.total_rows + 4) * sizeof(SynRow)));
-        HIPCHK(h, (hipError_t)host_pinned_reserve((void **)&b->hs_tile_row, &b->hs_tr_cap, tr_n * sizeof(int32_t)));
+        HIPCHK(h, (hipError_t)b->hs_rows.reserve(pl.total_rows + 4, (pl.total_rows + 4) / 4));
+        HIPCHK(h, (hipError_t)b->hs_tile_row.reserve(tr_n, tr_n / 4));
     }
-    HIPCHK(h, (hipError_t)host_pinned_reserve((void **)&b->hs_end, &b->hs_end_cap, nbc * sizeof(gpsbb_chan_state_t)));
+    HIPCHK(h, (hipError_t)b->hs_end.reserve(nbc, nbc / 4));
     const size_t nchains = 2 * nbc;
     if (!h->pool) {
         const unsigned hw = std::thread::hardware_concurrency();
@@ -1745,13 +1750,13 @@ static int host_seed_run(gpsbb_batch *b, const TableSet &ts, hipStream_t stream)
             return GPSBB_E_INTERNAL;
     }
     if (pl.ev) {
-        HIPCHK(h, hipMemcpyAsync(ts.tile_x.p, b->hs_tile_x, tx_n * sizeof(double), hipMemcpyHostToDevice, stream));
-        HIPCHK(h, hipMemcpyAsync(ts.tile_nav.p, b->hs_tile_nav, tn_n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        HIPCHK(h, hipMemcpyAsync(ts.tile_x.p, b->hs_tile_x.p, tx_n * sizeof(double), hipMemcpyHostToDevice, stream));
+        HIPCHK(h, hipMemcpyAsync(ts.tile_nav.p, b->hs_tile_nav.p, tn_n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     } else {
-        HIPCHK(h, hipMemcpyAsync(ts.rows.p, b->hs_rows, pl.total_rows * sizeof(SynRow), hipMemcpyHostToDevice, stream));
-        HIPCHK(h, hipMemcpyAsync(ts.tile_row.p, b->hs_tile_row, tr_n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        HIPCHK(h, hipMemcpyAsync(ts.rows.p, b->hs_rows.p, pl.total_rows * sizeof(SynRow), hipMemcpyHostToDevice, stream));
+        HIPCHK(h, hipMemcpyAsync(ts.tile_row.p, b->hs_tile_row.p, tr_n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
     }
-    HIPCHK(h, hipMemcpyAsync(ts.end.p, b->hs_end, nbc * sizeof(gpsbb_chan_state_t), hipMemcpyHostToDevice, stream));
+    HIPCHK(h, hipMemcpyAsync(ts.end.p, b->hs_end.p, nbc * sizeof(gpsbb_chan_state_t), hipMemcpyHostToDevice, stream));
     return GPSBB_OK;
 }
 
@@ -1776,8 +1781,8 @@ static BatchDev batch_dev(const gpsbb_batch *b, const TableSet &ts, const Launch
     p.nstates = pl.nstates;
     p.delt = pl.delt;
     p.flags = pl.flags;
-    p.tabs = b->h->d_tabs;
-    p.ca_bits = b->h->d_ca;
+    p.tabs = b->h->d_tabs.p;
+    p.ca_bits = b->h->d_ca.p;
     p.rows = reinterpret_cast<SynRow *>(ts.rows.p);
     p.row_off = b->d_row_off.p;
     p.tile_row = ts.tile_row.p;
@@ -1786,8 +1791,8 @@ static BatchDev batch_dev(const gpsbb_batch *b, const TableSet &ts, const Launch
     p.kph0 = (pl.flags & GPSBB_FIXED_CARRIER) ? b->d_kph0.p : nullptr;
     p.kstep = (pl.flags & GPSBB_FIXED_CARRIER) ? b->d_kstep.p : nullptr;
     p.end = ts.end.p;
-    p.status = b->h->d_status;
-    p.hazards = b->h->d_hz;
+    p.status = b->h->d_status.p;
+    p.hazards = b->h->d_hz.p;
     p.digest = b->want_digest ? b->d_dig.p : nullptr;
     p.seed_order = b->d_seed_order.p;
     p.seed_lanes = lp.seed_lanes;
@@ -1903,15 +1908,14 @@ static hipError_t walk_chain_launch(hipStream_t ss, const BatchDev &p, int carr_
 }
 
 /* The timing events of this launch: seed start/end (pre-pass stream), synth start/end (synthesis stream). */
-static int launch_events(gpsbb_batch *b, hipEvent_t **ev)
+static int launch_events(gpsbb_batch *b, Event **ev)
 {
     gpsbb *h = b->h;
     /* (the drop-in call's scratch batch, everything on one stream and waited for before the call returns: no events — each record
      * is a packet between two kernels, 5 us of nothing on a call of 140) */
-    gpsbb_batch::Ev4 t = {{nullptr, nullptr, nullptr, nullptr}};
     if (b->one_stream) {
         if (b->evs.empty())
-            b->evs.push_back(t);
+            b->evs.emplace_back();
         b->ev_used = 0;
         *ev = b->evs[0].e;
         return GPSBB_OK;
@@ -1920,8 +1924,13 @@ static int launch_events(gpsbb_batch *b, hipEvent_t **ev)
         if (b->evs.size() >= 4096) {
             b->ev_used = 0; /* wrap: only the most recent runs are kept */
         } else {
-            for (auto &e : t.e)
-                HIPCHK(h, hipEventCreate(&e));
+            gpsbb_batch::Ev4 t;
+            for (Event &e : t.e) {
+                const hipError_t rc = e.make(hipEventDefault);
+                if (rc != hipSuccess)
+                    t.release(); /* all four or none */
+                HIPCHK(h, rc);
+            }
             b->evs.push_back(t);
         }
     }
@@ -2016,7 +2025,7 @@ static int batch_launch(gpsbb_batch *b, int16_t *d_iq)
     const LaunchPlan lp = batch_launch_plan(b, h->opt_skip_seed && b->run_count >= (unsigned)pl.nsets);
     const BatchDev p = batch_dev(b, ts, lp);
     const bool timed = !b->one_stream;
-    hipEvent_t *ev = nullptr;
+    Event *ev = nullptr;
     int rc = launch_events(b, &ev);
     if (rc != GPSBB_OK)
         return rc;
@@ -2108,9 +2117,9 @@ extern "C" int gpsbb_sync(gpsbb_t *h)
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, drain_streams(h));
     uint32_t st = 0;
-    HIPCHK(h, hipMemcpy(&st, h->d_status, 4, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(&st, h->d_status.p, 4, hipMemcpyDeviceToHost));
     if (st) {
-        HIPCHK(h, zero_now(h, h->d_status, 4));
+        HIPCHK(h, zero_now(h, h->d_status.p, 4));
         return GPSBB_E_INTERNAL;
     }
     return GPSBB_OK;
@@ -2189,12 +2198,12 @@ extern "C" int gpsbb_get_hazards(gpsbb_t *h, gpsbb_hazards_t *out, int reset)
         return GPSBB_E_BADARG;
     HIPCHK(h, hipSetDevice(h->device));
     unsigned long long v[2];
-    HIPCHK(h, hipMemcpy(v, h->d_hz, 16, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(v, h->d_hz.p, 16, hipMemcpyDeviceToHost));
     out->itable_512 = v[0];
     out->itable_512 += h->host_itable_512;
     out->dwrd_oob = v[1] + h->host_dwrd_oob;
     if (reset) {
-        HIPCHK(h, zero_now(h, h->d_hz, 16));
+        HIPCHK(h, zero_now(h, h->d_hz.p, 16));
         h->host_dwrd_oob = 0;
         h->host_itable_512 = 0;
     }
@@ -2206,7 +2215,7 @@ extern "C" int gpsbb_batch_last_timing(gpsbb_batch_t *b, float *ms_seed, float *
     if (!b || !b->ran || b->ev_used == 0)
         return GPSBB_E_STATE;
     gpsbb *h = b->h;
-    hipEvent_t *ev = b->evs[b->ev_used - 1].e;
+    const Event *ev = b->evs[b->ev_used - 1].e;
     float a = 0, c = 0, t = 0;
     HIPCHK(h, hipEventElapsedTime(&a, ev[0], ev[1]));
     HIPCHK(h, hipEventElapsedTime(&c, ev[2], ev[3]));
@@ -2225,7 +2234,7 @@ extern "C" int gpsbb_batch_timing_stats(gpsbb_batch_t *b, int *nruns, float *ms_
     gpsbb *h = b->h;
     float sa = 0, sc = 0, stt = 0;
     for (size_t k = 0; k < b->ev_used; k++) {
-        hipEvent_t *ev = b->evs[k].e;
+        const Event *ev = b->evs[k].e;
         float a = 0, c = 0, t = 0;
         HIPCHK(h, hipEventElapsedTime(&a, ev[0], ev[1]));
         HIPCHK(h, hipEventElapsedTime(&c, ev[2], ev[3]));
@@ -2248,9 +2257,10 @@ extern "C" int gpsbb_fill_ceiling(gpsbb_t *h, void *d_dst, size_t bytes, int ite
     if (!h || !d_dst || bytes < 16 || iters < 1 || !ms)
         return GPSBB_E_BADARG;
     HIPCHK(h, hipSetDevice(h->device));
-    hipEvent_t e0, e1;
-    HIPCHK(h, hipEventCreate(&e0));
-    HIPCHK(h, hipEventCreate(&e1));
+    Event e0, e1;
+    const AtExit done{[&] { release_all(e0, e1); }};
+    HIPCHK(h, e0.make(hipEventDefault));
+    HIPCHK(h, e1.make(hipEventDefault));
     const size_t n16 = bytes / 16;
     const int grid = (int)cu_count(h->sm_count) * 8;
     hipLaunchKernelGGL(k_fill_ceiling, dim3(grid), dim3(256), 0, h->s_compute, (uint4 *)d_dst, n16, 1u);
@@ -2262,8 +2272,6 @@ extern "C" int gpsbb_fill_ceiling(gpsbb_t *h, void *d_dst, size_t bytes, int ite
     float t = 0;
     HIPCHK(h, hipEventElapsedTime(&t, e0, e1));
     *ms = t / iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     return GPSBB_OK;
 }
 
@@ -2425,22 +2433,19 @@ static bool noise_args(const gpsbb_noise_t *nz, NoiseArgs *a)
 /* the knot table on the device and the clip counter: made on the handle's first call with noise */
 static hipError_t noise_ready(gpsbb *h)
 {
-    if (h->d_noise_tab)
+    if (h->d_noise_tab.p)
         return hipSuccess;
     const int32_t *k = noise_knots();
     std::vector<int2> t(NOISE_KNOTS - 1);
     for (int i = 0; i + 1 < NOISE_KNOTS; i++)
         t[i] = make_int2(k[i], k[i + 1] - k[i]);
-    hipError_t e = hipMalloc((void **)&h->d_nclip, 8);
-    if (e == hipSuccess) e = zero_now(h, h->d_nclip, 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_noise_tab, t.size() * sizeof(int2));
-    if (e == hipSuccess) e = hipMemcpy(h->d_noise_tab, t.data(), t.size() * sizeof(int2), hipMemcpyHostToDevice);
+    hipError_t e = (hipError_t)h->d_nclip.reserve(1);
+    if (e == hipSuccess) e = zero_now(h, h->d_nclip.p, 8);
+    if (e == hipSuccess) e = (hipError_t)h->d_noise_tab.reserve(t.size());
+    if (e == hipSuccess) e = hipMemcpy(h->d_noise_tab.p, t.data(), t.size() * sizeof(int2), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr); /* (the table is there before any non-blocking stream reads it) */
-    if (e != hipSuccess) {
-        if (h->d_noise_tab)
-            (void)hipFree(h->d_noise_tab);
-        h->d_noise_tab = nullptr;
-    }
+    if (e != hipSuccess)
+        release_all(h->d_noise_tab, h->d_nclip); /* both or neither (FixScratch::reserve): the next call with noise starts clean */
     return e;
 }
 
@@ -2662,9 +2667,9 @@ static hipError_t out_launch(gpsbb *h, int fmt, int shift8, const ImpairCall *ic
     if (!ic) {
         const int gwg = (int)GPSBB_KNOB_LONG("GPSBB_GATHER_WGS", 32);
         if (fmt == PACK_SC8)
-            hipLaunchKernelGGL(k_pack_iq<PACK_SC8>, dim3(gwg), dim3(256), 0, stream, src, (unsigned char *)dst, n, shift8, h->d_clip);
+            hipLaunchKernelGGL(k_pack_iq<PACK_SC8>, dim3(gwg), dim3(256), 0, stream, src, (unsigned char *)dst, n, shift8, h->d_clip.p);
         else if (fmt == PACK_SC1)
-            hipLaunchKernelGGL(k_pack_iq<PACK_SC1>, dim3(gwg), dim3(256), 0, stream, src, (unsigned char *)dst, n, shift8, h->d_clip);
+            hipLaunchKernelGGL(k_pack_iq<PACK_SC1>, dim3(gwg), dim3(256), 0, stream, src, (unsigned char *)dst, n, shift8, h->d_clip.p);
         else
             hipLaunchKernelGGL(k_gather_to_host, dim3(gwg), dim3(256), 0, stream, (const gather_u32x4 *)src, (gather_u32x4 *)dst,
                                (n * 2 + 15) / 16);
@@ -2681,8 +2686,8 @@ static hipError_t out_launch(gpsbb *h, int fmt, int shift8, const ImpairCall *ic
     static const ImpairKernelFn k[3][3] = {GPSBB_IMPAIR_ROW(NOISE_SC16), GPSBB_IMPAIR_ROW(PACK_SC8), GPSBB_IMPAIR_ROW(PACK_SC1)};
 #undef GPSBB_IMPAIR_ROW
     /* (a set without noise, an empty one too, runs the emitter loop: its shift still holds) */
-    hipLaunchKernelGGL(k[fmt][!ic->noise ? 2 : (a.it.n > 0 ? 1 : 0)], dim3(gwg), dim3(256), 0, stream, src, dst, n, a, h->d_noise_tab,
-                       h->d_tabs, h->d_nclip, h->d_clip);
+    hipLaunchKernelGGL(k[fmt][!ic->noise ? 2 : (a.it.n > 0 ? 1 : 0)], dim3(gwg), dim3(256), 0, stream, src, dst, n, a, h->d_noise_tab.p,
+                       h->d_tabs.p, h->d_nclip.p, h->d_clip.p);
     return hipGetLastError();
 }
 
@@ -2745,7 +2750,7 @@ static hipError_t level_launch(gpsbb *h, const ImpairArgs &a, bool noise, const 
     const bool interf = a.it.n > 0;
     typedef void (*LevelKernelFn)(const int16_t *, long, int, int, ImpairArgs, const int2 *, const int32_t *, LevelOut *);
     static const LevelKernelFn k[2][2] = GPSBB_NI_KERNELS(k_level);
-    hipLaunchKernelGGL(k[noise][interf], dim3(gwg), dim3(256), 0, stream, src, nblocks, nsamp, cpb, a, h->d_noise_tab, h->d_tabs, d_out);
+    hipLaunchKernelGGL(k[noise][interf], dim3(gwg), dim3(256), 0, stream, src, nblocks, nsamp, cpb, a, h->d_noise_tab.p, h->d_tabs.p, d_out);
     return hipGetLastError();
 }
 
@@ -2898,7 +2903,7 @@ static DsArgs iq_view(const gpsbb *h, const void *d_iq, int shift8, const Impair
     d.iq = static_cast<const uint32_t *>(d_iq);
     d.shift8 = shift8;
     d.nz = ic.a.nz;
-    d.ntab = h->d_noise_tab;
+    d.ntab = h->d_noise_tab.p;
     d.it = ic.a.it;
     return d;
 }
@@ -3081,13 +3086,13 @@ extern "C" int gpsbb_device_acquire(gpsbb_t *h, const int16_t *d_iq, long nsamp,
     if (grid)
         HIPCHK(h, hipMemsetAsync(h->d_acq_grid.p, 0, grid_words * 8, cs));
     a.d = iq_view(h, d_iq, shift8, ic);
-    a.tabs = h->d_tabs;
+    a.tabs = h->d_tabs.p;
     a.chips = reinterpret_cast<const int8_t *>(h->d_acq_chips.p);
     a.grid = grid ? h->d_acq_grid.p : nullptr;
     a.part = d_part;
     const long long nchip = (long long)a.nnc * a.npad;
     HIPCHK(h, h->acq_tm.start(cs));
-    hipLaunchKernelGGL(k_acq_chips, dim3((unsigned)((nchip + 255) / 256)), dim3(256), 0, cs, h->d_ca, reinterpret_cast<int8_t *>(h->d_acq_chips.p),
+    hipLaunchKernelGGL(k_acq_chips, dim3((unsigned)((nchip + 255) / 256)), dim3(256), 0, cs, h->d_ca.p, reinterpret_cast<int8_t *>(h->d_acq_chips.p),
                        cfg->prn_mask, (unsigned long long)cfg->code_step, a.ncoh, a.npad, a.nnc);
     HIPCHK(h, hipGetLastError());
     /* x: runs of four delay tiles (at most 256), y: the bins (at most 64) */
@@ -3161,8 +3166,8 @@ extern "C" int gpsbb_device_track(gpsbb_t *h, const int16_t *d_iq, long nsamp, u
     TrkArgs a;
     memset(&a, 0, sizeof a);
     a.d = iq_view(h, d_iq, shift8, ic);
-    a.tabs = h->d_tabs;
-    a.ca_bits = h->d_ca;
+    a.tabs = h->d_tabs.p;
+    a.ca_bits = h->d_ca.p;
     a.cfg = *cfg;
     a.states = reinterpret_cast<gpsbb_trk_state_t *>(h->d_trk.p);
     a.counts = reinterpret_cast<int32_t *>(h->d_trk.p + st_words);
@@ -3231,7 +3236,7 @@ extern "C" int gpsbb_device_fir(gpsbb_t *h, const int16_t *d_iq, long nsamp, con
     FirArgs a;
     memset(&a, 0, sizeof a);
     a.d = iq_view(h, d_iq, 0, ic);
-    a.tabs = h->d_tabs;
+    a.tabs = h->d_tabs.p;
     a.clipped = h->d_fir.p;
     uint32_t *d_hist_in = reinterpret_cast<uint32_t *>(h->d_fir.p + 1), *d_hist_out = reinterpret_cast<uint32_t *>(h->d_fir.p + 1 + hist_words);
     a.hist_in = d_hist_in;
@@ -3299,19 +3304,18 @@ static int fill_block_finish(gpsbb_t *h, gpsbb_batch *b, int nch, int nsamp, int
                              const void *src, size_t bytes)
 {
     const size_t end_bytes = (size_t)GPSBB_MAX_CHAN * sizeof(gpsbb_chan_state_t);
-    if (!h->h_fill)
-        HIPCHK(h, hipHostMalloc((void **)&h->h_fill, end_bytes + 64, hipHostMallocDefault));
+    HIPCHK(h, (hipError_t)h->h_fill.reserve(end_bytes + 64));
     hipStream_t cs = b->last_cs;
-    uint32_t *st = reinterpret_cast<uint32_t *>(h->h_fill + end_bytes);
+    uint32_t *st = reinterpret_cast<uint32_t *>(h->h_fill.p + end_bytes);
     *st = 0xffffffffu;
     if (GPSBB_KNOB_LONG("GPSBB_FILL_TAIL_KERNEL", 1) != 0) {
         static_assert(sizeof(gpsbb_chan_state_t) % 4 == 0, "copied as 32-bit words");
-        hipLaunchKernelGGL(k_fill_tail, dim3(1), dim3(256), 0, cs, end_state ? b->sets[b->last_set].end.p : nullptr, h->d_status, h->h_fill, nch, st);
+        hipLaunchKernelGGL(k_fill_tail, dim3(1), dim3(256), 0, cs, end_state ? b->sets[b->last_set].end.p : nullptr, h->d_status.p, h->h_fill.p, nch, st);
         HIPCHK(h, hipGetLastError());
     } else {
         if (end_state)
-            HIPCHK(h, hipMemcpyAsync(h->h_fill, b->sets[b->last_set].end.p, (size_t)nch * sizeof(gpsbb_chan_state_t), hipMemcpyDeviceToHost, cs));
-        HIPCHK(h, hipMemcpyAsync(st, h->d_status, 4, hipMemcpyDeviceToHost, cs));
+            HIPCHK(h, hipMemcpyAsync(h->h_fill.p, b->sets[b->last_set].end.p, (size_t)nch * sizeof(gpsbb_chan_state_t), hipMemcpyDeviceToHost, cs));
+        HIPCHK(h, hipMemcpyAsync(st, h->d_status.p, 4, hipMemcpyDeviceToHost, cs));
     }
     PUSH_MARK("tail");
     /* (iq_out null: the synthesis kernel wrote into the caller's registered buffer.)  A destination that lies partly in pages a
@@ -3325,26 +3329,19 @@ static int fill_block_finish(gpsbb_t *h, gpsbb_batch *b, int nch, int nsamp, int
         }
     }
     if (bounce) {
-        if (h->bounce_cap < bytes) {
-            if (h->h_bounce)
-                (void)hipHostFree(h->h_bounce);
-            h->h_bounce = nullptr;
-            h->bounce_cap = 0;
-            HIPCHK(h, hipHostMalloc((void **)&h->h_bounce, bytes, hipHostMallocDefault));
-            h->bounce_cap = bytes;
-        }
-        HIPCHK(h, hipMemcpyAsync(h->h_bounce, src, bytes, hipMemcpyDeviceToHost, cs));
+        HIPCHK(h, (hipError_t)h->h_bounce.reserve(bytes));
+        HIPCHK(h, hipMemcpyAsync(h->h_bounce.p, src, bytes, hipMemcpyDeviceToHost, cs));
     } else if (iq_out) {
         HIPCHK(h, hipMemcpyAsync(iq_out, src, bytes, hipMemcpyDeviceToHost, cs));
     }
     PUSH_MARK("iq copy");
     HIPCHK(h, hipStreamSynchronize(cs));
     if (bounce)
-        memcpy(iq_out, h->h_bounce, bytes);
+        memcpy(iq_out, h->h_bounce.p, bytes);
     if (end_state)
-        memcpy(end_state, h->h_fill, (size_t)nch * sizeof(gpsbb_chan_state_t));
+        memcpy(end_state, h->h_fill.p, (size_t)nch * sizeof(gpsbb_chan_state_t));
     if (*st) {
-        HIPCHK(h, zero_now(h, h->d_status, 4));
+        HIPCHK(h, zero_now(h, h->d_status.p, 4));
         return GPSBB_E_INTERNAL;
     }
     return GPSBB_OK;
@@ -3589,20 +3586,27 @@ struct gpsbb_stream {
     unsigned long long out_pos = 0; /* the stream position of the next push's first sample */
     struct Slot {
         gpsbb_batch *batch = nullptr;
-        int16_t *h_iq = nullptr;            /* pinned */
-        gpsbb_chan_state_t *h_end = nullptr; /* pinned */
-        unsigned long long *h_dig = nullptr; /* pinned, on the first GPSBB_PUSH_DIGEST: the push's block digests */
+        PinnedBuf<unsigned char> h_iq;     /* the gather, in the stream's output format (none: GPSBB_STREAM_DEVICE_ONLY) */
+        PinnedBuf<unsigned char> h_end;    /* the end states, and the status word behind them */
+        PinnedBuf<unsigned long long> h_dig; /* on the first GPSBB_PUSH_DIGEST: the push's block digests */
         bool has_dig = false;
-        LevelOut *d_lvl = nullptr;           /* on the first GPSBB_PUSH_LEVEL: the push's block levels on the device ... */
-        LevelOut *h_lvl = nullptr;           /* ... and pinned, behind the gather on its stream */
+        DevBuf<LevelOut> d_lvl;            /* on the first GPSBB_PUSH_LEVEL: the push's block levels on the device ... */
+        PinnedBuf<LevelOut> h_lvl;         /* ... and pinned, behind the gather on its stream */
         bool has_lvl = false;
-        hipEvent_t computed = nullptr, copied = nullptr;
+        Event computed, copied;
+        void release()
+        {
+            if (batch)
+                gpsbb_batch_destroy(batch);
+            batch = nullptr;
+            release_all(h_iq, h_dig, h_lvl, d_lvl, h_end, computed, copied);
+        }
     };
     std::vector<Slot> slots;
     uint64_t head = 0, tail = 0; /* pushes / pops so far */
     StreamChain chain;           /* where the carrier chain stands after the last push */
-    ChainCarryDev *d_carry = nullptr; /* the carry while it is on the device (gpsbb_walk.hip.h): the exact phase never leaves it */
-    hipEvent_t ev_prefix = nullptr, ev_fix = nullptr;
+    DevBuf<ChainCarryDev> d_carry; /* the carry while it is on the device (gpsbb_walk.hip.h): the exact phase never leaves it */
+    Event ev_prefix, ev_fix;       /* ... and what orders its users across pushes: all three or none (push_carry_to_device) */
     std::vector<gpsbb_chan_t> seeded; /* a host-side push: its descriptors with every block's start phase */
     std::vector<double> seeds;
     bool poisoned = false; /* a push failed after part of it had been enqueued: the chain's state on the device has
@@ -3615,22 +3619,9 @@ extern "C" void gpsbb_stream_destroy(gpsbb_stream_t *s)
         return;
     (void)hipSetDevice(s->h->device);
     (void)drain_streams(s->h); /* the carry, the pinned slots and the events: pre-pass, synthesis and copy streams hold work on them */
-    if (s->d_carry)
-        (void)hipFree(s->d_carry);
-    if (s->ev_prefix)
-        (void)hipEventDestroy(s->ev_prefix);
-    if (s->ev_fix)
-        (void)hipEventDestroy(s->ev_fix);
-    for (auto &sl : s->slots) {
-        if (sl.batch) gpsbb_batch_destroy(sl.batch);
-        if (sl.h_iq) (void)hipHostFree(sl.h_iq);
-        if (sl.h_dig) (void)hipHostFree(sl.h_dig);
-        if (sl.h_lvl) (void)hipHostFree(sl.h_lvl);
-        if (sl.d_lvl) (void)hipFree(sl.d_lvl);
-        if (sl.h_end) (void)hipHostFree(sl.h_end);
-        if (sl.computed) (void)hipEventDestroy(sl.computed);
-        if (sl.copied) (void)hipEventDestroy(sl.copied);
-    }
+    release_all(s->d_carry, s->ev_prefix, s->ev_fix);
+    for (auto &sl : s->slots)
+        sl.release();
     delete s;
 }
 
@@ -3670,10 +3661,10 @@ extern "C" int gpsbb_stream_create(gpsbb_t *h, int nch, double delt, int nsamp, 
         if (e == hipSuccess) sl.batch->max_sets = 1; /* consecutive pushes use different slots: one table set each */
         if (e == hipSuccess) e = (hipError_t)sl.batch->d_iq.reserve(iq_bytes / 2);
         if (e == hipSuccess && !(flags & GPSBB_STREAM_DEVICE_ONLY))
-            e = hipHostMalloc((void **)&sl.h_iq, host_bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&sl.h_end, end_bytes + 32, hipHostMallocDefault); /* + the status word */
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.computed, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming);
+            e = (hipError_t)sl.h_iq.reserve(host_bytes);
+        if (e == hipSuccess) e = (hipError_t)sl.h_end.reserve(end_bytes + 32); /* + the status word */
+        if (e == hipSuccess) e = sl.computed.make(hipEventDisableTiming);
+        if (e == hipSuccess) e = sl.copied.make(hipEventDisableTiming);
         if (e != hipSuccess) {
             h->last_hip = (int)e;
             gpsbb_stream_destroy(s);
@@ -3699,8 +3690,8 @@ extern "C" int gpsbb_stream_reset(gpsbb_stream_t *s)
     const int rc = gpsbb_sync(h);
     if (rc != GPSBB_OK)
         return rc;
-    if (s->d_carry)
-        HIPCHK(h, zero_now(h, s->d_carry, sizeof(ChainCarryDev)));
+    if (s->d_carry.p)
+        HIPCHK(h, zero_now(h, s->d_carry.p, sizeof(ChainCarryDev)));
     s->chain.forget(true);
     s->head = s->tail = 0;
     s->out_pos = s->noise_on || !s->interf_on ? s->impair.nz.sample0 : s->impair.it.sample0;
@@ -3807,10 +3798,8 @@ static int push_level_memory(gpsbb_stream *s, const ImpairCall &ic)
         return GPSBB_E_BADARG;
     auto &sl = s->slots[s->head % s->depth];
     HIPCHK(s->h, hipSetDevice(s->h->device));
-    if (!sl.d_lvl)
-        HIPCHK(s->h, hipMalloc((void **)&sl.d_lvl, (size_t)s->bps * sizeof(LevelOut)));
-    if (!sl.h_lvl)
-        HIPCHK(s->h, hipHostMalloc((void **)&sl.h_lvl, (size_t)s->bps * sizeof(LevelOut), hipHostMallocDefault));
+    HIPCHK(s->h, (hipError_t)sl.d_lvl.reserve((size_t)s->bps));
+    HIPCHK(s->h, (hipError_t)sl.h_lvl.reserve((size_t)s->bps));
     return GPSBB_OK;
 }
 
@@ -3819,11 +3808,14 @@ static int push_carry_to_device(gpsbb_stream *s, StreamChain &next)
 {
     gpsbb *h = s->h;
     StreamChain &at = s->chain;
-    if (!s->d_carry) {
-        HIPCHK(h, hipMalloc((void **)&s->d_carry, sizeof(ChainCarryDev)));
-        HIPCHK(h, zero_now(h, s->d_carry, sizeof(ChainCarryDev)));
-        HIPCHK(h, hipEventCreateWithFlags(&s->ev_prefix, hipEventDisableTiming));
-        HIPCHK(h, hipEventCreateWithFlags(&s->ev_fix, hipEventDisableTiming));
+    if (!s->ev_fix) { /* the last of the four steps: there only once all of them have succeeded */
+        hipError_t e = (hipError_t)s->d_carry.reserve(1);
+        e = e ? e : zero_now(h, s->d_carry.p, sizeof(ChainCarryDev));
+        e = e ? e : s->ev_prefix.make(hipEventDisableTiming);
+        e = e ? e : s->ev_fix.make(hipEventDisableTiming);
+        if (e != hipSuccess) /* all or none (FixScratch::reserve): a carry without its events would be used unordered, and maybe unzeroed */
+            release_all(s->d_carry, s->ev_prefix, s->ev_fix);
+        HIPCHK(h, e);
     }
     if (!at.on_device && s->head > 0) {
         /* host -> device: the exact phases as both the prediction and the truth */
@@ -3833,7 +3825,7 @@ static int push_carry_to_device(gpsbb_stream *s, StreamChain &next)
         const int rc = gpsbb_sync(h);
         if (rc != GPSBB_OK)
             return rc;
-        HIPCHK(h, hipMemcpy(s->d_carry, &c, sizeof c, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(s->d_carry.p, &c, sizeof c, hipMemcpyHostToDevice));
         HIPCHK(h, hipStreamSynchronize(nullptr)); /* (see zero_now) */
         for (int i = 0; i < s->nch; i++) {
             at.last_prn[i] = at.carry.prn[i];
@@ -3857,7 +3849,7 @@ static int push_carry_to_host(gpsbb_stream *s, StreamChain &next, PlanIn &in, Pu
         const int rc = gpsbb_sync(h);
         if (rc != GPSBB_OK)
             return rc;
-        HIPCHK(h, hipMemcpy(&c, s->d_carry, sizeof c, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(&c, s->d_carry.p, sizeof c, hipMemcpyDeviceToHost));
         for (int i = 0; i < s->nch; i++) {
             at.carry.prn[i] = at.last_prn[i];
             at.carry.phase[i] = c.exact_end[i];
@@ -3887,20 +3879,20 @@ static int push_outputs(gpsbb_stream *s, gpsbb_stream::Slot &sl, ImpairCall &ic,
      * event wait and no stream that holds one (a hardware queue whose head is a wait for a 1.5 ms kernel runs nothing that
      * shares it until then).  (The slot's previous D2H copy was waited for by the pop that freed it.) */
     hipStream_t cs = b->last_cs;
-    if (sl.h_iq) {
+    if (sl.h_iq.p) {
         if (!h->s_copy)
             HIPCHK(h, hipStreamCreateWithFlags(&h->s_copy, hipStreamNonBlocking));
         cs = h->s_copy;
         HIPCHK(h, hipStreamWaitEvent(cs, b->last_done, 0));
     }
     PUSH_MARK("wait");
-    if (sl.h_iq) {
+    if (sl.h_iq.p) {
         const bool sdma = GPSBB_KNOB_SET("GPSBB_GATHER_SDMA"); /* experiment: the runtime's copy instead */
         if (sdma && !ic.any() && !s->fmt) {
-            HIPCHK(h, hipMemcpyAsync(sl.h_iq, b->d_iq.p, (size_t)s->bps * s->nsamp * 4, hipMemcpyDeviceToHost, cs));
+            HIPCHK(h, hipMemcpyAsync(sl.h_iq.p, b->d_iq.p, (size_t)s->bps * s->nsamp * 4, hipMemcpyDeviceToHost, cs));
         } else {
             /* the plain gather, packed, or with noise and interference on the way out: the same launch that returns at once */
-            HIPCHK(h, out_launch(h, s->fmt, s->shift, ic.any() ? &ic : nullptr, b->d_iq.p, sl.h_iq, (size_t)s->bps * s->nsamp * 2, cs));
+            HIPCHK(h, out_launch(h, s->fmt, s->shift, ic.any() ? &ic : nullptr, b->d_iq.p, sl.h_iq.p, (size_t)s->bps * s->nsamp * 2, cs));
         }
     }
     PUSH_MARK("iq");
@@ -3908,16 +3900,16 @@ static int push_outputs(gpsbb_stream *s, gpsbb_stream::Slot &sl, ImpairCall &ic,
      * allocation's slack) + the self-check word, by a small kernel: see k_end_states_to_host */
     const size_t bytes = (size_t)s->bps * s->nch * sizeof(gpsbb_chan_state_t);
     hipLaunchKernelGGL(k_end_states_to_host, dim3(64), dim3(256), 0, cs, (const uint4 *)b->sets[b->last_set].end.p,
-                       (uint4 *)sl.h_end, (bytes + 15) / 16, h->d_status, (uint32_t *)((char *)sl.h_end + ((bytes + 15) & ~(size_t)15)));
+                       (uint4 *)sl.h_end.p, (bytes + 15) / 16, h->d_status.p, (uint32_t *)(sl.h_end.p + ((bytes + 15) & ~(size_t)15)));
     HIPCHK(h, hipGetLastError());
     if (want_digest) {
-        HIPCHK(h, hipMemcpyAsync(sl.h_dig, b->d_dig.p, (size_t)s->bps * sizeof(unsigned long long), hipMemcpyDeviceToHost, cs));
+        HIPCHK(h, hipMemcpyAsync(sl.h_dig.p, b->d_dig.p, (size_t)s->bps * sizeof(unsigned long long), hipMemcpyDeviceToHost, cs));
         sl.has_dig = true;
     }
     if (want_level) {
         /* the slot measured where it is gathered: behind the gather, on its stream, results through pinned memory */
-        HIPCHK(h, level_launch(h, ic.a, ic.noise, b->d_iq.p, s->bps, s->nsamp, sl.d_lvl, cs));
-        HIPCHK(h, hipMemcpyAsync(sl.h_lvl, sl.d_lvl, (size_t)s->bps * sizeof(LevelOut), hipMemcpyDeviceToHost, cs));
+        HIPCHK(h, level_launch(h, ic.a, ic.noise, b->d_iq.p, s->bps, s->nsamp, sl.d_lvl.p, cs));
+        HIPCHK(h, hipMemcpyAsync(sl.h_lvl.p, sl.d_lvl.p, (size_t)s->bps * sizeof(LevelOut), hipMemcpyDeviceToHost, cs));
         sl.has_lvl = true;
     }
     PUSH_MARK("endst");
@@ -3978,7 +3970,7 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
      * the copy); the accumulator's chaining state behind a first push */
     PushGuard guard{s, b};
     if (side.chain == PUSH_CHAIN_DEVICE) {
-        b->link.d_carry = s->d_carry;
+        b->link.d_carry = s->d_carry.p;
         b->link.carry_prn = s->chain.last_prn;
         b->link.carry_phase = next.rough_phase;
         b->link.ev_prefix = s->ev_prefix;
@@ -4009,8 +4001,8 @@ static int stream_push(gpsbb_stream_t *s, const gpsbb_chan_t *ch, bool new_chain
     b->last_iq = b->d_iq.p;
     guard.queued = true;
     b->want_digest = want_digest;
-    if (want_digest && !sl.h_dig)
-        HIPCHK(h, hipHostMalloc((void **)&sl.h_dig, (size_t)s->bps * sizeof(unsigned long long), hipHostMallocDefault));
+    if (want_digest)
+        HIPCHK(h, (hipError_t)sl.h_dig.reserve((size_t)s->bps));
     sl.has_dig = false;
     sl.has_lvl = false;
     rc = batch_launch(b, b->d_iq.p);
@@ -4061,18 +4053,18 @@ static int stream_pop(gpsbb_stream_t *s, const int16_t **iq, gpsbb_chan_state_t 
     HIPCHK(h, hipSetDevice(h->device));
     auto &sl = s->slots[s->tail % s->depth];
     HIPCHK(h, hipEventSynchronize(sl.copied));
-    *iq = sl.h_iq ? sl.h_iq : sl.batch->d_iq.p; /* GPSBB_STREAM_DEVICE_ONLY: the slot's buffer in HBM */
+    *iq = sl.h_iq.p ? reinterpret_cast<const int16_t *>(sl.h_iq.p) : sl.batch->d_iq.p; /* GPSBB_STREAM_DEVICE_ONLY: the slot's buffer in HBM */
     if (end_state)
-        memcpy(end_state, sl.h_end, (size_t)s->bps * s->nch * sizeof(gpsbb_chan_state_t));
+        memcpy(end_state, sl.h_end.p, (size_t)s->bps * s->nch * sizeof(gpsbb_chan_state_t));
     if (digests)
-        memcpy(digests, sl.h_dig, (size_t)s->bps * sizeof(unsigned long long));
+        memcpy(digests, sl.h_dig.p, (size_t)s->bps * sizeof(unsigned long long));
     if (levels)
-        memcpy(levels, sl.h_lvl, (size_t)s->bps * sizeof(gpsbb_level_t));
+        memcpy(levels, sl.h_lvl.p, (size_t)s->bps * sizeof(gpsbb_level_t));
     s->tail++;
     uint32_t st = 0;
-    memcpy(&st, (const char *)sl.h_end + (((size_t)s->bps * s->nch * sizeof(gpsbb_chan_state_t) + 15) & ~(size_t)15), 4);
+    memcpy(&st, sl.h_end.p + (((size_t)s->bps * s->nch * sizeof(gpsbb_chan_state_t) + 15) & ~(size_t)15), 4);
     if (st) {
-        HIPCHK(h, zero_now(h, h->d_status, 4));
+        HIPCHK(h, zero_now(h, h->d_status.p, 4));
         return GPSBB_E_INTERNAL;
     }
     return GPSBB_OK;
@@ -4178,13 +4170,13 @@ struct ChainOnly {
     DevBuf<ChainDesc> d_cd;
     DevBuf<double> d_start0;
     DevBuf<ChainAux> d_aux;
-    ChainCarryDev *d_carry = nullptr;
-    uint32_t *d_status = nullptr; /* a self-check word of its own: the handle's may belong to a push still in flight */
+    DevBuf<ChainCarryDev> d_carry;
+    DevBuf<uint32_t> d_status; /* a self-check word of its own: the handle's may belong to a push still in flight */
     FixScratch fix;
     /* the lap-parallel chain (gpsbb_laps.hip.h with nothing to emit): the phase after every block, scratch of the lap kernels */
     DevBuf<double> d_lap_end;
     LapScratch lap;
-    unsigned long long *d_hz_scratch = nullptr; /* (a chain alone counts no hazards: the render of those blocks does) */
+    DevBuf<unsigned long long> d_hz_scratch; /* (a chain alone counts no hazards: the render of those blocks does) */
     std::vector<double> h_lap_end;
 };
 
@@ -4193,13 +4185,7 @@ static void chain_only_free(gpsbb *h)
     ChainOnly *c = h->chain_only;
     if (!c)
         return;
-    release_all(c->d_cd, c->d_start0, c->d_aux, c->d_lap_end, c->lap, c->fix);
-    if (c->d_hz_scratch)
-        (void)hipFree(c->d_hz_scratch);
-    if (c->d_carry)
-        (void)hipFree(c->d_carry);
-    if (c->d_status)
-        (void)hipFree(c->d_status);
+    release_all(c->d_cd, c->d_start0, c->d_aux, c->d_lap_end, c->lap, c->fix, c->d_hz_scratch, c->d_carry, c->d_status);
     delete c;
     h->chain_only = nullptr;
 }
@@ -4208,16 +4194,13 @@ static void chain_only_free(gpsbb *h)
 static int chain_only_scratch(gpsbb *h, ChainOnly *c, size_t lap_seeds)
 {
     HIPCHK(h, hipSetDevice(h->device));
-    if (!c->d_carry)
-        HIPCHK(h, hipMalloc((void **)&c->d_carry, sizeof(ChainCarryDev)));
-    if (!c->d_status)
-        HIPCHK(h, hipMalloc((void **)&c->d_status, 4));
-    HIPCHK(h, hipMemsetAsync(c->d_carry, 0, sizeof(ChainCarryDev), h->s_seed));
-    HIPCHK(h, hipMemsetAsync(c->d_status, 0, 4, h->s_seed));
+    HIPCHK(h, (hipError_t)c->d_carry.reserve(1));
+    HIPCHK(h, (hipError_t)c->d_status.reserve(1));
+    HIPCHK(h, hipMemsetAsync(c->d_carry.p, 0, sizeof(ChainCarryDev), h->s_seed));
+    HIPCHK(h, hipMemsetAsync(c->d_status.p, 0, 4, h->s_seed));
     if (c->plan.laps) {
-        if (!c->d_hz_scratch)
-            HIPCHK(h, hipMalloc((void **)&c->d_hz_scratch, 64));
-        HIPCHK(h, hipMemsetAsync(c->d_hz_scratch, 0, 64, h->s_seed));
+        HIPCHK(h, (hipError_t)c->d_hz_scratch.reserve(8));
+        HIPCHK(h, hipMemsetAsync(c->d_hz_scratch.p, 0, c->d_hz_scratch.cap * sizeof *c->d_hz_scratch.p, h->s_seed));
         if (lap_seeds)
             c->h_lap_end.resize(lap_seeds);
     }
@@ -4237,13 +4220,13 @@ static BatchDev chain_only_dev(const ChainOnly *c, const ChainOnlyPiece &pc, con
     p.nstates = p.ntiles;
     p.delt = in.delt;
     p.flags = GPSBB_CHAIN_CARRIER;
-    p.status = c->d_status;
+    p.status = c->d_status.p;
     p.hazards = hazards;
     p.chain_dev = 1;
     p.nseg = 1;
     p.nvb = pc.nb;
     p.cd = c->d_cd.p;
-    p.carry = c->d_carry;
+    p.carry = c->d_carry.p;
     p.cont0_mask = pc.cont0_mask;
     return p;
 }
@@ -4261,7 +4244,7 @@ static int chain_only_lap_piece(gpsbb *h, ChainOnly *c, const ChainOnlyPiece &pc
     LapDev L;
     c->lap.dev(L);
     lap_dev_plan(L, pc.chunk0, true, nbc);
-    BatchDev p = chain_only_dev(c, pc, in, c->d_hz_scratch);
+    BatchDev p = chain_only_dev(c, pc, in, c->d_hz_scratch.p);
     p.lap_end = c->d_lap_end.p;
     lap_chain_launch(ss, p, L, in.nch, NCO_CARR, lap_pass2_kernel(NCO_CARR, false, 0));
     HIPCHK(h, hipGetLastError());
@@ -4283,7 +4266,7 @@ static int chain_only_walk_piece(gpsbb *h, ChainOnly *c, const ChainOnlyPiece &p
     HIPCHK(h, c->fix.reserve((size_t)GPSBB_MAX_CHAN * ((CHAIN_ONLY_BLOCKS + FIXP_WG_ALONE - 1) / FIXP_WG_ALONE), ss));
     HIPCHK(h, hipMemcpyAsync(c->d_cd.p, c->img.h_cd.data() + k0, nbc * sizeof(ChainDesc), hipMemcpyHostToDevice, ss));
     HIPCHK(h, hipMemcpyAsync(c->d_start0.p, c->img.h_start0.data() + k0, nbc * sizeof(double), hipMemcpyHostToDevice, ss));
-    BatchDev p = chain_only_dev(c, pc, in, h->d_hz);
+    BatchDev p = chain_only_dev(c, pc, in, h->d_hz.p);
     p.chain_starts = 1;
     p.model_start = 0; /* over tens of thousands of blocks a prediction drifts too far: pass A and the prefix stay */
     p.seg_tiles = p.ntiles;
@@ -4330,13 +4313,13 @@ static int chain_only_finish(gpsbb *h, const ChainOnly *c, const PlanIn &in, dou
 {
     if (carr_phase_end) {
         ChainCarryDev cc;
-        HIPCHK(h, hipMemcpy(&cc, c->d_carry, sizeof cc, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(&cc, c->d_carry.p, sizeof cc, hipMemcpyDeviceToHost));
         for (int i = 0; i < in.nch; i++)
             carr_phase_end[i] = c->img.h_cd[(size_t)(in.nblocks - 1) * in.nch + i].prn > 0 ? cc.exact_end[i] : 0.0;
     }
     h->last_chain_dev = 1;
     uint32_t st = 0;
-    HIPCHK(h, hipMemcpy(&st, c->d_status, 4, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(&st, c->d_status.p, 4, hipMemcpyDeviceToHost));
     return st ? GPSBB_E_INTERNAL : GPSBB_OK;
 }
 
@@ -4361,6 +4344,14 @@ extern "C" int gpsbb_chain_carrier(gpsbb_t *h, const gpsbb_chan_t *ch, int nbloc
     if (want_seeds)
         (c->plan.laps ? chain_only_lap_seeds : chain_only_walk_seeds)(c, in, carr_phase_seed);
     return chain_only_finish(h, c, in, carr_phase_end);
+}
+
+/* what this process holds right now: device buffers, pinned buffers, events (gpsbb_testhooks.h; in both builds) */
+extern "C" void gpsbb_test_live(long long out[3])
+{
+    out[0] = g_live_dev.load(std::memory_order_relaxed);
+    out[1] = g_live_pinned.load(std::memory_order_relaxed);
+    out[2] = g_live_events.load(std::memory_order_relaxed);
 }
 
 #ifdef GPSBB_EXPERIMENTS
@@ -4472,25 +4463,24 @@ extern "C" int gpsbb_test_model_err(gpsbb_batch_t *b, double *maxima, unsigned l
     if (rc != GPSBB_OK)
         return rc;
     const BatchDev p = batch_dev(b, b->sets[b->last_set], batch_launch_plan(b));
-    double *d_mx = nullptr;
-    unsigned long long *d_cnt = nullptr;
+    DevBuf<double> d_mx;
+    DevBuf<unsigned long long> d_cnt;
+    const AtExit done{[&] { release_all(d_mx, d_cnt); }};
     const size_t mx_bytes = sizeof(double) * GPSBB_MAX_CHAN * ME_NQ, cnt_bytes = sizeof(unsigned long long) * GPSBB_MAX_CHAN * MEC_NQ;
-    HIPCHK(h, hipMalloc((void **)&d_mx, mx_bytes));
-    HIPCHK(h, hipMalloc((void **)&d_cnt, cnt_bytes));
-    HIPCHK(h, hipMemsetAsync(d_mx, 0, mx_bytes, h->s_compute));
-    HIPCHK(h, hipMemsetAsync(d_cnt, 0, cnt_bytes, h->s_compute));
+    HIPCHK(h, (hipError_t)d_mx.reserve((size_t)GPSBB_MAX_CHAN * ME_NQ));
+    HIPCHK(h, (hipError_t)d_cnt.reserve((size_t)GPSBB_MAX_CHAN * MEC_NQ));
+    HIPCHK(h, hipMemsetAsync(d_mx.p, 0, mx_bytes, h->s_compute));
+    HIPCHK(h, hipMemsetAsync(d_cnt.p, 0, cnt_bytes, h->s_compute));
     const size_t threads = (size_t)pl.nblocks * pl.nch * pl.ntiles;
     const dim3 grid((unsigned)((threads + 255) / 256));
     if (pl.ev_all_dense)
-        hipLaunchKernelGGL(k_model_err_pd, grid, dim3(256), 0, h->s_compute, p, d_mx, d_cnt);
+        hipLaunchKernelGGL(k_model_err_pd, grid, dim3(256), 0, h->s_compute, p, d_mx.p, d_cnt.p);
     else
-        hipLaunchKernelGGL(k_model_err_ev, grid, dim3(256), 0, h->s_compute, p, d_mx, d_cnt);
+        hipLaunchKernelGGL(k_model_err_ev, grid, dim3(256), 0, h->s_compute, p, d_mx.p, d_cnt.p);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->s_compute));
-    HIPCHK(h, hipMemcpy(maxima, d_mx, mx_bytes, hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemcpy(counts, d_cnt, cnt_bytes, hipMemcpyDeviceToHost));
-    (void)hipFree(d_mx);
-    (void)hipFree(d_cnt);
+    HIPCHK(h, hipMemcpy(maxima, d_mx.p, mx_bytes, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(counts, d_cnt.p, cnt_bytes, hipMemcpyDeviceToHost));
     if (which)
         *which = pl.ev_all_dense ? 2 : 1;
     return GPSBB_OK;
@@ -4715,12 +4705,12 @@ extern "C" long long gpsbb_test_read_pattern(gpsbb_t *h, const void *d_src, size
     waves -= waves % 4;
     if (waves < 4)
         return GPSBB_E_BADARG;
-    double *d_sink = nullptr;
-    if (hipMalloc((void **)&d_sink, 8) != hipSuccess)
+    DevBuf<double> d_sink;
+    if (d_sink.reserve(1) != hipSuccess)
         return GPSBB_E_NOMEM;
-    hipLaunchKernelGGL(k_read_pattern, dim3((unsigned)(waves / 4)), dim3(256), 0, h->s_compute, (const double *)d_src, rows, cols, d_sink);
+    hipLaunchKernelGGL(k_read_pattern, dim3((unsigned)(waves / 4)), dim3(256), 0, h->s_compute, (const double *)d_src, rows, cols, d_sink.p);
     const hipError_t e = hipStreamSynchronize(h->s_compute);
-    (void)hipFree(d_sink);
+    d_sink.release();
     return e == hipSuccess ? (long long)(waves * per_wave) : (long long)GPSBB_E_HIP;
 }
 
@@ -4737,24 +4727,22 @@ extern "C" int gpsbb_test_fir_tile(void) { return FIR_TILE; }
  * _begin: (re)arm the trace with room for `cap` records; _read: wait for the device, copy out up to `cap` records of
  * WG_TRACE_WORDS 64-bit words, return how many were written (the device counts on past the capacity). */
 namespace {
-unsigned long long *g_trace_buf = nullptr;
-unsigned g_trace_cap = 0;
+DevBuf<unsigned long long> g_trace_buf;
+unsigned g_trace_cap = 0; /* records */
 }
 extern "C" int gpsbb_test_wg_trace_begin(unsigned cap)
 {
     if (hipDeviceSynchronize() != hipSuccess)
         return GPSBB_E_HIP;
     if (cap > g_trace_cap) {
-        if (g_trace_buf)
-            (void)hipFree(g_trace_buf);
-        g_trace_buf = nullptr;
         g_trace_cap = 0;
-        if (hipMalloc((void **)&g_trace_buf, (size_t)cap * WG_TRACE_WORDS * 8) != hipSuccess)
+        g_trace_buf.release(); /* (exactly what is asked, as ever: an empty DevBuf takes no head-room) */
+        if (g_trace_buf.reserve((size_t)cap * WG_TRACE_WORDS) != hipSuccess)
             return GPSBB_E_NOMEM;
         g_trace_cap = cap;
     }
     const unsigned zero = 0;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_wg_trace), &g_trace_buf, sizeof g_trace_buf) != hipSuccess ||
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_wg_trace), &g_trace_buf.p, sizeof g_trace_buf.p) != hipSuccess ||
         hipMemcpyToSymbol(HIP_SYMBOL(g_wg_trace_cap), &cap, sizeof cap) != hipSuccess ||
         hipMemcpyToSymbol(HIP_SYMBOL(g_wg_trace_n), &zero, sizeof zero) != hipSuccess)
         return GPSBB_E_HIP;
@@ -4768,7 +4756,7 @@ extern "C" long gpsbb_test_wg_trace_read(unsigned long long *out, unsigned cap)
     if (hipMemcpyFromSymbol(&n, HIP_SYMBOL(g_wg_trace_n), sizeof n) != hipSuccess)
         return GPSBB_E_HIP;
     const unsigned have = n < g_trace_cap ? n : g_trace_cap, take = have < cap ? have : cap;
-    if (take && hipMemcpy(out, g_trace_buf, (size_t)take * WG_TRACE_WORDS * 8, hipMemcpyDeviceToHost) != hipSuccess)
+    if (take && hipMemcpy(out, g_trace_buf.p, (size_t)take * WG_TRACE_WORDS * 8, hipMemcpyDeviceToHost) != hipSuccess)
         return GPSBB_E_HIP;
     return (long)n;
 }

@@ -96,6 +96,10 @@ int gpsbb_test_fir_tile(void);
 int gpsbb_test_state_log2(struct gpsbb_batch *b);
 int gpsbb_test_state_log2_carr(struct gpsbb_batch *b);
 void gpsbb_test_budgets(double out[3]); /* EV_MODEL_ERR, EV_T_EPS, PD_BAND of this build, in units of 2^-32 */
+/* What the library holds in this process right now: device buffers, pinned host buffers, HIP events — every one made and freed
+ * through its owner (DevBuf, PinnedBuf, Event in gpsbb.hip), counted there.  Exported by the product build as well: a cycle of
+ * create ... destroy must leave all three where it found them (tests/test_lifecycle_gpu.py). */
+void gpsbb_test_live(long long out[3]);
 
 #ifdef __cplusplus
 }
