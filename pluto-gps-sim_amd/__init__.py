@@ -246,6 +246,44 @@ class Fir(C.Structure):
 assert C.sizeof(Fir) == 276
 
 
+# the power spectrum (include/gpsbb.h gpsbb_device_psd): an averaged periodogram of N = 1 << log2n point integer transforms
+PSD_MIN_LOG2N, PSD_MAX_LOG2N, PSD_MAX_N, PSD_MAX_HOP, PSD_MAX_SHIFT, PSD_MAX_NSEG = 6, 12, 4096, 1 << 20, 30, 1 << 20
+PSD_RECT, PSD_HANN = 0, 1
+PSD_MIN_POINTS = 1024    # the points one of k_psd's workgroups holds at least: 1024 / N segments side by side (csrc/gpsbb_psd.hip.h)
+PSD_RUN_BATCHES = 2      # a workgroup's run is at least this many loads of its LDS ...
+PSD_MAX_WGS = 1024       # ... and longer where the grid would pass this many workgroups
+
+
+def psd_run(log2n):
+    """the segments of a workgroup's least run at N = 1 << log2n (gpsbb_test_psd_run says the same): a call of up to PSD_MAX_WGS
+    times as many segments gives every run of that length its own workgroup"""
+    return max(1, PSD_MIN_POINTS >> log2n) * PSD_RUN_BATCHES
+
+
+class Psd(C.Structure):
+    """gpsbb_psd_t: log2n, hop, shift, win[0..N-1]"""
+    _fields_ = [("log2n", C.c_int32), ("hop", C.c_int32), ("shift", C.c_int32), ("_pad", C.c_int32), ("win", C.c_int16 * PSD_MAX_N)]
+
+    def __init__(self, log2n=PSD_MIN_LOG2N, hop=0, shift=0, win=()):
+        super().__init__()
+        self.log2n, self.hop, self.shift = log2n, hop, shift
+        w = np.ascontiguousarray(win, np.int16)
+        C.memmove(self.win, w.ctypes.data, min(w.size, PSD_MAX_N) * 2)
+
+    def window(self):
+        """win[0..N-1] as int64"""
+        return np.frombuffer(self.win, np.int16, 1 << min(max(int(self.log2n), 0), PSD_MAX_LOG2N)).astype(np.int64)
+
+    def copy(self, **fields):
+        c = Psd.from_buffer_copy(self)
+        for k, v in fields.items():
+            setattr(c, k, v)
+        return c
+
+
+assert C.sizeof(Psd) == 8208
+
+
 ERRORS = {0: "GPSBB_OK", -1: "GPSBB_E_BADARG", -2: "GPSBB_E_BADCHAN", -3: "GPSBB_E_HIP", -4: "GPSBB_E_NOMEM",
           -5: "GPSBB_E_INTERNAL", -6: "GPSBB_E_NODEVICE", -7: "GPSBB_E_STATE"}
 
@@ -267,6 +305,7 @@ API_SYMBOLS = [
     "gpsbb_device_acquire", "gpsbb_acq_min_shift", "gpsbb_acq_make", "gpsbb_acq_best",
     "gpsbb_device_track", "gpsbb_trk_make", "gpsbb_trk_seed", "gpsbb_trk_bitsync", "gpsbb_trk_bits",
     "gpsbb_device_fir", "gpsbb_fir_make",
+    "gpsbb_device_psd", "gpsbb_psd_make", "gpsbb_psd_min_shift", "gpsbb_psd_twiddles", "gpsbb_psd_scale",
 ]
 # ... and include/gpsbb_node.h
 NODE_API_SYMBOLS = ["gpsbb_node_create", "gpsbb_node_run", "gpsbb_node_run_digest", "gpsbb_node_slot_digests", "gpsbb_node_destroy", "gpsbb_node_plan", "gpsbb_node_begin", "gpsbb_node_feed", "gpsbb_node_end",
@@ -405,6 +444,13 @@ def lib():
         if hasattr(L, "gpsbb_device_fir"):  # the filter's calls, as a group (an older build loaded for an A/B: tools/ab_lib.sh)
             L.gpsbb_device_fir.argtypes = [vp, vp, C.c_long, vp, vp, vp, vp, vp, vp, vp]
             L.gpsbb_fir_make.argtypes = [vp, i, i, d, d]
+        if hasattr(L, "gpsbb_device_psd"):  # the spectrum's calls, as a group (an older build loaded for an A/B: tools/ab_lib.sh)
+            L.gpsbb_device_psd.argtypes = [vp, vp, C.c_long, u, vp, vp, vp, vp, vp]
+            L.gpsbb_psd_make.argtypes = [vp, i, C.c_long, i, C.c_long]
+            L.gpsbb_psd_min_shift.argtypes = [C.c_long]
+            L.gpsbb_psd_twiddles.argtypes = [vp, vp]
+            L.gpsbb_psd_scale.argtypes = [vp, C.c_long, u]
+            L.gpsbb_psd_scale.restype = d
         if hasattr(L, "gpsbb_test_live"):  # (an older build loaded for an A/B: tools/ab_lib.sh)
             L.gpsbb_test_live.argtypes = [vp]
             L.gpsbb_test_live.restype = None
@@ -451,6 +497,10 @@ def exp_lib():
             L.gpsbb_test_fir_ms.argtypes = [vp]
             L.gpsbb_test_fir_ms.restype = C.c_float
             L.gpsbb_test_fir_tile.argtypes = []
+        if hasattr(L, "gpsbb_test_psd_ms"):  # (an older build loaded for an A/B: tools/ab_lib.sh)
+            L.gpsbb_test_psd_ms.argtypes = [vp]
+            L.gpsbb_test_psd_ms.restype = C.c_float
+            L.gpsbb_test_psd_run.argtypes = [i]
         _exp_lib = L
     return _exp_lib
 
@@ -729,6 +779,16 @@ class Synth:
                                     None if hin is None else hin.ctypes.data, hout.ctypes.data, C.c_void_p(int(d_out)), C.byref(clipped)),
              "gpsbb_device_fir")
         return hout, int(clipped.value)
+
+    def device_psd(self, d_ptr, nsamp, psd, view=OUT_SC16, noise=None, interf=None):
+        """gpsbb_device_psd: the power spectrum of the view `view` of nsamp int16 I/Q pairs in device memory at d_ptr under the plan
+        psd (a Psd) -> (uint64 [N] in natural bin order, the segments).  psd_host over view_host's output is the same in numpy"""
+        nz, js = _as_noise(noise), _as_interf(interf)
+        out = np.zeros(1 << min(max(int(psd.log2n), 0), PSD_MAX_LOG2N), np.uint64)
+        nseg = C.c_long(0)
+        _chk(lib().gpsbb_device_psd(self._h, C.c_void_p(int(d_ptr)), int(nsamp), view, _ref(nz), _ref(js), C.byref(psd), out.ctypes.data,
+                                    C.byref(nseg)), "gpsbb_device_psd")
+        return out, int(nseg.value)
 
     def device_noise(self, d_src, nblocks, nsamp, noise, d_dst=None):
         """gpsbb_device_noise: nblocks blocks of int16 IQ in device memory at d_src, with noise, into d_dst (default: in place)"""
@@ -1759,6 +1819,98 @@ def fir_host(w, fir, hist=None):
     y = (acc + (1 << (shift - 1))) >> shift if shift else acc
     out = np.clip(y, -32768, 32767)
     return out.astype(np.int16), x[x.shape[0] - (T - 1):].astype(np.int16), int(np.count_nonzero(out != y))
+
+
+# ---- the power spectrum (include/gpsbb.h, gpsbb_device_psd): the numpy restatement the GPU's output is checked against ----
+
+def psd_make(log2n, nsamp, hop=0, window=PSD_RECT):
+    """gpsbb_psd_make: the plan for nsamp samples -> Psd (hop 0: N for the rectangular window, N / 2 for Hann; the smallest legal shift)"""
+    p = Psd()
+    _chk(lib().gpsbb_psd_make(C.byref(p), int(log2n), int(hop), int(window), int(nsamp)), "gpsbb_psd_make")
+    return p
+
+
+def psd_min_shift(nseg):
+    """gpsbb_psd_min_shift: the smallest shift the overflow rule allows nseg segments"""
+    rc = lib().gpsbb_psd_min_shift(int(nseg))
+    if rc < 0:
+        raise GpsbbError(rc, "gpsbb_psd_min_shift")
+    return rc
+
+
+_psd_tw = None
+
+
+def psd_twiddles():
+    """gpsbb_psd_twiddles -> (c int64 [2048], s int64 [2048]): the library's own table, fetched once"""
+    global _psd_tw
+    if _psd_tw is None:
+        c, s = np.zeros(2048, np.int32), np.zeros(2048, np.int32)
+        _chk(lib().gpsbb_psd_twiddles(c.ctypes.data, s.ctypes.data), "gpsbb_psd_twiddles")
+        _psd_tw = (c.astype(np.int64), s.astype(np.int64))
+    return _psd_tw
+
+
+def psd_scale(psd, nseg, view=OUT_SC16):
+    """gpsbb_psd_scale: the factor from psd[k] to mean square per bin in the view's units (NaN for arguments it refuses)"""
+    return float(lib().gpsbb_psd_scale(C.byref(psd), int(nseg), view))
+
+
+def psd_nseg(psd, nsamp):
+    """the segments of nsamp samples under the plan, 0 where none fits"""
+    N = 1 << int(psd.log2n)
+    return (int(nsamp) - N) // int(psd.hop) + 1 if nsamp >= N and psd.hop >= 1 else 0
+
+
+def psd_wbits(view):
+    return (15, 7, 0)[(view & OUT_FORMAT_MASK) >> 8]
+
+
+def psd_transform(x):
+    """the definition's transform of x int64 [nseg, N, 2] (loaded: windowed, scaled, halved) -> X int64 [nseg, N, 2], a stage at a time"""
+    tc, ts = psd_twiddles()
+    nseg, N = x.shape[0], x.shape[1]
+    L = N.bit_length() - 1
+    rev = np.zeros(N, np.int64)
+    for b in range(L):
+        rev |= ((np.arange(N) >> b) & 1) << (L - 1 - b)
+    a = np.empty_like(x)
+    a[:, rev] = x
+    m = 2
+    while m <= N:
+        h = m // 2
+        k = np.arange(h) * (4096 // m)
+        c, s = tc[k], ts[k]
+        a = a.reshape(nseg, N // m, m, 2)
+        u, v = a[:, :, :h], a[:, :, h:]
+        t = np.stack([(v[..., 0] * c + v[..., 1] * s + (1 << 29)) >> 30, (v[..., 1] * c - v[..., 0] * s + (1 << 29)) >> 30], -1)
+        a = np.concatenate([(u + t + 1) >> 1, (u - t + 1) >> 1], 2).reshape(nseg, N, 2)
+        m *= 2
+    return a
+
+
+def psd_host(w, psd, view=OUT_SC16):
+    """gpsbb_device_psd in numpy on view samples w [nsamp, 2] (view_host's output for `view`: impaired and quantised) ->
+    (uint64 [N], the segments)"""
+    L, hop, shift = int(psd.log2n), int(psd.hop), int(psd.shift)
+    w = np.asarray(w, np.int64)
+    if not (PSD_MIN_LOG2N <= L <= PSD_MAX_LOG2N and 1 <= hop <= PSD_MAX_HOP and 0 <= shift <= PSD_MAX_SHIFT):
+        raise ValueError("a plan gpsbb_device_psd refuses")
+    N = 1 << L
+    if w.ndim != 2 or w.shape[1] != 2 or w.shape[0] < N:
+        raise ValueError("w of shape (nsamp, 2) with nsamp >= %d wanted, got %r" % (N, w.shape))
+    nseg = (w.shape[0] - N) // hop + 1
+    if nseg > PSD_MAX_NSEG or nseg * 2 * (((1 << 30) >> shift) + 1) ** 2 >= 1 << 64:
+        raise ValueError("a plan gpsbb_device_psd refuses: %d segments at shift %d" % (nseg, shift))
+    win = psd.window()
+    out = np.zeros(N, np.uint64)
+    step = max(1, (1 << 16) // N)   # segments at a time: a few MB of int64
+    for s0 in range(0, nseg, step):
+        idx = (np.arange(s0, min(nseg, s0 + step))[:, None] * hop + np.arange(N)[None, :])
+        x = (w[idx] * win[None, :, None] * (1 << (15 - psd_wbits(view)))) >> 1
+        X = psd_transform(x) >> shift
+        out += (X * X).sum(-1).sum(0).astype(np.uint64)
+    return out, nseg
 
 
 def block_digest_host(iq):

@@ -35,6 +35,7 @@
 #include "gpsbb_acq.hip.h"
 #include "gpsbb_track.hip.h"
 #include "gpsbb_fir.hip.h"
+#include "gpsbb_psd.hip.h"
 #include "gpsbb_walk.hip.h"
 #include "gpsbb_laps.hip.h"
 #include "gpsbb_nco.h"
@@ -695,7 +696,9 @@ struct gpsbb {
                                               but for that, a first allocation every time, of exactly what was asked */
     DevBuf<unsigned long long> d_trk;      /* gpsbb_device_track's: the states, the counts, the records */
     DevBuf<unsigned long long> d_fir;      /* gpsbb_device_fir's: the clip count, the two histories */
-    KernelTimer acq_tm, trk_tm, fir_tm;    /* around the kernels of the last gpsbb_device_acquire, _track, _fir (gpsbb_test_*_ms) */
+    DevBuf<unsigned long long> d_psd_tab;  /* gpsbb_device_psd's: the twiddles as k_psd reads them (uploaded once), the window, the result */
+    DevBuf<unsigned long long> d_psd;      /* ... and the workgroups' partials */
+    KernelTimer acq_tm, trk_tm, fir_tm, psd_tm; /* around the kernels of the last gpsbb_device_acquire, _track, _fir, _psd (gpsbb_test_*_ms) */
 };
 
 /* every stream the handle has created, in no particular order */
@@ -1118,8 +1121,8 @@ extern "C" void gpsbb_destroy(gpsbb_t *h)
     chain_only_free(h);
     (void)drain_streams(h);
     release_all(h->d_tabs, h->d_ca, h->d_status, h->d_hz, h->d_clip, h->d_noise_tab, h->d_nclip);
-    release_all(h->d_pack, h->d_level, h->d_digest, h->d_acq_chips, h->d_acq_rows, h->d_acq_grid, h->d_trk, h->d_fir);
-    release_all(h->acq_tm, h->trk_tm, h->fir_tm);
+    release_all(h->d_pack, h->d_level, h->d_digest, h->d_acq_chips, h->d_acq_rows, h->d_acq_grid, h->d_trk, h->d_fir, h->d_psd_tab, h->d_psd);
+    release_all(h->acq_tm, h->trk_tm, h->fir_tm, h->psd_tm);
     delete h->pool;
     h->pool = nullptr;
     for_each_stream(h, [](hipStream_t st) { (void)hipStreamDestroy(st); });
@@ -3276,6 +3279,104 @@ extern "C" int gpsbb_device_fir(gpsbb_t *h, const int16_t *d_iq, long nsamp, con
     return GPSBB_OK;
 }
 
+/* ---- the power spectrum (include/gpsbb.h gpsbb_device_psd; gpsbb_psd.h, gpsbb_psd.hip.h) ---- */
+
+static_assert(sizeof(gpsbb_psd_t) == 8208 && sizeof(psd_c) == 8, "gpsbb_psd_t layout");
+
+/* the table, made once: c [2048] then s [2048] */
+static const int32_t *psd_table()
+{
+    static const std::vector<int32_t> t = [] {
+        std::vector<int32_t> v(2 * PSD_TW);
+        psd_twiddles(v.data(), v.data() + PSD_TW);
+        return v;
+    }();
+    return t.data();
+}
+
+extern "C" int gpsbb_psd_twiddles(int32_t c[2048], int32_t s[2048])
+{
+    if (!c || !s)
+        return GPSBB_E_BADARG;
+    memcpy(c, psd_table(), PSD_TW * sizeof(int32_t));
+    memcpy(s, psd_table() + PSD_TW, PSD_TW * sizeof(int32_t));
+    return GPSBB_OK;
+}
+
+extern "C" int gpsbb_psd_min_shift(long nseg) { return psd_min_shift(nseg); }
+
+extern "C" int gpsbb_psd_make(gpsbb_psd_t *p, int log2n, long hop, int window, long nsamp) { return psd_make(p, log2n, hop, window, nsamp); }
+
+extern "C" double gpsbb_psd_scale(const gpsbb_psd_t *p, long nseg, unsigned view)
+{
+    int shift8 = 0;
+    return psd_scale(p, nseg, acq_view_format(view, &shift8));
+}
+
+typedef void (*PsdKernelFn)(PsdArgs);
+static PsdKernelFn psd_kernel(int fmt, bool noise, bool interf)
+{
+    static const PsdKernelFn k[3][2][2] = GPSBB_VNI_KERNELS(k_psd);
+    return k[fmt][noise][interf];
+}
+
+extern "C" int gpsbb_device_psd(gpsbb_t *h, const int16_t *d_iq, long nsamp, unsigned view, const gpsbb_noise_t *nz, const gpsbb_interf_set_t *set,
+                                const gpsbb_psd_t *p, uint64_t *psd, long *nseg_out)
+{
+    int shift8 = 0;
+    const int fmt = acq_view_format(view, &shift8);
+    ImpairCall ic;
+    long nseg = 0;
+    if (!h || !d_iq || !p || !psd || ((uintptr_t)d_iq & 3) || fmt < 0 || !psd_ok(p, nsamp, &nseg) || !impair_make(nz, set, (uint64_t)nsamp, &ic))
+        return GPSBB_E_BADARG;
+    const int rc = iq_call_begin(h, ic.noise);
+    if (rc != GPSBB_OK)
+        return rc;
+    const int L = p->log2n, N = 1 << L;
+    int run = 0, nwg = 0;
+    psd_geometry(L, nseg, &run, &nwg);
+    /* ---- scratch, in 8-byte words: the table (uploaded when the buffer is made), the window, the result; the partials ---- */
+    constexpr size_t win_words = GPSBB_PSD_MAX_N / 4;
+    hipStream_t cs = h->s_compute;
+    if (!h->d_psd_tab.p) {
+        HIPCHK(h, (hipError_t)h->d_psd_tab.reserve(PSD_TW + win_words + GPSBB_PSD_MAX_N));
+        std::vector<psd_c> tw(PSD_TW); /* k_psd's order: entry brev11(2 y) at y, y < 1024 (the second half is not read) */
+        for (uint32_t y = 0; y < (uint32_t)PSD_TW; y++)
+            tw[y] = psd_c{psd_table()[psd_brev11(2 * y & 2047u)], psd_table()[PSD_TW + psd_brev11(2 * y & 2047u)]};
+        HIPCHK(h, hipMemcpy(h->d_psd_tab.p, tw.data(), PSD_TW * sizeof(psd_c), hipMemcpyHostToDevice));
+    }
+    HIPCHK(h, (hipError_t)h->d_psd.reserve((size_t)nwg * (size_t)N));
+    PsdArgs a;
+    memset(&a, 0, sizeof a);
+    a.d = iq_view(h, d_iq, shift8, ic);
+    a.tabs = h->d_tabs.p;
+    a.tw = reinterpret_cast<const psd_c *>(h->d_psd_tab.p);
+    int16_t *d_win = reinterpret_cast<int16_t *>(h->d_psd_tab.p + PSD_TW);
+    unsigned long long *d_out = h->d_psd_tab.p + PSD_TW + win_words;
+    a.win = d_win;
+    a.part = h->d_psd.p;
+    a.nseg = nseg;
+    a.hop = p->hop;
+    a.run = run;
+    a.log2n = L;
+    a.shift = p->shift;
+    a.wmul = 1 << (15 - psd_wbits(fmt));
+    HIPCHK(h, hipMemcpyAsync(d_win, p->win, (size_t)N * sizeof(int16_t), hipMemcpyHostToDevice, cs));
+    HIPCHK(h, h->psd_tm.start(cs));
+    hipLaunchKernelGGL(psd_kernel(fmt, ic.noise, ic.set), dim3((unsigned)nwg), dim3(PSD_WG), psd_lds_bytes(L), cs, a);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(k_psd_fold, dim3((unsigned)(N / PSD_FOLD_BINS)), dim3(PSD_FOLD_BINS * PSD_FOLD_SLICES), 0, cs, h->d_psd.p, d_out, L, nwg);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, h->psd_tm.stop(cs));
+    std::vector<uint64_t> out((size_t)N);
+    HIPCHK(h, hipMemcpyAsync(out.data(), d_out, (size_t)N * sizeof(uint64_t), hipMemcpyDeviceToHost, cs));
+    HIPCHK(h, hipStreamSynchronize(cs));
+    memcpy(psd, out.data(), (size_t)N * sizeof(uint64_t));
+    if (nseg_out)
+        *nseg_out = nseg;
+    return GPSBB_OK;
+}
+
 extern "C" double gpsbb_cn0_estimate(const gpsbb_corr_t *p, long n, long stride, double seg_seconds)
 {
     if (!p || n < 2 || stride < 1 || !(seg_seconds > 0.0) || !std::isfinite(seg_seconds))
@@ -4721,6 +4822,8 @@ extern "C" float gpsbb_test_track_ms(gpsbb *h) { return h ? h->trk_tm.ms() : -1.
 extern "C" float gpsbb_test_fir_ms(gpsbb *h) { return h ? h->fir_tm.ms() : -1.0f; }
 
 extern "C" int gpsbb_test_fir_tile(void) { return FIR_TILE; }
+extern "C" float gpsbb_test_psd_ms(gpsbb *h) { return h ? h->psd_tm.ms() : -1.0f; }
+extern "C" int gpsbb_test_psd_run(int log2n) { return log2n < PSD_MIN_LOG2N || log2n > PSD_MAX_LOG2N ? -1 : psd_min_run(log2n); }
 
 #ifdef GPSBB_WG_TRACE
 /* The workgroup trace of the measurement build (gpsbb_kernels.hip.h: wg_trace_leave; make trace; tools/corun_diag.py).

@@ -91,6 +91,9 @@ float gpsbb_test_track_ms(struct gpsbb *h);
 /* ... and of its last gpsbb_device_fir (k_fir); the outputs one of k_fir's workgroups takes (FIR_TILE) */
 float gpsbb_test_fir_ms(struct gpsbb *h);
 int gpsbb_test_fir_tile(void);
+/* ... and of its last gpsbb_device_psd (k_psd, k_psd_fold); the segments of a workgroup's least run at N = 1 << log2n */
+float gpsbb_test_psd_ms(struct gpsbb *h);
+int gpsbb_test_psd_run(int log2n);
 /* the state granule of the batch's tile tables as log2 of its tiles: the code rows' (BatchDev::st_log2) and the carrier rows'
  * (ev_carr_log2 of it, gpsbb_events.hip.h) */
 int gpsbb_test_state_log2(struct gpsbb_batch *b);
