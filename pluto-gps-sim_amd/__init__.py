@@ -284,6 +284,59 @@ class Psd(C.Structure):
 assert C.sizeof(Psd) == 8208
 
 
+# interference excision (include/gpsbb.h gpsbb_device_excise): half-overlapped segments transformed, bins zeroed, transformed back
+EXC_MIN_LOG2N, EXC_MAX_LOG2N, EXC_MAX_N, EXC_WIN_ONE = 6, 12, 4096, 16384
+EXC_RUN_BATCHES = 4      # a workgroup's run is at least this many loads of its LDS, less the block it recomputes (csrc/gpsbb_exc.hip.h)
+
+
+def exc_run(log2n):
+    """the blocks (N / 2 samples each) of a workgroup's least run at N = 1 << log2n (gpsbb_test_exc_run says the same)"""
+    return max(1, PSD_MIN_POINTS >> log2n) * EXC_RUN_BATCHES - 1
+
+
+class Exc(C.Structure):
+    """gpsbb_exc_t: log2n, thr, win[0..N-1], mask (bit k % 8 of byte k / 8 is bin k)"""
+    _fields_ = [("log2n", C.c_int32), ("_pad", C.c_int32), ("thr", C.c_uint64), ("win", C.c_int16 * EXC_MAX_N), ("mask", C.c_uint8 * (EXC_MAX_N // 8))]
+
+    def __init__(self, log2n=EXC_MIN_LOG2N, thr=0, win=(), bins=()):
+        super().__init__()
+        self.log2n, self.thr = log2n, thr
+        w = np.ascontiguousarray(win, np.int16)
+        C.memmove(self.win, w.ctypes.data, min(w.size, EXC_MAX_N) * 2)
+        self.set_bins(bins)
+
+    def _n(self):
+        return 1 << min(max(int(self.log2n), 0), EXC_MAX_LOG2N)
+
+    def window(self):
+        """win[0..N-1] as int64"""
+        return np.frombuffer(self.win, np.int16, self._n()).astype(np.int64)
+
+    def bins(self):
+        """the mask as bool [N], natural bin order"""
+        return np.unpackbits(np.frombuffer(self.mask, np.uint8), bitorder="little")[:self._n()].astype(bool)
+
+    def set_bins(self, bins):
+        """the mask from bool [N] (or fewer: the rest is cleared)"""
+        b = np.zeros(EXC_MAX_N, np.uint8)
+        v = np.asarray(bins, bool).ravel()[:EXC_MAX_N]
+        b[:v.size] = v
+        m = np.packbits(b, bitorder="little")
+        C.memmove(self.mask, m.ctypes.data, EXC_MAX_N // 8)
+
+    def copy(self, **fields):
+        c = Exc.from_buffer_copy(self)
+        for k, v in fields.items():
+            if k == "bins":
+                c.set_bins(v)
+            else:
+                setattr(c, k, v)
+        return c
+
+
+assert C.sizeof(Exc) == 8720
+
+
 ERRORS = {0: "GPSBB_OK", -1: "GPSBB_E_BADARG", -2: "GPSBB_E_BADCHAN", -3: "GPSBB_E_HIP", -4: "GPSBB_E_NOMEM",
           -5: "GPSBB_E_INTERNAL", -6: "GPSBB_E_NODEVICE", -7: "GPSBB_E_STATE"}
 
@@ -306,6 +359,7 @@ API_SYMBOLS = [
     "gpsbb_device_track", "gpsbb_trk_make", "gpsbb_trk_seed", "gpsbb_trk_bitsync", "gpsbb_trk_bits",
     "gpsbb_device_fir", "gpsbb_fir_make",
     "gpsbb_device_psd", "gpsbb_psd_make", "gpsbb_psd_min_shift", "gpsbb_psd_twiddles", "gpsbb_psd_scale",
+    "gpsbb_device_excise", "gpsbb_exc_make", "gpsbb_exc_from_psd",
 ]
 # ... and include/gpsbb_node.h
 NODE_API_SYMBOLS = ["gpsbb_node_create", "gpsbb_node_run", "gpsbb_node_run_digest", "gpsbb_node_slot_digests", "gpsbb_node_destroy", "gpsbb_node_plan", "gpsbb_node_begin", "gpsbb_node_feed", "gpsbb_node_end",
@@ -451,6 +505,10 @@ def lib():
             L.gpsbb_psd_twiddles.argtypes = [vp, vp]
             L.gpsbb_psd_scale.argtypes = [vp, C.c_long, u]
             L.gpsbb_psd_scale.restype = d
+        if hasattr(L, "gpsbb_device_excise"):  # the excision's calls, as a group (an older build loaded for an A/B: tools/ab_lib.sh)
+            L.gpsbb_device_excise.argtypes = [vp, vp, C.c_long, vp, vp, vp, vp, vp, vp, vp, vp]
+            L.gpsbb_exc_make.argtypes = [vp, i]
+            L.gpsbb_exc_from_psd.argtypes = [vp, vp, vp, C.c_long, d, d]
         if hasattr(L, "gpsbb_test_live"):  # (an older build loaded for an A/B: tools/ab_lib.sh)
             L.gpsbb_test_live.argtypes = [vp]
             L.gpsbb_test_live.restype = None
@@ -501,6 +559,11 @@ def exp_lib():
             L.gpsbb_test_psd_ms.argtypes = [vp]
             L.gpsbb_test_psd_ms.restype = C.c_float
             L.gpsbb_test_psd_run.argtypes = [i]
+        if hasattr(L, "gpsbb_test_exc_ms"):  # (an older build loaded for an A/B: tools/ab_lib.sh)
+            L.gpsbb_test_exc_ms.argtypes = [vp]
+            L.gpsbb_test_exc_ms.restype = C.c_float
+            L.gpsbb_test_exc_run.argtypes = [i]
+            L.gpsbb_test_exc_host.argtypes = [vp, vp, C.c_long, vp, vp, vp, vp, vp, vp]
         _exp_lib = L
     return _exp_lib
 
@@ -789,6 +852,21 @@ class Synth:
         _chk(lib().gpsbb_device_psd(self._h, C.c_void_p(int(d_ptr)), int(nsamp), view, _ref(nz), _ref(js), C.byref(psd), out.ctypes.data,
                                     C.byref(nseg)), "gpsbb_device_psd")
         return out, int(nseg.value)
+
+    def device_excise(self, d_ptr, nsamp, exc, d_out, hist=None, noise=None, interf=None):
+        """gpsbb_device_excise: nsamp int16 I/Q pairs in device memory at d_ptr, the bins the plan exc (an Exc) names taken out,
+        into nsamp pairs at d_out, delayed by N / 2 -> (the history to hand to the next call, int16 [N, 2]; the components the
+        clamp changed; the (segment, bin) pairs zeroed).  hist: the history a call before returned, or None (zeros).  excise_host
+        over view_host's output is the same in numpy"""
+        nz, js = _as_noise(noise), _as_interf(interf)
+        N = 1 << min(max(int(exc.log2n), 0), EXC_MAX_LOG2N)
+        hin = None if hist is None else np.ascontiguousarray(hist, np.int16).reshape(N, 2)
+        hout = np.zeros((N, 2), np.int16)
+        clipped, excised = C.c_uint64(0), C.c_uint64(0)
+        _chk(lib().gpsbb_device_excise(self._h, C.c_void_p(int(d_ptr)), int(nsamp), _ref(nz), _ref(js), C.byref(exc),
+                                       None if hin is None else hin.ctypes.data, hout.ctypes.data, C.c_void_p(int(d_out)), C.byref(clipped),
+                                       C.byref(excised)), "gpsbb_device_excise")
+        return hout, int(clipped.value), int(excised.value)
 
     def device_noise(self, d_src, nblocks, nsamp, noise, d_dst=None):
         """gpsbb_device_noise: nblocks blocks of int16 IQ in device memory at d_src, with noise, into d_dst (default: in place)"""
@@ -1911,6 +1989,110 @@ def psd_host(w, psd, view=OUT_SC16):
         X = psd_transform(x) >> shift
         out += (X * X).sum(-1).sum(0).astype(np.uint64)
     return out, nseg
+
+
+# ---- interference excision (include/gpsbb.h, gpsbb_device_excise): the numpy restatement the GPU's output is checked against ----
+
+def exc_make(log2n):
+    """gpsbb_exc_make: the plan with the periodic Hann window, an empty mask and no threshold -> Exc"""
+    e = Exc()
+    _chk(lib().gpsbb_exc_make(C.byref(e), int(log2n)), "gpsbb_exc_make")
+    return e
+
+
+def exc_from_psd(exc, psd, plan, nseg, mask_db=0.0, thr_db=0.0):
+    """gpsbb_exc_from_psd: a copy of exc with the mask (bins more than mask_db above the median of psd) and the threshold (thr_db
+    above the median, in a single segment's units) from a spectrum device_psd or psd_host made at SC16 under plan"""
+    e = exc.copy()
+    p = np.ascontiguousarray(psd, np.uint64)
+    if p.size != 1 << min(max(int(exc.log2n), 0), EXC_MAX_LOG2N):
+        raise ValueError("a spectrum of the plan's N bins wanted")
+    _chk(lib().gpsbb_exc_from_psd(C.byref(e), p.ctypes.data, C.byref(plan), int(nseg), float(mask_db), float(thr_db)), "gpsbb_exc_from_psd")
+    return e
+
+
+def exc_inverse(z, shadow=None):
+    """the definition's inverse transform of Z int64 [nseg, N, 2] (natural bin order) -> y int64 [nseg, N, 2], a stage at a time.
+    shadow: a list that takes the largest |component| after every stage"""
+    tc, ts = psd_twiddles()
+    nseg, N = z.shape[0], z.shape[1]
+    L = N.bit_length() - 1
+    rev = np.zeros(N, np.int64)
+    for b in range(L):
+        rev |= ((np.arange(N) >> b) & 1) << (L - 1 - b)
+    a = np.empty_like(z)
+    a[:, rev] = z
+    m = 2
+    while m <= N:
+        h = m // 2
+        k = np.arange(h) * (4096 // m)
+        c, s = tc[k], ts[k]
+        a = a.reshape(nseg, N // m, m, 2)
+        u, v = a[:, :, :h], a[:, :, h:]
+        t = np.stack([(v[..., 0] * c - v[..., 1] * s + (1 << 29)) >> 30, (v[..., 1] * c + v[..., 0] * s + (1 << 29)) >> 30], -1)
+        a = np.concatenate([u + t, u - t], 2).reshape(nseg, N, 2)
+        if shadow is not None:
+            shadow.append(int(np.abs(a).max()) if a.size else 0)
+        m *= 2
+    return a
+
+
+def exc_ok(exc):
+    """what gpsbb_device_excise asks of a plan"""
+    L = int(exc.log2n)
+    if not EXC_MIN_LOG2N <= L <= EXC_MAX_LOG2N:
+        return False
+    w, H = exc.window(), 1 << (L - 1)
+    return bool((w[:H] >= 0).all() and (w[:H] <= EXC_WIN_ONE).all() and (w[:H] + w[H:] == EXC_WIN_ONE).all())
+
+
+def excise_host(w, exc, hist=None, shadow=None, cells=None):
+    """gpsbb_device_excise in numpy on view samples w [nsamp, 2] (view_host's output: already impaired) -> (out int16 [nsamp, 2],
+    the history to hand on int16 [N, 2], the components the clamp changed, the (segment, bin) pairs zeroed).  hist: [N, 2] or
+    None (zeros).  shadow: a list that takes the largest |component| of every inverse stage (int64: nothing wraps here); cells: a
+    list that takes the zeroed cells, bool [nsamp / H + 1, N]"""
+    if not exc_ok(exc):
+        raise ValueError("a plan gpsbb_device_excise refuses")
+    L, thr = int(exc.log2n), int(exc.thr)
+    N, H, G = 1 << L, 1 << (L - 1), (L + 1) // 2
+    S = 13 - G
+    w = np.asarray(w, np.int64)
+    if w.ndim != 2 or w.shape[1] != 2 or w.shape[0] < H or w.shape[0] % H:
+        raise ValueError("w of shape (nsamp, 2) with nsamp a multiple of %d wanted, got %r" % (H, w.shape))
+    nblk = w.shape[0] // H
+    hin = np.zeros((N, 2), np.int64) if hist is None else np.asarray(hist, np.int64).reshape(N, 2)
+    x = np.concatenate([hin, w])              # x[N + n] = w[n]; segment s covers x[s H .. s H + N)
+    win, masked = exc.window(), exc.bins()
+    y = np.empty((nblk + 1, N, 2), np.int64)
+    excised = 0
+    step = max(1, (1 << 16) // N)             # segments at a time: a few MB of int64
+    for s0 in range(0, nblk + 1, step):
+        sg = np.arange(s0, min(nblk + 1, s0 + step))
+        X = psd_transform((x[sg[:, None] * H + np.arange(N)[None, :]] * win[None, :, None]) >> 1)
+        pw = (X * X).sum(-1)                  # < 2^62
+        zero = masked[None, :] | ((pw > thr) if 0 < thr < 1 << 62 else np.zeros(pw.shape, bool))
+        excised += int(np.count_nonzero(zero[sg >= 1]))
+        if cells is not None:
+            cells.append(zero)
+        Z = np.sign(X) * ((np.abs(X) + (1 << (G - 1))) >> G)
+        Z[zero] = 0
+        y[sg] = exc_inverse(Z, shadow)
+    o = (y[:-1, H:] + y[1:, :H] + (1 << (S - 1))) >> S
+    out = np.clip(o, -32768, 32767)
+    return (out.reshape(nblk * H, 2).astype(np.int16), x[x.shape[0] - N:].astype(np.int16), int(np.count_nonzero(out != o)), excised)
+
+
+def excise_plain_c(w, exc, hist=None):
+    """csrc/gpsbb_exc.h's plain-C definition (exc_host, through the experiments build's hook gpsbb_test_exc_host) on host memory ->
+    (out, hist_out, clipped, excised, the largest |component| any inverse step produced)"""
+    w = np.ascontiguousarray(w, np.int16)
+    N = 1 << min(max(int(exc.log2n), 0), EXC_MAX_LOG2N)
+    hin = None if hist is None else np.ascontiguousarray(hist, np.int16).reshape(N, 2)
+    out, hout = np.zeros_like(w), np.zeros((N, 2), np.int16)
+    clipped, excised, peak = C.c_uint64(0), C.c_uint64(0), C.c_int64(0)
+    _chk(exp_lib().gpsbb_test_exc_host(C.byref(exc), w.ctypes.data, w.shape[0], None if hin is None else hin.ctypes.data, out.ctypes.data,
+                                       hout.ctypes.data, C.byref(clipped), C.byref(excised), C.byref(peak)), "gpsbb_test_exc_host")
+    return out, hout, int(clipped.value), int(excised.value), int(peak.value)
 
 
 def block_digest_host(iq):

@@ -36,6 +36,7 @@
 #include "gpsbb_track.hip.h"
 #include "gpsbb_fir.hip.h"
 #include "gpsbb_psd.hip.h"
+#include "gpsbb_exc.hip.h"
 #include "gpsbb_walk.hip.h"
 #include "gpsbb_laps.hip.h"
 #include "gpsbb_nco.h"
@@ -698,7 +699,8 @@ struct gpsbb {
     DevBuf<unsigned long long> d_fir;      /* gpsbb_device_fir's: the clip count, the two histories */
     DevBuf<unsigned long long> d_psd_tab;  /* gpsbb_device_psd's: the twiddles as k_psd reads them (uploaded once), the window, the result */
     DevBuf<unsigned long long> d_psd;      /* ... and the workgroups' partials */
-    KernelTimer acq_tm, trk_tm, fir_tm, psd_tm; /* around the kernels of the last gpsbb_device_acquire, _track, _fir, _psd (gpsbb_test_*_ms) */
+    DevBuf<unsigned long long> d_exc;      /* gpsbb_device_excise's: the inverse's tables (uploaded once), the plan, the histories, the counts */
+    KernelTimer acq_tm, trk_tm, fir_tm, psd_tm, exc_tm; /* around the kernels of the last gpsbb_device_acquire, _track, _fir, _psd, _excise (gpsbb_test_*_ms) */
 };
 
 /* every stream the handle has created, in no particular order */
@@ -1121,8 +1123,8 @@ extern "C" void gpsbb_destroy(gpsbb_t *h)
     chain_only_free(h);
     (void)drain_streams(h);
     release_all(h->d_tabs, h->d_ca, h->d_status, h->d_hz, h->d_clip, h->d_noise_tab, h->d_nclip);
-    release_all(h->d_pack, h->d_level, h->d_digest, h->d_acq_chips, h->d_acq_rows, h->d_acq_grid, h->d_trk, h->d_fir, h->d_psd_tab, h->d_psd);
-    release_all(h->acq_tm, h->trk_tm, h->fir_tm, h->psd_tm);
+    release_all(h->d_pack, h->d_level, h->d_digest, h->d_acq_chips, h->d_acq_rows, h->d_acq_grid, h->d_trk, h->d_fir, h->d_psd_tab, h->d_psd, h->d_exc);
+    release_all(h->acq_tm, h->trk_tm, h->fir_tm, h->psd_tm, h->exc_tm);
     delete h->pool;
     h->pool = nullptr;
     for_each_stream(h, [](hipStream_t st) { (void)hipStreamDestroy(st); });
@@ -3313,6 +3315,24 @@ extern "C" double gpsbb_psd_scale(const gpsbb_psd_t *p, long nseg, unsigned view
     return psd_scale(p, nseg, acq_view_format(view, &shift8));
 }
 
+/* d_psd_tab, in 8-byte words: k_psd's table (uploaded when the buffer is made), then room for a window and a result */
+constexpr size_t win_words = GPSBB_PSD_MAX_N / 4;
+static hipError_t psd_tab_ready(gpsbb *h)
+{
+    if (h->d_psd_tab.p)
+        return hipSuccess;
+    hipError_t e = (hipError_t)h->d_psd_tab.reserve(PSD_TW + win_words + GPSBB_PSD_MAX_N);
+    if (e != hipSuccess)
+        return e;
+    std::vector<psd_c> tw(PSD_TW); /* k_psd's order: entry brev11(2 y) at y, y < 1024 (the second half is not read) */
+    for (uint32_t y = 0; y < (uint32_t)PSD_TW; y++)
+        tw[y] = psd_c{psd_table()[psd_brev11(2 * y & 2047u)], psd_table()[PSD_TW + psd_brev11(2 * y & 2047u)]};
+    e = hipMemcpy(h->d_psd_tab.p, tw.data(), PSD_TW * sizeof(psd_c), hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+        release_all(h->d_psd_tab); /* the table or no buffer: the next call uploads again */
+    return e;
+}
+
 typedef void (*PsdKernelFn)(PsdArgs);
 static PsdKernelFn psd_kernel(int fmt, bool noise, bool interf)
 {
@@ -3336,15 +3356,8 @@ extern "C" int gpsbb_device_psd(gpsbb_t *h, const int16_t *d_iq, long nsamp, uns
     int run = 0, nwg = 0;
     psd_geometry(L, nseg, &run, &nwg);
     /* ---- scratch, in 8-byte words: the table (uploaded when the buffer is made), the window, the result; the partials ---- */
-    constexpr size_t win_words = GPSBB_PSD_MAX_N / 4;
     hipStream_t cs = h->s_compute;
-    if (!h->d_psd_tab.p) {
-        HIPCHK(h, (hipError_t)h->d_psd_tab.reserve(PSD_TW + win_words + GPSBB_PSD_MAX_N));
-        std::vector<psd_c> tw(PSD_TW); /* k_psd's order: entry brev11(2 y) at y, y < 1024 (the second half is not read) */
-        for (uint32_t y = 0; y < (uint32_t)PSD_TW; y++)
-            tw[y] = psd_c{psd_table()[psd_brev11(2 * y & 2047u)], psd_table()[PSD_TW + psd_brev11(2 * y & 2047u)]};
-        HIPCHK(h, hipMemcpy(h->d_psd_tab.p, tw.data(), PSD_TW * sizeof(psd_c), hipMemcpyHostToDevice));
-    }
+    HIPCHK(h, psd_tab_ready(h));
     HIPCHK(h, (hipError_t)h->d_psd.reserve((size_t)nwg * (size_t)N));
     PsdArgs a;
     memset(&a, 0, sizeof a);
@@ -3374,6 +3387,113 @@ extern "C" int gpsbb_device_psd(gpsbb_t *h, const int16_t *d_iq, long nsamp, uns
     memcpy(psd, out.data(), (size_t)N * sizeof(uint64_t));
     if (nseg_out)
         *nseg_out = nseg;
+    return GPSBB_OK;
+}
+
+/* ---- interference excision (include/gpsbb.h gpsbb_device_excise; gpsbb_exc.h, gpsbb_exc.hip.h) ---- */
+
+static_assert(sizeof(gpsbb_exc_t) == 8720 && sizeof(exc_tw) == 16, "gpsbb_exc_t layout");
+
+extern "C" int gpsbb_exc_make(gpsbb_exc_t *e, int log2n) { return exc_make(e, log2n); }
+
+extern "C" int gpsbb_exc_from_psd(gpsbb_exc_t *e, const uint64_t *psd, const gpsbb_psd_t *p, long nseg, double mask_db, double thr_db)
+{
+    return exc_from_psd(e, psd, p, nseg, mask_db, thr_db);
+}
+
+typedef void (*ExcKernelFn)(ExcArgs);
+static ExcKernelFn exc_kernel(bool noise, bool interf)
+{
+    static const ExcKernelFn k[2][2] = GPSBB_NI_KERNELS(k_excise);
+    return k[noise][interf];
+}
+
+extern "C" int gpsbb_device_excise(gpsbb_t *h, const int16_t *d_iq, long nsamp, const gpsbb_noise_t *nz, const gpsbb_interf_set_t *set,
+                                   const gpsbb_exc_t *e, const int16_t *hist_in, int16_t *hist_out, int16_t *d_out, uint64_t *clipped,
+                                   uint64_t *excised)
+{
+    ImpairCall ic;
+    if (!h || !d_iq || !e || !d_out || (((uintptr_t)d_iq | (uintptr_t)d_out) & 3) || !exc_ok(e, nsamp) || !impair_make(nz, set, (uint64_t)nsamp, &ic))
+        return GPSBB_E_BADARG;
+    const uintptr_t in0 = (uintptr_t)d_iq, in1 = in0 + 4 * (uintptr_t)nsamp, out0 = (uintptr_t)d_out, out1 = out0 + 4 * (uintptr_t)nsamp;
+    if (out0 < in1 && in0 < out1)
+        return GPSBB_E_BADARG;
+    const int rc = iq_call_begin(h, ic.noise);
+    if (rc != GPSBB_OK)
+        return rc;
+    const int L = e->log2n, N = 1 << L;
+    const long nblk = nsamp / (N / 2);
+    int run = 0, nwg = 0;
+    exc_geometry(L, nblk, &run, &nwg);
+    /* ---- scratch, in 8-byte words: the tables of every log2n (uploaded when the buffer is made), the window, the mask in point
+     * order, the two histories, the two counts, two counts per workgroup ---- */
+    constexpr size_t mask_words = GPSBB_EXC_MAX_N / 64, hist_words = GPSBB_EXC_MAX_N / 2;
+    const size_t tab_words = exc_tab_offset(EXC_MAX_LOG2N + 1);
+    const size_t o_win = tab_words, o_mask = o_win + win_words, o_hin = o_mask + mask_words, o_hout = o_hin + hist_words, o_cnt = o_hout + hist_words,
+                 o_part = o_cnt + 2;
+    hipStream_t cs = h->s_compute;
+    HIPCHK(h, psd_tab_ready(h));
+    if (!h->d_exc.p) {
+        HIPCHK(h, (hipError_t)h->d_exc.reserve(o_part + 2 * (size_t)EXC_MAX_WGS));
+        std::vector<unsigned long long> t(tab_words + 1); /* (8-byte words: exc_tw is two of them, 16-byte aligned where its offset is even) */
+        for (int l = EXC_MIN_LOG2N; l <= EXC_MAX_LOG2N; l++) {
+            exc_tw *tw = reinterpret_cast<exc_tw *>(t.data() + exc_tab_offset(l));
+            exc_tables(l, psd_table(), psd_table() + PSD_TW, tw, reinterpret_cast<psd_c *>(tw + exc_tw_entries(l)));
+        }
+        hipError_t er = hipMemcpy(h->d_exc.p, t.data(), tab_words * 8, hipMemcpyHostToDevice);
+        for (int n = 0; n < 2 && er == hipSuccess; n++)
+            for (int i = 0; i < 2 && er == hipSuccess; i++) /* 80 KB of dynamic LDS at N = 4096: above the 64 KB default limit */
+                er = hipFuncSetAttribute(reinterpret_cast<const void *>(exc_kernel(n != 0, i != 0)), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)exc_lds_bytes(EXC_MAX_LOG2N));
+        if (er != hipSuccess)
+            release_all(h->d_exc); /* the tables or no buffer: the next call uploads again */
+        HIPCHK(h, er);
+    }
+    uint32_t maskp[GPSBB_EXC_MAX_N / 32];
+    exc_mask_points(e, maskp);
+    ExcArgs a;
+    memset(&a, 0, sizeof a);
+    a.d = iq_view(h, d_iq, 0, ic);
+    a.tabs = h->d_tabs.p;
+    a.tw = reinterpret_cast<const psd_c *>(h->d_psd_tab.p);
+    a.itw = reinterpret_cast<const exc_tw *>(h->d_exc.p + exc_tab_offset(L));
+    a.fin = reinterpret_cast<const psd_c *>(a.itw + exc_tw_entries(L));
+    int16_t *d_win = reinterpret_cast<int16_t *>(h->d_exc.p + o_win);
+    uint32_t *d_mask = reinterpret_cast<uint32_t *>(h->d_exc.p + o_mask), *d_hin = reinterpret_cast<uint32_t *>(h->d_exc.p + o_hin);
+    uint32_t *d_hout = reinterpret_cast<uint32_t *>(h->d_exc.p + o_hout);
+    a.win = d_win;
+    a.maskp = d_mask;
+    a.hist_in = d_hin;
+    a.hist_out = d_hout;
+    a.out = reinterpret_cast<uint32_t *>(d_out);
+    a.part = h->d_exc.p + o_part;
+    a.thr = e->thr;
+    a.nblk = nblk;
+    a.run = run;
+    a.log2n = L;
+    HIPCHK(h, hipMemcpyAsync(d_win, e->win, (size_t)N * sizeof(int16_t), hipMemcpyHostToDevice, cs));
+    HIPCHK(h, hipMemcpyAsync(d_mask, maskp, (size_t)N / 8, hipMemcpyHostToDevice, cs));
+    if (hist_in)
+        HIPCHK(h, hipMemcpyAsync(d_hin, hist_in, (size_t)N * 4, hipMemcpyHostToDevice, cs));
+    else
+        HIPCHK(h, hipMemsetAsync(d_hin, 0, (size_t)N * 4, cs));
+    HIPCHK(h, h->exc_tm.start(cs));
+    hipLaunchKernelGGL(exc_kernel(ic.noise, ic.set), dim3((unsigned)nwg), dim3(PSD_WG), exc_lds_bytes(L), cs, a);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(k_exc_fold, dim3(1), dim3(PSD_WG), 0, cs, a.part, h->d_exc.p + o_cnt, nwg);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, h->exc_tm.stop(cs));
+    std::vector<uint32_t> tail((size_t)N);
+    unsigned long long cnt[2] = {0, 0};
+    HIPCHK(h, hipMemcpyAsync(cnt, h->d_exc.p + o_cnt, sizeof cnt, hipMemcpyDeviceToHost, cs));
+    HIPCHK(h, hipMemcpyAsync(tail.data(), d_hout, (size_t)N * 4, hipMemcpyDeviceToHost, cs));
+    HIPCHK(h, hipStreamSynchronize(cs));
+    if (hist_out)
+        memcpy(hist_out, tail.data(), (size_t)N * 4);
+    if (clipped)
+        *clipped = cnt[0];
+    if (excised)
+        *excised = cnt[1];
     return GPSBB_OK;
 }
 
@@ -4824,6 +4944,18 @@ extern "C" float gpsbb_test_fir_ms(gpsbb *h) { return h ? h->fir_tm.ms() : -1.0f
 extern "C" int gpsbb_test_fir_tile(void) { return FIR_TILE; }
 extern "C" float gpsbb_test_psd_ms(gpsbb *h) { return h ? h->psd_tm.ms() : -1.0f; }
 extern "C" int gpsbb_test_psd_run(int log2n) { return log2n < PSD_MIN_LOG2N || log2n > PSD_MAX_LOG2N ? -1 : psd_min_run(log2n); }
+extern "C" float gpsbb_test_exc_ms(gpsbb *h) { return h ? h->exc_tm.ms() : -1.0f; }
+extern "C" int gpsbb_test_exc_run(int log2n) { return log2n < EXC_MIN_LOG2N || log2n > EXC_MAX_LOG2N ? -1 : exc_min_run(log2n); }
+extern "C" int gpsbb_test_exc_host(const gpsbb_exc_t *e, const int16_t *w, long nsamp, const int16_t *hist_in, int16_t *out, int16_t *hist_out,
+                                   uint64_t *clipped, uint64_t *excised, int64_t *peak)
+{
+    if (!e || e->log2n < EXC_MIN_LOG2N || e->log2n > EXC_MAX_LOG2N)
+        return GPSBB_E_BADARG;
+    std::vector<psd_c> work((size_t)1 << e->log2n), half((size_t)1 << (e->log2n - 1), psd_c{0, 0});
+    return exc_host(e, w, nsamp, hist_in, psd_table(), psd_table() + PSD_TW, work.data(), half.data(), out, hist_out, clipped, excised, peak)
+               ? GPSBB_OK
+               : GPSBB_E_BADARG;
+}
 
 #ifdef GPSBB_WG_TRACE
 /* The workgroup trace of the measurement build (gpsbb_kernels.hip.h: wg_trace_leave; make trace; tools/corun_diag.py).

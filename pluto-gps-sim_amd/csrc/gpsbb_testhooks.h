@@ -94,6 +94,12 @@ int gpsbb_test_fir_tile(void);
 /* ... and of its last gpsbb_device_psd (k_psd, k_psd_fold); the segments of a workgroup's least run at N = 1 << log2n */
 float gpsbb_test_psd_ms(struct gpsbb *h);
 int gpsbb_test_psd_run(int log2n);
+/* ... and of its last gpsbb_device_excise (k_excise, k_exc_fold); the blocks of a workgroup's least run at N = 1 << log2n */
+float gpsbb_test_exc_ms(struct gpsbb *h);
+int gpsbb_test_exc_run(int log2n);
+/* gpsbb_exc.h's plain-C definition (exc_host) over host memory; peak: the largest |component| any inverse step produced */
+int gpsbb_test_exc_host(const gpsbb_exc_t *e, const int16_t *w, long nsamp, const int16_t *hist_in, int16_t *out, int16_t *hist_out,
+                        uint64_t *clipped, uint64_t *excised, int64_t *peak);
 /* the state granule of the batch's tile tables as log2 of its tiles: the code rows' (BatchDev::st_log2) and the carrier rows'
  * (ev_carr_log2 of it, gpsbb_events.hip.h) */
 int gpsbb_test_state_log2(struct gpsbb_batch *b);
