@@ -564,8 +564,21 @@ def exp_lib():
             L.gpsbb_test_exc_ms.restype = C.c_float
             L.gpsbb_test_exc_run.argtypes = [i]
             L.gpsbb_test_exc_host.argtypes = [vp, vp, C.c_long, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "gpsbb_test_nav_sign"):  # (an older build loaded for an A/B: tools/ab_lib.sh)
+            L.gpsbb_test_nav_sign.argtypes = [C.c_ulonglong, i, i, i, i, vp]
+            L.gpsbb_test_nav_sign.restype = None
         _exp_lib = L
     return _exp_lib
+
+
+def nav_sign(state, minus, g, e=0, used=1):
+    """gpsbb_test_nav_sign (csrc/gpsbb_testhooks.h): how a table with a state granule of 2^g tiles keeps a code state (a float64,
+    not negative) under a data bit of -1 (minus) or +1, and where a reader finds the bit after a roll-over inside entry e of a row
+    of `used` entries.  Returns (stored bit pattern, magnitude's bit pattern, bit, from the end state?, row entry or -1, in the
+    sign at all?)."""
+    out = np.zeros(6, np.int64)
+    exp_lib().gpsbb_test_nav_sign(int(np.float64(state).view(np.uint64)), int(bool(minus)), int(g), int(e), int(used), out.ctypes.data)
+    return (int(out[0]) & 0xFFFFFFFFFFFFFFFF, int(out[1]) & 0xFFFFFFFFFFFFFFFF, int(out[2]), bool(out[3]), int(out[4]), bool(out[5]))
 
 
 PLAN_FIELDS = ("nblocks", "nch", "nsamp", "ntiles", "delt", "flags", "ev", "ev_dense", "ev_all_dense", "laps", "host_seed", "st_log2",

@@ -4722,6 +4722,19 @@ extern "C" int gpsbb_test_state_log2_carr(gpsbb_batch_t *b)
     return b ? ev_carr_log2(b->plan.st_log2) : GPSBB_E_BADARG;
 }
 
+/* the rule of a granule table's data bits (ev_nav_in_sign, gpsbb_events.hip.h), as the host and the kernels compile it */
+extern "C" void gpsbb_test_nav_sign(unsigned long long state_bits, int minus, int g, int e, int used, long long out[6])
+{
+    const uint64_t stored = ev_nav_in_sign(g) ? ev_state_signed(state_bits, minus != 0) : state_bits;
+    const EvNextBitAt nx = ev_next_bit_at(e, used);
+    out[0] = (long long)stored;
+    out[1] = (long long)ev_state_mag(stored);
+    out[2] = (long long)ev_state_bit(stored);
+    out[3] = nx.from_end ? 1 : 0;
+    out[4] = nx.entry;
+    out[5] = ev_nav_in_sign(g) ? 1 : 0;
+}
+
 /* plan_batch on its own (no handle, no GPU): the BatchPlan scalars and a 64-bit FNV-1a of every image the plan defines for that
  * batch (0: not one of them), in the order gpsbb_testhooks.h names */
 static unsigned long long fnv1a(const void *p, size_t n)
@@ -4880,6 +4893,29 @@ extern "C" int gpsbb_test_table_digest(gpsbb_batch_t *b, unsigned long long out[
         if (hc[k].prn <= 0)
             continue;
         const size_t blk = k / (size_t)pl.nch, i = k % (size_t)pl.nch;
+        if (ev_nav_in_sign(pl.st_log2)) {
+            /* A granule table has no tile_nav words: its code states carry the data bit in force in their signs (ev_nav_in_sign).
+             * The states and the words every other table holds, from them: bit 0 is the sign; bit 1 — the bit in force after the
+             * next roll-over — is the bit in force behind the first roll-over from the entry on (a state below the one before it:
+             * a granule advances by less than a period), and past the block's last one what the end state's counters say */
+            unsigned long long *x = &hx[ev_tile_x_row(blk, pl.nch, (int)i, NCO_CODE, nst)];
+            uint32_t *nv = &hn[ev_tile_nav_row(blk, pl.nch, (int)i, nst)];
+            const uint32_t nav_end = nav_pack(he[k].icode, he[k].ibit, he[k].iword);
+            uint32_t after = nav_bit(hc[k].dwrd, nav_advance(nav_end)) < 0 ? 1u : 0u;
+            /* (what follows the row's last entry is the block's end state: ev_next_bit_at) */
+            uint32_t next_bit = he[k].dataBit < 0 ? 1u : 0u;
+            unsigned long long next_mag;
+            memcpy(&next_mag, &he[k].code_phase, 8);
+            for (int e = nst - 1; e >= 0; e--) {
+                const uint32_t here = ev_state_bit(x[e]);
+                x[e] = ev_state_mag(x[e]);
+                if (next_mag < x[e]) /* (non-negative doubles compare as their bits do) */
+                    after = next_bit;
+                nv[e] = here | (after << 1);
+                next_bit = here;
+                next_mag = x[e];
+            }
+        }
         for (int kind = 0; kind < 2; kind++)
             for (int t = 0; t < pl.ntiles; t += 1 << ev_kind_log2(kg, kind)) {
                 const size_t at = ev_tile_x_row(blk, pl.nch, (int)i, kind, pl.ntiles) + t;

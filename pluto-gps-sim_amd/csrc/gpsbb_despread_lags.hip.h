@@ -132,8 +132,10 @@ __global__ __launch_bounds__(DS_WG) void k_despread_lags(BatchDev p, DslArgs al)
                 const int i = __builtin_ctz(mk);
                 const double S = scalar_load(&kb[i].S), sc = scalar_load(&kb[i].sc);
                 const uint32_t down = scalar_load(&kb[i].down) != 0 ? 1u : 0u;
-                const double xt = txb[ev_tile_x_row(0, p.nch, i, NCO_CODE, nst) + g], yt = txb[ev_tile_x_row(0, p.nch, i, NCO_CARR, nst) + gy];
-                const uint32_t nav = tnb[ev_tile_nav_row(0, p.nch, i, nst) + g];
+                const double xt_s = txb[ev_tile_x_row(0, p.nch, i, NCO_CODE, nst) + g], yt = txb[ev_tile_x_row(0, p.nch, i, NCO_CARR, nst) + gy];
+                /* (a granule table's code states carry the data bits in their signs: ev_nav_in_sign) */
+                const double xt = ev_nav_in_sign(SG) ? __builtin_fabs(xt_s) : xt_s;
+                const uint32_t nav = ev_nav_in_sign(SG) ? ev_nav_of_signs(p, (size_t)b, i, g) : tnb[ev_tile_nav_row(0, p.nch, i, nst) + g];
                 const double yg = (down ? 512.0 - yt : yt) + guard, xg = xt + guard;
                 const uint32_t flip = down ? 511u : 0u;
                 const uint32_t *chips = L.chips[i];

@@ -149,6 +149,37 @@ constexpr int ev_states_used(int g, int kind, int ntiles)
 /* ... and where the rows start: nst is the rows' stride, BatchDev::nstates (ntiles where g == 0: one state per tile) */
 constexpr size_t ev_tile_x_row(size_t b, int nch, int i, int kind, int nst) { return (b * 2 * (size_t)nch + (size_t)(2 * i + kind)) * (size_t)nst; }
 constexpr size_t ev_tile_nav_row(size_t b, int nch, int i, int nst) { return (b * (size_t)nch + (size_t)i) * (size_t)nst; }
+/* THE DATA BITS OF A GRANULE TABLE (g >= 1: k_synth_ev / k_synth_ev_digest behind the lap-parallel pre-pass).  A code state is a
+ * non-negative double below 1024 — its sign bit is free — and the data bit changes once in 20 code periods, so a table with g >= 1
+ * has no tile_nav words: every writer of its code rows (lap_emit_row) sets the SIGN of a state where the data bit in force at the
+ * granule's first sample is -1 (a state of exactly 0 becomes -0.0; the 52-bit state is otherwise what it was; carrier rows are
+ * untouched), and every reader takes the magnitude.  A granule holds at most one roll-over (ev_state_log2), so the bit after a
+ * roll-over inside granule e is the bit in force at the first sample of granule e + 1: the sign of the row's next state — or, for
+ * the row's last used state, the dataBit of the block's end state, which the same pre-pass leaves (gpsbb_chan_state_t: +1 / -1,
+ * so the sign bit of the int32 says the same thing as the sign bit of a state's high word).  Where granule e holds no roll-over
+ * the two bits are equal and nobody asks for the second (ev_second<DF>, stage_tile's rolled_over, ev_exact_run_body's wraps).
+ * Tables with g == 0 keep tile_nav and plain states. */
+constexpr uint64_t EV_STATE_SIGN = 1ull << 63;
+constexpr bool ev_nav_in_sign(int g) { return g >= 1; }
+constexpr uint64_t ev_state_signed(uint64_t state_bits, bool bit_is_minus) { return bit_is_minus ? state_bits | EV_STATE_SIGN : state_bits; }
+constexpr uint64_t ev_state_mag(uint64_t stored_bits) { return stored_bits & ~EV_STATE_SIGN; }
+constexpr uint32_t ev_state_bit(uint64_t stored_bits) { return (uint32_t)(stored_bits >> 63); } /* 1: the bit in force is -1 */
+/* where the bit after the roll-over of entry e of a code row lies: entry e + 1 of the row, or (from_end) the block's end state */
+struct EvNextBitAt {
+    bool from_end;
+    int entry;
+};
+constexpr EvNextBitAt ev_next_bit_at(int e, int used) { return EvNextBitAt{e + 1 >= used, e + 1 >= used ? -1 : e + 1}; }
+/* ... as the word tile_nav would hold for entry e of channel i's code row of block b (bit 0: the bit in force is -1, bit 1: the
+ * one after the granule's roll-over is), for the readers that are not short of registers (the despreaders) */
+__device__ __forceinline__ uint32_t ev_nav_of_signs(const BatchDev &p, size_t b, int i, int e)
+{
+    const uint32_t *row = reinterpret_cast<const uint32_t *>(p.tile_x + ev_tile_x_row(b, p.nch, i, NCO_CODE, p.nstates));
+    const EvNextBitAt nx = ev_next_bit_at(e, p.nstates);
+    const uint32_t cur = row[2 * e + 1] >> 31;
+    const uint32_t nxt = (nx.from_end ? (uint32_t)p.end[b * (size_t)p.nch + (size_t)i].dataBit : row[2 * nx.entry + 1]) >> 31;
+    return cur | (nxt << 1);
+}
 #ifdef GPSBB_EV_MODEL_ERR_OWN
 static_assert(ev_carr_granule_fits(EV_STATE_LOG2_MAX), "the carrier model of the largest state granule must stay inside the error budget");
 static_assert(EV_STATE_LOG2_MAX == 2, "ev_second names the one granule whose carrier's differs (ev_exact_run_2g<1>)");
@@ -292,7 +323,7 @@ __device__ __forceinline__ T scalar_load(const T *p)
  * tile_x, n_off steps back, the carrier (TWO_G; else as the code) from tile_y (its row base, as tile_x is the code's), n_off_y
  * steps back.
  */
-template <bool FIXED, bool TWO_G = false, class LDS>
+template <bool FIXED, bool TWO_G = false, bool NAV_IN_SIGN = false, class LDS>
 __device__ __forceinline__ uint32_t ev_exact_run_body(LDS &L, int wave, int lane, int i, const EvConst *kbi, const double *tile_x,
                                                       int ntiles, uint32_t nb, int n_off, const double *tile_y, int n_off_y,
                                                       uint32_t fx_phase, int32_t fx_step)
@@ -300,7 +331,8 @@ __device__ __forceinline__ uint32_t ev_exact_run_body(LDS &L, int wave, int lane
     constexpr bool fixed = FIXED;
     const bool down = kbi->down != 0;
     const double S = down ? -kbi->S : kbi->S, sc = kbi->sc;
-    const double xt = tile_x[(size_t)(2 * i) * ntiles], yt = (TWO_G ? tile_y : tile_x)[(size_t)(2 * i + 1) * ntiles];
+    const double xt_s = tile_x[(size_t)(2 * i) * ntiles], yt = (TWO_G ? tile_y : tile_x)[(size_t)(2 * i + 1) * ntiles];
+    const double xt = NAV_IN_SIGN ? __builtin_fabs(xt_s) : xt_s; /* (a granule table's code state: ev_nav_in_sign) */
     /* code NCO: at most one roll-over between the tile start and the end of the run (checked by the host) */
     int64_t wraps = 0;
     double x = code_jump(xt, sc, (int64_t)n_off, &wraps);
@@ -345,6 +377,14 @@ __device__ __noinline__ uint32_t ev_exact_run(LDS &L, int wave, int lane, int i,
 {
     return ev_exact_run_body<false>(L, wave, lane, i, kbi, tile_x, ntiles, nb, n_off, nullptr, 0, 0u, 0);
 }
+/* ... from a granule table whose kinds share the granule (g = EV_STATE_LOG2_MAX): its code state carries a data bit in its sign
+ * (ev_nav_in_sign).  A function of its own, so that the kernels of tables with a state per tile call what they called */
+template <class LDS>
+__device__ __noinline__ uint32_t ev_exact_run_g(LDS &L, int wave, int lane, int i, const EvConst *kbi, const double *tile_x,
+                                                int ntiles, uint32_t nb, int n_off)
+{
+    return ev_exact_run_body<false, false, true>(L, wave, lane, i, kbi, tile_x, ntiles, nb, n_off, nullptr, 0, 0u, 0);
+}
 /* ... behind a carrier granule that is not the code's (ev_carr_log2(SG) != SG): each NCO from the state of its kind's granule of
  * tile wt.  tile_x: the block's first state (chain c's row at [c * nst]); wt_nb: wt << 2 | nb; off: the run's first sample in the
  * tile.  Where the two states lie is worked out here, behind the call: its caller has no registers for it.  (ev_state_at's rule,
@@ -355,7 +395,7 @@ __device__ __noinline__ uint32_t ev_exact_run_2g(LDS &L, int wave, int lane, int
 {
     constexpr int GC = ev_carr_log2(SG);
     const int wt = (int)(wt_nb >> 2);
-    return ev_exact_run_body<false, true>(L, wave, lane, i, kbi, tile_x + (wt >> SG), nst, wt_nb & 3u, (wt & ((1 << SG) - 1)) * TILE + off,
+    return ev_exact_run_body<false, true, ev_nav_in_sign(SG)>(L, wave, lane, i, kbi, tile_x + (wt >> SG), nst, wt_nb & 3u, (wt & ((1 << SG) - 1)) * TILE + off,
                                           tile_x + (wt >> GC), (wt & ((1 << GC) - 1)) * TILE + off, 0u, 0);
 }
 /* ... with the fixed-point carrier: the accumulator at the tile's first sample and its step take the carrier NCO's place */
@@ -587,6 +627,8 @@ __device__ __forceinline__ void ev_second(LDS &L, uint32_t &drow, int wave, int 
             else if (ev_exact_2g(T)) /* (only GPSBB_EV_STATE_LOG2 = 1 has two granules: EV_STATE_LOG2_MAX is 2) */
                 acc0 += ev_exact_run_2g<1>(L, wave, lane, i, kb + i, T.tile_x, (T.ntiles + 1) >> 1,
                                            ((uint32_t)T.wt << 2) | ((T.dbits >> i) & 1u) | (((T.dnext >> i) & 1u) << 1), (int)off);
+            else if (T.sg) /* (a constant of the kernel: one of the two is compiled) */
+                acc0 += ev_exact_run_g(L, wave, lane, i, kb + i, x.tile_x, x.stride, x.nb, x.n_skip + (int)off);
             else
                 acc0 += ev_exact_run(L, wave, lane, i, kb + i, x.tile_x, x.stride, x.nb, x.n_skip + (int)off);
             atomicAdd(n_exact, 1ull);
@@ -935,6 +977,15 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
                                     and the host can check it (GPSBB_INFO_TILES_RENDERED) */
     double ts_v = 0.0;
     uint32_t nav_v = 0;
+    /* sg: the data bits in force behind the block's last sample, bit 2 i channel i's (as the ballots of stage_tile): what follows a
+     * roll-over in a row's last granule (ev_next_bit_at).  The pre-pass that left the states left the end states; one scalar
+     * register for the whole block */
+    uint32_t end_bits = 0u;
+    if (sg) {
+        const bool code_lane = chain_lane && !(lane & 1);
+        const int end_bit = code_lane ? p.end[(size_t)b * p.nch + (lane >> 1)].dataBit : 0;
+        end_bits = (uint32_t)__ballot(end_bit < 0) & 0x55555555u;
+    }
     /* A tile's states go into this wavefront's LDS slot and its data bits into scalar masks in the epilogue of the tile BEFORE it
      * (and ahead of the loop for a wavefront's first): by then the channel loops have read the slot for the last time and the
      * prefetched granule state has been on its way for a tile's time, so that the top of a tile waits for no vector memory —
@@ -949,7 +1000,10 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
         uint32_t ln = (uint32_t)lane;
         asm volatile("" : "+v"(ln));
         if (chain_lane) {
-            double v = (mirror ? mirror_at - ts_v : ts_v) + guard_w; /* one rounding, half a unit of 2^-32 */
+            /* (sg: a code state carries its granule's data bit in its sign, ev_nav_in_sign — the magnitude is an operand modifier of
+             * the add; a carrier state, mirrored or not, is not negative) */
+            const double ts_m = mirror ? mirror_at - ts_v : ts_v;
+            double v = (sg ? __builtin_fabs(ts_m) : ts_m) + guard_w; /* one rounding, half a unit of 2^-32 */
             if (sg) {
                 /* The anchor of tile r of the granule: the model r*1024 steps on (one more rounding, half a unit), reduced by whole
                  * periods where it has passed one — exactly (an integer off a number in [2^20, 2^21) that stays there), so that index
@@ -978,16 +1032,34 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
         /* the tile's data bits as the model sees them (bit i: channel i), merged in scalar registers: a channel past its granule's
          * roll-over (r > 0 only: bit 2 i of the ballot is its code lane) has the next bit in force and no further roll-over in
          * the tile */
+        if (sg) {
+            /* the bits are the signs of the code lanes' states (ev_nav_in_sign): the granule's own, which the lane holds anyway, and
+             * the one fetch_granule asked for beside it — bit 2 i of either ballot is channel i's (a carrier lane's state is not
+             * negative and its nav_v stays zero; the other lanes' are zero for good).  Merged where they are, then brought together
+             * in scalar registers: twelve scalar instructions a mask, beside a tile's thousands of vector ones */
+            uint32_t s0 = (uint32_t)__ballot(__double2hiint(ts_v) < 0) & 0x55555555u;
+            uint32_t s1 = (uint32_t)__ballot((int32_t)nav_v < 0) & 0x55555555u;
+            s1 = (t >> sg) + 1 < nst ? s1 : end_bits; /* (behind the row's last state: the block's end state, ev_next_bit_at) */
+            if (r)
+                s0 = (s0 & ~(uint32_t)__ballot(rolled_over)) | (s1 & (uint32_t)__ballot(rolled_over));
+            s0 = (s0 | (s0 >> 1)) & 0x33333333u;
+            s1 = (s1 | (s1 >> 1)) & 0x33333333u;
+            s0 = (s0 | (s0 >> 2)) & 0x0f0f0f0fu;
+            s1 = (s1 | (s1 >> 2)) & 0x0f0f0f0fu;
+            s0 = (s0 | (s0 >> 4)) & 0x00ff00ffu;
+            s1 = (s1 | (s1 >> 4)) & 0x00ff00ffu;
+            /* (an idle channel's rows are whatever the allocation held: its bits must not send the tile's live channels to the
+             * instantiations for a data-bit edge) */
+            uint32_t live_ch = mkd;
+#pragma unroll
+            for (int k = 0; k < EV_KC_MAX; k++)
+                live_ch |= mk[k];
+            dbits = (s0 | (s0 >> 8)) & live_ch; /* bit i: channel i (at most 16 of them) */
+            dnext = (s1 | (s1 >> 8)) & live_ch;
+            return;
+        }
         dbits = (uint32_t)__ballot(nav_v & 1u);
         dnext = (uint32_t)__ballot(nav_v & 2u);
-        if (sg && r) {
-            uint32_t ro = (uint32_t)__ballot(rolled_over) & 0x55555555u; /* at most 32 chain lanes */
-            ro = (ro | (ro >> 1)) & 0x33333333u;
-            ro = (ro | (ro >> 2)) & 0x0f0f0f0fu;
-            ro = (ro | (ro >> 4)) & 0x00ff00ffu;
-            ro = (ro | (ro >> 8)) & 0x0000ffffu; /* bit i: channel i */
-            dbits = (dbits & ~ro) | (dnext & ro);
-        }
     };
     uint32_t t_dbits = 0u, t_dnext = 0u; /* of the tile being worked on */
     /* (the other lanes' ts_v and nav_v stay zero for good: only the loads write them — a move into a register that a load may
@@ -998,8 +1070,15 @@ __device__ __forceinline__ void synth_ev_body(const BatchDev &p, int16_t *__rest
         const uint32_t at = ln * (uint32_t)nst + (uint32_t)g;
         if (chain_lane) /* (a carrier lane reads its granule's state again where only the code's granule is new) */
             ts_v = txb[gc == sg ? at : at - ((ln & 1u) ? (uint32_t)g - ((uint32_t)g >> (gc - sg)) : 0u)];
-        if (lane < p.nch)
+        if (sg) {
+            /* the bit after the granule's roll-over (ev_nav_in_sign, ev_next_bit_at): a code lane takes the high word of its row's
+             * next state — the line it has just asked for, or the one behind it.  Behind the row's last state it reads that one
+             * again, and stage_tile takes the block's end state instead (end_bits). */
+            if (chain_lane && !(ln & 1u))
+                nav_v = reinterpret_cast<const uint32_t *>(txb)[2u * (at + (g + 1 < nst ? 1u : 0u)) + 1u];
+        } else if (lane < p.nch) {
             nav_v = tnb[at];
+        }
     };
     if (base < ntw) {
         fetch_granule(base >> sg);

@@ -262,9 +262,12 @@ struct BatchDev {
     uint32_t pd_danger;             /* k_synth_pd: a model's low word below this sends the lane to the exact path (2 * PD_BAND) */
     double *tile_x;                 /* [nblocks][2*nch][nstates]: row 2*channel = code phase (chips), 2*channel+1 =
                                        carrier phase * 512, at sample g*(TILE << st_log2) (state-contiguous per chain: the
-                                       pre-pass writes it coalesced, k_synth_ev reads it through the L2)  */
+                                       pre-pass writes it coalesced, k_synth_ev reads it through the L2).  st_log2 >= 1: a
+                                       code state carries the data bit in force in its SIGN and readers take the magnitude
+                                       (ev_nav_in_sign, gpsbb_events.hip.h)  */
     uint32_t *tile_nav;             /* [nblocks][nch][nstates]: bit 0 = the data bit in force is -1, bit 1 = the data
-                                       bit after the next code roll-over is -1                         */
+                                       bit after the next code roll-over is -1.  st_log2 == 0 only: a granule table has none
+                                       (neither written nor read)  */
     const EvConst *evc;             /* [nblocks*nch]                                                  */
     int chain_dev;                  /* 1: GPSBB_CHAIN_CARRIER is resolved on the device (k_chain_prefix / k_chain_fix) */
     int chain_starts;               /* ... for the per-sample kernel: the chain kernels only put the exact start phase of every

@@ -455,7 +455,9 @@ __device__ __forceinline__ void lap_enter_block(const BatchDev &p, const LapDev 
  * for every tile whose first sample lies in the period, so they go out when the period is over (or the lane's walk is) — two dozen
  * consecutive words, in 32- and 16-byte pieces — instead of one word with every tile state: stored one by one, four bytes at a
  * time, they were more than half of what the pre-pass writes to HBM (a sector of 32 bytes per word: WRITE_SIZE).  Tiles
- * [w.navt, the first tile whose first sample is n_excl or later). */
+ * [w.navt, the first tile whose first sample is n_excl or later).  Tables with a state per tile only: a granule table keeps the
+ * bit in the sign of its code states (lap_stored) and has no tile_nav words — even in pieces they were a quarter of what
+ * code pass 2 wrote (profiles/nv01_profile.json). */
 /* SG (here and in lap_emit_row, lap_run, lap_walk): the batch's state granule BatchDev::st_log2 as a constant (pass 2: what
  * costs registers as a variable shift), or -1: read it from p (the repair).  It is the CODE's granule; a carrier chain leaves a
  * state per 2^ev_carr_log2(SG) tiles (gpsbb_events.hip.h), into the same row with the same stride p.nstates: lap_tsl is the log2 of
@@ -473,6 +475,20 @@ __device__ __forceinline__ int lap_nstates(const BatchDev &p)
         return p.nstates;
     const int gc = ev_carr_log2(SG >= 0 ? SG : p.st_log2);
     return (p.ntiles + (1 << gc) - 1) >> gc;
+}
+/* A code state as a granule table holds it (ev_nav_in_sign, gpsbb_events.hip.h): the data bit in force — bit 0 of `bits`, the
+ * row's: a tile state of a row lies in the row's code period — in the sign of the non-negative state.  Every other state as it is. */
+template <int KIND, int SG>
+__device__ __forceinline__ bool lap_nav_in_sign(const BatchDev &p)
+{
+    return KIND == NCO_CODE && ev_nav_in_sign(SG >= 0 ? SG : p.st_log2);
+}
+template <int KIND, int SG>
+__device__ __forceinline__ double lap_stored(const BatchDev &p, double v, uint32_t bits)
+{
+    if (!lap_nav_in_sign<KIND, SG>(p))
+        return v;
+    return __hiloint2double(__double2hiint(v) | (int)(bits << 31), __double2loint(v));
 }
 template <int KIND, int SG = -1>
 __device__ __forceinline__ void lap_nav_out(const BatchDev &p, int i, LapLane<KIND> &w, bool on, int n_excl, uint32_t bits)
@@ -544,8 +560,8 @@ __device__ __forceinline__ void lap_emit_row(const BatchDev &p, int i, bool on, 
             for (int q = lane; q < c; q += 64) {
                 const int tt = t0 + q;
                 const double v = __fma_rn((double)((tt << tsl) - nn), SS, xx);
-                txs[tt] = KIND == NCO_CARR ? mul_rn(v, 512.0) : v;
-                if (!WIDE && KIND == NCO_CODE)
+                txs[tt] = KIND == NCO_CARR ? mul_rn(v, 512.0) : lap_stored<KIND, SG>(p, v, bb);
+                if (!WIDE && KIND == NCO_CODE && !lap_nav_in_sign<KIND, SG>(p))
                     tns[tt] = bb;
             }
             if (lane == src)
@@ -562,8 +578,8 @@ __device__ __forceinline__ void lap_emit_row(const BatchDev &p, int i, bool on, 
         uint32_t *pn = p.tile_nav + ((size_t)b * (size_t)p.nch + i) * (size_t)p.nstates + t;
         for (; __ballot(cnt > 0); cnt--) {
             if (cnt > 0) {
-                *px = KIND == NCO_CARR ? mul_rn(v, 512.0) : v;
-                if (KIND == NCO_CODE)
+                *px = KIND == NCO_CARR ? mul_rn(v, 512.0) : lap_stored<KIND, SG>(p, v, bits);
+                if (KIND == NCO_CODE && !lap_nav_in_sign<KIND, SG>(p))
                     *pn = bits;
             }
             v = add_rn(v, dv);
@@ -587,7 +603,8 @@ __device__ __forceinline__ void lap_emit_row(const BatchDev &p, int i, bool on, 
             if (pair) {
                 v3 = add_rn(v, dv);
                 lap_d2 *q = reinterpret_cast<lap_d2 *>(px);
-                q[0] = KIND == NCO_CARR ? lap_d2{mul_rn(v, 512.0), mul_rn(v3, 512.0)} : lap_d2{v, v3};
+                q[0] = KIND == NCO_CARR ? lap_d2{mul_rn(v, 512.0), mul_rn(v3, 512.0)}
+                                        : lap_d2{lap_stored<KIND, SG>(p, v, bits), lap_stored<KIND, SG>(p, v3, bits)};
             }
         }
         if (__ballot(quad)) {
@@ -599,13 +616,13 @@ __device__ __forceinline__ void lap_emit_row(const BatchDev &p, int i, bool on, 
                     q[0] = lap_d2{mul_rn(v, 512.0), mul_rn(v1, 512.0)};
                     q[1] = lap_d2{mul_rn(v2, 512.0), mul_rn(v3, 512.0)};
                 } else {
-                    q[0] = lap_d2{v, v1};
-                    q[1] = lap_d2{v2, v3};
+                    q[0] = lap_d2{lap_stored<KIND, SG>(p, v, bits), lap_stored<KIND, SG>(p, v1, bits)};
+                    q[1] = lap_d2{lap_stored<KIND, SG>(p, v2, bits), lap_stored<KIND, SG>(p, v3, bits)};
                 }
             }
         }
         if (one)
-            *px = KIND == NCO_CARR ? mul_rn(v, 512.0) : v;
+            *px = KIND == NCO_CARR ? mul_rn(v, 512.0) : lap_stored<KIND, SG>(p, v, bits);
         const int adv = quad ? 4 : (pair ? 2 : (one ? 1 : 0));
         v = add_rn(quad || pair ? v3 : v, dv);
         px += adv;
@@ -801,7 +818,8 @@ __device__ __forceinline__ void lap_run(const BatchDev &p, int i, LapLane<KIND> 
                 w.acc = lap_compose(E, lap_compose(F, w.acc));
                 w.so = 0;
             }
-            if (KIND == NCO_CODE && EMIT && WIDE && p.tile_x)
+            /* (a granule table has no tile_nav words: its code states carry the bit, lap_stored) */
+            if (KIND == NCO_CODE && EMIT && WIDE && !lap_nav_in_sign<KIND, SG>(p) && p.tile_x)
                 lap_nav_out<KIND, SG>(p, i, w, wrapped, n1 + 1, w.bits); /* the period's tiles: up to the one the next period's first sample starts */
             if (KIND == NCO_CODE && wrapped) {
                 /* a code period is over (c:2714-2733): the data bits of the next one, should the lane go on into it — and its
@@ -954,7 +972,7 @@ __device__ __forceinline__ void lap_walk(const BatchDev &p, const LapDev &L, int
         }
         w.active = w.active && w.outcome == 0;
     }
-    if (KIND == NCO_CODE && EMIT && WIDE && p.tile_x)
+    if (KIND == NCO_CODE && EMIT && WIDE && !lap_nav_in_sign<KIND, SG>(p) && p.tile_x)
         lap_nav_out<KIND, SG>(p, i, w, walked, w.n, w.bits); /* what is left of the lane's last period */
 }
 

@@ -238,7 +238,8 @@ __global__ __launch_bounds__(256) void k_model_err_ev(BatchDev p, double *mx, un
     const int sg = p.st_log2, nst = p.nstates;
     const EvStateAt cx = ev_state_at(sg, NCO_CODE, wt), cy = ev_state_at(sg, NCO_CARR, wt);
     const int r = cx.since, ry_t = cy.since;
-    const double ts_x_g = p.tile_x[ev_tile_x_row(b, p.nch, i, NCO_CODE, nst) + cx.entry];
+    const double ts_x_s = p.tile_x[ev_tile_x_row(b, p.nch, i, NCO_CODE, nst) + cx.entry];
+    const double ts_x_g = ev_nav_in_sign(sg) ? fabs(ts_x_s) : ts_x_s; /* (a granule table's code state carries a data bit in its sign) */
     const double ts_y = p.tile_x[ev_tile_x_row(b, p.nch, i, NCO_CARR, nst) + cy.entry];
     const bool down = kb.down != 0;
     /* exactly what synth_ev_body puts into EvLds::tstate (IEEE carrier) */

@@ -105,6 +105,12 @@ int gpsbb_test_exc_host(const gpsbb_exc_t *e, const int16_t *w, long nsamp, cons
 int gpsbb_test_state_log2(struct gpsbb_batch *b);
 int gpsbb_test_state_log2_carr(struct gpsbb_batch *b);
 void gpsbb_test_budgets(double out[3]); /* EV_MODEL_ERR, EV_T_EPS, PD_BAND of this build, in units of 2^-32 */
+/* The data bits of a table with a state granule of 2^g tiles, g >= 1, travel in the signs of its code states (ev_nav_in_sign,
+ * gpsbb_events.hip.h).  For a state (its bit pattern, non-negative) under a data bit of -1 (minus) or +1: out[0] the pattern as
+ * the table of granule g holds it, out[1] the magnitude and out[2] the bit a reader gets back from that, out[3] whether the bit
+ * after a roll-over inside entry e of a row that uses `used` entries comes from the block's end state (1) or from the row (0),
+ * out[4] the row's entry it comes from (-1: none), out[5] whether granule g keeps its bits this way at all. */
+void gpsbb_test_nav_sign(unsigned long long state_bits, int minus, int g, int e, int used, long long out[6]);
 /* What the library holds in this process right now: device buffers, pinned host buffers, HIP events — every one made and freed
  * through its owner (DevBuf, PinnedBuf, Event in gpsbb.hip), counted there.  Exported by the product build as well: a cycle of
  * create ... destroy must leave all three where it found them (tests/test_lifecycle_gpu.py). */
