@@ -337,6 +337,33 @@ class Exc(C.Structure):
 assert C.sizeof(Exc) == 8720
 
 
+# pulse blanking (include/gpsbb.h gpsbb_device_blank): a boxcar power detector in time, the samples around every trigger zeroed
+BLANK_MAX_WIN, BLANK_MAX_PRE, BLANK_MAX_HOLD, BLANK_MAX_HIST = 64, 255, 1023, 1341
+BLANK_TILE, BLANK_MIN_RUN = 4096, 2   # the outputs of one of k_blank's tiles, the tiles of a workgroup's least run (csrc/gpsbb_blank.h)
+
+
+class Blank(C.Structure):
+    """gpsbb_blank_t: win (L), pre (G), hold, thr"""
+    _fields_ = [("win", C.c_int32), ("pre", C.c_int32), ("hold", C.c_int32), ("_pad", C.c_int32), ("thr", C.c_uint64)]
+
+    def __init__(self, win=8, pre=8, hold=8, thr=0):
+        super().__init__()
+        self.win, self.pre, self.hold, self.thr = win, pre, hold, thr
+
+    def hist(self):
+        """K = G + hold + L - 1: the samples of the history"""
+        return int(self.pre) + int(self.hold) + int(self.win) - 1
+
+    def copy(self, **fields):
+        c = Blank.from_buffer_copy(self)
+        for k, v in fields.items():
+            setattr(c, k, v)
+        return c
+
+
+assert C.sizeof(Blank) == 24
+
+
 ERRORS = {0: "GPSBB_OK", -1: "GPSBB_E_BADARG", -2: "GPSBB_E_BADCHAN", -3: "GPSBB_E_HIP", -4: "GPSBB_E_NOMEM",
           -5: "GPSBB_E_INTERNAL", -6: "GPSBB_E_NODEVICE", -7: "GPSBB_E_STATE"}
 
@@ -360,6 +387,7 @@ API_SYMBOLS = [
     "gpsbb_device_fir", "gpsbb_fir_make",
     "gpsbb_device_psd", "gpsbb_psd_make", "gpsbb_psd_min_shift", "gpsbb_psd_twiddles", "gpsbb_psd_scale",
     "gpsbb_device_excise", "gpsbb_exc_make", "gpsbb_exc_from_psd",
+    "gpsbb_device_blank", "gpsbb_blank_make", "gpsbb_blank_from_level",
 ]
 # ... and include/gpsbb_node.h
 NODE_API_SYMBOLS = ["gpsbb_node_create", "gpsbb_node_run", "gpsbb_node_run_digest", "gpsbb_node_slot_digests", "gpsbb_node_destroy", "gpsbb_node_plan", "gpsbb_node_begin", "gpsbb_node_feed", "gpsbb_node_end",
@@ -509,6 +537,10 @@ def lib():
             L.gpsbb_device_excise.argtypes = [vp, vp, C.c_long, vp, vp, vp, vp, vp, vp, vp, vp]
             L.gpsbb_exc_make.argtypes = [vp, i]
             L.gpsbb_exc_from_psd.argtypes = [vp, vp, vp, C.c_long, d, d]
+        if hasattr(L, "gpsbb_device_blank"):  # the blanker's calls, as a group (an older build loaded for an A/B: tools/ab_lib.sh)
+            L.gpsbb_device_blank.argtypes = [vp, vp, C.c_long, vp, vp, vp, vp, vp, vp, vp, vp]
+            L.gpsbb_blank_make.argtypes = [vp, i, i, i, d, d]
+            L.gpsbb_blank_from_level.argtypes = [vp, vp, C.c_long, i, d]
         if hasattr(L, "gpsbb_test_live"):  # (an older build loaded for an A/B: tools/ab_lib.sh)
             L.gpsbb_test_live.argtypes = [vp]
             L.gpsbb_test_live.restype = None
@@ -564,6 +596,11 @@ def exp_lib():
             L.gpsbb_test_exc_ms.restype = C.c_float
             L.gpsbb_test_exc_run.argtypes = [i]
             L.gpsbb_test_exc_host.argtypes = [vp, vp, C.c_long, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "gpsbb_test_blank_ms"):  # (an older build loaded for an A/B: tools/ab_lib.sh)
+            L.gpsbb_test_blank_ms.argtypes = [vp]
+            L.gpsbb_test_blank_ms.restype = C.c_float
+            L.gpsbb_test_blank_tile.argtypes = [vp]
+            L.gpsbb_test_blank_host.argtypes = [vp, vp, C.c_long, vp, vp, vp, vp, vp]
         if hasattr(L, "gpsbb_test_nav_sign"):  # (an older build loaded for an A/B: tools/ab_lib.sh)
             L.gpsbb_test_nav_sign.argtypes = [C.c_ulonglong, i, i, i, i, vp]
             L.gpsbb_test_nav_sign.restype = None
@@ -880,6 +917,21 @@ class Synth:
                                        None if hin is None else hin.ctypes.data, hout.ctypes.data, C.c_void_p(int(d_out)), C.byref(clipped),
                                        C.byref(excised)), "gpsbb_device_excise")
         return hout, int(clipped.value), int(excised.value)
+
+    def device_blank(self, d_ptr, nsamp, blank, d_out, hist=None, noise=None, interf=None):
+        """gpsbb_device_blank: nsamp int16 I/Q pairs in device memory at d_ptr, the samples around every trigger of the plan blank
+        (a Blank) zeroed, into nsamp pairs at d_out, delayed by blank.pre -> (the history to hand to the next call, int16 [K, 2];
+        the outputs zeroed; the triggers).  hist: the history a call before returned, or None (zeros).  blank_host over view_host's
+        output is the same in numpy"""
+        nz, js = _as_noise(noise), _as_interf(interf)
+        K = min(max(blank.hist(), 0), BLANK_MAX_HIST)
+        hin = None if hist is None else np.ascontiguousarray(hist, np.int16).reshape(K, 2)
+        hout = np.zeros((K, 2), np.int16)
+        blanked, triggers = C.c_uint64(0), C.c_uint64(0)
+        _chk(lib().gpsbb_device_blank(self._h, C.c_void_p(int(d_ptr)), int(nsamp), _ref(nz), _ref(js), C.byref(blank),
+                                      None if hin is None or K == 0 else hin.ctypes.data, hout.ctypes.data if K else None, C.c_void_p(int(d_out)),
+                                      C.byref(blanked), C.byref(triggers)), "gpsbb_device_blank")
+        return hout, int(blanked.value), int(triggers.value)
 
     def device_noise(self, d_src, nblocks, nsamp, noise, d_dst=None):
         """gpsbb_device_noise: nblocks blocks of int16 IQ in device memory at d_src, with noise, into d_dst (default: in place)"""
@@ -2002,6 +2054,73 @@ def psd_host(w, psd, view=OUT_SC16):
         X = psd_transform(x) >> shift
         out += (X * X).sum(-1).sum(0).astype(np.uint64)
     return out, nseg
+
+
+# ---- pulse blanking (include/gpsbb.h, gpsbb_device_blank): the numpy restatement the GPU's output is checked against ----
+
+def blank_make(win=0, pre=-1, hold=-1, floor_ms=0.0, thr_db=0.0):
+    """gpsbb_blank_make: the plan from a quiet floor (the mean of |w|^2); the defaults are the call's: L = 8, G = hold = L, 6 dB"""
+    b = Blank()
+    _chk(lib().gpsbb_blank_make(C.byref(b), int(win), int(pre), int(hold), float(floor_ms), float(thr_db)), "gpsbb_blank_make")
+    return b
+
+
+def blank_from_level(blank, levels, shift=0, thr_db=6.0):
+    """gpsbb_blank_from_level: a copy of blank with thr set thr_db above the lower median of the short blocks' levels (LEVEL_DTYPE
+    [n], device_level's or level_host's, measured before the shift)"""
+    b = blank.copy()
+    lv = _as_levels(levels)
+    _chk(lib().gpsbb_blank_from_level(C.byref(b), lv.ctypes.data, lv.size, int(shift), float(thr_db)), "gpsbb_blank_from_level")
+    return b
+
+
+def blank_ok(blank):
+    """what gpsbb_device_blank asks of a plan"""
+    return (1 <= int(blank.win) <= BLANK_MAX_WIN and 0 <= int(blank.pre) <= BLANK_MAX_PRE and 0 <= int(blank.hold) <= BLANK_MAX_HOLD
+            and int(blank._pad) == 0)
+
+
+def blank_host(w, blank, hist=None):
+    """gpsbb_device_blank in numpy on view samples w [nsamp, 2] (view_host's output: already impaired) -> (out int16 [nsamp, 2],
+    hist_out int16 [K, 2], blanked, triggers), from the definition in include/gpsbb.h: the boxcar is a difference of two prefix
+    sums of the powers, the dilation a difference of two prefix counts of the triggers"""
+    if not blank_ok(blank):
+        raise ValueError("a plan gpsbb_device_blank refuses")
+    w = np.asarray(w, np.int64)
+    if w.ndim != 2 or w.shape[1] != 2 or w.shape[0] < 1:
+        raise ValueError("w of shape (nsamp >= 1, 2) wanted, got %r" % (w.shape,))
+    L, G, D, K, thr, n = int(blank.win), int(blank.pre), int(blank.pre) + int(blank.hold), blank.hist(), int(blank.thr), w.shape[0]
+    h = np.zeros((K, 2), np.int64) if hist is None else np.asarray(hist, np.int64).reshape(K, 2)
+    x = np.concatenate([h, w])                                   # x[K + n'] is w[n'], n' in [-K, nsamp)
+    cp = np.concatenate([[0], np.cumsum((x * x).sum(1))])        # cp[i]: the powers before x[i]; below 2^31 * 2^31
+    j = np.arange(-D, n)                                         # s[j] = p[j - L + 1] + .. + p[j]
+    s = cp[j + K + 1] - cp[j + K + 1 - L]
+    trig = s.astype(np.uint64) > np.uint64(thr)
+    ct = np.concatenate([[0], np.cumsum(trig)])                  # ct[i]: the triggers before j = i - D
+    m = np.arange(n)
+    z = ct[m + D + 1] - ct[m] > 0                                # any trig[j], j in [m - D, m]
+    out = np.where(z[:, None], 0, x[m + K - G])
+    return out.astype(np.int16), x[x.shape[0] - K:].astype(np.int16), int(np.count_nonzero(z)), int(np.count_nonzero(trig[D:]))
+
+
+def blank_plain_c(w, blank, hist=None):
+    """csrc/gpsbb_blank.h's plain-C definition (blank_host, through the experiments build's hook gpsbb_test_blank_host) on host
+    memory -> (out, hist_out, blanked, triggers)"""
+    w = np.ascontiguousarray(w, np.int16)
+    K = min(max(blank.hist(), 0), BLANK_MAX_HIST)
+    hin = None if hist is None else np.ascontiguousarray(hist, np.int16).reshape(K, 2)
+    out, hout = np.zeros(w.shape, np.int16), np.zeros((K, 2), np.int16)
+    blanked, triggers = C.c_uint64(0), C.c_uint64(0)
+    _chk(exp_lib().gpsbb_test_blank_host(C.byref(blank), w.ctypes.data, w.shape[0], None if hin is None or K == 0 else hin.ctypes.data, out.ctypes.data,
+                                         hout.ctypes.data if K else None, C.byref(blanked), C.byref(triggers)), "gpsbb_test_blank_host")
+    return out, hout, int(blanked.value), int(triggers.value)
+
+
+def blank_tile():
+    """(the outputs of one of k_blank's tiles, the tiles of a workgroup's least run): gpsbb_test_blank_tile"""
+    run = C.c_int(0)
+    t = exp_lib().gpsbb_test_blank_tile(C.byref(run))
+    return int(t), int(run.value)
 
 
 # ---- interference excision (include/gpsbb.h, gpsbb_device_excise): the numpy restatement the GPU's output is checked against ----

@@ -37,6 +37,7 @@
 #include "gpsbb_fir.hip.h"
 #include "gpsbb_psd.hip.h"
 #include "gpsbb_exc.hip.h"
+#include "gpsbb_blank.hip.h"
 #include "gpsbb_walk.hip.h"
 #include "gpsbb_laps.hip.h"
 #include "gpsbb_nco.h"
@@ -700,7 +701,8 @@ struct gpsbb {
     DevBuf<unsigned long long> d_psd_tab;  /* gpsbb_device_psd's: the twiddles as k_psd reads them (uploaded once), the window, the result */
     DevBuf<unsigned long long> d_psd;      /* ... and the workgroups' partials */
     DevBuf<unsigned long long> d_exc;      /* gpsbb_device_excise's: the inverse's tables (uploaded once), the plan, the histories, the counts */
-    KernelTimer acq_tm, trk_tm, fir_tm, psd_tm, exc_tm; /* around the kernels of the last gpsbb_device_acquire, _track, _fir, _psd, _excise (gpsbb_test_*_ms) */
+    DevBuf<unsigned long long> d_blank;    /* gpsbb_device_blank's: the histories, the counts */
+    KernelTimer acq_tm, trk_tm, fir_tm, psd_tm, exc_tm, blank_tm; /* around the kernels of the last gpsbb_device_acquire, _track, _fir, _psd, _excise, _blank (gpsbb_test_*_ms) */
 };
 
 /* every stream the handle has created, in no particular order */
@@ -1123,8 +1125,8 @@ extern "C" void gpsbb_destroy(gpsbb_t *h)
     chain_only_free(h);
     (void)drain_streams(h);
     release_all(h->d_tabs, h->d_ca, h->d_status, h->d_hz, h->d_clip, h->d_noise_tab, h->d_nclip);
-    release_all(h->d_pack, h->d_level, h->d_digest, h->d_acq_chips, h->d_acq_rows, h->d_acq_grid, h->d_trk, h->d_fir, h->d_psd_tab, h->d_psd, h->d_exc);
-    release_all(h->acq_tm, h->trk_tm, h->fir_tm, h->psd_tm, h->exc_tm);
+    release_all(h->d_pack, h->d_level, h->d_digest, h->d_acq_chips, h->d_acq_rows, h->d_acq_grid, h->d_trk, h->d_fir, h->d_psd_tab, h->d_psd, h->d_exc, h->d_blank);
+    release_all(h->acq_tm, h->trk_tm, h->fir_tm, h->psd_tm, h->exc_tm, h->blank_tm);
     delete h->pool;
     h->pool = nullptr;
     for_each_stream(h, [](hipStream_t st) { (void)hipStreamDestroy(st); });
@@ -3497,6 +3499,95 @@ extern "C" int gpsbb_device_excise(gpsbb_t *h, const int16_t *d_iq, long nsamp, 
     return GPSBB_OK;
 }
 
+/* ---- pulse blanking (include/gpsbb.h gpsbb_device_blank; gpsbb_blank.h, gpsbb_blank.hip.h) ---- */
+
+extern "C" int gpsbb_blank_make(gpsbb_blank_t *b, int win, int pre, int hold, double floor_ms, double thr_db)
+{
+    return blank_make(b, win, pre, hold, floor_ms, thr_db);
+}
+
+extern "C" int gpsbb_blank_from_level(gpsbb_blank_t *b, const gpsbb_level_t *lv, long n, int shift, double thr_db)
+{
+    return blank_from_level(b, lv, n, shift, thr_db);
+}
+
+static int g_blank_nt = 0; /* gpsbb_test_blank_nt (the experiments build): the stores' policy, for tools/blank_rate.py's alternation */
+
+typedef void (*BlankKernelFn)(BlankArgs);
+static BlankKernelFn blank_kernel(bool noise, bool interf)
+{
+    static const BlankKernelFn k[2][2] = GPSBB_NI_KERNELS(k_blank);
+    return k[noise][interf];
+}
+
+extern "C" int gpsbb_device_blank(gpsbb_t *h, const int16_t *d_iq, long nsamp, const gpsbb_noise_t *nz, const gpsbb_interf_set_t *set,
+                                  const gpsbb_blank_t *b, const int16_t *hist_in, int16_t *hist_out, int16_t *d_out, uint64_t *blanked,
+                                  uint64_t *triggers)
+{
+    ImpairCall ic;
+    if (!h || !d_iq || !b || !d_out || (((uintptr_t)d_iq | (uintptr_t)d_out) & 3) || nsamp < 1 || !blank_ok(b) ||
+        !impair_make(nz, set, (uint64_t)nsamp, &ic))
+        return GPSBB_E_BADARG;
+    const uintptr_t in0 = (uintptr_t)d_iq, in1 = in0 + 4 * (uintptr_t)nsamp, out0 = (uintptr_t)d_out, out1 = out0 + 4 * (uintptr_t)nsamp;
+    if (out0 < in1 && in0 < out1)
+        return GPSBB_E_BADARG;
+    const int rc = iq_call_begin(h, ic.noise);
+    if (rc != GPSBB_OK)
+        return rc;
+    const int K = blank_hist(b);
+    long run = 0, nwg = 0;
+    blank_geometry(nsamp, &run, &nwg); /* nwg <= BLANK_MAX_WGS */
+    /* ---- scratch, in 8-byte words: the two histories, the two counts, two counts per workgroup ---- */
+    constexpr size_t hist_words = (GPSBB_BLANK_MAX_HIST + 1) / 2;
+    constexpr size_t o_hin = 0, o_hout = hist_words, o_cnt = 2 * hist_words, o_part = o_cnt + 2;
+    hipStream_t cs = h->s_compute;
+    HIPCHK(h, (hipError_t)h->d_blank.reserve(o_part + 2 * (size_t)BLANK_MAX_WGS));
+    BlankArgs a;
+    memset(&a, 0, sizeof a);
+    a.d = iq_view(h, d_iq, 0, ic);
+    a.tabs = h->d_tabs.p;
+    uint32_t *d_hin = reinterpret_cast<uint32_t *>(h->d_blank.p + o_hin), *d_hout = reinterpret_cast<uint32_t *>(h->d_blank.p + o_hout);
+    a.hist_in = d_hin;
+    a.hist_out = d_hout;
+    a.out = reinterpret_cast<uint32_t *>(d_out);
+    a.part = h->d_blank.p + o_part;
+    a.thr = b->thr;
+    a.nsamp = nsamp;
+    a.run = run;
+    a.L = b->win;
+    a.G = b->pre;
+    a.hold = b->hold;
+    a.K = K;
+    a.R = blank_share(b->pre, b->hold);
+    a.rcp = ((1u << BLANK_RCP_BITS) + (uint32_t)a.R - 1u) / (uint32_t)a.R;
+    a.nt = g_blank_nt;
+    if (K > 0) {
+        if (hist_in)
+            HIPCHK(h, hipMemcpyAsync(d_hin, hist_in, (size_t)K * 4, hipMemcpyHostToDevice, cs));
+        else
+            HIPCHK(h, hipMemsetAsync(d_hin, 0, (size_t)K * 4, cs));
+    }
+    HIPCHK(h, h->blank_tm.start(cs));
+    hipLaunchKernelGGL(blank_kernel(ic.noise, ic.set), dim3((unsigned)nwg), dim3(BLANK_WG), blank_lds_bytes(K), cs, a);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(k_exc_fold, dim3(1), dim3(PSD_WG), 0, cs, a.part, h->d_blank.p + o_cnt, (int)nwg);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, h->blank_tm.stop(cs));
+    uint32_t tail[GPSBB_BLANK_MAX_HIST];
+    unsigned long long cnt[2] = {0, 0};
+    HIPCHK(h, hipMemcpyAsync(cnt, h->d_blank.p + o_cnt, sizeof cnt, hipMemcpyDeviceToHost, cs));
+    if (K > 0)
+        HIPCHK(h, hipMemcpyAsync(tail, d_hout, (size_t)K * 4, hipMemcpyDeviceToHost, cs));
+    HIPCHK(h, hipStreamSynchronize(cs));
+    if (hist_out && K > 0)
+        memcpy(hist_out, tail, (size_t)K * 4);
+    if (blanked)
+        *blanked = cnt[0];
+    if (triggers)
+        *triggers = cnt[1];
+    return GPSBB_OK;
+}
+
 extern "C" double gpsbb_cn0_estimate(const gpsbb_corr_t *p, long n, long stride, double seg_seconds)
 {
     if (!p || n < 2 || stride < 1 || !(seg_seconds > 0.0) || !std::isfinite(seg_seconds))
@@ -4991,6 +5082,19 @@ extern "C" int gpsbb_test_exc_host(const gpsbb_exc_t *e, const int16_t *w, long 
     return exc_host(e, w, nsamp, hist_in, psd_table(), psd_table() + PSD_TW, work.data(), half.data(), out, hist_out, clipped, excised, peak)
                ? GPSBB_OK
                : GPSBB_E_BADARG;
+}
+extern "C" float gpsbb_test_blank_ms(gpsbb *h) { return h ? h->blank_tm.ms() : -1.0f; }
+extern "C" void gpsbb_test_blank_nt(int on) { g_blank_nt = on != 0; }
+extern "C" int gpsbb_test_blank_tile(int *run)
+{
+    if (run)
+        *run = BLANK_MIN_RUN;
+    return BLANK_TILE;
+}
+extern "C" int gpsbb_test_blank_host(const gpsbb_blank_t *b, const int16_t *w, long nsamp, const int16_t *hist_in, int16_t *out, int16_t *hist_out,
+                                     uint64_t *blanked, uint64_t *triggers)
+{
+    return blank_host(b, w, nsamp, hist_in, out, hist_out, blanked, triggers) ? GPSBB_OK : GPSBB_E_BADARG;
 }
 
 #ifdef GPSBB_WG_TRACE

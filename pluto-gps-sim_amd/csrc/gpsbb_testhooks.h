@@ -100,6 +100,15 @@ int gpsbb_test_exc_run(int log2n);
 /* gpsbb_exc.h's plain-C definition (exc_host) over host memory; peak: the largest |component| any inverse step produced */
 int gpsbb_test_exc_host(const gpsbb_exc_t *e, const int16_t *w, long nsamp, const int16_t *hist_in, int16_t *out, int16_t *hist_out,
                         uint64_t *clipped, uint64_t *excised, int64_t *peak);
+/* ... and of its last gpsbb_device_blank (k_blank, k_exc_fold); the outputs of one of k_blank's tiles, *run (where given): the
+ * tiles of a workgroup's least run */
+float gpsbb_test_blank_ms(struct gpsbb *h);
+int gpsbb_test_blank_tile(int *run);
+/* k_blank's output stores from the next call on: non-temporal (1) or plain (0, the product's); process-wide, for tools/blank_rate.py */
+void gpsbb_test_blank_nt(int on);
+/* gpsbb_blank.h's plain-C definition (blank_host) over host memory */
+int gpsbb_test_blank_host(const gpsbb_blank_t *b, const int16_t *w, long nsamp, const int16_t *hist_in, int16_t *out, int16_t *hist_out,
+                          uint64_t *blanked, uint64_t *triggers);
 /* the state granule of the batch's tile tables as log2 of its tiles: the code rows' (BatchDev::st_log2) and the carrier rows'
  * (ev_carr_log2 of it, gpsbb_events.hip.h) */
 int gpsbb_test_state_log2(struct gpsbb_batch *b);
